@@ -7,6 +7,7 @@ i.e. 2*B train images (and B val images) per step per GPU.  `value` = train imag
 whole job (all ranks), inputs already resident in HBM, optimizer steps / clipping / projection included.
 
   python bench.py --gpus 1 --steps 10 --warmup 3                  (single GPU)
+  python bench.py ... --dump-outputs DIR     also write what the last timed pair computed as DIR/<name>.npy (dump_outputs)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU, RCCL)
 
 Prints ONE JSON line (rank 0).  Extra objects:
@@ -360,6 +361,26 @@ def retrain_leg(dev, batch=256, steps=10, warmup=3):
     return out
 
 
+DUMP_WEIGHT_SAMPLE = 1 << 22       # 16 MB of the 33 M supernet weights (133 MB): a fixed, seeded sample
+
+
+def dump_outputs(out_dir, model, last):
+    """What the last timed iteration pair computed, as float32 .npy files (about 17 MB at batch 128): the returns of its
+    w-step / alpha-step / w-step, every architecture parameter, and a fixed seeded sample of the weights they updated."""
+    import numpy as np
+    (loss_w1, logits_w1), (loss_a, loss_l, lat, _), (loss_w2, logits_w2) = last
+    arrays = dict(w_step1_loss=loss_w1, w_step1_logits=logits_w1, a_step_loss=loss_a, a_step_loss_lat=loss_l, a_step_lat=lat,
+                  w_step2_loss=loss_w2, w_step2_logits=logits_w2,
+                  arch_params=torch.cat([p.detach().reshape(-1) for p in model.arch_parameters()]))
+    flat = torch.cat([p.detach().reshape(-1) for p in model.weight_parameters()])
+    idx = np.sort(np.random.RandomState(0).choice(flat.numel(), min(DUMP_WEIGHT_SAMPLE, flat.numel()), replace=False))
+    arrays['weights_sample'] = flat[torch.from_numpy(idx).to(flat.device)]
+    del flat
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def run_gpu(args):
     from tfnas_amd import Network, load_lat_lookup, geometry, search, _lib
     rank = int(os.environ.get('RANK', '0'))
@@ -391,8 +412,12 @@ def run_gpu(args):
     val = [batch() for _ in range(pool)]
 
     def pair(i):
-        search.search_iteration_pair(state, opt_w, opt_a, (train[(2 * i) % len(train)], train[(2 * i + 1) % len(train)]),
-                                     val[i % len(val)], noise)
+        # search.search_iteration_pair's three steps, keeping what each returns (--dump-outputs writes the last pair's)
+        bw, ba = (train[(2 * i) % len(train)], train[(2 * i + 1) % len(train)]), val[i % len(val)]
+        r1 = search.w_step(state, bw[0][0], bw[0][1], opt_w, 5.0, noise.exp(dev), noise.rand_pos())
+        ra = search.a_step(state, ba[0], ba[1], opt_a, 15.0, 0.1, 5.0, noise.exp(dev))
+        r2 = search.w_step(state, bw[1][0], bw[1][1], opt_w, 5.0, noise.exp(dev), noise.rand_pos())
+        return r1, ra, r2
 
     lib = _lib.lib()
     nfam = lib.tfnas_prof_count()
@@ -426,9 +451,11 @@ def run_gpu(args):
     ar0 = (search.ALLREDUCE_CALLS, search.ALLREDUCE_BYTES)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        pair(args.warmup + 1 + i)
+        last = pair(args.warmup + 1 + i)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last)
     ar1 = (search.ALLREDUCE_CALLS, search.ALLREDUCE_BYTES)
     if dist.is_initialized():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -778,7 +805,11 @@ def main():
     ap.add_argument('--batch', type=int, default=128, help='images per GPU per step-half (BASELINE configs[1]: 128)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-baseline-only', default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed iteration pair computed as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.cpu_baseline_only:
         print(json.dumps(run_cpu_baseline(args.cpu_baseline_only)))
         return

@@ -66,3 +66,35 @@ def tiny_masks(seed=0):
 def flat_masks(masks):
     import torch
     return torch.cat([m for st in masks.values() for blk in st.values() for m in blk.values()]).numpy().astype('uint8')
+
+
+def encode(obj):
+    """JSON-storable form of a nested structure that keeps what ``==`` on the original sees: key types, list vs tuple,
+    int vs float, the order of an OrderedDict's items (a plain dict's are sorted: its == ignores order); numpy scalars
+    become Python numbers."""
+    if isinstance(obj, OrderedDict):
+        return ['odict', [[encode(k), encode(v)] for k, v in obj.items()]]
+    if isinstance(obj, dict):
+        return ['dict', sorted(([encode(k), encode(v)] for k, v in obj.items()), key=lambda kv: repr(kv[0]))]
+    if isinstance(obj, (list, tuple)):
+        return ['list' if isinstance(obj, list) else 'tuple', [encode(v) for v in obj]]
+    if isinstance(obj, np.generic):
+        return obj.item()
+    return obj
+
+
+def probe_close(got, want, n, atol, rtol):
+    """Two probes (see ``probe``) of tensors with n elements: the sampled entries within atol + rtol * |want| of each other,
+    the sum and the abs-sum within what that elementwise bound implies for n elements."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    bound = atol * n + rtol * abs(want[1])
+    return (abs(got[0] - want[0]) <= bound and abs(got[1] - want[1]) <= bound
+            and np.allclose(got[2:], want[2:], atol=atol, rtol=rtol))
+
+
+def lut_digest(lut):
+    """sha256 of a latency table's content: outer keys in order, each inner {width: ms} table as a set of items."""
+    import hashlib
+    import json
+    rows = [[k, sorted((int(w), float(v)) for w, v in t.items()) if isinstance(t, dict) else float(t)] for k, t in lut.items()]
+    return hashlib.sha256(json.dumps(rows).encode()).hexdigest()

@@ -1,4 +1,5 @@
-"""Import helpers for the read-only reference tree (build container only; never on the GPU box).
+"""Import helpers for a checkout of the reference (TF-NAS), used by tests/golden/make_golden.py to record the reference's
+outputs; no test imports it.  Point TFNAS_REFERENCE at the reference's directory.
 
 Nothing here is copied from the reference: the reference's modules are imported from where they lie,
 and the un-importable ``train_search.py`` (argparse/mkdir/sys.exit at import) is
@@ -10,15 +11,17 @@ import os
 import sys
 import types
 
-REF = '/root/reference'
+REF = os.environ.get('TFNAS_REFERENCE', '')
 
 
 def available():
-    return os.path.isdir(os.path.join(REF, 'models'))
+    return bool(REF) and os.path.isdir(os.path.join(REF, 'models'))
 
 
 def import_reference():
     """Returns a namespace with the reference's classes/tables."""
+    if not available():
+        raise SystemExit('set TFNAS_REFERENCE to a checkout of the reference (the directory holding models/)')
     sys.dont_write_bytecode = True
     if REF not in sys.path:
         sys.path.insert(0, REF)

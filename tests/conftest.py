@@ -14,15 +14,11 @@ os.environ.setdefault('TFNAS_FX', '1')
 
 def pytest_configure(config):
     config.addinivalue_line('markers', 'gpu: needs a real MI355X (run through gpurun)')
-    config.addinivalue_line('markers', 'reference: needs /root/reference (build container only)')
 
 
 def pytest_collection_modifyitems(config, items):
     import torch
     has_gpu = torch.cuda.is_available()
-    has_ref = os.path.isdir('/root/reference/models')
     for item in items:
         if 'gpu' in item.keywords and not has_gpu:
             item.add_marker(pytest.mark.skip(reason='no GPU in this container'))
-        if 'reference' in item.keywords and not has_ref:
-            item.add_marker(pytest.mark.skip(reason='/root/reference not present'))

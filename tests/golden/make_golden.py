@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Generate golden vectors by running the REFERENCE itself (imported from /root/reference) on CPU.
+"""Generate golden vectors by running the REFERENCE itself (imported from $TFNAS_REFERENCE, tests/_refload.py) on CPU.
 
-Build-container only:   PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+Where the reference exists:   TFNAS_REFERENCE=<reference dir> PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [part ...]
 Outputs (committed):    tests/golden/*.npz, tests/golden/latency_kat.json
-The fixtures are data only (inputs + the reference's outputs); they let tests/test_oracle_golden.py pin
-oracle/tfnas_oracle.py on a box where the reference does not exist (the GPU box).
+The fixtures are data only (inputs + the reference's outputs); they let tests/test_oracle_golden.py,
+tests/test_epoch_golden.py and tests/test_oracle_vs_reference.py pin the oracle and the host logic without the reference.
 """
 import json
 import os
@@ -140,7 +140,15 @@ def net_fixtures():
         lr_, _ = m(x, sampling=True, mode='random')
     fx.update(samp_noise=noise.numpy(), samp_x_seed=99, samp_gumbel_idx=np.array(gidx),
               samp_logits_g=lg.numpy(), samp_logits_r=lr_.numpy(), samp_random_seed=12)
-    # bi-level trajectory: the reference's own train_w_arch, 6 iterations (3 alpha steps), B=2
+    fx.update(trajectory())
+    np.savez_compressed(os.path.join(HERE, 'network.npz'), **fx)
+    print('net zero-noise lat', float(lat0), 'gumbel idx', gidx)
+
+
+def trajectory():
+    """Bi-level trajectory: the reference's own train_w_arch, 6 iterations (3 alpha steps), B=2, in float64.  (In float32 the
+    three Adam steps of the arch parameters amplify rounding noise -- different on every host and thread count -- to ~1e-3.)"""
+    fx = {}
     import types
     args = types.SimpleNamespace(grad_clip=5.0, target_lat=15.0, lambda_lat=0.1, print_freq=1e9)
     ts = _refload.slice_train_search(('train_w_arch',), dict(args=args, AverageMeter=ref.AverageMeter,
@@ -155,7 +163,7 @@ def net_fixtures():
         def __call__(self, *a, **k): return self.module(*a, **k)
         def train(self): self.module.train()
 
-    m = build_net()
+    m = build_net().double()
     B, iters = 2, 6
     g = torch.Generator().manual_seed(2024)
     xs = [torch.randn(B, 3, 224, 224, generator=g) for _ in range(iters)]
@@ -164,11 +172,13 @@ def net_fixtures():
     ya = [torch.randint(0, 100, (B,), generator=g) for _ in range(iters // 2)]
     ng = [torch.empty(18, 8).exponential_(generator=g) for _ in range(iters)]
     na = [torch.empty(18, 8).exponential_(generator=g) for _ in range(iters // 2)]
+    x0_probe = probe(xs[0])
+    xs, xa = [x.double() for x in xs], [x.double() for x in xa]
     rows = []
     for it in range(iters):
-        rows.extend(ng[it])
+        rows.extend(ng[it].double())
         if it % 2 == 0:
-            rows.extend(na[it // 2])
+            rows.extend(na[it // 2].double())
     opt_w = torch.optim.SGD(m.weight_parameters(), lr=0.025, momentum=0.9, weight_decay=1e-5)
     opt_a = torch.optim.Adam(m.arch_parameters(), lr=0.01, betas=(0.5, 0.999), weight_decay=5e-4)
     random.seed(5)
@@ -178,11 +188,18 @@ def net_fixtures():
         ts['train_w_arch'](tq, vq, Wrap(m), torch.nn.CrossEntropyLoss(), opt_w, opt_a)
     fx['traj_seed'] = 2024
     fx['traj_random_seed'] = 5
-    fx['traj_x0_probe'] = probe(xs[0])
+    fx['traj_x0_probe'] = x0_probe
     fx['traj_final_arch'] = np.concatenate([p.detach().reshape(-1).numpy() for p in m.arch_parameters()])
     fx['traj_final_wprobe'] = np.stack([probe(p) for p in m.weight_parameters()])
-    np.savez_compressed(os.path.join(HERE, 'network.npz'), **fx)
-    print('net zero-noise lat', float(lat0), 'gumbel idx', gidx)
+    return fx
+
+
+def trajectory_fixture():
+    """Re-record only the trajectory keys of network.npz."""
+    path = os.path.join(HERE, 'network.npz')
+    fx = dict(np.load(path, allow_pickle=False))
+    fx.update(trajectory())
+    np.savez_compressed(path, **fx)
 
 
 # ---------------------------------------------------------------- 4. latency known answers
@@ -261,11 +278,284 @@ def epoch_fixture():
     np.savez_compressed(os.path.join(HERE, 'epoch_boundary.npz'), **out)
 
 
+# ---------------------------------------------------------------- 6. the reference's side of tests/test_oracle_vs_reference.py
+class _CudaNoop(torch.Tensor):
+    def cuda(self, *a, **k):
+        return self
+
+
+class _Wrap:
+    """Stands in for nn.DataParallel: .module + call-through."""
+    def __init__(self, m):
+        self.module = m
+
+    def __call__(self, *a, **k):
+        return self.module(*a, **k)
+
+    def train(self):
+        self.module.train()
+
+
+def oracle_vs_reference_fixture():
+    """What the reference computes in each test of tests/test_oracle_vs_reference.py (same seeds, same inputs), so that those
+    tests replay it -> tests/golden/oracle_vs_reference.npz (arrays) + oracle_vs_reference.json (structures, _golden.encode)."""
+    import copy, importlib, logging, types
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), 'tf-nas_amd'))
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), 'oracle'))
+    import _golden
+    enc = _golden.encode
+    arr, js = {}, OrderedDict()
+
+    def net(seed=2, T=5.0):
+        torch.manual_seed(seed)
+        m = ref.Network(100, ref.get_mc_num_dddict(ref.mc_mask_dddict), lut)
+        m.set_temperature(T)
+        m.train()
+        return m
+
+    def probes(named):
+        named = list(named)
+        return [k for k, _ in named], np.stack([probe(v) for _, v in named]), [int(v.numel()) for _, v in named]
+
+    # geometry tables
+    masks = ref.mc_mask_dddict
+    js['mask_shapes'] = enc(OrderedDict((st, OrderedDict((b, OrderedDict((i, list(m.shape)) for i, m in ops.items()))
+                                                         for b, ops in bl.items())) for st, bl in masks.items()))
+    js['mask_dtype'] = str(next(iter(next(iter(masks.values())).values()))[0].dtype)
+    arr['masks'] = torch.cat([m.reshape(-1).float() for bl in masks.values() for ops in bl.values()
+                              for m in ops.values()]).numpy()
+    js['lat_lookup_key_dddict'] = enc(ref.lat_lookup_key_dddict)
+    js['mc_num'] = enc(ref.get_mc_num_dddict(masks))
+    js['mc_num_max'] = enc(ref.get_mc_num_dddict(masks, True))
+    # the reference's latency pickles: a digest of their content (outer key order; inner dicts compare as dicts)
+    js['lut_sha256'] = {w: _golden.lut_digest(_refload.load_lut(w)) for w in ('gpu', 'cpu')}
+
+    # same-seed parameters
+    rm = net()
+    js['state_keys'], arr['init_probe'], js['init_numel'] = probes(rm.state_dict().items())
+    js['param_keys'] = [k for k, _ in rm.named_parameters()]
+
+    # soft forward / backward (float64: gradients to 2e-6 are not reproducible across hosts in float32)
+    rm = net().double()
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(2, 3, 224, 224, generator=g).double()
+    y = torch.tensor([3, 77])
+    noise = torch.empty(18, 8).exponential_(generator=g).double()
+    with _refload.inject_gumbel(noise):
+        rl, rlat = rm(x, sampling=False)
+    loss = F.cross_entropy(rl, y) + torch.abs(rlat / 15.0 - 1.) * 0.1
+    loss.backward()
+    arr['soft_logits'], arr['soft_lat'] = rl.detach().numpy(), np.array(float(rlat))
+    _, arr['soft_grad_probe'], js['param_numel'] = probes((k, p.grad) for k, p in rm.named_parameters())
+
+    # torch's RNG stream, no injected noise
+    rm = net()
+    torch.manual_seed(6)
+    x = torch.randn(1, 3, 224, 224)
+    torch.manual_seed(5)
+    rl, rlat = rm(x, sampling=False)
+    arr['rng_logits'], arr['rng_lat'] = rl.detach().numpy(), np.array(float(rlat))
+
+    # sampled modes
+    for mode in ('gumbel', 'gumbel_2', 'min_alphas', 'max_alphas', 'random'):
+        rm = net()
+        torch.manual_seed(12)
+        with torch.no_grad():
+            for a in rm.log_alphas_parameters():
+                a.copy_(F.log_softmax(torch.randn(8), -1))
+        x = torch.randn(2, 3, 224, 224)
+        noise = torch.empty(18, 8).exponential_()
+        random.seed(4)
+        with _refload.inject_gumbel(noise):
+            rl, rlat = rm(x, sampling=True, mode=mode)
+        arr['mode_%s_logits' % mode] = rl.detach().numpy()
+        js['mode_%s_switches' % mode] = [m.switches[:] for m in rm.modules() if isinstance(m, ref.MixedOP)]
+        js['mode_%s_lat' % mode] = float(rlat)
+
+    # bi-sampling pair, invalid mode
+    rm = net()
+    torch.manual_seed(13)
+    x = torch.randn(1, 3, 224, 224)
+    noise = torch.empty(18, 8).exponential_()
+    random.seed(9)
+    with _refload.inject_gumbel(noise):
+        rm(x, sampling=True, mode='gumbel')
+        js['bisample_gumbel_idx'] = [m.switches.index(False) for m in rm.modules() if isinstance(m, ref.MixedOP)]
+        rl, _ = rm(x, sampling=True, mode='random')
+    arr['bisample_logits'] = rl.detach().numpy()
+    try:
+        rm(x, sampling=True, mode='max')
+        js['invalid_mode_raises'] = None
+    except Exception as ex:                      # noqa: BLE001  (what the reference raises is the record)
+        js['invalid_mode_raises'] = type(ex).__name__
+
+    # search loop: the reference's own train_w_arch, 4 iterations (2 alpha steps)
+    args = types.SimpleNamespace(grad_clip=5.0, target_lat=15.0, lambda_lat=0.1, print_freq=1e9)
+    ts = _refload.slice_train_search(('train_w_arch', 'train_wo_arch'),
+                                     dict(args=args, AverageMeter=ref.AverageMeter, accuracy=ref.accuracy))
+    import tfnas_oracle as orc                   # (its optimizer factory only: the torch.optim classes of train_search.py)
+    rm = net().double()                          # (float64: see trajectory())
+    g = torch.Generator().manual_seed(21)
+    B, iters = 2, 4
+    xs = [torch.randn(B, 3, 224, 224, generator=g) for _ in range(iters)]
+    ys = [torch.randint(0, 100, (B,), generator=g) for _ in range(iters)]
+    xa = [torch.randn(B, 3, 224, 224, generator=g) for _ in range(iters)]
+    ya = [torch.randint(0, 100, (B,), generator=g) for _ in range(iters)]
+    xs, xa = [x.double() for x in xs], [x.double() for x in xa]
+    rows = []
+    for it in range(iters):
+        rows.extend(torch.empty(18, 8).exponential_(generator=g).double())
+        if it % 2 == 0:
+            rows.extend(torch.empty(18, 8).exponential_(generator=g).double())
+    ropt_w, ropt_a = orc.make_optimizers(rm)
+    tq = [(a.as_subclass(_CudaNoop), b.as_subclass(_CudaNoop)) for a, b in zip(xs, ys)]
+    vq = [(a.as_subclass(_CudaNoop), b.as_subclass(_CudaNoop)) for a, b in zip(xa[0::2], ya[0::2])]
+    random.seed(3)
+    with _refload.inject_gumbel(rows):
+        ts['train_w_arch'](tq, vq, _Wrap(rm), torch.nn.CrossEntropyLoss(), ropt_w, ropt_a)
+    _, arr['loop_param_probe'], _ = probes(rm.named_parameters())
+
+    # warm-up loop: train_wo_arch, 2 iterations
+    args = types.SimpleNamespace(grad_clip=5.0, print_freq=1e9)
+    ts = _refload.slice_train_search(('train_wo_arch',), dict(args=args, AverageMeter=ref.AverageMeter, accuracy=ref.accuracy))
+    rm = net()
+    g = torch.Generator().manual_seed(8)
+    xs = [torch.randn(2, 3, 224, 224, generator=g) for _ in range(2)]
+    ys = [torch.randint(0, 100, (2,), generator=g) for _ in range(2)]
+    noise = [torch.empty(18, 8).exponential_(generator=g) for _ in range(2)]
+    ropt_w, _ = orc.make_optimizers(rm)
+    with _refload.inject_gumbel([r for n in noise for r in n]):
+        ts['train_wo_arch']([(a.as_subclass(_CudaNoop), b.as_subclass(_CudaNoop)) for a, b in zip(xs, ys)],
+                            _Wrap(rm), torch.nn.CrossEntropyLoss(), ropt_w)
+    _, arr['warmup_param_probe'], _ = probes(rm.named_parameters())
+
+    # validate
+    args = types.SimpleNamespace(print_freq=1e9)
+    ts = _refload.slice_train_search(('validate',), dict(args=args, AverageMeter=ref.AverageMeter, accuracy=ref.accuracy))
+    rm = net()
+    g = torch.Generator().manual_seed(31)
+    xs = [torch.randn(n, 3, 224, 224, generator=g) for n in (3, 2, 3)]
+    ys = [torch.randint(0, 5, (a.size(0),), generator=g) for a in xs]
+    with torch.no_grad():
+        rm.classifier.linear.bias[:5] += 2.0
+    noise = [torch.empty(18, 8).exponential_(generator=g) for _ in xs]
+    with _refload.inject_gumbel([r for n in noise for r in n]):
+        js['validate_top1'] = float(ts['validate']([(a.as_subclass(_CudaNoop), b.as_subclass(_CudaNoop)) for a, b in zip(xs, ys)],
+                                                   _Wrap(rm), torch.nn.CrossEntropyLoss()))
+
+    # epoch boundary: the inline blocks of main()
+    blocks = _refload.slice_main_epoch_blocks()
+    ts = _refload.slice_train_search(('get_lookup_latency', 'fit_mc_num_by_latency', 'bound_clip'))
+    masks = _golden.tiny_masks()
+    torch.manual_seed(3)
+    full = torch.nn.DataParallel(ref.Network(100, ref.get_mc_num_dddict(masks, is_max=True), lut))
+    store = {k: v.clone() for k, v in full.state_dict().items()}
+    torch.manual_seed(4)
+    model = torch.nn.DataParallel(ref.Network(100, ref.get_mc_num_dddict(masks), lut))
+    ns = dict(model=model, state_dict=store, mc_mask_dddict=masks, torch=torch, np=np, logging=logging,
+              mc_maxnum_dddict=ref.get_mc_num_dddict(masks, is_max=True), lat_lookup=lut,
+              lat_lookup_key_dddict=ref.lat_lookup_key_dddict, args=types.SimpleNamespace(target_lat=12.0),
+              get_op_and_depth_weights=ref.get_op_and_depth_weights, parse_architecture=ref.parse_architecture,
+              get_mc_num_dddict=ref.get_mc_num_dddict, get_lookup_latency=ts['get_lookup_latency'],
+              fit_mc_num_by_latency=ts['fit_mc_num_by_latency'])
+    with _refload.cuda_is_identity():
+        exec(blocks['load'], ns)
+    js['epoch_loaded_keys'], arr['epoch_loaded_probe'], _ = probes(model.module.state_dict().items())
+    gen = torch.Generator().manual_seed(9)
+    with torch.no_grad():
+        for a in model.module.parameters():
+            a.add_(torch.randn(a.shape, generator=gen) * 0.1)
+    with _refload.cuda_is_identity():
+        exec(blocks['update'], ns)
+        exec(blocks['shrink'], ns)
+    js['epoch_store_keys'], arr['epoch_store_probe'], _ = probes(store.items())
+    js['epoch_parsed_arch'] = enc(ns['parsed_arch'])
+    js['epoch_mc_num'] = enc(ns['mc_num_dddict'])
+    js['epoch_lat'] = [ns['before_lat'], ns['after_lat']]
+    arr['epoch_masks'] = torch.cat([m.reshape(-1).float() for bl in masks.values() for ops in bl.values()
+                                    for m in ops.values()]).numpy()
+
+    # parse_architecture
+    rng = np.random.RandomState(0)
+    parsed = []
+    for _ in range(20):
+        ops = [rng.rand(8) for _ in range(18)]
+        depths = [rng.rand(n) for n in (2, 3, 4, 4, 4, 1)]
+        parsed.append(enc(ref.parse_architecture(ops, depths)))
+    js['parse_architecture'] = parsed
+
+    # derived config / flops / params / lookup latency (models/model_eval.py, tools/flops_benchmark.py, tools/utils.py)
+    from tfnas_amd import geometry as geo
+    me = importlib.import_module('models.model_eval')
+    fb = importlib.import_module('tools.flops_benchmark')
+    utils = importlib.import_module('tools.utils')
+    rng = np.random.RandomState(1)
+    derived = []
+    for trial in range(3):
+        ops = [rng.rand(8) for _ in range(18)]
+        depths = [rng.rand(n) for n in (2, 3, 4, 4, 4, 1)]
+        parsed_t = ref.parse_architecture(ops, depths)
+        mc = geo.initial_mc_num_dddict()
+        for st in mc:
+            for b in mc[st]:
+                for op in mc[st][b]:
+                    mc[st][b][op] = int(mc[st][b][op] * (0.7 + 0.6 * rng.rand()))
+        m_eval = me.Network(1000, parsed_t, mc, lut, 0.0, 0.0)
+        rec = dict(parsed=enc(parsed_t), config=enc(m_eval.config), params_MB=float(utils.count_parameters_in_MB(m_eval)))
+        m2 = fb.add_flops_counting_methods(m_eval)
+        m2.eval()
+        with torch.no_grad():
+            m2(torch.zeros(1, 3, 224, 224))
+        rec['macs_M'] = float(fb.compute_average_flops_cost(m2) / 1e6)
+        rec['latency'] = float(me.Network(1000, parsed_t, mc, lut, 0.0, 0.0).get_lookup_latency(torch.zeros(1, 3, 224, 224)))
+        cfg_json = json.loads(json.dumps(m_eval.config))
+        rec['config_json'] = enc(cfg_json)
+        me.NetworkCfg(1000, cfg_json, None, 0.0, 0.0)         # the reference's NetworkCfg accepts the JSON of its config
+        derived.append(rec)
+    js['derived'] = derived
+
+    # derived network (models/model_eval.Network): init, train-mode forward / backward, running statistics, eval forward
+    arch = OrderedDict((st, OrderedDict((b, (i * 3 + j) % 8) for j, b in enumerate(bl) if j < 2))
+                       for i, (st, bl) in enumerate(geo.initial_mc_num_dddict().items()))
+    mc = geo.initial_mc_num_dddict()
+    torch.manual_seed(1)
+    r = me.Network(20, arch, mc, lut, 0.2, 0.2)
+    js['dnet_state_keys'], arr['dnet_init_probe'], _ = probes(r.state_dict().items())
+    js['dnet_config'] = enc(r.config)
+    js['dnet_latency'] = float(copy.deepcopy(r).get_lookup_latency(torch.zeros(1, 3, 224, 224)))
+    # the arithmetic in float64, as the soft forward / backward above; float64 default dtype: the test's oracle then draws
+    # its drop-connect samples in float64 as the reference does (torch.rand(..., dtype=x.dtype))
+    r.double()
+    torch.manual_seed(6)
+    x = torch.randn(3, 3, 64, 64).double()
+    y = torch.randint(0, 20, (3,))
+    r.train()
+    torch.set_default_dtype(torch.float64)
+    try:
+        torch.manual_seed(7)
+        lg = r(x)
+        orc.label_smooth_loss(lg, y, 20, 0.1).backward()
+        r.eval()
+        with torch.no_grad():
+            le = r(x)
+    finally:
+        torch.set_default_dtype(torch.float32)
+    arr['dnet_train_logits'], arr['dnet_eval_logits'] = lg.detach().numpy(), le.numpy()
+    js['dnet_param_keys'], arr['dnet_grad_probe'], js['dnet_param_numel'] = probes((k, p.grad) for k, p in r.named_parameters())
+    js['dnet_buffer_keys'] = [k for k, _ in r.named_buffers()]
+    arr['dnet_buffers'] = torch.cat([b.reshape(-1).double() for _, b in r.named_buffers()]).numpy()
+
+    np.savez_compressed(os.path.join(HERE, 'oracle_vs_reference.npz'), **arr)
+    with open(os.path.join(HERE, 'oracle_vs_reference.json'), 'w') as f:
+        json.dump(js, f, separators=(',', ':'))
+
+
+PARTS = OrderedDict([('gumbel_kat', gumbel_kat), ('cells', cell_fixtures), ('net', net_fixtures), ('trajectory', trajectory_fixture), ('latency', latency_kat),
+                     ('epoch', epoch_fixture), ('oracle_vs_reference', oracle_vs_reference_fixture)])
+
 if __name__ == '__main__':
-    gumbel_kat()
-    cell_fixtures()
-    net_fixtures()
-    latency_kat()
+    # no argument: every fixture; otherwise only the named parts (e.g. `make_golden.py oracle_vs_reference`)
+    for part in sys.argv[1:] or list(PARTS):
+        PARTS[part]()
     for fn in sorted(os.listdir(HERE)):
         print(fn, os.path.getsize(os.path.join(HERE, fn)))
-    epoch_fixture()
