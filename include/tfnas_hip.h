@@ -37,11 +37,11 @@ extern "C" {
 #endif
 
 /* 4 (round 6): every route switch of a launch lives in its descriptor (TfnasCellDesc.route: TFNAS_ROUTE_*); the library reads no
- * environment variable at launch time (the TFNAS_* variables only seed the Python-side defaults, functions.HipModes.from_env).
+ * environment variable at launch time (the TFNAS_* variables only seed the Python-side defaults, functions.route_from_env).
  * tfnas_cell_route() + TfnasCellDesc.fwd_route: a backward refuses a descriptor whose route differs from the forward's.
  * TfnasCellDesc.wgrad_stream[3]: caller-owned streams for the three weight-gradient forks of ONE launch (the stem cell's backward
  * runs alone on the chip: its four weight-gradient kernels spread over the queues the two finished paths left idle).
- * tfnas_cls_ce_fwd_bwd / tfnas_cls_wgrad: classifier + cross-entropy of the weight step in two launches.
+ * tfnas_cls_ce / tfnas_cls_wgrad: classifier + cross-entropy of the weight step in two launches.
  * 3 (round 5): tfnas_fx_supported (fused per-image route of the late cells); per-launch modes in TfnasCellDesc (gemm_mode, flags,
  * sync_fn / sync_user / sync_world: the process-wide setters only provide defaults).
  * 2 (round 4): arithmetic modes of the GEMMs (tfnas_set_gemm_mode); the per-group input / output mode of TfnasCellDesc (xg /

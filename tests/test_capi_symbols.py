@@ -124,7 +124,7 @@ def test_library_reads_no_environment_variable():
     from tfnas_amd import _lib
     from tfnas_amd import functions as F
     out = subprocess.run(['strings', _lib.LIB_PATH], capture_output=True, text=True).stdout.split()
-    hits = [w for w in out if w.startswith('TFNAS_') and w not in ('TFNAS_ABLATE_MASK',)]
+    hits = [w for w in out if w.startswith('TFNAS_')]
     assert not hits, hits
     assert F.route_from_env({}) == 0
     assert F.route_from_env({'TFNAS_FX': '0', 'TFNAS_DW': 'lds', 'TFNAS_SE': 'fused', 'TFNAS_XG': 'all'}) == (

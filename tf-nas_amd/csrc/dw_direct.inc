@@ -104,9 +104,9 @@ __global__ __launch_bounds__(256, (K == 3 ? 4 : (JW == 2 ? 3 : 2))) void k_dwd_w
 
     const size_t numel_e = (size_t)N * H * W * M, numel_d = (size_t)N * Ho * Wo * M;
     BufView bZ, bD, bE;
-    bZ.bind(dZ, numel_d, d.stor);
-    bD.bind(D, numel_d, d.stor);
-    bE.bind(E, numel_e, d.stor);
+    bZ.bind(dZ, numel_d);
+    bD.bind(D, numel_d);
+    bE.bind(E, numel_e);
 
     // this wave's range of macro-steps
     const int seg = sq * 4 + wv;
@@ -321,8 +321,8 @@ __global__ __launch_bounds__(256, (K == 3 ? 4 : (JW == 2 ? 4 : 3))) void k_dwd_f
     const int e_lane = wi0 * M + off + ch, d_lane = wo0 * M + off + ch;
 
     BufView bE, bD;
-    bE.bind(E, (size_t)N * H * W * M, d.stor);
-    bD.bind(D, (size_t)N * Ho * Wo * M, d.stor);
+    bE.bind(E, (size_t)N * H * W * M);
+    bD.bind(D, (size_t)N * Ho * Wo * M);
 
     const int HA = (S == 1 ? H : Ho) + XT;             // macro-steps per image
     const int seg = sq * 4 + wv;
@@ -539,10 +539,10 @@ __global__ __launch_bounds__(256, dwd_bwd_occ(K, S, JW)) void k_dwd_bwd(
 
     const size_t numel_e = (size_t)N * H * W * M, numel_d = (size_t)N * Ho * Wo * M;
     BufView bZ, bD, bE, bO;
-    bZ.bind(dZ, numel_d, d.stor);
-    bD.bind(D, numel_d, d.stor);
-    bE.bind(E, numel_e, d.stor);
-    bO.bind(dEh, numel_e, d.stor);
+    bZ.bind(dZ, numel_d);
+    bD.bind(D, numel_d);
+    bE.bind(E, numel_e);
+    bO.bind(dEh, numel_e);
 
     const int HA = Ho + XT;                            // events per image: its dd rows + XT zero rows
     const int seg = sq * 4 + wv;

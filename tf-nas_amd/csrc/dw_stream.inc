@@ -69,30 +69,17 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 struct BufView {
     __amdgpu_buffer_rsrc_t r;
-    __device__ __forceinline__ void bind(const float* p, size_t numel, int = 0) {
+    __device__ __forceinline__ void bind(const float* p, size_t numel) {
         r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (int)(unsigned)(numel * 4), 0x00020000);
     }
-#ifdef TFNAS_HALF_BYTES            // timing-only build (tfnas_dev.h): 8 bytes per quad at byte offset 2 * off
-    __device__ __forceinline__ f32x4 ld4(unsigned off) const {
-        return hb_expand(__builtin_bit_cast(hb_u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)(off * 2u), 0, TFNAS_LD_AUX)));
-    }
-    __device__ __forceinline__ void st4(unsigned off, f32x4 v) const {
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hb_pack(v)), r, (int)(off * 2u), 0, TFNAS_ST_AUX);
-    }
-#else
     __device__ __forceinline__ f32x4 ld4(unsigned off) const {
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(off * 4u), 0, TFNAS_LD_AUX));
     }
     __device__ __forceinline__ void st4(unsigned off, f32x4 v) const {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)(off * 4u), 0, TFNAS_ST_AUX);
     }
-#endif
 };
-#ifdef TFNAS_HALF_BYTES
-constexpr unsigned BUF_OOB = 0x7fffffffu;      // (timing-only build: byte offset = 2 * element offset)
-#else
 constexpr unsigned BUF_OOB = 0x3fffffffu;      // element offset that is out of range for every tensor (numel < 2^30)
-#endif
 
 // Wave-uniform position in the stream: image i, row h in [-PAD, H) (h < 0 = separator row), ring slot.
 struct StreamPos {
@@ -241,8 +228,8 @@ __global__ __launch_bounds__(256, PIPE ? 3 : 4) void k_dws_fwd(TfnasCellDesc d, 
     rb.init(gm, W, M, mcp - c0, PAD);
     StreamPos bpos = {0, -PAD, 0};                                // block 0 starts at virtual row 0
     BufView bE, bD;
-    bE.bind(E, (size_t)d.N * H * W * M, d.stor);
-    bD.bind(D, (size_t)d.N * H * W * M, d.stor);
+    bE.bind(E, (size_t)d.N * H * W * M);
+    bD.bind(D, (size_t)d.N * H * W * M);
     if (PIPE) {
         rb.issue(ge, bpos, bE, bE);
         rb.commit(ring, ge, bpos, xf);
@@ -446,10 +433,10 @@ __global__ __launch_bounds__(256, WGR ? 2 : ((PIPE || KQ > 0) ? 3 : 4)) void k_d
     };
     const size_t numel = (size_t)d.N * H * W * M;
     BufView bZ, bDd, bE, bO;
-    bZ.bind(dZ, numel, d.stor);
-    bDd.bind(D, numel, d.stor);
-    bE.bind(E, numel, d.stor);
-    bO.bind(dEh, numel, d.stor);
+    bZ.bind(dZ, numel);
+    bDd.bind(D, numel);
+    bE.bind(E, numel);
+    bO.bind(dEh, numel);
     RingBlock<true> rb;
     rb.init(gm, W, M, mcp - c0, PAD);
     StreamPos bpos = {0, -PAD, 0};
@@ -672,9 +659,9 @@ __global__ __launch_bounds__(256, (!PIPE && K == 3) ? 4 : 2) void k_dws_wgrad(Tf
     };
     const size_t numel = (size_t)d.N * H * W * M;
     BufView bZ, bDd, bE;
-    bZ.bind(dZ, numel, d.stor);
-    bDd.bind(D, numel, d.stor);
-    bE.bind(E, numel, d.stor);
+    bZ.bind(dZ, numel);
+    bDd.bind(D, numel);
+    bE.bind(E, numel);
     RingBlock<false> rb;
     rb.init(gm, W, M, mcp - c0, PAD);
     StreamPos bpos = {0, -PAD, 0};
@@ -902,7 +889,7 @@ bool dw_bwd_fuses_wgrad(const TfnasCellDesc& d, const float* E) {
     // top of 130-170: 900-1100 bytes of scratch per thread at 256 registers -- measured in the ISA, not launched)
     for (int g = 0; g < d.G; ++g)
         if (d.g[g].k != 3) return false;
-    // measured alone at B = 128 (tools/r4_dwwg.sh, one 3 x 3 candidate, whole cell): 56 x 56 1.17 -> 0.94 ms, 28 x 28 0.57 -> 0.51 ms,
+    // measured alone at B = 128 (DESIGN.md section 4c, one 3 x 3 candidate, whole cell): 56 x 56 1.17 -> 0.94 ms, 28 x 28 0.57 -> 0.51 ms,
     // 14 x 14 equal (there the separate register-window weight gradient is already cheap and the fused pass runs at two waves per
     // SIMD instead of four); in the pair the change is inside the noise (69.3-69.7 vs 69.4-69.9 ms)
     if (d.W < 28) return false;

@@ -27,41 +27,11 @@
 #include "gemm_x3.h"
 #include <type_traits>
 
-// timing-only ablation of the fused kernels (tools/r5_fxabl.sh): bit 0 no stencil taps, 1 no expand MFMAs, 2 no D / E stores,
-// 3 no blob copies, 4 no activation in the expand epilogue.  Never set in the product build.
-#ifndef FX_ABL
-#define FX_ABL 0
-#endif
-
-// -DFX_TIMING (tools/fx_timeline.py): shader-clock stamps of one chunk interval (FXT_CHUNK) of the first 64 workgroups, per wave
-#ifdef FX_TIMING
-#ifndef FXT_CHUNK
-#define FXT_CHUNK 3
-#endif
-__device__ unsigned long long g_fxt[64 * 8 * 16];
-#define FXT(chunk_, slot_)                                                                                   \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 64 && ((chunk_) == FXT_CHUNK || (chunk_) < 0))              \
-        g_fxt[(blockIdx.x * 8 + (threadIdx.x >> 6)) * 16 + (slot_)] = __builtin_readcyclecounter();
-extern "C" int tfnas_dbg_fx_timing(unsigned long long* out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fxt), sizeof(unsigned long long) * (size_t)n);
-}
-#else
-#define FXT(chunk_, slot_)
-#endif
-
 // ---------------------------------------------------------------------------------------------------------------- plan
 static int fx_ks(int ic) { return (ic + 31) / 32; }
 
 bool fx_plan(const TfnasCellDesc& d, FxPlan& pl, bool bwd) {
-#ifdef TFNAS_FXW_TIMING
-    // TIMING-ONLY build (tools/r6_fxw.sh): the fused per-image route also for launches that want weight
-    // gradients -- the existing weight-gradient kernels then read ehat as if it were E and the dx-partial scratch as if it were dE
-    // (wrong numerics by construction; never shipped, never tested for parity): what would the sampled late cells of the w-step
-    // gain from a fused route BEFORE anybody builds its weight gradients?
-    if (d.mode != TFNAS_MODE_CELL) return false;
-#else
     if (d.mode != TFNAS_MODE_CELL || d.need_wgrad) return false;
-#endif
     if (stats_sync_on(d)) return false;                     // (BN1 statistics come from the Gram matrix of x: efree_kernels.hip)
     if (d.ic < 64 || d.ic > 192 || (d.ic & 15)) return false;
     if (d.stride != 1) return false;                       // (stride-2 cells keep the materialised route)
@@ -270,7 +240,7 @@ struct FxCopy {
 //  instruction counts; tiles past the end of the workgroup's pixels multiply zero x planes instead)
 #define FX_TERM(A_, B_)                                                                                                  \
     _Pragma("unroll") for (int ct = 0; ct < 2; ++ct) _Pragma("unroll") for (int pt = 0; pt < RT; ++pt)                   \
-        if (!(FX_ABL & 2)) acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_[ct], X.B_[pt][ks], acc[ct][pt], 0, 0, 0);
+        acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_[ct], X.B_[pt][ks], acc[ct][pt], 0, 0, 0);
 
 // e = BN1(x W1_chunk^T) for the wave's pixel tiles: A = W1 planes (LDS blob), B = x planes (registers).  Lane (n, q) of tile
 // (ct, pt) ends up with channels 16 ct + 4 q .. + 3 of pixel 16 (wave + 8 pt) + n; OUT = 0 / 1: act(e) -> tile, 2: e -> tile.
@@ -312,11 +282,11 @@ __device__ __forceinline__ void fx_expand(const u8* P, const FxX<KS, RT>& X, flo
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 e[r] = (acc[ct][pt][r] - c[r].x) * c[r].y;
-                v[r] = (OUT == 2 || (FX_ABL & 16)) ? e[r] : act_f<(OUT == 2 ? 0 : OUT)>(e[r]);
+                v[r] = (OUT == 2) ? e[r] : act_f<(OUT == 2 ? 0 : OUT)>(e[r]);
             }
             st4(tile + slot[pt] * 32 + 16 * ct + 4 * q, v);
             // (columns between mc and the chunk's end are the group's padding in the [pixels][M] row: zeros may go there)
-            if (!(FX_ABL & 4) && eg && pv[pt]) st4_nt(eg + egoff[pt] + 16 * ct + 4 * q, e);
+            if (eg && pv[pt]) st4_nt(eg + egoff[pt] + 16 * ct + 4 * q, e);
         }
     }
 }
@@ -353,8 +323,9 @@ __device__ __forceinline__ void fx_stat_emit(const float* stat, float* __restric
 // Seven WORKER waves (pixel tiles wave + 7 pt; one stencil item each) and one COPIER wave (wave 7).  The workers never wait
 // on vector memory inside the chunk loop: they only issue stores (D, ehat).  On gfx950 loads and stores share one counter, so
 // a wave that prefetches the next chunk's blob AND stores results ends every interval in `s_waitcnt vmcnt(0)`, i.e. waiting for
-// its store acknowledgements (ablation, tools/r5_fxabl.sh: the kernel without taps and without MFMAs still took 60 % of its
-// time).  The copier moves the blobs (global -> registers -> LDS, all pieces in flight at once) and writes the statistics rows.
+// its store acknowledgements (timing-only ablation, DESIGN.md section 4d: the kernel without taps and without MFMAs still took
+// 60 % of its time).  The copier moves the blobs (global -> registers -> LDS, all pieces in flight at once) and writes the
+// statistics rows.
 constexpr int FX_WORKERS = 7;
 
 struct FxFItem {
@@ -372,7 +343,7 @@ __device__ __forceinline__ void fx_fwd_stencil(const float* tile, const float* t
         const float* base = tile + it.toff;
         f32x4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
 #pragma unroll 1
-        for (int ky = 0; ky < ((FX_ABL & 1) ? 0 : K); ++ky) {
+        for (int ky = 0; ky < K; ++ky) {
             const float* rowp = base + ky * WP * 32;
             const float* wp = taps + ky * K * 32 + 4 * cq;
             f32x4 win[K + 3];
@@ -390,7 +361,7 @@ __device__ __forceinline__ void fx_fwd_stencil(const float* tile, const float* t
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
                 if (jj < it.npx) {
-                    if (!(FX_ABL & 4)) st4_nt(o + (size_t)jj * M, acc[jj]);
+                    st4_nt(o + (size_t)jj * M, acc[jj]);
                     ssum += acc[jj];
                     ssq += acc[jj] * acc[jj];
                 }
@@ -402,7 +373,7 @@ __device__ __forceinline__ void fx_fwd_stencil(const float* tile, const float* t
 
 // One interval of a worker wave as ONE instruction stream: the MFMAs of chunk i + 1 (k-step by k-step) with the tap rows of chunk i's
 // stencil item between them.  A wave is in-order: run one after the other, its interval is t(MFMA) + t(stencil) however busy the
-// partner wave keeps the other pipe (measured: the two added up exactly, tools/r5_fxabl.sh); in one basic block the scheduler
+// partner wave keeps the other pipe (measured: the two added up exactly); in one basic block the scheduler
 // fills the 16-cycle shadow of every v_mfma_f32_16x16x32_bf16 with the stencil's LDS reads and v_pk_fma_f32.
 template <int K, int ACT, int KS, int RT>
 __device__ __forceinline__ void fx_fwd_interval(const u8* P, const FxX<KS, RT>& X, float* tnext, const int (&slot)[RT],
@@ -568,9 +539,7 @@ __device__ __forceinline__ void fx_fwd_body(const TfnasCellDesc& d, const FxPlan
                 const int o = (lane + 64 * u) * 16;
                 vw[u] = *reinterpret_cast<const u32x4*>(sw + (o < WBK ? o : WBK - 16));
             }
-            FXT(i, 0)
             __syncthreads();
-            FXT(i, 1)
             if (i > 0 && lane < 64) {                                      // statistics of chunk i - 1 -> this group's partial row
                 const int ch = lane & 31, which = lane >> 5, c0p = sl.c0 + 32 * (i - 1);
                 const float* st = St((i - 1) & 1);
@@ -579,7 +548,7 @@ __device__ __forceinline__ void fx_fwd_body(const TfnasCellDesc& d, const FxPlan
                 for (int w = 0; w < FX_WORKERS; ++w) t += st[w * 64 + which * 32 + ch];
                 if (c0p + ch < mcp) prow[2 * (size_t)(c0p + ch) + which] = t;
             }
-            if (p2 && !(FX_ABL & 8)) {
+            if (p2) {
                 u8* dp = Pb(i & 1);
 #pragma unroll
                 for (int u = 0; u < NCP1; ++u) {
@@ -600,7 +569,7 @@ __device__ __forceinline__ void fx_fwd_body(const TfnasCellDesc& d, const FxPlan
                     }
                 }
             }
-            if (w1 && !(FX_ABL & 8)) {
+            if (w1) {
                 u8* dw = Wb((i + 1) & 1);
 #pragma unroll
                 for (int u = 0; u < NCW; ++u) {
@@ -608,7 +577,6 @@ __device__ __forceinline__ void fx_fwd_body(const TfnasCellDesc& d, const FxPlan
                     if (o < WBK) *reinterpret_cast<u32x4*>(dw + o) = vw[u];
                 }
             }
-            FXT(i, 2)
         }
         __syncthreads();
         {
@@ -664,15 +632,12 @@ __device__ __forceinline__ void fx_fwd_body(const TfnasCellDesc& d, const FxPlan
     for (int i = 0; i < nch; ++i) {
         // interval i: stencil of chunk i  ||  MFMAs of chunk i + 1  (the copier brings planes of chunk i + 2, taps of chunk i + 1)
         const bool w1 = i + 1 < nch;
-        FXT(i, 0)
         __syncthreads();
-        FXT(i, 1)
         const int c0 = sl.c0 + 32 * i;
         const bool chok = c0 + 4 * cq < mcp;
         // (the last interval runs the MFMAs on the stale planes of the buffer and drops the result: no branch in the stream)
         fx_fwd_interval<K, ACT, KS, RT>(Pb((i + 1) & 1), X, T((i + 1) & 1), slot, pv, Eg ? Eg + c0 + 32 : nullptr, egoff, w1,
                                         T(i & 1), reinterpret_cast<const float*>(Wb(i & 1)), it, WP, M, chok, Dg + c0, St(i & 1));
-        FXT(i, 2)
     }
     __syncthreads();
 }
@@ -958,7 +923,7 @@ __device__ __forceinline__ void fx_bwde_body(const TfnasCellDesc& d, const FxPla
                                              const float* __restrict__ Dt, const float* __restrict__ gate,
                                              const float* __restrict__ dpooled, float* __restrict__ dxp,
                                              float* __restrict__ part, u8* lds, int ig, const FxSlice sl, int si) {
-    // Seven worker waves + one copier wave, as in the forward (fx_fwd_body).  Per-wave cycle stamps (tools/fx_timeline.py) of the
+    // Seven worker waves + one copier wave, as in the forward (fx_fwd_body).  Per-wave cycle stamps of the
     // first version -- every wave loading, computing and copying -- showed ~2 200 of the 14 500 cycles of a chunk spent at the top of
     // phase A waiting for the dZ / D loads issued just before the barrier, and ~1 500 in the stencil epilogue waiting for the blob
     // copies issued just before the taps (the vector-memory counter is in-order: a wait for ehat drags every younger load along).
@@ -1085,23 +1050,21 @@ __device__ __forceinline__ void fx_bwde_body(const TfnasCellDesc& d, const FxPla
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         const size_t a = (pixbase + lpix[r]) * M + goff + sl.c0 + 4 * cq;
-        dz[r] = (FX_ABL & 512) ? splat4(0.25f) : ld4_nt(dZ + a);
-        dv[r] = (FX_ABL & 512) ? splat4(0.75f) : ld4_nt(Dt + a);
+        dz[r] = ld4_nt(dZ + a);
+        dv[r] = ld4_nt(Dt + a);
     }
     __syncthreads();
     for (int i = 0; i <= nch; ++i) {
         const int c0 = sl.c0 + 32 * i;
         const bool chok = c0 + 4 * cq < mcp;
         // ---- phase A: dx += dE(i - 1) Wr(i - 1)  (MFMA);  dd(i) = BN2-backward(dZ, D) -> LDS image tile
-        FXT(i, 0)
         f32x4 ev[4];
         {
             const int ce = i < nch ? c0 : c0 - 32;
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj)
-                ev[jj] = (FX_ABL & 256) ? splat4(0.5f) : ld4_nt(Eh + eaddr + ce + (size_t)(jj < it.npx ? jj : 0) * M);
+                ev[jj] = ld4_nt(Eh + eaddr + ce + (size_t)(jj < it.npx ? jj : 0) * M);
         }
-        FXT(i, 1)
         if (i > 0) {
             bf16x8 bh[RT], bm[RT], bl[RT];
 #pragma unroll
@@ -1122,7 +1085,7 @@ __device__ __forceinline__ void fx_bwde_body(const TfnasCellDesc& d, const FxPla
                 }
 #define FX_GTERM(A_, B_)                                                                                             \
     _Pragma("unroll") for (int u = 0; u < 2; ++u) _Pragma("unroll") for (int pt = 0; pt < RT; ++pt) {                \
-        if (ct0 + u < CT && !(FX_ABL & 32))                                                                          \
+        if (ct0 + u < CT)                                                                                            \
             dx[ct0 + u < CT ? ct0 + u : ct0][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                          \
                 A_[u], B_[pt], dx[ct0 + u < CT ? ct0 + u : ct0][pt], 0, 0, 0);                                       \
     }
@@ -1130,10 +1093,9 @@ __device__ __forceinline__ void fx_bwde_body(const TfnasCellDesc& d, const FxPla
 #undef FX_GTERM
             }
         }
-        FXT(i, 2)
         if (i == nch) break;
         // (the MFMAs and the BN2-backward transform below were also tried as ONE interleaved stream, a column-tile pair + a loader
-        //  round per scheduling region: 5 750 cycles against 2 200 + 3 170 -- no gain, tools/fx_timeline.py)
+        //  round per scheduling region: 5 750 cycles against 2 200 + 3 170 -- no gain, per-wave cycle stamps)
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             if (lslot[r] >= 0) {
@@ -1143,34 +1105,31 @@ __device__ __forceinline__ void fx_bwde_body(const TfnasCellDesc& d, const FxPla
                     g4 = ld4(gate + o);
                     dp4 = ld4(dpooled + o) * splat4(inv_hw);
                 }
-                f32x4 v = (FX_ABL & 128) ? dz[r] + dv[r] : fx_bn2_dd<ACT>(C2 + 4 * cq, dz[r], dv[r], has_se, g4, dp4);
+                f32x4 v = fx_bn2_dd<ACT>(C2 + 4 * cq, dz[r], dv[r], has_se, g4, dp4);
                 if (!chok) v = zero4();
                 st4(DD + lslot[r], v);
             }
         }
-        FXT(i, 3)
         __syncthreads();
-        FXT(i, 4)
         // ---- phase B: dZ / D of chunk i + 1 requested; stencil of chunk i (flipped taps), * act'(ehat), dE -> LDS, t1 / t2
         // (requested at the END of the phase instead -- behind the wait for ehat -- the next phase A opens with a ~2 000-cycle wait:
-        //  the compiler puts a vmcnt(0) in front of the ehat requests; measured, tools/fx_timeline.py)
+        //  the compiler puts a vmcnt(0) in front of the ehat requests; measured with per-wave cycle stamps)
         {
             const int cn = i + 1 < nch ? c0 + 32 : c0;
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
                 const size_t a = (pixbase + lpix[r]) * M + goff + cn + 4 * cq;
-                dz[r] = (FX_ABL & 512) ? splat4(0.25f) : ld4_nt(dZ + a);
-                dv[r] = (FX_ABL & 512) ? splat4(0.75f) : ld4_nt(Dt + a);
+                dz[r] = ld4_nt(dZ + a);
+                dv[r] = ld4_nt(Dt + a);
             }
         }
-        FXT(i, 5)
         {
             const float* taps = reinterpret_cast<const float*>(Wb(i & 1));
             f32x4 t1 = zero4(), t2 = zero4();
             const float* base = DD + it.toff;
             f32x4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
 #pragma unroll 1
-            for (int ky = 0; ky < ((FX_ABL & 64) ? 0 : K); ++ky) {
+            for (int ky = 0; ky < K; ++ky) {
                 const float* rowp = base + ky * WP * 32;
                 const float* wp = taps + (K * K - 1 - ky * K) * 32 + 4 * cq;      // flipped taps
                 f32x4 win[K + 3];
@@ -1183,7 +1142,6 @@ __device__ __forceinline__ void fx_bwde_body(const TfnasCellDesc& d, const FxPla
                     for (int jj = 0; jj < 4; ++jj) acc[jj] += win[jj + kx] * wv;
                 }
             }
-            FXT(i, 6)
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
                 const bool ok = chok && jj < it.npx;
@@ -1197,9 +1155,7 @@ __device__ __forceinline__ void fx_bwde_body(const TfnasCellDesc& d, const FxPla
             }
             fx_stat_park(t1, t2, St);
         }
-        FXT(i, 7)
         __syncthreads();
-        FXT(i, 10)
     }
     float* __restrict__ dst = dxp + (size_t)si * d.N * HW * ic;
 #pragma unroll
@@ -1482,11 +1438,8 @@ int launch_fx_fwd(const TfnasCellDesc& d, const float* x, const double* stats1, 
 }
 
 // TFNAS_ROUTE_FX_OFF in the launch's descriptor: the materialised route instead of the fused per-image kernels (ABI 4: no environment
-// variable is read here; a timing build can flip the default with -DTFNAS_FX_DEFAULT=0)
-#ifndef TFNAS_FX_DEFAULT
-#define TFNAS_FX_DEFAULT 1
-#endif
-static bool fx_enabled(const TfnasCellDesc& d) { return TFNAS_FX_DEFAULT != 0 && !(d.route & TFNAS_ROUTE_FX_OFF); }
+// variable is read here)
+static bool fx_enabled(const TfnasCellDesc& d) { return !(d.route & TFNAS_ROUTE_FX_OFF); }
 
 // scratch layout of the backward: dxp [nsl + 1][P][ic] floats | blobs (256-byte aligned) -- in `scratch` (the cell's dEh buffer,
 // which the fused route never uses for dE) when it is large enough, else the blobs go behind the statistics rows in `part`

@@ -53,22 +53,6 @@ constexpr int gemm_lb(int nt, int mm, bool heavy = false) {
     return mm == 0 ? (nt >= 5 ? TFNAS_LB_BIG : TFNAS_LB_SMALL) : ((nt >= 5 || heavy) ? TFNAS_LB_X3_BIG : TFNAS_LB_X3_SMALL);
 }
 
-// -DTFNAS_WG_TIMING (tools/wg_timeline.py): per-workgroup wall-clock stamps (100 MHz s_memrealtime) of the weight-gradient
-// GEMMs: [wg][0..3] = start, after prologue, after K loop, end
-#ifdef TFNAS_WG_TIMING
-__device__ unsigned long long g_wgt[4 * 16384];
-#define WGT(slot)                                                                                                      \
-    if (threadIdx.x == 0) {                                                                                            \
-        const unsigned f_ = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);                            \
-        if (f_ < 16384) g_wgt[4 * f_ + (slot)] = wall_clock64();                                                       \
-    }
-extern "C" int tfnas_dbg_wg_timing(unsigned long long* out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wgt), sizeof(unsigned long long) * (size_t)n);
-}
-#else
-#define WGT(slot)
-#endif
-
 // raw registers of the two-phase loaders (gemm_core.h): what the load phase leaves for the transform phase
 struct Raw2 { f32x4 a, b; };             // two stream pieces (D | gate,  dOut | Pr,  dEh | E)
 struct RawWS { f32x4 w; float s; };      // a weight quad and its row scale
@@ -137,7 +121,7 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_expand_fwd(TfnasCellDe
         gemm_adirect<NT, true, MM>(pre, la, xa, lb, xb, nchunks, acc, lds);
         emit_tile_rows<NT>(acc, lds, [&](int lrow, int lc, f32x4 v) {
             const int p = rt * 128 + lrow;
-            if (p < P && n0 + lc < mcp) stS4_nt(E, (size_t)p * M + off + n0 + lc, v, d.stor);
+            if (p < P && n0 + lc < mcp) st4_nt(E + ((size_t)p * M + off + n0 + lc), v);
         });
         acc_colstats<NT>(acc, cs, cq);
     }
@@ -207,13 +191,13 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_project_fwd(TfnasCellD
         auto la = [&](int c, int i, int kl) -> Raw2 {
             const int k = min((cb + c) * 16 + kl, mcp - 4);
             Raw2 r;
-            r.a = ldS4_raw(D, arow[i] + k, d.stor);
+            r.a = ld4(D + (arow[i] + k));
             r.b = ld4(gbase + grow[i] + k * se01);                // no SE: one fixed (ignored) quad
             return r;
         };
         auto xa = [&](Raw2 r, int c, int i, int kl) -> f32x4 {
             const int k = (cb + c) * 16 + kl;
-            f32x4 v = ldS4_fin(r.a, d.stor);
+            f32x4 v = r.a;
             const int kc = min(k, mcp - 4);
             const float2 c0 = cst[kc], c1 = cst[kc + 1], c2 = cst[kc + 2], c3 = cst[kc + 3];
             v.x = act_f<ACT>((v.x - c0.x) * c0.y);
@@ -490,7 +474,7 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_project_dgrad(TfnasCel
         if (!FOLD) {
             emit_tile_rows<NT>(acc, lds, [&](int lrow, int lc, f32x4 v) {
                 const int p = rt * 128 + lrow;
-                if (p < Po && n0 + lc < mcp) stS4_nt(dZ, (size_t)p * M + off + n0 + lc, v, d.stor);
+                if (p < Po && n0 + lc < mcp) st4_nt(dZ + ((size_t)p * M + off + n0 + lc), v);
             });
         } else {
             constexpr int LDC = T::BN + 4;
@@ -508,7 +492,7 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_project_dgrad(TfnasCel
             emit_tile_rows<NT>(acc, lds,
                                [&](int lrow, int lc, f32x4 v) {
                                    const int p = rt * 128 + lrow;
-                                   if (p < Po && n0 + lc < mcp) stS4_nt(dZ, (size_t)p * M + off + n0 + lc, v, d.stor);
+                                   if (p < Po && n0 + lc < mcp) st4_nt(dZ + ((size_t)p * M + off + n0 + lc), v);
                                },
                                [&](int i, const float* st) {        // the wave's slab i (16 rows x BN) is still in LDS
                                    if (d.act == TFNAS_ACT_RELU)
@@ -547,7 +531,7 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_project_dgrad(TfnasCel
     }
 }
 
-// Weight-gradient GEMMs: workgroups per CU the register budget must allow (tools/wg_timeline.py, round 4: the 7-tile variants
+// Weight-gradient GEMMs: workgroups per CU the register budget must allow (per-workgroup timelines, round 4: the 7-tile variants
 // took 260 / 248 registers -> ONE workgroup per CU, a 330-workgroup launch ran as two rounds of 65 us with every SIMD waiting on
 // one wave's loads).  The split count below is sized to exactly these resident slots.
 constexpr int wgrad_lb(int nt) { return nt >= 5 ? 2 : (nt >= 3 ? 3 : 4); }
@@ -566,7 +550,6 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_project_wgrad(TfnasCellDe
                                                        int ntiles_o, float* __restrict__ part, size_t out_size) {
     using T = GT<NT>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    WGT(0)
     const int g = blockIdx.z / ntiles_o, n0 = (blockIdx.z % ntiles_o) * T::BN;
     const int mc = d.g[g].mc, mcp = d.g[g].mcp, off = d.g[g].off;
     const bool has_se = d.g[g].se > 0;
@@ -631,12 +614,12 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_project_wgrad(TfnasCellDe
     auto la = [&](int c, int i, int kl, int m) -> Raw2 {
         const int p = min(r0 + c * 16 + kl, r1 - 1);
         Raw2 r;
-        r.a = ldS4_raw(D, (size_t)p * M + acol, d.stor);
+        r.a = ld4(D + ((size_t)p * M + acol));
         r.b = ld4(gbase + ((size_t)image_of(p) * M + acol) * se01);        // no SE: one fixed (ignored) quad
         return r;
     };
     auto xa = [&](Raw2 r, int c, int i, int kl, int m) -> f32x4 {
-        f32x4 v = ldS4_fin(r.a, d.stor);
+        f32x4 v = r.a;
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = act_f<ACT>((v[j] - c2[j].x) * c2[j].y);
         if (has_se) v *= r.b;
@@ -653,9 +636,7 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_project_wgrad(TfnasCellDe
         const f32x4 v = (k_a3[i] * r.a - k_ab[i]) - (r.b - k_mean[i]) * k_s[i];
         return (bok[i] && r0 + c * 16 + kl < r1) ? v : zero4();
     };
-    WGT(1)
     gemm_mainloop2<NT, false, false, false, TFNAS_WGRAD_PF2>(la, xa, lb, xb, nchunks, acc, lds);
-    WGT(2)
     // The gradient is [oc][mc] (mid channel fastest) and a lane's accumulator quad is 4 consecutive mid channels of one
     // output channel: one 16-byte store per quad (the four lane groups of an output channel then cover 64 contiguous
     // bytes) instead of four 4-byte stores that each scatter a wave over 64 different cache lines.
@@ -677,7 +658,6 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_project_wgrad(TfnasCellDe
             }
         }
     }
-    WGT(3)
 }
 
 // ---------------------------------------------------------------------------- BN1-backward operand
@@ -794,9 +774,6 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_expand_dgrad(TfnasCell
         for (int i = 0; i < 2; ++i) prow[i] = rt * 128 + wrow + 16 * i + lr;
         auto la = [&](int c, int i, int kl) -> f32x4 {
             const int pc = min(prow[i], P - 1), k = min(k0 + kl, klim_a - 4);
-#ifdef TFNAS_HALF_BYTES
-            if (!is_x) return ldS4(dEh, (size_t)pc * ld_a + aoff + k, 0);      // (timing-only build, tfnas_dev.h)
-#endif
             return ld4((is_x ? x : dEh) + (size_t)pc * ld_a + aoff + k);       // wave-uniform select, one unconditional load
         };
         auto xa = [&](f32x4 r, int c, int i, int kl) -> f32x4 {
@@ -1074,8 +1051,8 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_expand_wgrad(TfnasCellDes
             r.b = r.a;
         } else {
             const size_t at = (size_t)p * M + acol;
-            r.a = ldS4_raw(dEh, at, d.stor);
-            r.b = ldS4_raw(E, at, d.stor);
+            r.a = ld4(dEh + at);
+            r.b = ld4(E + at);
         }
         return r;
     };
@@ -1085,7 +1062,7 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_expand_wgrad(TfnasCellDes
             if (aone) v.x = 1.f;
             return (r0 + c * 16 + kl < r1) ? v : zero4();
         }
-        const f32x4 v = (k_r * ldS4_fin(r.a, d.stor) - k_rt1) - (ldS4_fin(r.b, d.stor) - k_mu) * k_s;
+        const f32x4 v = (k_r * r.a - k_rt1) - (r.b - k_mu) * k_s;
         return (chok && r0 + c * 16 + kl < r1) ? v : zero4();
     };
     auto lb = [&](int c, int i, int kl, int n) -> f32x4 {
@@ -1238,7 +1215,7 @@ static inline bool gemm_everywhere(const TfnasCellDesc& d) {
     return (d.gemm_mode & TFNAS_GEMM_EXPLICIT) ? (d.gemm_mode & TFNAS_GEMM_EVERYWHERE) != 0 : g_gemm_everywhere != 0;
 }
 // The data-gradient GEMMs gain little from the bf16 pipe (their K loops are bound by the BN3-backward transform / the chunk ->
-// group bookkeeping and, with one candidate or large images, by bytes): measured per cell at B = 128 (tools/r4_cf.sh), split-bf16
+// group bookkeeping and, with one candidate or large images, by bytes): measured per cell at B = 128, split-bf16
 // vs fp32 MFMA: all-candidate launches of the 14x14 / 7x7 cells 0.94-0.98x, 28x28 up to 1.19x, one-candidate launches 0.9-1.8x.
 // They keep the fp32 loop except where they won.
 static inline int gemm_mode_dgrad(const TfnasCellDesc& d) {
@@ -1534,7 +1511,7 @@ int launch_expand_dgrad_x(const TfnasCellDesc& d, const float* x, const float* c
 }
 
 // Expand weight gradient without reading E (Gram form, k_expand_wgrad<XG>) where E is at least 100 MB (measured alone at
-// B = 128, tools/r5_xg.sh: cell 0 0.33 -> 0.24 ms, cells 1 / 2 equal; from 28 x 28 on E comes from the last-level cache and the
+// B = 128, DESIGN.md section 4d: cell 0 0.33 -> 0.24 ms, cells 1 / 2 equal; from 28 x 28 on E comes from the last-level cache and the
 // extension rows + the fix-up launch cost more than the second stream: cell 10 0.08 -> 0.11 ms); TFNAS_ROUTE_XG_OFF: never,
 // TFNAS_ROUTE_XG_ALL: wherever the shape allows (tests); every choice is compared with the oracle (tests/test_gpu_cell.py)
 static bool expand_wgrad_xg(const TfnasCellDesc& d) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Median time of the two step kinds in SEPARATE loops (w-steps only, then alpha-steps only), so that a timing-only build with
-wrong numerics (TFNAS_LIB=..., e.g. the half-bytes library of tools/r5_halfbytes.sh) cannot feed NaN architecture parameters into
+wrong numerics (TFNAS_LIB=...) cannot feed NaN architecture parameters into
 the sampler of the next w-step.  usage: steps_split.py [B] [iters]   -- runs on the GPU box"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
