@@ -8,14 +8,18 @@ whole job (all ranks), inputs already resident in HBM, optimizer steps / clippin
 
   python bench.py --gpus 1 --steps 10 --warmup 3                  (single GPU)
   python bench.py ... --dump-outputs DIR     also write what the last timed pair computed as DIR/<name>.npy (dump_outputs)
+  python bench.py ... --full                 also run every leg after the timed region (below; --no-* skips one of them)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU, RCCL)
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, dumps if asked and prints the line; what it
+carries besides the headline comes from the warm-up and the timed region themselves (no runs of their own):
   roofline      dominant HIP kernel family of the timed region, timed live with HIP events on the launch
                 stream (tfnas_prof_* hooks), vs its algorithmic flops / HBM bytes (DESIGN.md section 5);
                 roofline.pair = the whole iteration pair against SURVEY.md 8(d)'s algorithmic floor
                 (t_lower_ms, achieved = t_lower / t, hbm_fraction vs F0, mfma_fraction of the 1x1 flops).
-  kernel_roofline  every modelled kernel family of one profiled pair: ms per pair, nearer bound, fraction of it.
+  kernel_roofline  every modelled kernel family of the last (profiled) warm-up pair: ms per pair, nearer bound, fraction of it.
+  dist          (N > 1) backend, ranks, gradient all-reduce calls / bytes per pair of the timed region.
+Only with --full (null, or absent for cpu_baseline, in a plain run):
   retrain       BASELINE configs[4] at its own size: derived-network retrain step at 224x224, 256 images per GPU
                 (retrain_images_per_s; finiteness + bit-determinism checked).
   w_step_ms / a_step_ms   GPU time of the two kinds of step (HIP events on the launch stream, a few pairs after
@@ -24,8 +28,10 @@ Prints ONE JSON line (rank 0).  Extra objects:
                 (train_search.py:370-426: sequential model(x, True, 'gumbel') / model(x, True, 'random') forwards,
                 sampling on the device, torch's clip_grad_norm_ / per-parameter projection loop) -- what a user gets
                 from the two-line import swap of INTEGRATION.md without adopting tfnas_amd.search.
+  width_sweep   BASELINE configs[3]: six supernet widths, a few pairs each.
   cpu_baseline  the CPU oracle (plain PyTorch restatement, proven equal to the reference) timed on this host's
                 cores on a bounded sample of the same loop at the reference's batch 32 (N=1, rank 0 only).
+  dist (N > 1)  + every rank's own w-step / alpha-step times and a hash of every rank's parameters (replicas bit-identical).
 """
 import argparse
 import ctypes as C
@@ -381,6 +387,31 @@ def dump_outputs(out_dir, model, last):
         np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
 
 
+def step_split(args, state, opt_w, opt_a, noise, train, val, dev):
+    """(--full, after the timed region) GPU time of the w-step and the alpha-step (HIP events on the launch stream; the
+    w-step's side streams fork from and join it) over a few more pairs: (w_ms, a_ms)."""
+    from tfnas_amd import search
+    nsplit = max(1, min(10, args.steps))
+    evs = []
+    for i in range(nsplit):
+        j = args.warmup + 1 + args.steps + i
+        bw = (train[(2 * j) % len(train)], train[(2 * j + 1) % len(train)])
+        ba = val[j % len(val)]
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record()
+        search.w_step(state, bw[0][0], bw[0][1], opt_w, 5.0, noise.exp(dev), noise.rand_pos())
+        e[1].record()
+        search.a_step(state, ba[0], ba[1], opt_a, 15.0, 0.1, 5.0, noise.exp(dev))
+        e[2].record()
+        search.w_step(state, bw[1][0], bw[1][1], opt_w, 5.0, noise.exp(dev), noise.rand_pos())
+        e[3].record()
+        evs.append(e)
+    torch.cuda.synchronize()
+    w_ms = sum(e[0].elapsed_time(e[1]) + e[2].elapsed_time(e[3]) for e in evs) / (2 * nsplit)
+    a_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / nsplit
+    return w_ms, a_ms
+
+
 def run_gpu(args):
     from tfnas_amd import Network, load_lat_lookup, geometry, search, _lib
     rank = int(os.environ.get('RANK', '0'))
@@ -468,44 +499,27 @@ def run_gpu(args):
     lib.tfnas_prof_enable(0)
     _require_finite(model, 'the timed region')
 
-    # ---- after the timed region: GPU time of the w-step and the alpha-step (HIP events on the launch stream; the
-    # w-step's side streams fork from and join it) over a few more pairs
-    nsplit = max(1, min(10, args.steps))
-    evs = []
-    for i in range(nsplit):
-        j = args.warmup + 1 + args.steps + i
-        bw = (train[(2 * j) % len(train)], train[(2 * j + 1) % len(train)])
-        ba = val[j % len(val)]
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        e[0].record()
-        search.w_step(state, bw[0][0], bw[0][1], opt_w, 5.0, noise.exp(dev), noise.rand_pos())
-        e[1].record()
-        search.a_step(state, ba[0], ba[1], opt_a, 15.0, 0.1, 5.0, noise.exp(dev))
-        e[2].record()
-        search.w_step(state, bw[1][0], bw[1][1], opt_w, 5.0, noise.exp(dev), noise.rand_pos())
-        e[3].record()
-        evs.append(e)
-    torch.cuda.synchronize()
-    w_ms = sum(e[0].elapsed_time(e[1]) + e[2].elapsed_time(e[3]) for e in evs) / (2 * nsplit)
-    a_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / nsplit
-    # multi-GPU self-evidence (VERDICT r3 item 9): how many ranks the first collective really spanned, and every rank's own
-    # step times (a straggler or a rank on a colliding hardware queue shows up as spread here, not only in the max-over-ranks time)
     dist_info = None
     if dist.is_initialized():
+        # the gradient exchange of this rank inside the timed region: collectives and payload per iteration pair
+        # (two weight steps' sampled-path gradients, ~35 MB each, + the 162 architecture scalars)
+        dist_info = dict(backend=dist.get_backend(), rccl_ranks=dist.get_world_size(),
+                         allreduce_calls_per_pair=round((ar1[0] - ar0[0]) / max(1, args.steps), 2),
+                         allreduce_bytes_per_pair=int((ar1[1] - ar0[1]) / max(1, args.steps)),
+                         gpu_max_hw_queues=os.environ.get('GPU_MAX_HW_QUEUES'))
+    w_ms, a_ms = step_split(args, state, opt_w, opt_a, noise, train, val, dev) if args.full else (None, None)
+    # multi-GPU self-evidence (VERDICT r3 item 9): how many ranks the first collective really spanned, and every rank's own
+    # step times (a straggler or a rank on a colliding hardware queue shows up as spread here, not only in the max-over-ranks time)
+    if dist_info is not None and args.full:
         mine = torch.tensor([w_ms, a_ms, float(rank)], device=dev, dtype=torch.float64)
         allr = [torch.zeros_like(mine) for _ in range(dist.get_world_size())]
         dist.all_gather(allr, mine)
         rows = sorted((int(t[2]), float(t[0]), float(t[1])) for t in allr)
-        dist_info = dict(backend=dist.get_backend(), rccl_ranks=dist.get_world_size(), ranks_seen=[r for r, _, _ in rows],
+        dist_info.update(ranks_seen=[r for r, _, _ in rows],
                          w_step_ms_per_rank=[round(w, 3) for _, w, _ in rows], a_step_ms_per_rank=[round(a, 3) for _, _, a in rows],
                          w_step_ms_spread=round(max(w for _, w, _ in rows) - min(w for _, w, _ in rows), 3),
                          w_step_ms_min_max=[round(min(w for _, w, _ in rows), 3), round(max(w for _, w, _ in rows), 3)],
-                         a_step_ms_min_max=[round(min(a for _, _, a in rows), 3), round(max(a for _, _, a in rows), 3)],
-                         # the gradient exchange of this rank inside the timed region: collectives and payload per iteration pair
-                         # (two weight steps' sampled-path gradients, ~35 MB each, + the 162 architecture scalars)
-                         allreduce_calls_per_pair=round((ar1[0] - ar0[0]) / max(1, args.steps), 2),
-                         allreduce_bytes_per_pair=int((ar1[1] - ar0[1]) / max(1, args.steps)),
-                         gpu_max_hw_queues=os.environ.get('GPU_MAX_HW_QUEUES'))
+                         a_step_ms_min_max=[round(min(a for _, _, a in rows), 3), round(max(a for _, _, a in rows), 3)])
         # replica consistency (tools/dp_check.py's hash): every rank hashes all of its parameters after the
         # timed region; data-parallel replicas must be bit-identical
         import hashlib
@@ -521,7 +535,7 @@ def run_gpu(args):
 
     # ---- the reference-style loop on the drop-in model (world 1 only: it has no gradient all-reduce)
     dropin = None
-    if world == 1 and not args.no_dropin:
+    if world == 1 and args.dropin:
         import random
         random.seed(2)
         model.reset_switches()
@@ -631,7 +645,8 @@ def run_gpu(args):
                                                    6: 'split-bf16 x3 MFMA: every fp32 operand as three bf16 planes, fp32 '
                                                       'accumulation (fp32-accurate products; the oracle tolerance is unchanged)'
                                                    }.get(int(lib.tfnas_gemm_mode()) & 0xff, str(lib.tfnas_gemm_mode()))),
-                      roofline=roof, w_step_ms=round(w_ms, 3), a_step_ms=round(a_ms, 3),
+                      roofline=roof, w_step_ms=None if w_ms is None else round(w_ms, 3),
+                      a_step_ms=None if a_ms is None else round(a_ms, 3),
                       all_images_per_s=round(3.0 * B * world * args.steps / dt, 2),
                       dropin_images_per_s=None if dropin is None else round(dropin, 2), width_sweep=sweep,
                       retrain=retrain, dist=dist_info,
@@ -791,25 +806,39 @@ def dry_rank():
     dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
+    """Command line -> args.  The legs after the timed region (args.dropin / width_sweep / retrain / cpu_baseline, and the
+    step split) run only with --full; each --no-* option turns one of them off there."""
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50, help='timed iteration pairs (SURVEY 8(d): >= 50)')
     ap.add_argument('--warmup', type=int, default=10, help='untimed warm-up pairs (>= 10)')
-    ap.add_argument('--no-dropin', action='store_true', help='skip the reference-style drop-in loop timing')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure w-step / alpha-step times, the drop-in loop, the width sweep, the '
+                         'retrain step and the CPU baseline (and, at N > 1, per-rank times and the replica check)')
+    ap.add_argument('--no-dropin', action='store_true', help='with --full: skip the reference-style drop-in loop timing')
     ap.add_argument('--no-bf16', dest='bf16', action='store_false', help='(accepted and ignored: the bf16-storage mode was removed in round 3)')
     ap.add_argument('--no-width-sweep', dest='width_sweep', action='store_false',
-                    help='skip the BASELINE configs[3] width sweep (6 widths x 6 pairs after the timed region)')
+                    help='with --full: skip the BASELINE configs[3] width sweep (6 widths x 6 pairs after the timed region)')
     ap.add_argument('--no-retrain', dest='retrain', action='store_false',
-                    help='skip the BASELINE configs[4] leg (derived-network retrain step, 256 images at 224x224)')
+                    help='with --full: skip the BASELINE configs[4] leg (derived-network retrain step, 256 images at 224x224)')
     ap.add_argument('--batch', type=int, default=128, help='images per GPU per step-half (BASELINE configs[1]: 128)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle baseline')
     ap.add_argument('--cpu-baseline-only', default=None, help=argparse.SUPPRESS)
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed iteration pair computed as DIR/<name>.npy')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    args.dropin = args.full and not args.no_dropin
+    args.width_sweep = args.full and args.width_sweep
+    args.retrain = args.full and args.retrain
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    return args
+
+
+def main():
+    args = parse_args()
     if args.cpu_baseline_only:
         print(json.dumps(run_cpu_baseline(args.cpu_baseline_only)))
         return
@@ -820,7 +849,7 @@ def main():
         return
     res = run_gpu(args)
     if res is not None:
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.gpus == 1 and args.cpu_baseline:
             res['cpu_baseline'] = cpu_baseline_subprocess()
         _attach_pmc_traffic(res)
         print(json.dumps(res))

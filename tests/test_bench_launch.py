@@ -48,3 +48,20 @@ def test_dist_object_of_the_bench_line_is_self_explanatory():
     for key in ('w_step_ms_per_rank', 'a_step_ms_per_rank', 'w_step_ms_min_max', 'a_step_ms_min_max', 'allreduce_bytes_per_pair',
                 'allreduce_calls_per_pair', 'replicas_bit_identical', 'rccl_ranks'):
         assert key in src, key
+
+
+def test_plain_run_leaves_the_extra_legs_to_full():
+    """A plain run times the steps and prints the line; the legs after the timed region run only with --full, where each
+    --no-* option still turns one of them off."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    legs = ('full', 'dropin', 'width_sweep', 'retrain', 'cpu_baseline')
+    plain = bench.parse_args(['--gpus', '1', '--steps', '3', '--warmup', '1'])
+    assert not any(getattr(plain, k) for k in legs)
+    full = bench.parse_args(['--gpus', '1', '--steps', '3', '--warmup', '1', '--full'])
+    assert all(getattr(full, k) for k in legs)
+    some = bench.parse_args(['--full', '--no-dropin', '--no-width-sweep', '--no-retrain', '--no-cpu-baseline'])
+    assert some.full and not any(getattr(some, k) for k in legs[1:])
+    assert (full.steps, full.warmup, full.dump_outputs) == (plain.steps, plain.warmup, plain.dump_outputs) == (3, 1, None)

@@ -8,7 +8,7 @@ mkdir -p $OUT
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  env $cfg python $REPO/bench.py --steps ${AB_STEPS:-12} --warmup 4 --no-cpu-baseline --no-dropin --no-width-sweep --no-bf16 --no-retrain > $OUT/ab$i.json 2> $OUT/ab$i.err
+  env $cfg python $REPO/bench.py --steps ${AB_STEPS:-12} --warmup 4 --full --no-cpu-baseline --no-dropin --no-width-sweep --no-bf16 --no-retrain > $OUT/ab$i.json 2> $OUT/ab$i.err
   python - <<PY
 import json
 try:
