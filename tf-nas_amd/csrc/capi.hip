@@ -269,7 +269,7 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
 
 extern "C" int tfnas_efree_supported(const TfnasCellDesc* dp) { return (dp && efree_supported(*dp)) ? 1 : 0; }
 extern "C" int tfnas_fx_supported(const TfnasCellDesc* dp) {
-    return (dp && dp->mode == TFNAS_MODE_CELL && !dp->need_wgrad && !efree_ic_small(dp->ic) && fx_supported(*dp)) ? 1 : 0;
+    return (dp && dp->mode == TFNAS_MODE_CELL && !dp->need_wgrad && !efree_ic_ok(dp->ic) && fx_supported(*dp)) ? 1 : 0;
 }
 // what a forward of this descriptor leaves in the saved buffers (tfnas_hip.h): the one decision of cell_fwd_impl that changes
 // their MEANING is the fused per-image route (ehat instead of E); affine / eval BatchNorm launches (tfnas_mbconv_*) never take it
@@ -442,9 +442,10 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
         }
         return 0;
     }
-    // stride-1 ring cells: the depthwise weight gradient comes out of the backward-data pass below (same dd window, same E
-    // elements: no second read of E, dZ and D -- dw_stream.inc, WGR)
-    const bool dw_fused = d.need_wgrad && dw_bwd_fuses_wgrad(d, b.E);
+    // the depthwise backward-data pass below, planned once; on the stride-1 ring cells and the stride-2 register-window cells
+    // it also produces the depthwise weight gradient (same dd window, same E elements: no second read of E, dZ and D)
+    const DwPlan dw_bwd = dw_plan_bwd_data(d, b.E == nullptr, b.x != nullptr);
+    const bool dw_fused = dw_bwd.fuse_wgrad;
     if (d.need_wgrad) {
         // ONE fork for the SE and the depthwise weight gradients (every fork is an event record + a stream wait on the
         // host-bound w-step; cells without SE launch nothing for it)
@@ -457,12 +458,12 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
     // depthwise dgrad + BN1-backward sums; the reduction of its partial rows also fills the cb1 table
     if (bn || stats_sync_on(d)) {
         // (unfused: the reduction that also builds cb1 would use the sums before the affine fix / the cross-rank reduction)
-        TRY(launch_dw_bwd_data(d, b.dZ, gate, dpooled, b.D, stats2, red2, b.E, b.x, stats1, b.dEh, red1, part, s, nullptr, dw_fused));
+        TRY(launch_dw_bwd_data(dw_bwd, d, b.dZ, gate, dpooled, b.D, stats2, red2, b.E, b.x, stats1, b.dEh, red1, part, s));
         TRY(stats_sync(d, red1, 2 * (size_t)d.M, s));
         if (bn) TRY(bn_bwd_fix(d0, bn, 0, red1, s));
         TRY(launch_bn1_consts(d, stats1, red1, cb1, s));
     } else {
-        TRY(launch_dw_bwd_data(d, b.dZ, gate, dpooled, b.D, stats2, red2, b.E, b.x, stats1, b.dEh, red1, part, s, cb1, dw_fused));
+        TRY(launch_dw_bwd_data(dw_bwd, d, b.dZ, gate, dpooled, b.D, stats2, red2, b.E, b.x, stats1, b.dEh, red1, part, s, cb1));
     }
     if (d.need_wgrad) TRY(launch_expand_wgrad(d, b.dEh, b.E, cb1, b.x, part_w2, fork_to(so, 2, s)));
     if (b.dx && d.mode != TFNAS_MODE_STEM) {

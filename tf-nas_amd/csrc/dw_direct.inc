@@ -18,14 +18,7 @@
 // evenly over `nseg` waves, each of which starts R-1 macro-steps early with the FMAs disabled.
 // Partial sums: one row of part[] per workgroup (its 4 waves are 4 consecutive segments), summed by k_reduce_rows.
 
-struct DwDirect {
-    int chunks;      // 32-channel chunks of the groups with this kernel size
-    int ncg;         // column groups per image: ceil(Wo / (4 * JW))
-    int nseg;        // waves per (chunk, column group), a multiple of 4
-    int per;         // macro-steps per wave
-    int steps;       // N * (Ho + A)
-    int nwg;         // chunks * ncg * nseg / 4
-};
+// Geometry: DwDirect (kernels.h).
 
 // the input rows are re-read by the neighbouring column blocks (halo) and by the K x K kernel of the next column group:
 // ordinary (cached) loads for E, non-temporal ones for the once-through dZ / D rows
@@ -762,211 +755,4 @@ __global__ __launch_bounds__(256, dwd_bwd_occ(K, S, JW)) void k_dwd_bwd(
             }
         }
     }
-}
-
-static bool dwd_enabled(const TfnasCellDesc& d) { return dw_variant(d) < 2; }
-// weight gradient, measured: 1.5x on the stride-2 cells, 1.1-2.8x at 14 x 14 / 7 x 7, 0.8-1.1x against the ring kernel at
-// 56 x 56 / 28 x 28 stride 1
-static bool dwd_wgrad_use(const TfnasCellDesc& d) {
-    if (dw_variant(d) == 1) return true;
-    return d.stride == 2 || d.W <= 14 || d.W > 56;
-}
-static int dwd_jw(const TfnasCellDesc& d) {
-    return (d.Wo <= 8 || d.Wo == 56) ? 2 : 4;
-}
-
-// returns the number of partial rows (0: unsupported geometry -> the LDS kernels)
-// kind 0: weight gradient (macro-steps per image Ho + A, row_floats = the weight-gradient row), kind 1: forward (H + P or
-// Ho + 1 macro-steps, rows of 2 * M statistics partials), kind 2: backward w.r.t. the input (Ho + P or Ho + 1 dd-row events).  Returns the number of partial rows (0: unsupported geometry).
-static int dwd_plan(const TfnasCellDesc& d, size_t row_floats, int jw, int lpp, int kind, DwDirect (&gms)[2]) {
-    if (d.stride != 1 && d.stride != 2) return 0;
-    if ((size_t)d.N * d.H * d.W * d.M >= ((size_t)1 << 30)) return 0;                 // 32-bit element offsets
-    for (int g = 0; g < d.G; ++g)
-        if (d.g[g].mc & 1) return 0;
-    // one resident round: 256 CUs x 4 SIMDs x the waves per SIMD the kernel's registers allow (launch bounds); a wave walks at
-    // least `minper` macro-steps (its prologue -- constants from the double statistics -- and the R-1 warm-up steps are paid once)
-    const int wscale = 100, minper_w = 8, minper_f = 8;      // (% of a round; minper_f 16: +10..15 % on the 28 x 28 / 14 x 14 stride-2 cells)
-    const int minper = kind == 0 ? minper_w : (kind == 1 ? minper_f : (d.stride == 1 ? minper_f : minper_f / 2));
-    const int ncg = cdiv(d.Wo, (64 / lpp) * jw);
-    int nseg = 1 << 30;
-    int steps_k[2] = {0, 0};
-    for (int i = 0; i < 2; ++i) {
-        const int kk = 3 + 2 * i;
-        gms[i].chunks = dw_chunks(d, kk, 2 * lpp);
-        if (!gms[i].chunks) continue;
-        int per_img;
-        if (kind == 0) per_img = d.Ho + (d.stride == 1 ? kk / 2 : 1);
-        else if (kind == 1) per_img = d.stride == 1 ? d.H + kk / 2 : d.Ho + 1;
-        else per_img = d.Ho + (d.stride == 1 ? kk / 2 : 1);
-        const int steps = d.N * per_img;
-        steps_k[i] = steps;
-        int occ;
-        if (kind == 0) occ = kk == 3 ? 4 : (jw == 2 ? 3 : 2);
-        else if (kind == 1) occ = kk == 3 ? 4 : (jw == 2 ? 4 : 3);
-        else occ = dwd_bwd_occ(kk, d.stride, jw);
-        const int want = 1024 * occ * wscale / 100;
-        int ns = want / (gms[i].chunks * ncg);
-        if (ns > steps / minper) ns = steps / minper;
-        ns &= ~3;
-        if (ns < 4) ns = 4;
-        if (ns < nseg) nseg = ns;
-    }
-    size_t cap = TFNAS_PART_FLOATS / (row_floats ? row_floats : 1);
-    if (cap > 1024) cap = 1024;
-    while (nseg > 4 && (size_t)ncg * (nseg >> 2) > cap) nseg -= 4;
-    if ((size_t)ncg * (nseg >> 2) > cap) return 0;
-    for (int i = 0; i < 2; ++i) {
-        gms[i].ncg = ncg;
-        gms[i].nseg = nseg;
-        gms[i].steps = steps_k[i];
-        gms[i].per = cdiv(steps_k[i], nseg);
-        gms[i].nwg = gms[i].chunks * ncg * (nseg >> 2);
-    }
-    return ncg * (nseg >> 2);
-}
-
-static int launch_dw_wgrad_direct(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
-                                  const float* D, const double* stats2, const double* red2, const float* E,
-                                  const double* stats1, float* part, size_t out_size, hipStream_t s, bool& done) {
-    done = false;
-    if (!dwd_wgrad_use(d)) return 0;
-    const int jw = dwd_jw(d), lpp = 16;
-    DwDirect gms[2];
-    const int nrows = dwd_plan(d, out_size, jw, lpp, 0, gms);
-    if (!nrows) return 0;
-    for (int i = 0; i < 2; ++i) {
-        if (!gms[i].chunks) continue;
-        const DwDirect gm = gms[i];
-        ProfScope _prof(TK_DW_WGRAD, s);
-        const dim3 grid(gm.nwg);
-#define DWD_WG(K_, S_, A_)                                                                                              \
-    {                                                                                                                   \
-        if (jw == 2)                                                                                                    \
-            hipLaunchKernelGGL((k_dwd_wgrad<K_, S_, A_, 2>), grid, dim3(256), 0, s, d, dZ, gate, dpooled, D, stats2, red2, E, \
-                               stats1, part, out_size, gm);                                                             \
-        else                                                                                                            \
-            hipLaunchKernelGGL((k_dwd_wgrad<K_, S_, A_, 4>), grid, dim3(256), 0, s, d, dZ, gate, dpooled, D, stats2, red2, E, \
-                               stats1, part, out_size, gm);                                                             \
-    }
-        DW_DISPATCH(3 + 2 * i, d.stride, d.act, DWD_WG(K, S, ACT))
-#undef DWD_WG
-    }
-    size_t poff = 0;
-    for (int g = 0; g < d.G; ++g) {
-        const int n = d.g[g].mc * d.g[g].k * d.g[g].k;
-        int rc = launch_reduce_rows(part + poff, nrows, n, out_size, nullptr, d.g[g].g_dw, s);
-        if (rc) return rc;
-        poff += n;
-    }
-    done = true;
-    return (int)hipGetLastError();
-}
-
-// the forward through k_dwd_fwd where measured faster
-// measured (tools/sweep_env.sh, sampled launches at B = 128): against the LDS-tiled kernel of the stride-2 cells 1.4-1.7x
-// at 112 x 112 / 56 x 56 (k5; k3 equal), equal at 28 x 28, slower below (a wave's prologue -- K*K taps and the constants of its
-// two channels -- is paid for a dozen rows); against the ring kernels of the stride-1 cells 0.8-1.0x
-static bool dwd_fwd_use(const TfnasCellDesc& d) {
-    if (dw_variant(d) == 1) return true;
-    return (d.stride == 2 && d.H >= 56) || d.W > 56;          // (W > 56: no ring kernel either -- the stems at 112 x 112)
-}
-static int launch_dw_fwd_direct(const TfnasCellDesc& d, const float* E, const double* stats1, float* D, double* stats2,
-                                float* part, hipStream_t s, bool& done) {
-    done = false;
-    if (!dwd_fwd_use(d)) return 0;
-    const int jw = dwd_jw(d);
-    DwDirect gms[2];
-    const int nrows = dwd_plan(d, 2 * (size_t)d.M, jw, 16, 1, gms);
-    if (!nrows) return 0;
-    for (int i = 0; i < 2; ++i) {
-        if (!gms[i].chunks) continue;
-        const DwDirect gm = gms[i];
-        ProfScope _prof(TK_DW_FWD, s, d.G > 2);
-        const dim3 grid(gm.nwg);
-#define DWD_FW(K_, S_, A_)                                                                                            \
-    {                                                                                                                 \
-        if (jw == 2) hipLaunchKernelGGL((k_dwd_fwd<K_, S_, A_, 2>), grid, dim3(256), 0, s, d, E, stats1, D, part, gm); \
-        else hipLaunchKernelGGL((k_dwd_fwd<K_, S_, A_, 4>), grid, dim3(256), 0, s, d, E, stats1, D, part, gm);         \
-    }
-        DW_DISPATCH(3 + 2 * i, d.stride, d.act, DWD_FW(K, S, ACT))
-#undef DWD_FW
-    }
-    done = true;
-    return launch_reduce_rows(part, nrows, 2 * d.M, 2 * (size_t)d.M, stats2, nullptr, s);
-}
-
-// the backward w.r.t. the input through k_dwd_bwd where measured faster
-// measured: 1.2-1.7x against the LDS-tiled kernel on every stride-2 cell (112 x 112 ... 14 x 14), 0.7-1.1x against the ring
-// kernels of the stride-1 cells
-static bool dwd_bwd_use(const TfnasCellDesc& d) {
-    if (dw_variant(d) == 1) return true;
-    return d.stride == 2 || d.W > 56;
-}
-// TFNAS_ROUTE_DWWG2_OFF: depthwise weight gradient of the stride-2 cells from its own kernel instead of the register-window
-// backward pass (k_dwd_bwd<.., WG>)
-static bool dwd_fuse_wgrad_enabled(const TfnasCellDesc& d) { return !(d.route & TFNAS_ROUTE_DWWG2_OFF); }
-static size_t dwd_wout_size(const TfnasCellDesc& d) {
-    size_t n = 0;
-    for (int g = 0; g < d.G; ++g) n += (size_t)d.g[g].mc * d.g[g].k * d.g[g].k;
-    return n;
-}
-static int dwd_bwd_plan(const TfnasCellDesc& d, bool fuse_wgrad, int& jw, DwDirect (&gms)[2]) {
-    jw = d.stride == 2 ? 2 : dwd_jw(d);                    // (stride 2: a lane owns 2 * JW input columns)
-    return dwd_plan(d, 2 * (size_t)d.M + (fuse_wgrad ? dwd_wout_size(d) + 64 : 0), jw, 16, 2, gms);
-}
-// would launch_dw_bwd_data_direct(..., fuse_wgrad = true) run (and produce g_dw)?
-static bool dwd_bwd_fuses_wgrad(const TfnasCellDesc& d) {
-    if (!dwd_fuse_wgrad_enabled(d) || !d.need_wgrad || !dwd_bwd_use(d) || d.stride != 2) return false;
-    for (int g = 0; g < d.G; ++g)
-        if (d.g[g].k != 3 && d.g[g].k != 5) return false;
-    int jw = 0;
-    DwDirect gms[2];
-    return dwd_bwd_plan(d, true, jw, gms) > 0 && jw == 2;
-}
-static int launch_dw_bwd_data_direct(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
-                                     const float* D, const double* stats2, const double* red2, const float* E,
-                                     const double* stats1, float* dEh, double* red1, float* part, hipStream_t s, float* cb1,
-                                     bool& done, bool fuse_wgrad) {
-    done = false;
-    if (!dwd_bwd_use(d)) return 0;
-    if (fuse_wgrad && !dwd_bwd_fuses_wgrad(d)) return TFNAS_EINVAL;
-    int jw;
-    DwDirect gms[2];
-    const int nrows = dwd_bwd_plan(d, fuse_wgrad, jw, gms);
-    if (!nrows) return 0;
-    const size_t wout_size = dwd_wout_size(d);
-    float* wpart = part + (((size_t)nrows * 2 * d.M + 63) & ~(size_t)63);
-    for (int i = 0; i < 2; ++i) {
-        if (!gms[i].chunks) continue;
-        const DwDirect gm = gms[i];
-        ProfScope _prof(TK_DW_BWD_DATA, s, d.G > 2);
-        const dim3 grid(gm.nwg);
-#define DWD_BW(K_, S_, A_)                                                                                              \
-    {                                                                                                                   \
-        if (fuse_wgrad)        /* (stride 2, JW = 2 only: dwd_bwd_fuses_wgrad) */                                       \
-            hipLaunchKernelGGL((k_dwd_bwd<K_, 2, A_, 2, true>), grid, dim3(256), 0, s, d, dZ, gate, dpooled, D,          \
-                               stats2, red2, E, stats1, dEh, part, gm, wpart, wout_size);                               \
-        else if (jw == 2)                                                                                               \
-            hipLaunchKernelGGL((k_dwd_bwd<K_, S_, A_, 2>), grid, dim3(256), 0, s, d, dZ, gate, dpooled, D, stats2, red2, E, \
-                               stats1, dEh, part, gm);                                                                  \
-        else                                                                                                            \
-            hipLaunchKernelGGL((k_dwd_bwd<K_, S_, A_, 4>), grid, dim3(256), 0, s, d, dZ, gate, dpooled, D, stats2, red2, E, \
-                               stats1, dEh, part, gm);                                                                  \
-    }
-        DW_DISPATCH(3 + 2 * i, d.stride, d.act, DWD_BW(K, S, ACT))
-#undef DWD_BW
-    }
-    done = true;
-    if (fuse_wgrad) {
-        ProfScope _prof(TK_DW_WGRAD, s);
-        size_t poff = 0;
-        for (int g = 0; g < d.G; ++g) {
-            const int n = d.g[g].mc * d.g[g].k * d.g[g].k;
-            int rc = launch_reduce_rows(wpart + poff, nrows, n, wout_size, nullptr, d.g[g].g_dw, s);
-            if (rc) return rc;
-            poff += n;
-        }
-    }
-    if (cb1) return launch_reduce_bn1(d, part, nrows, stats1, red1, cb1, s);
-    return launch_reduce_rows(part, nrows, 2 * d.M, 2 * (size_t)d.M, red1, nullptr, s);
 }

@@ -17,12 +17,7 @@
 // stream is wave-uniform (scalar registers) and a thread only adds its constant row offset; global addresses are 32-bit
 // element offsets from a uniform base (tensors here are < 2^30 elements; checked on the host); accesses are buffer
 // instructions whose hardware range check replaces the branches around out-of-image loads.
-struct DwSlide {
-    int TH, TW;            // rows per block, columns of the band (multiple of 4)
-    int CC, CCP, cq_shift; // channels per workgroup, pixel stride in LDS (floats)
-    int RB, L1;            // ring rows, ring columns (pixels) = TW + K - 1
-    int chunks, gx;        // channel chunks of this launch, image lanes (= partial rows)
-};
+// Geometry: DwSlide (kernels.h).
 
 // LDS ring, pixel swizzle.  A pixel is CC = 32 floats = HALF of the 64-bank row, and the strips of the 16 lanes that one
 // ds_read_b128 lane group serves are 4 pixels apart: with pixels in natural order all four strips of a group start on the same
@@ -769,272 +764,4 @@ __global__ __launch_bounds__(256, (!PIPE && K == 3) ? 4 : 2) void k_dws_wgrad(Tf
             gw[(size_t)(c0 + cl) * (K * K) + u] = sum;
         }
     }
-}
-
-// ---------------------------------------------------------------------------------------------------- host (streaming)
-static bool dws_enabled(const TfnasCellDesc& d) { return dw_variant(d) != 3; }
-
-// geometry of the streaming kernels for images of Hs x Ws pixels (stride 1): false if unsupported
-static bool pick_slide(const TfnasCellDesc& d, int Hs, int Ws, int K, int rings, DwSlide& gm) {
-    const int ws_min = 14;                // (7-wide images: only the weight gradient gained, and the register-window kernel has it)
-    if (d.stride != 1 || Ws > 56 || Ws < ws_min) return false;
-    if ((size_t)d.N * Hs * Ws * d.M >= ((size_t)1 << 30)) return false;     // 32-bit element offsets
-    gm.TW = (Ws + 3) & ~3;
-    gm.L1 = gm.TW + K - 1;
-    gm.CC = 32;
-    gm.CCP = gm.CC;                       // (pixel stride of the LDS ring; the kernels have CC = CCP = 32 compiled in; bank conflicts: ring_swz)
-    gm.cq_shift = 3;
-    const int per_row = (gm.TW >> 2) * (gm.CC >> 2);
-    gm.TH = 256 / per_row;
-    if (gm.TH > 7) gm.TH = 7;
-    while (gm.TH > 1 && (gm.TH * gm.L1 * (gm.CC >> 2) > 1024 ||
-                         (size_t)rings * (gm.TH - 1 + K) * gm.L1 * gm.CCP * sizeof(float) > 46 * 1024))
-        --gm.TH;
-    gm.RB = gm.TH - 1 + K;
-    if (gm.TH < 1 || gm.TH > Hs || gm.TH * gm.L1 * (gm.CC >> 2) > 1024 ||
-        (size_t)rings * gm.RB * gm.L1 * gm.CCP * sizeof(float) > 48 * 1024 || gm.RB * gm.L1 * gm.CCP < 2048)
-        return false;
-    gm.chunks = dw_chunks(d, K, gm.CC);
-    return true;
-}
-
-static int dws_common_gx(const TfnasCellDesc& d, int Hs, int Ws, int rings, size_t row_floats) {
-    int gx = d.N;
-    for (int kk = 3; kk <= 5; kk += 2) {
-        DwSlide gm;
-        if (!pick_slide(d, Hs, Ws, kk, rings, gm)) return 0;
-        if (!gm.chunks) continue;
-        int g1 = cdiv(4096, gm.chunks);
-        if (g1 < 8) g1 = 8;
-        if (g1 < gx) gx = g1;
-    }
-    const size_t cap = TFNAS_PART_FLOATS / (row_floats ? row_floats : 1);
-    if ((size_t)gx > cap) gx = (int)cap;
-    if (gx > d.N) gx = d.N;
-    if (gx >= 8) gx &= ~7;
-    return gx < 1 ? 1 : gx;
-}
-
-// Register-prefetch (PIPE) variants where measured faster: 56-wide images (LDS-limited to 3 workgroups per CU whatever the
-// register count) and the wide soft-mode launches at 28x28; the 4+-wave variants elsewhere (sampled launches, 14x14).
-static bool dws_pipe(const TfnasCellDesc& d) {
-    return d.W > 40 || (d.W > 20 && d.M >= 512);
-}
-
-static bool dws_efree_ring() { return true; }
-
-static bool dws_pipe_wg(const TfnasCellDesc& d) { return dws_pipe(d); }
-
-int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const double* stats1, float* D,
-                  double* stats2, float* part, hipStream_t s) {
-    if (E && dwd_enabled(d)) {                             // register-window kernel (dw_direct.inc) where it is the faster one
-        bool done = false;
-        const int rc = launch_dw_fwd_direct(d, E, stats1, D, stats2, part, s, done);
-        if (rc || done) return rc;
-    }
-    // E == nullptr: E-free; the ring kernels recompute their rows from x for ic = 24 / 40 (TFNAS_EFREE_RING=0: tile kernels)
-    const bool ef = E == nullptr;
-    const bool ring_ok = ef ? (dws_efree_ring() && (d.ic == 24 || d.ic == 40) && x != nullptr) : true;
-    const int gx = (ring_ok && dws_enabled(d)) ? dws_common_gx(d, d.H, d.W, 1, 2 * (size_t)d.M) : 0;
-    if (!gx) return launch_dw_fwd_tiled(d, E, x, stats1, D, stats2, part, s);
-    for (int kk = 3; kk <= 5; kk += 2) {
-        DwSlide gm;
-        pick_slide(d, d.H, d.W, kk, 1, gm);
-        if (!gm.chunks) continue;
-        gm.gx = gx;
-        const size_t shm = (size_t)(gm.RB * gm.L1 * gm.CCP + kk * kk * gm.CC + 2 * gm.CC) * sizeof(float);
-        ProfScope _prof(TK_DW_FWD, s, d.G > 2);
-        const dim3 grid(gx * gm.chunks);
-        if (ef) {
-#define DWS_FWDX(K_, A_)                                                                                               \
-    {                                                                                                                  \
-        if (d.ic == 24)                                                                                                \
-            hipLaunchKernelGGL((k_dws_fwd<K_, A_, false, 6>), grid, dim3(256), shm, s, d, E, stats1, D, part, gm, x); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_dws_fwd<K_, A_, false, 10>), grid, dim3(256), shm, s, d, E, stats1, D, part, gm, x); \
-    }
-            if (kk == 3) {
-                if (d.act == TFNAS_ACT_RELU) DWS_FWDX(3, 0) else DWS_FWDX(3, 1)
-            } else {
-                if (d.act == TFNAS_ACT_RELU) DWS_FWDX(5, 0) else DWS_FWDX(5, 1)
-            }
-#undef DWS_FWDX
-            continue;
-        }
-#define DWS_FWD(K_, A_)                                                                                                \
-    {                                                                                                                  \
-        if (pipe) hipLaunchKernelGGL((k_dws_fwd<K_, A_, true>), grid, dim3(256), shm, s, d, E, stats1, D, part, gm);   \
-        else hipLaunchKernelGGL((k_dws_fwd<K_, A_, false>), grid, dim3(256), shm, s, d, E, stats1, D, part, gm);       \
-    }
-        const bool pipe = dws_pipe(d);
-        if (kk == 3) {
-            if (d.act == TFNAS_ACT_RELU) DWS_FWD(3, 0) else DWS_FWD(3, 1)
-        } else {
-            if (d.act == TFNAS_ACT_RELU) DWS_FWD(5, 0) else DWS_FWD(5, 1)
-        }
-#undef DWS_FWD
-    }
-    return launch_reduce_rows(part, gx, 2 * d.M, 2 * (size_t)d.M, stats2, nullptr, s);
-}
-
-// TFNAS_ROUTE_DWWG_OFF: the depthwise weight gradient of the stride-1 ring cells from its own kernel instead of the
-// backward-data pass (WGR variant of k_dws_bwd)
-static bool dws_fuse_wgrad_enabled(const TfnasCellDesc& d) { return !(d.route & TFNAS_ROUTE_DWWG_OFF); }
-// would launch_dw_bwd_data(..., fuse_wgrad = true) produce the weight gradient too?  (same conditions as its ring path; the
-// partial rows of the weight gradient go behind the statistics partials in `part`)
-bool dw_bwd_fuses_wgrad(const TfnasCellDesc& d, const float* E) {
-    if (d.need_wgrad && E && dwd_enabled(d) && dwd_bwd_use(d)) return dwd_bwd_fuses_wgrad(d);     // register-window pass (stride 2)
-    if (!dws_fuse_wgrad_enabled(d) || !d.need_wgrad || !E || !dws_enabled(d)) return false;
-    // 3 x 3 taps only: 9 more float4 accumulators fit the register budget of two waves per SIMD; 5 x 5 needs 25 (100 registers on
-    // top of 130-170: 900-1100 bytes of scratch per thread at 256 registers -- measured in the ISA, not launched)
-    for (int g = 0; g < d.G; ++g)
-        if (d.g[g].k != 3) return false;
-    // measured alone at B = 128 (DESIGN.md section 4c, one 3 x 3 candidate, whole cell): 56 x 56 1.17 -> 0.94 ms, 28 x 28 0.57 -> 0.51 ms,
-    // 14 x 14 equal (there the separate register-window weight gradient is already cheap and the fused pass runs at two waves per
-    // SIMD instead of four); in the pair the change is inside the noise (69.3-69.7 vs 69.4-69.9 ms)
-    if (d.W < 28) return false;
-    if (dwd_enabled(d) && dwd_bwd_use(d)) return false;
-    const int gx = dws_common_gx(d, d.H, d.W, 1, 2 * (size_t)d.M);
-    if (!gx) return false;
-    size_t out_size = 0;
-    for (int g = 0; g < d.G; ++g) out_size += (size_t)d.g[g].mc * d.g[g].k * d.g[g].k;
-    return (size_t)gx * (2 * (size_t)d.M + 64) + (size_t)gx * out_size <= TFNAS_PART_FLOATS;
-}
-
-int launch_dw_bwd_data(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
-                       const float* D, const double* stats2,
-                       const double* red2, const float* E, const float* x, const double* stats1, float* dEh,
-                       double* red1, float* part, hipStream_t s, float* cb1, bool fuse_wgrad) {
-    if (E && dwd_enabled(d)) {
-        bool done = false;
-        const int rc = launch_dw_bwd_data_direct(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, dEh, red1, part, s, cb1, done,
-                                                 fuse_wgrad);
-        if (rc || done) return rc;
-    }
-    const bool ef = E == nullptr;
-    const bool ring_ok = ef ? (dws_efree_ring() && (d.ic == 24 || d.ic == 40) && x != nullptr) : true;
-    const int gx = (ring_ok && dws_enabled(d)) ? dws_common_gx(d, d.H, d.W, 1, 2 * (size_t)d.M) : 0;
-    if (fuse_wgrad && (!gx || ef)) return TFNAS_EINVAL;           // (the caller asked dw_bwd_fuses_wgrad first)
-    if (!gx) return launch_dw_bwd_data_tiled(d, dZ, gate, dpooled, D, stats2, red2, E, x, stats1, dEh, red1, part, s, cb1);
-    size_t wout_size = 0;
-    for (int g = 0; g < d.G; ++g) wout_size += (size_t)d.g[g].mc * d.g[g].k * d.g[g].k;
-    float* wpart = part + (((size_t)gx * 2 * d.M + 63) & ~(size_t)63);
-    for (int kk = 3; kk <= 5; kk += 2) {
-        DwSlide gm;
-        pick_slide(d, d.H, d.W, kk, 1, gm);
-        if (!gm.chunks) continue;
-        gm.gx = gx;
-        size_t shm = (size_t)(gm.RB * gm.L1 * gm.CCP + kk * kk * gm.CC + 4 * gm.CC + 2 * gm.CC +
-                              (ef ? gm.TH * gm.TW * gm.CCP : 0)) * sizeof(float);
-        if (fuse_wgrad && shm < (size_t)4 * kk * kk * gm.CC * sizeof(float)) shm = (size_t)4 * kk * kk * gm.CC * sizeof(float);
-        ProfScope _prof(TK_DW_BWD_DATA, s, d.G > 2);
-        const dim3 grid(gx * gm.chunks);
-        if (fuse_wgrad) {
-#define DWS_BWDW(K_, A_)                                                                                                  \
-    {                                                                                                                     \
-        /* (the non-prefetching variant only: with the 9 accumulators the prefetching one spills) */                      \
-        hipLaunchKernelGGL((k_dws_bwd<K_, A_, false, 0, true>), grid, dim3(256), shm, s, d, dZ, gate, dpooled, D, stats2, red2, \
-                           E, stats1, dEh, part, gm, nullptr, wpart, wout_size);                                          \
-    }
-            if (kk != 3) return TFNAS_EINVAL;
-            if (d.act == TFNAS_ACT_RELU) DWS_BWDW(3, 0) else DWS_BWDW(3, 1)
-#undef DWS_BWDW
-            continue;
-        }
-        if (ef) {
-#define DWS_BWDX(K_, A_)                                                                                                  \
-    {                                                                                                                     \
-        if (d.ic == 24)                                                                                                   \
-            hipLaunchKernelGGL((k_dws_bwd<K_, A_, false, 6>), grid, dim3(256), shm, s, d, dZ, gate, dpooled, D, stats2, red2, \
-                               E, stats1, dEh, part, gm, x);                                                        \
-        else                                                                                                              \
-            hipLaunchKernelGGL((k_dws_bwd<K_, A_, false, 10>), grid, dim3(256), shm, s, d, dZ, gate, dpooled, D, stats2, red2, \
-                               E, stats1, dEh, part, gm, x);                                                        \
-    }
-            if (kk == 3) {
-                if (d.act == TFNAS_ACT_RELU) DWS_BWDX(3, 0) else DWS_BWDX(3, 1)
-            } else {
-                if (d.act == TFNAS_ACT_RELU) DWS_BWDX(5, 0) else DWS_BWDX(5, 1)
-            }
-#undef DWS_BWDX
-            continue;
-        }
-#define DWS_BWD(K_, A_)                                                                                                   \
-    {                                                                                                                     \
-        if (dws_pipe(d)   )                                                                                            \
-            hipLaunchKernelGGL((k_dws_bwd<K_, A_, true>), grid, dim3(256), shm, s, d, dZ, gate, dpooled, D, stats2, red2, \
-                               E, stats1, dEh, part, gm);                                                           \
-        else                                                                                                              \
-            hipLaunchKernelGGL((k_dws_bwd<K_, A_, false>), grid, dim3(256), shm, s, d, dZ, gate, dpooled, D, stats2, red2, \
-                               E, stats1, dEh, part, gm);                                                           \
-    }
-        if (kk == 3) {
-            if (d.act == TFNAS_ACT_RELU) DWS_BWD(3, 0) else DWS_BWD(3, 1)
-        } else {
-            if (d.act == TFNAS_ACT_RELU) DWS_BWD(5, 0) else DWS_BWD(5, 1)
-        }
-#undef DWS_BWD
-    }
-    if (fuse_wgrad) {
-        ProfScope _prof(TK_DW_WGRAD, s);
-        size_t poff = 0;
-        for (int g = 0; g < d.G; ++g) {
-            const int n = d.g[g].mc * d.g[g].k * d.g[g].k;
-            int rc = launch_reduce_rows(wpart + poff, gx, n, wout_size, nullptr, d.g[g].g_dw, s);
-            if (rc) return rc;
-            poff += n;
-        }
-    }
-    if (cb1) return launch_reduce_bn1(d, part, gx, stats1, red1, cb1, s);
-    return launch_reduce_rows(part, gx, 2 * d.M, 2 * (size_t)d.M, red1, nullptr, s);
-}
-
-int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
-                    const double* stats2,
-                    const double* red2, const float* E, const double* stats1, float* part, hipStream_t s) {
-    size_t out_size = 0;
-    for (int g = 0; g < d.G; ++g) out_size += (size_t)d.g[g].mc * d.g[g].k * d.g[g].k;
-    if (dwd_enabled(d)) {                                  // register-window kernels (dw_direct.inc)
-        bool done = false;
-        const int rc = launch_dw_wgrad_direct(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, s, done);
-        if (rc || done) return rc;
-    }
-    const int gx = dws_enabled(d) ? dws_common_gx(d, d.H, d.W, 1, out_size) : 0;
-    if (!gx) return launch_dw_wgrad_tiled(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, s);
-    for (int kk = 3; kk <= 5; kk += 2) {
-        DwSlide gm;
-        pick_slide(d, d.H, d.W, kk, 1, gm);
-        if (!gm.chunks) continue;
-        gm.gx = gx;
-        int ringf = gm.RB * gm.L1 * gm.CCP;
-        if (ringf < 4 * kk * kk * gm.CC) ringf = 4 * kk * kk * gm.CC;   // cross-wave reduction reuses the ring
-        const size_t shm = (size_t)(gm.RB * gm.L1 * gm.CCP + 4 * gm.CC + 2 * gm.CC) * sizeof(float) +
-                           (size_t)(ringf - gm.RB * gm.L1 * gm.CCP) * sizeof(float);
-        ProfScope _prof(TK_DW_WGRAD, s);
-        const dim3 grid(gx * gm.chunks);
-#define DWS_WG(K_, A_)                                                                                                  \
-    {                                                                                                                   \
-        if (pipe)                                                                                                       \
-            hipLaunchKernelGGL((k_dws_wgrad<K_, A_, true>), grid, dim3(256), shm, s, d, dZ, gate, dpooled, D, stats2,   \
-                               red2, E, stats1, part, out_size, gm);                                                    \
-        else                                                                                                            \
-            hipLaunchKernelGGL((k_dws_wgrad<K_, A_, false>), grid, dim3(256), shm, s, d, dZ, gate, dpooled, D, stats2,  \
-                               red2, E, stats1, part, out_size, gm);                                                    \
-    }
-        const bool pipe = dws_pipe_wg(d);
-        if (kk == 3) {
-            if (d.act == TFNAS_ACT_RELU) DWS_WG(3, 0) else DWS_WG(3, 1)
-        } else {
-            if (d.act == TFNAS_ACT_RELU) DWS_WG(5, 0) else DWS_WG(5, 1)
-        }
-#undef DWS_WG
-    }
-    size_t poff = 0;
-    for (int g = 0; g < d.G; ++g) {
-        const int n = d.g[g].mc * d.g[g].k * d.g[g].k;
-        int rc = launch_reduce_rows(part + poff, gx, n, out_size, nullptr, d.g[g].g_dw, s);
-        if (rc) return rc;
-        poff += n;
-    }
-    return (int)hipGetLastError();
 }

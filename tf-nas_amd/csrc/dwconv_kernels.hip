@@ -13,18 +13,11 @@
 // LDS access is one ds_read_b128 of 4 channels and the k-wide sliding window lives in registers.  Tile loads
 // are issued 4 at a time per thread before any of them is consumed (memory-level parallelism).
 #include <cstring>
+#include <type_traits>
 #include "tfnas_dev.h"
 #include "kernels.h"
 #include "prof.h"
 #include "efree.h"
-
-struct DwGeom {
-    int T0, T1;        // tile height / width (in outputs for fwd & wgrad, in inputs for bwd-data)
-    int CC;            // channels per workgroup (16/32/64)
-    int cq_shift;      // log2(CC/4)
-    int tilesH, tilesW, ntiles;   // ntiles = N * tilesH * tilesW
-    int L0, L1;        // LDS tile extent (rows, cols)
-};
 
 __device__ __forceinline__ int floordiv(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
@@ -587,9 +580,44 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
     }
 }
 
+#include "dw_stream.inc"
+#include "dw_direct.inc"
+
 // ============================================================================ host side
+// One planner per pass (dw_plan_fwd, dw_plan_bwd_data, dw_plan_wgrad) picks the kernel family and computes its geometry; the
+// launchers below only carry the plan out.  Families in order of preference, each one falling through to the next:
+//   1. register-window kernels (dw_direct.inc) where the measured policy dwd_*_use picks them and dwd_plan finds a grid;
+//   2. LDS ring kernels (dw_stream.inc) unless the route asks for tiles, where the ring fits (stride 1); E-free only for
+//      ic 24 / 40 (dws_efree_ic);
+//   3. LDS tile kernels (above).
+// TfnasCellDesc.route, TFNAS_ROUTE_DW_*: 0 per launch, whichever kernel measured faster | 1 register-window kernels wherever the
+// geometry allows | 2 ring / tile kernels only | 3 tile kernels only: every choice is compared with the oracle
+// (tests/test_gpu_cell.py::test_variant_against_oracle)
+
+static int dw_chunks(const TfnasCellDesc& d, int K, int CC) {
+    int t = 0;
+    for (int g = 0; g < d.G; ++g)
+        if (d.g[g].k == K) t += cdiv(d.g[g].mcp, CC);
+    return t;
+}
+
+// floats of one weight-gradient partial row: the groups' mc x K x K blocks in group order
+static size_t dw_wout_size(const TfnasCellDesc& d) {
+    size_t n = 0;
+    for (int g = 0; g < d.G; ++g) n += (size_t)d.g[g].mc * d.g[g].k * d.g[g].k;
+    return n;
+}
+
+// every group has kernel size 3 (or 5 where k5 is set)
+static bool dw_groups_k(const TfnasCellDesc& d, bool k5) {
+    for (int g = 0; g < d.G; ++g)
+        if (d.g[g].k != 3 && !(k5 && d.g[g].k == 5)) return false;
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------- tile kernels
 // force32: the E-free producer (efree.h) works on 32-channel chunks
-static void pick_tile(int N, int Th, int Tw, int K, int S, bool fwd_like, DwGeom& gm, bool force32 = false) {
+static void pick_tile(int N, int Th, int Tw, int K, int S, bool fwd_like, DwGeom& gm, bool force32) {
     // T1 (width) multiple of 4 (strips), up to 16; T0 so that a tile has ~128 (64 for stride 2) pixels
     gm.T1 = Tw >= 16 ? 16 : ((Tw + 3) / 4) * 4;
     const int target = (S == 2 && fwd_like) ? 64 : 128;
@@ -615,155 +643,394 @@ static void pick_tile(int N, int Th, int Tw, int K, int S, bool fwd_like, DwGeom
     gm.cq_shift = gm.CC == 16 ? 2 : gm.CC == 32 ? 3 : 4;
 }
 
-static int dw_chunks(const TfnasCellDesc& d, int K, int CC) {
-    int t = 0;
-    for (int g = 0; g < d.G; ++g)
-        if (d.g[g].k == K) t += cdiv(d.g[g].mcp, CC);
-    return t;
-}
-
 static int dw_grid_x(const DwGeom& gm, int chunks, int target_blocks) {
     int gx = cdiv(target_blocks, chunks);
     if (gx > gm.ntiles) gx = gm.ntiles;
     return gx < 1 ? 1 : gx;
 }
 
-#define KQ_DISPATCH(kq, ...)                                      \
-    switch (kq) {                                                 \
-        case 0: { constexpr int KQ = 0; __VA_ARGS__; } break;     \
-        case 4: { constexpr int KQ = 4; __VA_ARGS__; } break;     \
-        case 6: { constexpr int KQ = 6; __VA_ARGS__; } break;     \
-        case 10: { constexpr int KQ = 10; __VA_ARGS__; } break;   \
-        default: return TFNAS_EINVAL;                             \
-    }
-#define DW_DISPATCH(K_, S_, ACT_, ...)                                                         \
-    if ((K_) == 3 && (S_) == 1 && (ACT_) == 0) { constexpr int K = 3, S = 1, ACT = 0; __VA_ARGS__; } \
-    else if ((K_) == 3 && (S_) == 1) { constexpr int K = 3, S = 1, ACT = 1; __VA_ARGS__; }     \
-    else if ((K_) == 3 && (S_) == 2 && (ACT_) == 0) { constexpr int K = 3, S = 2, ACT = 0; __VA_ARGS__; } \
-    else if ((K_) == 3 && (S_) == 2) { constexpr int K = 3, S = 2, ACT = 1; __VA_ARGS__; }     \
-    else if ((K_) == 5 && (S_) == 1 && (ACT_) == 0) { constexpr int K = 5, S = 1, ACT = 0; __VA_ARGS__; } \
-    else if ((K_) == 5 && (S_) == 1) { constexpr int K = 5, S = 1, ACT = 1; __VA_ARGS__; }     \
-    else if ((K_) == 5 && (S_) == 2 && (ACT_) == 0) { constexpr int K = 5, S = 2, ACT = 0; __VA_ARGS__; } \
-    else { constexpr int K = 5, S = 2, ACT = 1; __VA_ARGS__; }
-
-// Both kernel-size passes of one stage share grid.x so that they fill the same rows of the partials matrix.
-static int dw_common_gx(const TfnasCellDesc& d, int Th, int Tw, bool fwd_like, int target_blocks, size_t row_floats,
-                        bool force32 = false) {
+// Tiles of Th x Tw (outputs for fwd_like, inputs otherwise).  Both kernel-size launches of one pass share grid.x so that they
+// fill the same rows of the partials matrix.
+static void dw_tile_plan(const TfnasCellDesc& d, int Th, int Tw, bool fwd_like, int target_blocks, size_t row_floats,
+                         bool force32, DwPlan& p) {
     int gx = 1 << 30;
-    for (int kk = 3; kk <= 5; kk += 2) {
-        DwGeom gm;
-        pick_tile(d.N, Th, Tw, kk, d.stride, fwd_like, gm, force32);
-        const int chunks = dw_chunks(d, kk, gm.CC);
-        if (!chunks) continue;
-        const int g1 = dw_grid_x(gm, chunks, target_blocks);
+    for (int i = 0; i < 2; ++i) {
+        pick_tile(d.N, Th, Tw, 3 + 2 * i, d.stride, fwd_like, p.tile[i], force32);
+        p.chunks[i] = dw_chunks(d, 3 + 2 * i, p.tile[i].CC);
+        if (!p.chunks[i]) continue;
+        const int g1 = dw_grid_x(p.tile[i], p.chunks[i], target_blocks);
         if (g1 < gx) gx = g1;
     }
     const size_t cap = TFNAS_PART_FLOATS / (row_floats ? row_floats : 1);
     if ((size_t)gx > cap) gx = (int)cap;
     if (gx > 1024) gx = 1024;                      // partial rows to reduce afterwards
     if (gx >= 8) gx &= ~7;                         // multiple of 8 for the XCD-aware tile order
-    return gx < 1 ? 1 : gx;
+    p.fam = DW_TILE;
+    p.rows = gx < 1 ? 1 : gx;
 }
 
-// E == nullptr: E-free mode (the tile is recomputed from x, efree.h)
-static int launch_dw_fwd_tiled(const TfnasCellDesc& d, const float* E, const float* x, const double* stats1, float* D,
-                               double* stats2, float* part, hipStream_t s) {
-    const bool ef = E == nullptr;
-    if (ef && !efree_ic_ok(d.ic)) return TFNAS_EINVAL;
-    const int kq = ef ? d.ic / 4 : 0;
-    const int gx = dw_common_gx(d, d.Ho, d.Wo, true, 4096, 2 * (size_t)d.M, ef);
-    for (int kk = 3; kk <= 5; kk += 2) {
-        DwGeom gm;
-        pick_tile(d.N, d.Ho, d.Wo, kk, d.stride, true, gm, ef);
-        const int chunks = dw_chunks(d, kk, gm.CC);
-        if (!chunks) continue;
-        const int tile = gm.L0 * gm.L1 * gm.CC > 2048 ? gm.L0 * gm.L1 * gm.CC : 2048;
-        const size_t shm = (size_t)(tile + kk * kk * gm.CC + 2 * gm.CC) * sizeof(float);
-        dim3 grid(gx, chunks);
-        ProfScope _prof(TK_DW_FWD, s, d.G > 2);
-        if ((size_t)shm > 64 * 1024) return TFNAS_ERANGE;
-        DW_DISPATCH(kk, d.stride, d.act, KQ_DISPATCH(kq, {
-            hipLaunchKernelGGL((k_dw_fwd<K, S, ACT, KQ>), grid, dim3(256), shm, s, d, E, x, stats1, D, part, gm);
-        }))
-    }
-    return launch_reduce_rows(part, gx, 2 * d.M, 2 * (size_t)d.M, stats2, nullptr, s);
+// ---------------------------------------------------------------------------------------------------- ring kernels
+// geometry of the ring kernels for d.H x d.W images (stride 1): false if unsupported
+static bool pick_slide(const TfnasCellDesc& d, int K, DwSlide& gm) {
+    const int ws_min = 14;                // (7-wide images: only the weight gradient gained, and the register-window kernel has it)
+    if (d.stride != 1 || d.W > 56 || d.W < ws_min) return false;
+    if ((size_t)d.N * d.H * d.W * d.M >= ((size_t)1 << 30)) return false;     // 32-bit element offsets
+    gm.TW = (d.W + 3) & ~3;
+    gm.L1 = gm.TW + K - 1;
+    gm.CC = 32;
+    gm.CCP = gm.CC;                       // (pixel stride of the LDS ring; the kernels have CC = CCP = 32 compiled in; bank conflicts: ring_swz)
+    gm.cq_shift = 3;
+    const int per_row = (gm.TW >> 2) * (gm.CC >> 2);
+    gm.TH = 256 / per_row;
+    if (gm.TH > 7) gm.TH = 7;
+    while (gm.TH > 1 && (gm.TH * gm.L1 * (gm.CC >> 2) > 1024 ||
+                         (size_t)(gm.TH - 1 + K) * gm.L1 * gm.CCP * sizeof(float) > 46 * 1024))
+        --gm.TH;
+    gm.RB = gm.TH - 1 + K;
+    if (gm.TH < 1 || gm.TH > d.H || gm.TH * gm.L1 * (gm.CC >> 2) > 1024 ||
+        (size_t)gm.RB * gm.L1 * gm.CCP * sizeof(float) > 48 * 1024 || gm.RB * gm.L1 * gm.CCP < 2048)
+        return false;
+    gm.chunks = dw_chunks(d, K, gm.CC);
+    return true;
 }
 
-static int launch_dw_bwd_data_tiled(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
-                       const float* D, const double* stats2,
-                       const double* red2, const float* E, const float* x, const double* stats1, float* dEh, double* red1,
-                       float* part, hipStream_t s, float* cb1) {
-    const bool ef = E == nullptr;
-    if (ef && !efree_ic_ok(d.ic)) return TFNAS_EINVAL;
-    const int kq = ef ? d.ic / 4 : 0;
-    const int gx = dw_common_gx(d, d.H, d.W, false, 4096, 2 * (size_t)d.M, ef);
-    for (int kk = 3; kk <= 5; kk += 2) {
-        DwGeom gm;
-        pick_tile(d.N, d.H, d.W, kk, d.stride, false, gm, ef);
-        const int chunks = dw_chunks(d, kk, gm.CC);
-        if (!chunks) continue;
-        const int tile = gm.L0 * gm.L1 * gm.CC > 2048 ? gm.L0 * gm.L1 * gm.CC : 2048;
-        const size_t shm = (size_t)(tile + kk * kk * gm.CC + 4 * gm.CC + 2 * gm.CC + (ef ? gm.T0 * gm.T1 * gm.CC : 0)) *
-                           sizeof(float);
-        if ((size_t)shm > 64 * 1024) return TFNAS_ERANGE;
-        dim3 grid(gx, chunks);
-        ProfScope _prof(TK_DW_BWD_DATA, s, d.G > 2);
-        DW_DISPATCH(kk, d.stride, d.act, KQ_DISPATCH(kq, {
-            hipLaunchKernelGGL((k_dw_bwd_data<K, S, ACT, KQ>), grid, dim3(256), shm, s, d, dZ, gate, dpooled, D, stats2,
-                               red2, E, x, stats1, dEh, part, gm);
-        }))
+// the ring kernels for both kernel sizes, one image lane (= partial row) count: false if the route or a geometry rules them out
+static bool dws_plan(const TfnasCellDesc& d, size_t row_floats, DwPlan& p) {
+    if (route_dw(d) == 3) return false;
+    int gx = d.N;
+    for (int i = 0; i < 2; ++i) {
+        if (!pick_slide(d, 3 + 2 * i, p.ring[i])) return false;
+        p.chunks[i] = p.ring[i].chunks;
+        if (!p.chunks[i]) continue;
+        int g1 = cdiv(4096, p.chunks[i]);
+        if (g1 < 8) g1 = 8;
+        if (g1 < gx) gx = g1;
     }
-    if (cb1) return launch_reduce_bn1(d, part, gx, stats1, red1, cb1, s);
-    return launch_reduce_rows(part, gx, 2 * d.M, 2 * (size_t)d.M, red1, nullptr, s);
+    const size_t cap = TFNAS_PART_FLOATS / (row_floats ? row_floats : 1);
+    if ((size_t)gx > cap) gx = (int)cap;
+    if (gx > d.N) gx = d.N;
+    if (gx >= 8) gx &= ~7;
+    p.fam = DW_RING;
+    p.rows = gx < 1 ? 1 : gx;
+    p.ring[0].gx = p.ring[1].gx = p.rows;
+    return true;
 }
 
-static int launch_dw_wgrad_tiled(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
-                    const double* stats2,
-                    const double* red2, const float* E, const double* stats1, float* part, hipStream_t s) {
-    size_t out_size = 0;
-    for (int g = 0; g < d.G; ++g) out_size += (size_t)d.g[g].mc * d.g[g].k * d.g[g].k;
-    const int gx = dw_common_gx(d, d.Ho, d.Wo, true, 2048, out_size);
-    for (int kk = 3; kk <= 5; kk += 2) {
-        DwGeom gm;
-        pick_tile(d.N, d.Ho, d.Wo, kk, d.stride, true, gm);
-        const int chunks = dw_chunks(d, kk, gm.CC);
-        if (!chunks) continue;
-        int tile = gm.L0 * gm.L1 * gm.CC;
-        if (tile < 4 * kk * kk * gm.CC) tile = 4 * kk * kk * gm.CC;
-        const size_t shm = (size_t)(tile + 4 * gm.CC + 2 * gm.CC) * sizeof(float);
-        dim3 grid(gx, chunks);
-        ProfScope _prof(TK_DW_WGRAD, s);
-        DW_DISPATCH(kk, d.stride, d.act, {
-            hipLaunchKernelGGL((k_dw_wgrad<K, S, ACT>), grid, dim3(256), shm, s, d, dZ, gate, dpooled, D, stats2, red2, E, stats1,
-                               part, out_size, gm);
-        })
+// The E-free ring kernels (rows recomputed from x, KQ = ic / 4) are compiled for these ic only.
+static bool dws_efree_ic(int ic) { return ic == 24 || ic == 40; }
+
+// Register-prefetch (PIPE) variants where measured faster: 56-wide images (LDS-limited to 3 workgroups per CU whatever the
+// register count) and the wide soft-mode launches at 28x28; the 4+-wave variants elsewhere (sampled launches, 14x14).
+static bool dws_pipe(const TfnasCellDesc& d) {
+    return d.W > 40 || (d.W > 20 && d.M >= 512);
+}
+
+// ---------------------------------------------------------------------------------------------------- register-window kernels
+// weight gradient, measured: 1.5x on the stride-2 cells, 1.1-2.8x at 14 x 14 / 7 x 7, 0.8-1.1x against the ring kernel at
+// 56 x 56 / 28 x 28 stride 1
+static bool dwd_wgrad_use(const TfnasCellDesc& d) {
+    const int r = route_dw(d);
+    return r == 1 || (r == 0 && (d.stride == 2 || d.W <= 14 || d.W > 56));
+}
+// forward, measured (sampled launches at B = 128): against the LDS-tiled kernel of the stride-2 cells 1.4-1.7x at 112 x 112 /
+// 56 x 56 (k5; k3 equal), equal at 28 x 28, slower below (a wave's prologue -- K*K taps and the constants of its two channels --
+// is paid for a dozen rows); against the ring kernels of the stride-1 cells 0.8-1.0x
+static bool dwd_fwd_use(const TfnasCellDesc& d) {
+    const int r = route_dw(d);
+    return r == 1 || (r == 0 && ((d.stride == 2 && d.H >= 56) || d.W > 56));   // (W > 56: no ring kernel either -- the stems)
+}
+// backward w.r.t. the input, measured: 1.2-1.7x against the LDS-tiled kernel on every stride-2 cell (112 x 112 ... 14 x 14),
+// 0.7-1.1x against the ring kernels of the stride-1 cells
+static bool dwd_bwd_use(const TfnasCellDesc& d) {
+    const int r = route_dw(d);
+    return r == 1 || (r == 0 && (d.stride == 2 || d.W > 56));
+}
+static int dwd_jw(const TfnasCellDesc& d) {
+    return (d.Wo <= 8 || d.Wo == 56) ? 2 : 4;
+}
+
+// kind 0: weight gradient (macro-steps per image Ho + A, row_floats = the weight-gradient row), kind 1: forward (H + P or
+// Ho + 1 macro-steps, rows of 2 * M statistics partials), kind 2: backward w.r.t. the input (Ho + P or Ho + 1 dd-row events).
+// False: unsupported geometry (p is then planned again by the next family).
+static bool dwd_plan(const TfnasCellDesc& d, size_t row_floats, int jw, int kind, DwPlan& p) {
+    constexpr int lpp = 16;                                  // lanes per pixel of the k_dwd_* kernels (2 channels each)
+    if (d.stride != 1 && d.stride != 2) return false;
+    if ((size_t)d.N * d.H * d.W * d.M >= ((size_t)1 << 30)) return false;                 // 32-bit element offsets
+    for (int g = 0; g < d.G; ++g)
+        if (d.g[g].mc & 1) return false;
+    // one resident round: 256 CUs x 4 SIMDs x the waves per SIMD the kernel's registers allow (launch bounds); a wave walks at
+    // least `minper` macro-steps (its prologue -- constants from the double statistics -- and the R-1 warm-up steps are paid once)
+    const int wscale = 100, minper_w = 8, minper_f = 8;      // (% of a round; minper_f 16: +10..15 % on the 28 x 28 / 14 x 14 stride-2 cells)
+    const int minper = kind == 0 ? minper_w : (kind == 1 ? minper_f : (d.stride == 1 ? minper_f : minper_f / 2));
+    const int ncg = cdiv(d.Wo, (64 / lpp) * jw);
+    DwDirect* gms = p.direct;
+    int nseg = 1 << 30;
+    int steps_k[2] = {0, 0};
+    for (int i = 0; i < 2; ++i) {
+        const int kk = 3 + 2 * i;
+        gms[i].chunks = dw_chunks(d, kk, 2 * lpp);
+        if (!gms[i].chunks) continue;
+        int per_img;
+        if (kind == 0) per_img = d.Ho + (d.stride == 1 ? kk / 2 : 1);
+        else if (kind == 1) per_img = d.stride == 1 ? d.H + kk / 2 : d.Ho + 1;
+        else per_img = d.Ho + (d.stride == 1 ? kk / 2 : 1);
+        const int steps = d.N * per_img;
+        steps_k[i] = steps;
+        int occ;
+        if (kind == 0) occ = kk == 3 ? 4 : (jw == 2 ? 3 : 2);
+        else if (kind == 1) occ = kk == 3 ? 4 : (jw == 2 ? 4 : 3);
+        else occ = dwd_bwd_occ(kk, d.stride, jw);
+        const int want = 1024 * occ * wscale / 100;
+        int ns = want / (gms[i].chunks * ncg);
+        if (ns > steps / minper) ns = steps / minper;
+        ns &= ~3;
+        if (ns < 4) ns = 4;
+        if (ns < nseg) nseg = ns;
     }
+    size_t cap = TFNAS_PART_FLOATS / (row_floats ? row_floats : 1);
+    if (cap > 1024) cap = 1024;
+    while (nseg > 4 && (size_t)ncg * (nseg >> 2) > cap) nseg -= 4;
+    if ((size_t)ncg * (nseg >> 2) > cap) return false;
+    for (int i = 0; i < 2; ++i) {
+        gms[i].ncg = ncg;
+        gms[i].nseg = nseg;
+        gms[i].steps = steps_k[i];
+        gms[i].per = cdiv(steps_k[i], nseg);
+        gms[i].nwg = gms[i].chunks * ncg * (nseg >> 2);
+        p.chunks[i] = gms[i].chunks;
+    }
+    p.fam = DW_DIRECT;
+    p.rows = ncg * (nseg >> 2);
+    p.jw = jw;
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------- planners
+static DwPlan dw_plan_fwd(const TfnasCellDesc& d, bool efree, bool has_x) {
+    DwPlan p = {};
+    const size_t row = 2 * (size_t)d.M;
+    if (!efree && dwd_fwd_use(d) && dwd_plan(d, row, dwd_jw(d), 1, p)) return p;
+    p.kq = efree ? d.ic / 4 : 0;
+    if ((!efree || (dws_efree_ic(d.ic) && has_x)) && dws_plan(d, row, p)) {
+        p.pipe = !efree && dws_pipe(d);
+        return p;
+    }
+    dw_tile_plan(d, d.Ho, d.Wo, true, 4096, row, efree, p);
+    return p;
+}
+
+DwPlan dw_plan_bwd_data(const TfnasCellDesc& d, bool efree, bool has_x) {
+    DwPlan p = {};
+    const size_t row = 2 * (size_t)d.M, wout = dw_wout_size(d);
+    const bool direct = !efree && dwd_bwd_use(d);
+    if (direct) {
+        const int jw = d.stride == 2 ? 2 : dwd_jw(d);          // (stride 2: a lane owns 2 * JW input columns)
+        // the weight gradient of the stride-2 cells from this pass (k_dwd_bwd<.., WG>; its partial rows go behind the statistics
+        // partials) unless TFNAS_ROUTE_DWWG2_OFF asks for its own kernel
+        p.fuse_wgrad = d.need_wgrad && !(d.route & TFNAS_ROUTE_DWWG2_OFF) && d.stride == 2 && dw_groups_k(d, true) &&
+                       dwd_plan(d, row + wout + 64, jw, 2, p);
+        if (p.fuse_wgrad || dwd_plan(d, row, jw, 2, p)) return p;
+        // (a geometry the register-window pass refuses takes the ring / tile kernels without fusing the weight gradient)
+    }
+    p.kq = efree ? d.ic / 4 : 0;
+    if ((!efree || (dws_efree_ic(d.ic) && has_x)) && dws_plan(d, row, p)) {
+        // The 3 x 3 weight gradient of the stride-1 ring cells from this pass (WGR variant of k_dws_bwd) unless
+        // TFNAS_ROUTE_DWWG_OFF asks for its own kernel.  3 x 3 taps only: 9 more float4 accumulators fit the register budget of
+        // two waves per SIMD; 5 x 5 needs 25 (100 registers on top of 130-170: 900-1100 bytes of scratch per thread at 256
+        // registers -- measured in the ISA, not launched).  Images >= 28 wide: measured alone at B = 128 (DESIGN.md section 4c,
+        // one 3 x 3 candidate, whole cell): 56 x 56 1.17 -> 0.94 ms, 28 x 28 0.57 -> 0.51 ms, 14 x 14 equal (there the separate
+        // register-window weight gradient is already cheap and the fused pass runs at two waves per SIMD instead of four); in
+        // the pair the change is inside the noise (69.3-69.7 vs 69.4-69.9 ms)
+        p.fuse_wgrad = !direct && !efree && d.need_wgrad && !(d.route & TFNAS_ROUTE_DWWG_OFF) && dw_groups_k(d, false) &&
+                       d.W >= 28 && (size_t)p.rows * (row + 64 + wout) <= TFNAS_PART_FLOATS;
+        p.pipe = !efree && !p.fuse_wgrad && dws_pipe(d);
+        return p;
+    }
+    dw_tile_plan(d, d.H, d.W, false, 4096, row, efree, p);
+    return p;
+}
+
+static DwPlan dw_plan_wgrad(const TfnasCellDesc& d) {
+    DwPlan p = {};
+    const size_t wout = dw_wout_size(d);
+    if (dwd_wgrad_use(d) && dwd_plan(d, wout, dwd_jw(d), 0, p)) return p;
+    if (dws_plan(d, wout, p)) {
+        p.pipe = dws_pipe(d);
+        return p;
+    }
+    dw_tile_plan(d, d.Ho, d.Wo, true, 2048, wout, false, p);
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------------- launchers
+// Template arguments of a launch from its runtime kernel size (3 | 5), stride (1 | 2), activation (ReLU -> 0, swish -> 1)
+// and variant (one of Vs): calls f(K, S, ACT, V) with std::integral_constant arguments.  False if the variant is not one of Vs.
+// (Every combination is instantiated: a kernel without a stride or variant parameter ignores that argument.)
+template <int... Vs, class F>
+static bool dw_dispatch(int k, int stride, int act, int v, F&& f) {
+    bool hit = false;
+    auto with_v = [&](auto K, auto S, auto A) {
+        ((v == Vs ? (f(K, S, A, std::integral_constant<int, Vs>{}), hit = true) : false) || ...);
+    };
+    auto with_a = [&](auto K, auto S) {
+        if (act == TFNAS_ACT_RELU) with_v(K, S, std::integral_constant<int, 0>{});
+        else with_v(K, S, std::integral_constant<int, 1>{});
+    };
+    auto with_s = [&](auto K) {
+        if (stride == 1) with_a(K, std::integral_constant<int, 1>{});
+        else with_a(K, std::integral_constant<int, 2>{});
+    };
+    if (k == 3) with_s(std::integral_constant<int, 3>{});
+    else with_s(std::integral_constant<int, 5>{});
+    return hit;
+}
+// variant of the launches with the weight gradient fused into the backward-data pass (k_dwd_bwd<.., WG>, k_dws_bwd<.., WGR>)
+constexpr int DW_WG = -1;
+// variant of a ring launch: 0 plain, 1 register prefetch (PIPE), KQ (6 | 10: E-free), DW_WG
+static int dws_variant(const DwPlan& p) { return p.fuse_wgrad ? DW_WG : p.kq ? p.kq : (int)p.pipe; }
+
+// sum the weight-gradient partial rows into each group's g_dw
+static int dw_reduce_wgrad(const TfnasCellDesc& d, const float* wpart, int rows, size_t wout, hipStream_t s) {
     size_t poff = 0;
     for (int g = 0; g < d.G; ++g) {
         const int n = d.g[g].mc * d.g[g].k * d.g[g].k;
-        int rc = launch_reduce_rows(part + poff, gx, n, out_size, nullptr, d.g[g].g_dw, s);
+        const int rc = launch_reduce_rows(wpart + poff, rows, n, wout, nullptr, d.g[g].g_dw, s);
         if (rc) return rc;
         poff += n;
     }
-    return (int)hipGetLastError();
+    return 0;
 }
 
-static int launch_dw_wgrad_direct(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
-                                  const float* D, const double* stats2, const double* red2, const float* E,
-                                  const double* stats1, float* part, size_t out_size, hipStream_t s, bool& done);
-// TfnasCellDesc.route, TFNAS_ROUTE_DW_*: 0 per launch, whichever kernel measured faster | 1 register-window kernels wherever the
-// geometry allows | 2 ring / tile kernels only | 3 tile kernels only: every choice is compared with the oracle
-// (tests/test_gpu_cell.py::test_variant_against_oracle)
-static inline int dw_variant(const TfnasCellDesc& d) { return route_dw(d); }
-static bool dwd_enabled(const TfnasCellDesc& d);
-static bool dwd_bwd_use(const TfnasCellDesc& d);
-static int launch_dw_bwd_data_direct(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
-                                     const float* D, const double* stats2, const double* red2, const float* E,
-                                     const double* stats1, float* dEh, double* red1, float* part, hipStream_t s, float* cb1,
-                                     bool& done, bool fuse_wgrad = false);
-static bool dwd_bwd_fuses_wgrad(const TfnasCellDesc& d);
-static int launch_dw_fwd_direct(const TfnasCellDesc& d, const float* E, const double* stats1, float* D, double* stats2,
-                                float* part, hipStream_t s, bool& done);
+int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const double* stats1, float* D,
+                  double* stats2, float* part, hipStream_t s) {
+    if (!E && !efree_ic_ok(d.ic)) return TFNAS_EINVAL;
+    const DwPlan p = dw_plan_fwd(d, E == nullptr, x != nullptr);
+    for (int i = 0; i < 2; ++i) {
+        if (!p.chunks[i]) continue;
+        const int kk = 3 + 2 * i;
+        ProfScope _prof(TK_DW_FWD, s, d.G > 2);
+        bool ok = false;
+        if (p.fam == DW_DIRECT) {
+            const DwDirect gm = p.direct[i];
+            ok = dw_dispatch<2, 4>(kk, d.stride, d.act, p.jw, [&](auto K, auto S, auto A, auto JW) {
+                hipLaunchKernelGGL((k_dwd_fwd<K, S, A, JW>), dim3(gm.nwg), dim3(256), 0, s, d, E, stats1, D, part, gm);
+            });
+        } else if (p.fam == DW_RING) {
+            const DwSlide gm = p.ring[i];
+            const size_t shm = (size_t)(gm.RB * gm.L1 * gm.CCP + kk * kk * gm.CC + 2 * gm.CC) * sizeof(float);
+            ok = dw_dispatch<0, 1, 6, 10>(kk, d.stride, d.act, dws_variant(p), [&](auto K, auto, auto A, auto V) {
+                hipLaunchKernelGGL((k_dws_fwd<K, A, V == 1, V == 1 ? 0 : V>), dim3(p.rows * gm.chunks), dim3(256), shm, s, d, E,
+                                   stats1, D, part, gm, V > 1 ? x : nullptr);
+            });
+        } else {
+            const DwGeom gm = p.tile[i];
+            const int tile = gm.L0 * gm.L1 * gm.CC > 2048 ? gm.L0 * gm.L1 * gm.CC : 2048;
+            const size_t shm = (size_t)(tile + kk * kk * gm.CC + 2 * gm.CC) * sizeof(float);
+            if (shm > 64 * 1024) return TFNAS_ERANGE;
+            ok = dw_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
+                hipLaunchKernelGGL((k_dw_fwd<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, E, x, stats1, D,
+                                   part, gm);
+            });
+        }
+        if (!ok) return TFNAS_EINVAL;
+    }
+    return launch_reduce_rows(part, p.rows, 2 * d.M, 2 * (size_t)d.M, stats2, nullptr, s);
+}
 
-#include "dw_stream.inc"
-#include "dw_direct.inc"
+int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
+                       const float* D, const double* stats2, const double* red2, const float* E, const float* x,
+                       const double* stats1, float* dEh, double* red1, float* part, hipStream_t s, float* cb1) {
+    if (!E && !efree_ic_ok(d.ic)) return TFNAS_EINVAL;
+    const size_t wout = dw_wout_size(d);
+    float* wpart = part + (((size_t)p.rows * 2 * d.M + 63) & ~(size_t)63);    // (fuse_wgrad: behind the statistics partials)
+    for (int i = 0; i < 2; ++i) {
+        if (!p.chunks[i]) continue;
+        const int kk = 3 + 2 * i;
+        ProfScope _prof(TK_DW_BWD_DATA, s, d.G > 2);
+        bool ok = false;
+        if (p.fam == DW_DIRECT) {
+            const DwDirect gm = p.direct[i];
+            ok = dw_dispatch<2, 4, DW_WG>(kk, d.stride, d.act, p.fuse_wgrad ? DW_WG : p.jw, [&](auto K, auto S, auto A, auto V) {
+                if constexpr (V == DW_WG)           // (stride 2, JW = 2 only)
+                    hipLaunchKernelGGL((k_dwd_bwd<K, 2, A, 2, true>), dim3(gm.nwg), dim3(256), 0, s, d, dZ, gate, dpooled, D,
+                                       stats2, red2, E, stats1, dEh, part, gm, wpart, wout);
+                else
+                    hipLaunchKernelGGL((k_dwd_bwd<K, S, A, V>), dim3(gm.nwg), dim3(256), 0, s, d, dZ, gate, dpooled, D, stats2,
+                                       red2, E, stats1, dEh, part, gm);
+            });
+        } else if (p.fam == DW_RING) {
+            const DwSlide gm = p.ring[i];
+            size_t shm = (size_t)(gm.RB * gm.L1 * gm.CCP + kk * kk * gm.CC + 4 * gm.CC + 2 * gm.CC +
+                                  (p.kq ? gm.TH * gm.TW * gm.CCP : 0)) * sizeof(float);
+            if (p.fuse_wgrad && shm < (size_t)4 * kk * kk * gm.CC * sizeof(float)) shm = (size_t)4 * kk * kk * gm.CC * sizeof(float);
+            ok = dw_dispatch<0, 1, 6, 10, DW_WG>(kk, d.stride, d.act, dws_variant(p), [&](auto K, auto, auto A, auto V) {
+                if constexpr (V == DW_WG) {
+                    // (3 x 3 only: dw_plan_bwd_data; the non-prefetching variant: with the 9 accumulators the prefetching one spills)
+                    if constexpr (K == 3)
+                        hipLaunchKernelGGL((k_dws_bwd<K, A, false, 0, true>), dim3(p.rows * gm.chunks), dim3(256), shm, s, d, dZ,
+                                           gate, dpooled, D, stats2, red2, E, stats1, dEh, part, gm, nullptr, wpart, wout);
+                } else {
+                    hipLaunchKernelGGL((k_dws_bwd<K, A, V == 1, V == 1 ? 0 : V>), dim3(p.rows * gm.chunks), dim3(256), shm, s, d,
+                                       dZ, gate, dpooled, D, stats2, red2, E, stats1, dEh, part, gm, V > 1 ? x : nullptr);
+                }
+            });
+        } else {
+            const DwGeom gm = p.tile[i];
+            const int tile = gm.L0 * gm.L1 * gm.CC > 2048 ? gm.L0 * gm.L1 * gm.CC : 2048;
+            const size_t shm = (size_t)(tile + kk * kk * gm.CC + 4 * gm.CC + 2 * gm.CC + (p.kq ? gm.T0 * gm.T1 * gm.CC : 0)) *
+                               sizeof(float);
+            if (shm > 64 * 1024) return TFNAS_ERANGE;
+            ok = dw_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
+                hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate,
+                                   dpooled, D, stats2, red2, E, x, stats1, dEh, part, gm);
+            });
+        }
+        if (!ok) return TFNAS_EINVAL;
+    }
+    if (p.fuse_wgrad) {
+        ProfScope _prof(TK_DW_WGRAD, s);
+        const int rc = dw_reduce_wgrad(d, wpart, p.rows, wout, s);
+        if (rc) return rc;
+    }
+    if (cb1) return launch_reduce_bn1(d, part, p.rows, stats1, red1, cb1, s);
+    return launch_reduce_rows(part, p.rows, 2 * d.M, 2 * (size_t)d.M, red1, nullptr, s);
+}
+
+int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
+                    const double* stats2, const double* red2, const float* E, const double* stats1, float* part,
+                    hipStream_t s) {
+    const DwPlan p = dw_plan_wgrad(d);
+    const size_t wout = dw_wout_size(d);
+    for (int i = 0; i < 2; ++i) {
+        if (!p.chunks[i]) continue;
+        const int kk = 3 + 2 * i;
+        ProfScope _prof(TK_DW_WGRAD, s);
+        if (p.fam == DW_DIRECT) {
+            const DwDirect gm = p.direct[i];
+            dw_dispatch<2, 4>(kk, d.stride, d.act, p.jw, [&](auto K, auto S, auto A, auto JW) {
+                hipLaunchKernelGGL((k_dwd_wgrad<K, S, A, JW>), dim3(gm.nwg), dim3(256), 0, s, d, dZ, gate, dpooled, D, stats2,
+                                   red2, E, stats1, part, wout, gm);
+            });
+        } else if (p.fam == DW_RING) {
+            const DwSlide gm = p.ring[i];
+            int ring = gm.RB * gm.L1 * gm.CCP;
+            if (ring < 4 * kk * kk * gm.CC) ring = 4 * kk * kk * gm.CC;     // cross-wave reduction reuses the ring
+            const size_t shm = (size_t)(ring + 4 * gm.CC + 2 * gm.CC) * sizeof(float);
+            dw_dispatch<0, 1>(kk, d.stride, d.act, p.pipe, [&](auto K, auto, auto A, auto PIPE) {
+                hipLaunchKernelGGL((k_dws_wgrad<K, A, PIPE == 1>), dim3(p.rows * gm.chunks), dim3(256), shm, s, d, dZ, gate,
+                                   dpooled, D, stats2, red2, E, stats1, part, wout, gm);
+            });
+        } else {
+            const DwGeom gm = p.tile[i];
+            int tile = gm.L0 * gm.L1 * gm.CC;
+            if (tile < 4 * kk * kk * gm.CC) tile = 4 * kk * kk * gm.CC;
+            const size_t shm = (size_t)(tile + 4 * gm.CC + 2 * gm.CC) * sizeof(float);
+            dw_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
+                hipLaunchKernelGGL((k_dw_wgrad<K, S, A>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate, dpooled, D,
+                                   stats2, red2, E, stats1, part, wout, gm);
+            });
+        }
+    }
+    const int rc = dw_reduce_wgrad(d, part, p.rows, wout, s);
+    return rc ? rc : (int)hipGetLastError();
+}

@@ -122,5 +122,3 @@ __device__ __forceinline__ void efree_lane_chunk(int& lane, int& cy) {
     lane = V / chunks;
     cy = V - lane * chunks;
 }
-
-static inline bool efree_ic_ok(int ic) { return ic == 16 || ic == 24 || ic == 40; }

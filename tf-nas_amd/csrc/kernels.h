@@ -65,12 +65,52 @@ int launch_expand_dgrad_x(const TfnasCellDesc& d, const float* x, const float* c
 int launch_expand_wgrad(const TfnasCellDesc& d, const float* dEh, const float* E, const float* cb1,
                         const float* x, float* part, hipStream_t s);
 
-// dwconv_kernels.hip
+// dwconv_kernels.hip: the depthwise k x k convolution (k = 3 | 5) in three kernel families, each with the geometry struct its
+// kernels take by value.  Register-window kernels (dw_direct.inc):
+struct DwDirect {
+    int chunks;      // 32-channel chunks of the groups with this kernel size
+    int ncg;         // column groups per image: ceil(Wo / (4 * JW))
+    int nseg;        // waves per (chunk, column group), a multiple of 4
+    int per;         // macro-steps per wave
+    int steps;       // N * (Ho + A)
+    int nwg;         // chunks * ncg * nseg / 4
+};
+// LDS ring kernels of the stride-1 cells (dw_stream.inc):
+struct DwSlide {
+    int TH, TW;            // rows per block, columns of the band (multiple of 4)
+    int CC, CCP, cq_shift; // channels per workgroup, pixel stride in LDS (floats)
+    int RB, L1;            // ring rows, ring columns (pixels) = TW + K - 1
+    int chunks, gx;        // channel chunks of this launch, image lanes (= partial rows)
+};
+// LDS tile kernels (dwconv_kernels.hip):
+struct DwGeom {
+    int T0, T1;        // tile height / width (in outputs for fwd & wgrad, in inputs for bwd-data)
+    int CC;            // channels per workgroup (16/32/64)
+    int cq_shift;      // log2(CC/4)
+    int tilesH, tilesW, ntiles;   // ntiles = N * tilesH * tilesW
+    int L0, L1;        // LDS tile extent (rows, cols)
+};
+// What one depthwise pass launches, chosen once by the pass's planner from the descriptor (route bits included), whether E is
+// present and whether x is given; the launcher carries it out: the k = 3 launch, the k = 5 launch, then the reductions of
+// the `rows` partial rows.
+enum DwFamily { DW_DIRECT, DW_RING, DW_TILE };
+struct DwPlan {
+    DwFamily fam;
+    int rows;             // partial rows of the pass
+    int chunks[2];        // channel chunks of the k = 3 / k = 5 launch (0: not launched)
+    DwDirect direct[2];   // geometry of the k = 3 / k = 5 launch: the planned family's member
+    DwSlide ring[2];
+    DwGeom tile[2];
+    int jw;               // DW_DIRECT: output columns per lane (JW)
+    bool pipe;            // DW_RING: the register-prefetch variant (PIPE)
+    int kq;               // E-free: ic / 4 of the expand recomputed from x (KQ); 0: E is read
+    bool fuse_wgrad;      // backward-data: the pass also writes every group's g_dw, so launch_dw_wgrad is not called
+};
 // E == nullptr: E-free mode (efree.h) -- the expanded activation is recomputed from x inside the depthwise kernels
 int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const double* stats1, float* D,
                   double* stats2, float* part, hipStream_t s);
 bool efree_supported(const TfnasCellDesc& d);
-static inline bool efree_ic_small(int ic) { return ic == 16 || ic == 24 || ic == 40; }   // (efree.h: the tile / ring E-free kernels)
+static inline bool efree_ic_ok(int ic) { return ic == 16 || ic == 24 || ic == 40; }   // (efree.h: the tile / ring E-free kernels)
 int launch_expand_stats_gram(const TfnasCellDesc& d, const float* x, double* stats1, float* part, hipStream_t s);
 int launch_x_colsum(const float* x, int P, int ic, int rps, int nb, float* part, hipStream_t s);
 // fx_kernels.hip: fused per-image route of the late cells (fx.h) -- E-free cells with 64 <= ic <= 192 and images <= 14 x 14
@@ -85,13 +125,11 @@ int launch_fx_fwd(const TfnasCellDesc& d, const float* x, const double* stats1, 
 int launch_fx_bwd(const TfnasCellDesc& d, const float* x, const float* Eh, const double* stats1, const double* stats2,
                   const double* red2, const float* dZ, const float* D, const float* gate, const float* dpooled, float* scratch,
                   size_t scratch_floats, double* red1, float* cb1, float* part, int* nsl, hipStream_t s);
-int launch_dw_bwd_data(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
-                       const float* D, const double* stats2,
-                       const double* red2, const float* E, const float* x, const double* stats1, float* dEh,
-                       double* red1, float* part, hipStream_t s, float* cb1 = nullptr, bool fuse_wgrad = false);
-// true: launch_dw_bwd_data(..., fuse_wgrad = true) also writes the depthwise weight gradients g_dw (stride-1 ring cells: the WGR
-// variant of k_dws_bwd) -- launch_dw_wgrad must then not be called for this cell
-bool dw_bwd_fuses_wgrad(const TfnasCellDesc& d, const float* E);   // cb1: also fill the BN1 table
+DwPlan dw_plan_bwd_data(const TfnasCellDesc& d, bool efree, bool has_x);
+// p = dw_plan_bwd_data(d, E == nullptr, x != nullptr); cb1: also fill the BN1 table
+int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
+                       const float* D, const double* stats2, const double* red2, const float* E, const float* x,
+                       const double* stats1, float* dEh, double* red1, float* part, hipStream_t s, float* cb1 = nullptr);
 int launch_reduce_bn1(const TfnasCellDesc& d, const float* part, int nb, const double* stats1, double* red1, float* cb1,
                       hipStream_t s);
 int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
