@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-/* 4 (round 6): every route switch of a launch lives in its descriptor (TfnasCellDesc.route: TFNAS_ROUTE_*); the library reads no
+/* 4, additive: TFNAS_CELL_ACCUM_WGRAD (weight gradients added to their destinations, per launch) and tfnas_path_set_wgrad_accum.
+ * 4 (round 6): every route switch of a launch lives in its descriptor (TfnasCellDesc.route: TFNAS_ROUTE_*); the library reads no
  * environment variable at launch time (the TFNAS_* variables only seed the Python-side defaults, functions.route_from_env).
  * tfnas_cell_route() + TfnasCellDesc.fwd_route: a backward refuses a descriptor whose route differs from the forward's.
  * TfnasCellDesc.wgrad_stream[3]: caller-owned streams for the three weight-gradient forks of ONE launch (the stem cell's backward
@@ -107,7 +108,8 @@ typedef struct TfnasCellDesc {
                                  of THIS launch's 1x1 GEMMs, whatever the default is (two models in one process in different
                                  modes: an fp32-exact search net beside a bf16-GEMM derived net)                      [in] */
     int32_t flags;            /* TFNAS_CELL_LAZY_JOIN: tfnas_mbconv_bwd returns without joining its weight-gradient side
-                                 stream (see tfnas_set_lazy_join, which sets the default for descriptors without the bit) [in]
+                                 stream (see tfnas_set_lazy_join, which sets the default for descriptors without the bit);
+                                 TFNAS_CELL_ACCUM_WGRAD: the backward adds its weight gradients to their destinations   [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -134,6 +136,19 @@ typedef struct TfnasCellDesc {
 } TfnasCellDesc;
 #define TFNAS_GEMM_EXPLICIT 0x1000
 #define TFNAS_CELL_LAZY_JOIN 1
+/* TfnasCellDesc.flags: every weight-gradient output of the launch is ADDED to what its destination already holds, g <- g + v,
+ * where v is bit for bit what the same launch stores without the bit (BLAS beta = 1; one more read of each gradient, no extra
+ * launch, no scratch).  Destinations: the g_* pointers of every group and, in the affine entry points, TfnasBnAffine.g_weight /
+ * g_bias.  Statistics outputs are never accumulated.  Honoured by tfnas_mixedop_bwd (cell, stem and head modes),
+ * tfnas_mbconv_bwd, tfnas_head_bwd, tfnas_head_wgrad, tfnas_head_affine_bwd and, through the planned cells,
+ * tfnas_paths_bwd (tfnas_path_set_wgrad_accum).  This is how gradients are summed over micro-batches and over several backward
+ * passes through the same weights (autograd's .grad semantics).
+ * Ordering is the caller's: a launch with the bit set must not read a gradient range that another stream may still be writing --
+ * the side stream that tfnas_mbconv_bwd leaves unjoined with TFNAS_CELL_LAZY_JOIN (tfnas_side_join first, or keep every launch
+ * that touches the range on the same caller stream, whose side stream is then the same), the caller-owned wgrad_stream[] forks
+ * of an earlier launch, and the other bi-sampling path of tfnas_paths_bwd (two paths never share a gradient range).
+ * (0x2, 0x4, 0x8 are undefined; 0x10 was TFNAS_CELL_FXP, retired: all are refused.) */
+#define TFNAS_CELL_ACCUM_WGRAD 0x20
 /* TfnasCellDesc.route (ABI 4; rounds 2-5 read these from TFNAS_* environment variables latched once per process) */
 #define TFNAS_ROUTE_FX_OFF 0x1        /* frozen-weight launches of the 14 x 14 / 7 x 7 cells through the materialised route instead
                                          of the fused per-image kernels (csrc/fx_kernels.hip)                                   */
@@ -244,7 +259,7 @@ int tfnas_mixedop_fwd(const TfnasCellDesc *d, const float *x, const float *wmix,
 
 /* MixedOP backward (what autograd does for the graph above).  Produces dx [N*H*W][ic], dwmix[G]
  * (d loss / d wmix[g]; may be NULL in sampled mode) and, when d->need_wgrad, the g_* weight gradients
- * (overwritten, not accumulated).  dZ/dEh/bsmall/red/part are scratch.  dx may be NULL when the input needs
+ * (overwritten; added to the destinations with TFNAS_CELL_ACCUM_WGRAD).  dZ/dEh/bsmall/red/part are scratch.  dx may be NULL when the input needs
  * no gradient: with need_wgrad == 0 only dwmix is produced (everything else is skipped). */
 int tfnas_mixedop_bwd(const TfnasCellDesc *d, const float *x, const float *wmix,
                       const float *E, const float *D, const float *Pr, const float *fsmall,
@@ -314,7 +329,7 @@ int tfnas_head_wgrad(const TfnasCellDesc *d, const float *x, const float *E, con
  * pooled [N][C] (C a multiple of 4), W [K][C], bias [K] or NULL, target int64 [N].
  * tfnas_cls_wgrad, one launch, everything that sums over images -- and over the npath <= 2 bi-sampling paths of a weight step:
  *   dW[k][c] = sum_p sum_n dlogits_p[n][k] pooled_p[n][c];  db[k] = sum_p sum_n dlogits_p[n][k];  loss = loss_scale * sum_p sum_n loss_n_p[n]
- * (overwritten, not accumulated; loss may be NULL).  Fixed summation orders, no atomics. */
+ * (overwritten, not accumulated; loss may be NULL: sum further micro-batches with tfnas_add_into).  Fixed summation orders, no atomics. */
 int tfnas_cls_ce(int N, int C, int K, const float *pooled, const float *W, const float *bias, const int64_t *target, float scale,
                  float *logits, float *loss_n, float *dlogits, float *dpooled, void *stream);
 int tfnas_cls_wgrad(int npath, int N, int C, int K, const float *const *pooled, const float *const *dlogits,
@@ -421,6 +436,11 @@ int tfnas_path_set_side_stream(void *ctx, void *stream);
 /* Validate + plan every cell (tfnas_cell_plan), chain the geometry (cell i+1's input extent = cell i's output), lay out
  * the arena.  May be called again on the same context with different candidates / widths (every weight step does). */
 int tfnas_path_plan(void *ctx, const TfnasPathDesc *pd, TfnasPathWs *ws);
+/* Set (bit c of cell_mask = 1) or clear TFNAS_CELL_ACCUM_WGRAD on planned cell c of the context, without re-planning: the arena
+ * and every offset stay where they are, so a caller may decide between a forward and its backward whether that backward
+ * overwrites or accumulates the cells' weight gradients.  TFNAS_EINVAL before the first tfnas_path_plan; TFNAS_ERANGE when
+ * a bit at or above ncell is set.  The next tfnas_path_plan takes the flags from its descriptor again. */
+int tfnas_path_set_wgrad_accum(void *ctx, uint32_t cell_mask);
 
 /* Forward of `npath` planned paths, enqueued interleaved cell by cell: path p runs on streams[p] with arena[p].
  *   x0[p]     device [N][H][W][ic0] input of the first cell (second_stem output)

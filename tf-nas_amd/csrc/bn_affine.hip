@@ -43,15 +43,17 @@ __global__ void k_bn_fwd_fix(double* __restrict__ stats, int nch, double inv_cnt
 }
 
 __global__ void k_bn_bwd_fix(double* __restrict__ red, int nch, double inv_cnt, const float* __restrict__ gamma,
-                             const float* __restrict__ beta, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+                             const float* __restrict__ beta, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                             int accum) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= nch) return;
     const double S1 = red[2 * c], S2 = red[2 * c + 1];
     double g = gamma ? (double)gamma[c] : 1.0;
     const double b = beta ? (double)beta[c] : 0.0;
     if (fabs(g) < 1e-12) g = g < 0.0 ? -1e-12 : 1e-12;
-    if (dbeta) dbeta[c] = (float)S1;
-    if (dgamma) dgamma[c] = (float)((S2 - b * S1) / g);
+    const float vb = (float)S1, vg = (float)((S2 - b * S1) / g);
+    if (dbeta) dbeta[c] = accum ? dbeta[c] + vb : vb;
+    if (dgamma) dgamma[c] = accum ? dgamma[c] + vg : vg;
     const double t1 = S1 * inv_cnt;
     const double cc = (S2 * inv_cnt - b * t1) / (g * g);
     red[2 * c] = (t1 - b * cc) / inv_cnt;
@@ -82,11 +84,11 @@ int launch_bn_fwd_fix(double* stats, int nch, uint64_t cnt, float eps, const flo
 }
 
 int launch_bn_bwd_fix(double* red, int nch, uint64_t cnt, const float* gamma, const float* beta, float* dgamma, float* dbeta,
-                      hipStream_t s) {
+                      hipStream_t s, int accum) {
     if (nch <= 0) return 0;
     ProfScope _prof(TK_SMALL, s);
     hipLaunchKernelGGL(k_bn_bwd_fix, dim3(cdiv(nch, 256)), dim3(256), 0, s, red, nch, 1.0 / (double)cnt, gamma, beta, dgamma,
-                       dbeta);
+                       dbeta, accum);
     return (int)hipGetLastError();
 }
 

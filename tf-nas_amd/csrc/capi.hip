@@ -170,7 +170,7 @@ static int check_modes(const TfnasCellDesc* d) {
         const int gm = d->gemm_mode & ~(TFNAS_GEMM_EXPLICIT | TFNAS_GEMM_EVERYWHERE);
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
-    if (d->flags & ~TFNAS_CELL_LAZY_JOIN) return TFNAS_EINVAL;
+    if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD)) return TFNAS_EINVAL;
     if (d->route & ~TFNAS_ROUTE_ALL) return TFNAS_EINVAL;
     if ((d->route & TFNAS_ROUTE_XG_OFF) && (d->route & TFNAS_ROUTE_XG_ALL)) return TFNAS_EINVAL;
     if ((d->route & TFNAS_ROUTE_SE_MASK) == TFNAS_ROUTE_SE_MASK) return TFNAS_EINVAL;     // (3 is not an excite-FC variant)
@@ -349,7 +349,8 @@ static int bn_bwd_fix(const TfnasCellDesc& d, const TfnasBnAffine* bn, int site,
     int nch;
     uint64_t cnt;
     bn_site(d, site, nch, cnt);
-    TRY(launch_bn_bwd_fix(red, nch, cnt, bn->weight[site], bn->bias[site], bn->g_weight[site], bn->g_bias[site], s));
+    TRY(launch_bn_bwd_fix(red, nch, cnt, bn->weight[site], bn->bias[site], bn->g_weight[site], bn->g_bias[site], s,
+                          wgrad_accum(d)));
     // eval mode: the statistics are constants, dx = r_eff * d -- the generic form r*(d - t1 - y*t2) with t1 = t2 = 0
     if (bn->eval) return (int)hipMemsetAsync(red, 0, sizeof(double) * 2 * (size_t)nch, s);
     return 0;
@@ -607,7 +608,8 @@ extern "C" int tfnas_head_affine_bwd(const TfnasCellDesc* dp, const TfnasBnAffin
     const uint64_t cnt = (uint64_t)d0.N * d0.H * d0.W;
     TRY(launch_head_bwd(d, E, stats, dpooled, dEh, red, part, s));
     TRY(stats_sync(d, red, 2 * (size_t)d.M, s));
-    TRY(launch_bn_bwd_fix(red, d0.g[0].mc, cnt, bn->weight[0], bn->bias[0], bn->g_weight[0], bn->g_bias[0], s));
+    TRY(launch_bn_bwd_fix(red, d0.g[0].mc, cnt, bn->weight[0], bn->bias[0], bn->g_weight[0], bn->g_bias[0], s,
+                          wgrad_accum(d0)));
     if (bn->eval) HIP_TRY(hipMemsetAsync(red, 0, sizeof(double) * 2 * (size_t)d0.g[0].mc, s));
     TRY(launch_bn1_consts(d, stats, red, cb1, s));
     float* gram = part + TFNAS_PART_FLOATS - expand_gram_floats(d);

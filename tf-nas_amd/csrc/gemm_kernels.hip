@@ -1128,7 +1128,9 @@ __global__ __launch_bounds__(256) void k_expand_wgrad_fix(TfnasCellDesc d, const
         const double wg = (ps[0][lane] + ps[1][lane]) + (ps[2][lane] + ps[3][lane]);
         const f32x4 t = reinterpret_cast<const f32x4*>(cb1)[d.g[g].off + m];
         const double sx = Gx[(size_t)ic * ic + c], mu = t.x, r = t.y, t1 = t.z, t2 = t.w;
-        d.g[g].g_expand[e - poff] = (float)(r * (red[e] - t1 * sx - t2 * r * (wg - mu * sx)));
+        const float v = (float)(r * (red[e] - t1 * sx - t2 * r * (wg - mu * sx)));
+        float* __restrict__ o = d.g[g].g_expand + (e - poff);
+        *o = (d.flags & TFNAS_CELL_ACCUM_WGRAD) ? *o + v : v;
     }
 }
 
@@ -1395,7 +1397,7 @@ int launch_project_wgrad(const TfnasCellDesc& d, const float* dout, const float*
     size_t poff = 0;
     for (int g = 0; g < d.G; ++g) {
         const int n = d.g[g].mc * d.oc;
-        int rc = launch_reduce_rows(part + poff, grid.x, n, out_size, nullptr, d.g[g].g_proj, s);
+        int rc = launch_reduce_rows(part + poff, grid.x, n, out_size, nullptr, d.g[g].g_proj, s, 1, 0, 0, wgrad_accum(d));
         if (rc) return rc;
         poff += n;
     }
@@ -1565,7 +1567,7 @@ int launch_expand_wgrad(const TfnasCellDesc& d, const float* dEh, const float* E
     size_t poff = 0;
     for (int g = 0; g < d.G; ++g) {
         const int n = d.g[g].mc * d.ic;
-        int rc = launch_reduce_rows(part + poff, grid.x, n, out_size, nullptr, d.g[g].g_expand, s);
+        int rc = launch_reduce_rows(part + poff, grid.x, n, out_size, nullptr, d.g[g].g_expand, s, 1, 0, 0, wgrad_accum(d));
         if (rc) return rc;
         poff += n;
     }

@@ -29,6 +29,8 @@ static inline uint64_t stats_world(const TfnasCellDesc& d) {
 static inline int route_dw(const TfnasCellDesc& d) { return (d.route & TFNAS_ROUTE_DW_MASK) >> TFNAS_ROUTE_DW_SHIFT; }   // 0 auto, 1 direct, 2 lds, 3 tiled
 static inline int route_se(const TfnasCellDesc& d) { return (d.route & TFNAS_ROUTE_SE_MASK) >> TFNAS_ROUTE_SE_SHIFT; }   // 0 wave, 1 fused, 2 gemm
 static inline bool route_side(const TfnasCellDesc& d) { return !(d.route & TFNAS_ROUTE_WGRAD_INLINE); }
+// TFNAS_CELL_ACCUM_WGRAD: every weight-gradient store of the launch adds to its destination (g <- g + v)
+static inline int wgrad_accum(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_ACCUM_WGRAD) ? 1 : 0; }
 
 // gemm_kernels.hip
 int gemm_mode();            // arithmetic of the row-tiled GEMMs (tfnas_hip.h: TFNAS_GEMM_*)
@@ -165,9 +167,10 @@ int launch_head_bwd(const TfnasCellDesc& d, const float* E, const double* stats1
                     double* red1, float* part, hipStream_t s);
 // out[c] = sum_{b<nb} part[b*stride + c]  (double and/or float output); the deterministic replacement of atomics
 // nbatch > 1: `nbatch` independent reductions in one launch (blockIdx.y): batch b reads part + b*in_stride and writes
-// out + b*out_stride
+// out + b*out_stride.  accum != 0: the float output is added to what out_f already holds (out_f[c] += (float)sum: the
+// weight-gradient outputs of a TFNAS_CELL_ACCUM_WGRAD launch; the double output is always overwritten)
 int launch_reduce_rows(const float* part, int nb, int ncols, size_t stride, double* out_d, float* out_f,
-                       hipStream_t s, int nbatch = 1, size_t in_stride = 0, size_t out_stride = 0);
+                       hipStream_t s, int nbatch = 1, size_t in_stride = 0, size_t out_stride = 0, int accum = 0);
 /* One `part` scratch region = TFNAS_PART_ALLOC floats (16 MiB): TFNAS_PART_FLOATS for per-workgroup partial rows / split-K
    tiles; the last TFNAS_TAIL_SLOTS words are reserved (they held the ticket counters of the removed "last workgroup reduces"
    epilogues; the size of the region is part of the workspace ABI and stays). */
@@ -208,6 +211,6 @@ int launch_arch_adam_project(int n, float* const* p, const float* const* g, cons
 int launch_bn_fwd_fix(double* stats, int nch, uint64_t cnt, float eps, const float* gamma, const float* beta, float* rmean,
                       float* rvar, float momentum, int eval, hipStream_t s, uint64_t world = 1);
 int launch_bn_bwd_fix(double* red, int nch, uint64_t cnt, const float* gamma, const float* beta, float* dgamma, float* dbeta,
-                      hipStream_t s);
+                      hipStream_t s, int accum = 0);
 int launch_rowscale(float* out, const float* y, const float* res, const float* scale, int N, uint64_t per_image,
                     hipStream_t s);

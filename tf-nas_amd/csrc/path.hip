@@ -292,6 +292,19 @@ extern "C" int tfnas_path_plan(void* ctx, const TfnasPathDesc* pd, TfnasPathWs* 
     return plan_path(*static_cast<PathCtx*>(ctx), *pd, ws);
 }
 
+// the TFNAS_CELL_ACCUM_WGRAD bit of the planned cells, changed without re-planning (the arena layout stays where it is)
+extern "C" int tfnas_path_set_wgrad_accum(void* ctx, uint32_t cell_mask) {
+    PathCtx* c = static_cast<PathCtx*>(ctx);
+    if (!c) return TFNAS_ENULL;
+    if (!c->planned) return TFNAS_EINVAL;
+    if (c->pd.ncell < 32 && (cell_mask >> c->pd.ncell) != 0) return TFNAS_ERANGE;
+    for (int i = 0; i < c->pd.ncell; ++i) {
+        if ((cell_mask >> i) & 1) c->pd.cell[i].flags |= TFNAS_CELL_ACCUM_WGRAD;
+        else c->pd.cell[i].flags &= ~TFNAS_CELL_ACCUM_WGRAD;
+    }
+    return 0;
+}
+
 static int check_paths(int npath, void* const* ctx) {
     if (npath < 1 || npath > 4) return TFNAS_ERANGE;
     if (!ctx) return TFNAS_ENULL;

@@ -555,7 +555,7 @@ __global__ __launch_bounds__(256) void k_head_bwd(TfnasCellDesc d, const float* 
 template <int CL>
 __global__ __launch_bounds__(256) void k_reduce_rows(const float* __restrict__ part, int nb, int ncols, size_t stride,
                                                      double* __restrict__ out_d, float* __restrict__ out_f,
-                                                     size_t in_stride, size_t out_stride) {
+                                                     size_t in_stride, size_t out_stride, int accum) {
     constexpr int RL = 256 / CL;
     __shared__ double buf[RL][CL + 1];
     part += blockIdx.y * in_stride;
@@ -580,7 +580,7 @@ __global__ __launch_bounds__(256) void k_reduce_rows(const float* __restrict__ p
 #pragma unroll
         for (int r = 0; r < RL; ++r) t += buf[r][cl];
         if (out_d) out_d[c] = t;
-        if (out_f) out_f[c] = (float)t;
+        if (out_f) out_f[c] = accum ? out_f[c] + (float)t : (float)t;
     }
 }
 
@@ -589,7 +589,7 @@ __global__ __launch_bounds__(256) void k_reduce_rows(const float* __restrict__ p
 template <int QN>
 __global__ __launch_bounds__(256) void k_reduce_rows_q(const float* __restrict__ part, int nb, int ncols, size_t stride,
                                                        double* __restrict__ out_d, float* __restrict__ out_f,
-                                                       size_t in_stride, size_t out_stride) {
+                                                       size_t in_stride, size_t out_stride, int accum) {
     constexpr int RL = 256 / QN;
     __shared__ double buf[RL][4 * QN + 2];
     part += blockIdx.y * in_stride;
@@ -617,13 +617,16 @@ __global__ __launch_bounds__(256) void k_reduce_rows_q(const float* __restrict__
 #pragma unroll
         for (int r = 0; r < RL; ++r) t += buf[r][tid];
         if (out_d) out_d[blockIdx.x * 4 * QN + tid] = t;
-        if (out_f) out_f[blockIdx.x * 4 * QN + tid] = (float)t;
+        if (out_f) {
+            float* __restrict__ o = out_f + blockIdx.x * 4 * QN + tid;
+            *o = accum ? *o + (float)t : (float)t;
+        }
     }
 }
 
 __global__ __launch_bounds__(256) void k_reduce_rows_wide(const float* __restrict__ part, int nb, int ncols, size_t stride,
                                                           double* __restrict__ out_d, float* __restrict__ out_f,
-                                                          size_t in_stride, size_t out_stride) {
+                                                          size_t in_stride, size_t out_stride, int accum) {
     __shared__ double buf[8][128 + 4];
     part += blockIdx.y * in_stride;
     if (out_d) out_d += blockIdx.y * out_stride;
@@ -650,7 +653,10 @@ __global__ __launch_bounds__(256) void k_reduce_rows_wide(const float* __restric
 #pragma unroll
         for (int r = 0; r < 8; ++r) t += buf[r][tid];
         if (out_d) out_d[blockIdx.x * 128 + tid] = t;
-        if (out_f) out_f[blockIdx.x * 128 + tid] = (float)t;
+        if (out_f) {
+            float* __restrict__ o = out_f + blockIdx.x * 128 + tid;
+            *o = accum ? *o + (float)t : (float)t;
+        }
     }
 }
 
@@ -717,22 +723,22 @@ int launch_reduce_bn1(const TfnasCellDesc& d, const float* part, int nb, const d
 }
 
 int launch_reduce_rows(const float* part, int nb, int ncols, size_t stride, double* out_d, float* out_f,
-                       hipStream_t s, int nbatch, size_t in_stride, size_t out_stride) {
+                       hipStream_t s, int nbatch, size_t in_stride, size_t out_stride, int accum) {
     ProfScope _prof(TK_REDUCE_ROWS, s);
     const bool al4 = (ncols & 3) == 0 && (stride & 3) == 0 && ((uintptr_t)part & 15) == 0 && (in_stride & 3) == 0;
     const unsigned nby = nbatch > 1 ? (unsigned)nbatch : 1u;
     if (al4 && nb <= 128 && ncols >= 1024)
         hipLaunchKernelGGL(k_reduce_rows_wide, dim3(cdiv(ncols, 128), nby), dim3(256), 0, s, part, nb, ncols, stride, out_d,
-                           out_f, in_stride, out_stride);
+                           out_f, in_stride, out_stride, accum);
     else if (al4 && nb > 64)
         hipLaunchKernelGGL(k_reduce_rows_q<4>, dim3(cdiv(ncols, 16), nby), dim3(256), 0, s, part, nb, ncols, stride, out_d, out_f,
-                           in_stride, out_stride);
+                           in_stride, out_stride, accum);
     else if (ncols <= 2048 && nb > 256)
         hipLaunchKernelGGL(k_reduce_rows<4>, dim3(cdiv(ncols, 4), nby), dim3(256), 0, s, part, nb, ncols, stride, out_d, out_f,
-                           in_stride, out_stride);
+                           in_stride, out_stride, accum);
     else
         hipLaunchKernelGGL(k_reduce_rows<8>, dim3(cdiv(ncols, 8), nby), dim3(256), 0, s, part, nb, ncols, stride, out_d, out_f,
-                           in_stride, out_stride);
+                           in_stride, out_stride, accum);
     return (int)hipGetLastError();
 }
 

@@ -192,10 +192,9 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
                         a.out0[(size_t)row * SE + so + col] = v * act_d<ACT>(a.hpre[(size_t)row * SE + so + col]);
                 } else if (MODE == 3) {
                     if (row < N && col < mcp) a.out0[(size_t)row * M + off + col] = v;
-                } else if (MODE == 4) {
-                    if (row < mc && col < se) d.g[g].g_se_e[(size_t)row * se + col] = v;
-                } else {
-                    if (row < mc && col < se) d.g[g].g_se_r[(size_t)col * mc + row] = v;
+                } else if (row < mc && col < se) {          // MODE 4 / 5: weight gradients (TFNAS_CELL_ACCUM_WGRAD: g += v)
+                    float* __restrict__ o = MODE == 4 ? d.g[g].g_se_e + (size_t)row * se + col : d.g[g].g_se_r + (size_t)col * mc + row;
+                    *o = (d.flags & TFNAS_CELL_ACCUM_WGRAD) ? *o + v : v;
                 }
             }
         }
@@ -260,8 +259,8 @@ __global__ __launch_bounds__(256) void k_se_bias_grad(TfnasCellDesc d, SeArgs a)
     __syncthreads();
     if (nl == 0) {
         const float t = (buf[0][cl] + buf[1][cl]) + (buf[2][cl] + buf[3][cl]);
-        if (idx < mc) d.g[g].gb_se_e[idx] = t;
-        else if (idx < mc + se) d.g[g].gb_se_r[idx - mc] = t;
+        float* __restrict__ o = idx < mc ? d.g[g].gb_se_e + idx : idx < mc + se ? d.g[g].gb_se_r + (idx - mc) : nullptr;
+        if (o) *o = (d.flags & TFNAS_CELL_ACCUM_WGRAD) ? *o + t : t;
     }
 }
 

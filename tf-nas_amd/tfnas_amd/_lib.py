@@ -23,6 +23,7 @@ _G_FIELDS = ('g_expand', 'g_dw', 'g_proj', 'g_se_r', 'gb_se_r', 'g_se_e', 'gb_se
 
 
 GEMM_EXPLICIT, GEMM_EVERYWHERE, CELL_LAZY_JOIN = 0x1000, 0x100, 1
+CELL_ACCUM_WGRAD = 0x20      # TfnasCellDesc.flags: the backward adds its weight gradients to their destinations
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
 ROUTE_FX_OFF, ROUTE_FOLD_OFF, ROUTE_DWWG_OFF, ROUTE_DWWG2_OFF, ROUTE_XG_OFF, ROUTE_XG_ALL = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 ROUTE_DW = {'auto': 0, 'direct': 1 << 6, 'lds': 2 << 6, 'tiled': 3 << 6}
@@ -99,6 +100,7 @@ _PROTOS = {
     'tfnas_path_create': (C.c_int, [C.POINTER(C.c_void_p)]),
     'tfnas_path_destroy': (C.c_int, [C.c_void_p]),
     'tfnas_path_set_side_stream': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'tfnas_path_set_wgrad_accum': (C.c_int, [C.c_void_p, C.c_uint32]),
     'tfnas_set_stats_sync': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     'tfnas_path_plan': (C.c_int, [C.c_void_p, C.POINTER(TfnasPathDesc), C.POINTER(TfnasPathWs)]),
     'tfnas_paths_fwd': (C.c_int, [C.c_int] + [_PP] * 8),

@@ -443,9 +443,9 @@ class Network(nn.Module):
     def _forward_paths(self, x, sampling, mode, exp_noise, rand_pos, stem_out, pos):
         """``forward`` on the path level (tfnas_paths_fwd / _bwd: ONE C call per direction for the 18 cells + 6 sinks instead
         of one autograd node per cell) -- what closes the gap between the two-line import swap and tfnas_amd.search's own
-        steps.  Same kernels, bit-identical results.  Sampled mode: the cells' weight gradients are written by the backward
-        straight into the weight arena and exposed as ``.grad`` views (overwriting, like the first backward after
-        ``zero_grad()``; two backward passes through the SAME candidate without a zero_grad in between are not summed)."""
+        steps.  Same kernels, bit-identical results.  Sampled mode: the cells' weight gradients are stored by the backward
+        straight into the weight arena and exposed as ``.grad`` views, with autograd's semantics: written where ``.grad`` is
+        None, added to it otherwise (several backward passes or micro-batches without a zero_grad in between are summed)."""
         st = self._path_state()
         if st is None:
             return None

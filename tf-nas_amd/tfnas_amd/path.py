@@ -377,7 +377,8 @@ class SoftPathFn(torch.autograd.Function):
 
 
 class OnePathFn(torch.autograd.Function):
-    """One sampled path; weight gradients go straight into the WeightArena (not through autograd)."""
+    """One sampled path; weight gradients go straight into the WeightArena (not through autograd).  With ``expose`` they are
+    summed into existing ``.grad`` the way autograd's AccumulateGrad would (SearchState.prepare_grad_targets)."""
 
     @staticmethod
     def forward(ctx, runner, x0, idxs, name, need_w, expose=None, main_stream=None):   # (grad mode is off inside forward: need_w comes from outside)
@@ -400,6 +401,11 @@ class OnePathFn(torch.autograd.Function):
         x0h, = ctx.saved_tensors
         dx0 = torch.empty_like(x0h) if s.pd.need_dx0 else None
         cur = torch.cuda.current_stream(x0h.device)
+        if ctx.expose is not None and ctx.need_w:
+            # module-API route: sum into .grad like AccumulateGrad would, decided per cell now (a zero_grad() between this
+            # path's forward and its backward still makes it write); the plan of the forward stays where it is
+            mask = ctx.expose.prepare_grad_targets(ctx.idxs)
+            check(runner.lib.tfnas_path_set_wgrad_accum(s.ctx, mask), 'tfnas_path_set_wgrad_accum')
         args = ([s], [x0h], [None], [None], [_nhwc(dout)], [None], [dx0], [None], [None], [cur])
         hook, k = runner.segment_hook, runner.split_stage
         if hook is not None and 0 < k < len(runner.stages):

@@ -443,6 +443,28 @@ class SearchState:
             plan.wgrad_streams = [self._wgrad_streams[0], self._wgrad_streams[1], self._side_stream]
         return True
 
+    def prepare_grad_targets(self, idxs):
+        """Before the backward of one module-API sampled path (path.OnePathFn): autograd's ``.grad`` semantics for the weight
+        gradients the cells' kernels store straight into the arena.  Per cell, from its sampled candidate's parameters: every
+        ``.grad`` None -> the kernels write; otherwise they add (TFNAS_CELL_ACCUM_WGRAD) to the arena range, after a ``.grad``
+        that is some other tensor has been copied into it (and ``.grad`` re-pointed at the view) and the ranges of parameters
+        whose ``.grad`` is None have been zeroed.  Enqueued on the current stream, i.e. before the backward's kernels.  Returns
+        the cell mask for tfnas_path_set_wgrad_accum."""
+        mask = 0
+        for ci, idx in enumerate(idxs):
+            ps = self.op_params(ci, idx)
+            if all(p.grad is None for p in ps):
+                continue
+            for p in ps:
+                v, g = self.arena.grad_view(p), p.grad
+                if g is None:
+                    v.zero_()
+                elif g.data_ptr() != v.data_ptr() or g.dtype != v.dtype or g.shape != v.shape or g.stride() != v.stride():
+                    v.copy_(g)
+                    p.grad = v
+            mask |= 1 << ci
+        return mask
+
     def expose_weight_grads(self, idx_lists, track=True):
         """After backward: point .grad of the sampled candidates' parameters at the arena ranges the kernels wrote.
         ``track``: remember them so that the next path-level w-step drops the views again (begin_weight_grads); the module-API
