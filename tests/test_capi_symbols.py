@@ -117,6 +117,37 @@ def test_fused_route_queries_on_the_supernet_geometries(lib):
     assert lib.tfnas_cell_plan(C.byref(d)) == -1
 
 
+def test_expand_dgrad_split_workspace_on_the_supernet_geometries(lib):
+    """ws.dxp is the one value of the GEMM launch plans visible through the ABI: K-splits of the expand dgrad x [P][ic] floats
+    (4 = unsplit).  Batch 128, the supernet's 18 cells as the all-candidate launch and as a one-candidate launch with weight
+    gradients (the wider mid), and the stem; the expected sizes were recorded from the library before the planners existed."""
+    from tfnas_amd import _lib
+    cells = [(16, 24, 2, 112), (24, 24, 1, 56), (24, 40, 2, 56), (40, 40, 1, 28), (40, 40, 1, 28), (40, 80, 2, 28),
+             (80, 80, 1, 14), (80, 80, 1, 14), (80, 80, 1, 14), (80, 112, 1, 14), (112, 112, 1, 14), (112, 112, 1, 14),
+             (112, 112, 1, 14), (112, 192, 2, 14), (192, 192, 1, 7), (192, 192, 1, 7), (192, 192, 1, 7), (192, 320, 1, 7)]
+    want_all = [4] * 6 + [12042240] * 4 + [16859136] * 4 + [8429568] * 4        # 6 splits on the 14 x 14 cells, 7 on the 7 x 7
+    want_one = [4] * 6 + [4014080] * 4 + [5619712] * 4 + [2408448] * 4          # capped at 2
+
+    def dxp(d):
+        assert lib.tfnas_cell_plan(C.byref(d)) == 0
+        ws = _lib.TfnasCellWs()
+        assert lib.tfnas_cell_ws(C.byref(d), C.byref(ws)) == 0
+        return ws.dxp
+
+    got_all, got_one = [], []
+    for ic, oc, stride, hw in cells:
+        geo = dict(N=128, H=hw, W=hw, ic=ic, oc=oc, stride=stride)
+        got_all.append(dxp(_desc(mids=(3 * ic, 6 * ic) * 4, ks=(3, 3, 5, 5) * 2, ses=(0,) * 4 + (4 * (ic // 4),) * 4, **geo)))
+        d = _desc(mids=(6 * ic,), ks=(5,), ses=(4 * (ic // 4),), **geo)
+        d.need_wgrad = 1
+        got_one.append(dxp(d))
+    assert got_all == want_all
+    assert got_one == want_one
+    stem = _desc(N=128, H=224, W=224, ic=27, oc=16, mids=(32,), ks=(3,), ses=(8,))
+    stem.mode, stem.Hi, stem.Wi, stem.act, stem.has_res = _lib.MODE_STEM, 224, 224, 0, 0
+    assert dxp(stem) == 4
+
+
 def test_library_reads_no_environment_variable():
     """ABI 4: every route switch is in the descriptor; the TFNAS_* variables only seed the Python mirror's default route word."""
     import os

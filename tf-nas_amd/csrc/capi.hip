@@ -261,7 +261,7 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     ws->part = (d->need_wgrad ? 2 : 1) * (uint64_t)TFNAS_PART_ALLOC;   // second half: weight-gradient side stream
     ws->dx = P * d->ic;
     {
-        const int ns = d->mode == TFNAS_MODE_STEM ? 1 : expand_dgrad_splits(*d);
+        const int ns = d->mode == TFNAS_MODE_STEM ? 1 : gemm_plan_expand_dgrad(*d, true).splits;
         ws->dxp = ns > 1 ? (uint64_t)ns * P * d->ic : 4;   /* split-K partials of the expand dgrad */
     }
     return 0;

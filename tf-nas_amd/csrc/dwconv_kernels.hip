@@ -894,7 +894,7 @@ static int dw_reduce_wgrad(const TfnasCellDesc& d, const float* wpart, int rows,
     size_t poff = 0;
     for (int g = 0; g < d.G; ++g) {
         const int n = d.g[g].mc * d.g[g].k * d.g[g].k;
-        const int rc = launch_reduce_rows(wpart + poff, rows, n, wout, nullptr, d.g[g].g_dw, s, 1, 0, 0, wgrad_accum(d));
+        const int rc = launch_reduce_rows(wpart + poff, rows, n, wout, nullptr, d.g[g].g_dw, s, wgrad_accum(d));
         if (rc) return rc;
         poff += n;
     }

@@ -1466,7 +1466,7 @@ bool fx_supported(const TfnasCellDesc& d) {
     // the fused kernels' expand / dgrad products exist in the split-bf16 x3 arithmetic only: a launch in another mode (the
     // descriptor's own, else the process default) takes the materialised route, so that one model runs ONE arithmetic in both
     // step kinds
-    if (((d.gemm_mode & TFNAS_GEMM_EXPLICIT) ? (d.gemm_mode & 7) : gemm_mode()) != TFNAS_GEMM_X3) return false;
+    if (gemm_mode_of(d) != TFNAS_GEMM_X3) return false;
     if (fx_fwd_lds(d, pl) > 160 * 1024) return false;
     // forward scratch in `part`: statistics partial rows | blobs | (top) xsum, C
     const size_t rows = (((size_t)pl.nig * 2 * d.M) + 63) & ~(size_t)63, blobs = ((size_t)pl.nchunks * pl.BLOB + 3) / 4;

@@ -32,26 +32,10 @@ __device__ __forceinline__ f32x4 stem_patch4(const float* __restrict__ img, cons
 
 // resident workgroups per CU the row-tiled GEMM kernels are compiled for (register cap 512 / n per lane): 5-/7-tile and
 // narrower variants
-#ifndef TFNAS_WGRAD_PF2
-#define TFNAS_WGRAD_PF2 false  /* prefetch distance 2 in the weight-gradient GEMMs (A/B) */
-#endif
-#ifndef TFNAS_LB_BIG
-#define TFNAS_LB_BIG 3
-#endif
-#ifndef TFNAS_LB_SMALL
-#define TFNAS_LB_SMALL 4
-#endif
+constexpr int kLbBig = 3, kLbSmall = 4;
 // the split-bf16 loop (MM != 0) keeps two chunks of raw operands and three A planes in registers: one resident workgroup less
-#ifndef TFNAS_LB_X3_BIG
-#define TFNAS_LB_X3_BIG 2
-#endif
-#ifndef TFNAS_LB_X3_SMALL
-#define TFNAS_LB_X3_SMALL 3
-#endif
-// (heavy: k_project_dgrad, whose BN3-backward transform keeps 40 table values per chunk pair live: 217-249 registers)
-constexpr int gemm_lb(int nt, int mm, bool heavy = false) {
-    return mm == 0 ? (nt >= 5 ? TFNAS_LB_BIG : TFNAS_LB_SMALL) : ((nt >= 5 || heavy) ? TFNAS_LB_X3_BIG : TFNAS_LB_X3_SMALL);
-}
+constexpr int kLbX3Big = 2, kLbX3Small = 3;
+constexpr int gemm_lb(int nt, int mm) { return mm == 0 ? (nt >= 5 ? kLbBig : kLbSmall) : (nt >= 5 ? kLbX3Big : kLbX3Small); }
 
 // raw registers of the two-phase loaders (gemm_core.h): what the load phase leaves for the transform phase
 struct Raw2 { f32x4 a, b; };             // two stream pieces (D | gate,  dOut | Pr,  dEh | E)
@@ -636,7 +620,7 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_project_wgrad(TfnasCellDe
         const f32x4 v = (k_a3[i] * r.a - k_ab[i]) - (r.b - k_mean[i]) * k_s[i];
         return (bok[i] && r0 + c * 16 + kl < r1) ? v : zero4();
     };
-    gemm_mainloop2<NT, false, false, false, TFNAS_WGRAD_PF2>(la, xa, lb, xb, nchunks, acc, lds);
+    gemm_mainloop2<NT, false, false, false, false>(la, xa, lb, xb, nchunks, acc, lds);
     // The gradient is [oc][mc] (mid channel fastest) and a lane's accumulator quad is 4 consecutive mid channels of one
     // output channel: one 16-byte store per quad (the four lane groups of an output channel then cover 64 contiguous
     // bytes) instead of four 4-byte stores that each scatter a wave over 64 different cache lines.
@@ -1077,7 +1061,7 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_expand_wgrad(TfnasCellDes
         if (STEM) return r;
         return (bok[i] && r0 + c * 16 + kl < r1) ? r : zero4();
     };
-    gemm_mainloop2<NT, false, false, false, TFNAS_WGRAD_PF2>(la, xa, lb, xb, nchunks, acc, lds);
+    gemm_mainloop2<NT, false, false, false, false>(la, xa, lb, xb, nchunks, acc, lds);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1134,43 +1118,70 @@ __global__ __launch_bounds__(256) void k_expand_wgrad_fix(TfnasCellDesc d, const
     }
 }
 
-// ============================================================================ host launchers
+// ============================================================================ host: launch plans and launchers
+// (gemm_plan_* fill a GemmPlan, kernels.h; the family's launcher carries it out: one dispatch, then the reductions)
 static const int kNtSmall[] = {1, 2, 3, 4, 5, 7};   // N extents that are channel counts (ic / oc)
+static constexpr int kGtLdsFloats[8] = {0, GT<1>::LDS_FLOATS, GT<2>::LDS_FLOATS, GT<3>::LDS_FLOATS, GT<4>::LDS_FLOATS,
+                                        GT<5>::LDS_FLOATS, 0, GT<7>::LDS_FLOATS};
 
-#define DISPATCH_NT(nt, ...)                                  \
-    switch (nt) {                                             \
-        case 1: { constexpr int NT = 1; __VA_ARGS__; } break; \
-        case 2: { constexpr int NT = 2; __VA_ARGS__; } break; \
-        case 3: { constexpr int NT = 3; __VA_ARGS__; } break; \
-        case 4: { constexpr int NT = 4; __VA_ARGS__; } break; \
-        case 5: { constexpr int NT = 5; __VA_ARGS__; } break; \
-        case 7: { constexpr int NT = 7; __VA_ARGS__; } break; \
-        default: return TFNAS_EINVAL;                         \
+#define NT_CASE(n, ...) case n: { constexpr int NT = n; __VA_ARGS__; } break;
+// the group-tiled families (column tiles cannot straddle groups): pick_nt_groups only returns 4, 5 or 7
+#define DISPATCH_NT_GROUPS(nt, ...)   \
+    switch (nt) {                     \
+        NT_CASE(4, __VA_ARGS__)       \
+        NT_CASE(5, __VA_ARGS__)       \
+        NT_CASE(7, __VA_ARGS__)       \
+        default: return TFNAS_EINVAL; \
     }
-// Arithmetic of the row-tiled 1x1-convolution GEMMs (gemm_x3.h): 6 = split-bf16 with six products per element pair (fp32-level
-// accuracy on the bf16 matrix pipe; the default), 0 = v_mfma_f32_16x16x4_f32, 3 = split-bf16 keeping the 2^-16 terms,
-// 1 = plain bf16.  tfnas_set_gemm_mode sets the process default (6 until then; the Python mirror seeds it from TFNAS_GEMM).
-static int g_gemm_mode = 6;
-static int g_gemm_everywhere = 0;      // TFNAS_GEMM_EVERYWHERE: no per-launch shape policy (tests compare every mode with the oracle)
-int gemm_mode() { return g_gemm_mode; }
-int set_gemm_mode(int m) {
-    const int base = m & ~TFNAS_GEMM_EVERYWHERE;
-    if (base != 0 && base != 1 && base != 3 && base != 6) return TFNAS_EINVAL;
-    g_gemm_mode = base;
-    g_gemm_everywhere = (m & TFNAS_GEMM_EVERYWHERE) ? 1 : 0;
-    return 0;
-}
-#define DISPATCH_MM(...) DISPATCH_MM_(gemm_mode(), __VA_ARGS__)
-#define DISPATCH_MM_(mode, ...)                               \
-    switch (mode) {                                    \
-        case 0: { constexpr int MM = 0; __VA_ARGS__; } break; \
-        case 1: { constexpr int MM = 1; __VA_ARGS__; } break; \
-        case 3: { constexpr int MM = 3; __VA_ARGS__; } break; \
+#define DISPATCH_NT(nt, ...)                         \
+    switch (nt) {                                    \
+        NT_CASE(1, __VA_ARGS__)                      \
+        NT_CASE(2, __VA_ARGS__)                      \
+        NT_CASE(3, __VA_ARGS__)                      \
+        default: DISPATCH_NT_GROUPS(nt, __VA_ARGS__) \
+    }
+#define DISPATCH_MM(mode, ...)                                 \
+    switch (mode) {                                            \
+        case 0: { constexpr int MM = 0; __VA_ARGS__; } break;  \
+        case 1: { constexpr int MM = 1; __VA_ARGS__; } break;  \
+        case 3: { constexpr int MM = 3; __VA_ARGS__; } break;  \
         default: { constexpr int MM = 6; __VA_ARGS__; } break; \
     }
 #define DISPATCH_ACT(act, ...)                                                        \
     if ((act) == TFNAS_ACT_RELU) { constexpr int ACT = TFNAS_ACT_RELU; __VA_ARGS__; } \
     else { constexpr int ACT = TFNAS_ACT_SWISH; __VA_ARGS__; }
+
+// Arithmetic of the row-tiled 1x1-convolution GEMMs (gemm_x3.h): 6 = split-bf16 with six products per element pair (fp32-level
+// accuracy on the bf16 matrix pipe; the default), 0 = v_mfma_f32_16x16x4_f32, 3 = split-bf16 keeping the 2^-16 terms,
+// 1 = plain bf16.  tfnas_set_gemm_mode sets the process default (6 until then; the Python mirror seeds it from TFNAS_GEMM),
+// with TFNAS_GEMM_EVERYWHERE: no per-launch shape policy (tests compare every mode with the oracle).
+static int g_gemm_mode = 6;
+int gemm_mode() { return g_gemm_mode & 7; }
+int set_gemm_mode(int m) {
+    const int base = m & ~TFNAS_GEMM_EVERYWHERE;
+    if (base != 0 && base != 1 && base != 3 && base != 6) return TFNAS_EINVAL;
+    g_gemm_mode = m;
+    return 0;
+}
+// the launch's mode word: the descriptor's own (TFNAS_GEMM_EXPLICIT) or the process default
+static inline int gemm_word(const TfnasCellDesc& d) { return (d.gemm_mode & TFNAS_GEMM_EXPLICIT) ? d.gemm_mode : g_gemm_mode; }
+int gemm_mode_of(const TfnasCellDesc& d) { return gemm_word(d) & 7; }
+// Which arithmetic this descriptor's launch of a pass runs.
+// Ragged mid widths (mc % 4 != 0 after the elasticity re-masking): the split-bf16 instantiations only have the aligned weight
+// loaders (the guarded ones cost ~50 registers, i.e. a resident workgroup), such launches keep the fp32 loop.
+// The data-gradient GEMMs gain little from the bf16 pipe (their K loops are bound by the BN3-backward transform / the chunk ->
+// group bookkeeping and, with one candidate or large images, by bytes): measured per cell at B = 128 (DESIGN.md section 4c), split-bf16
+// vs fp32 MFMA: all-candidate launches of the 14x14 / 7x7 cells 0.94-0.98x, 28x28 up to 1.19x, one-candidate launches 0.9-1.8x.
+// They keep the fp32 loop except where they won.
+static int gemm_arith(const TfnasCellDesc& d, bool dgrad) {
+    for (int g = 0; g < d.G; ++g)
+        if (d.g[g].mc & 3) return 0;
+    const int m = gemm_mode_of(d);
+    if (!dgrad || m == 0 || (gemm_word(d) & TFNAS_GEMM_EVERYWHERE)) return m;
+    if (m == 1) return m;                                  // plain bf16 is a reduced-precision MODE, not a policy: everywhere
+    return (d.G > 1 && d.Ho * d.Wo <= 196) ? m : 0;
+}
+static inline int gemm_slots(int nt, int mm) { return 256 * gemm_lb(nt, mm); }
 
 // kernels with a statistics epilogue: at most 1024 partial rows (k_reduce_rows folds 512 per round trip) and they must fit
 static size_t stats_row_cap(size_t row_floats) {
@@ -1184,7 +1195,7 @@ static size_t stats_row_cap(size_t row_floats) {
 // (~4096 workgroups in total) left the 14x14 / 7x7 cells with a nearly empty last round (e.g. 2.04 rounds -> 3: 68 %
 // efficient); this picks the gx that minimises the product, the larger gx on ties (finer dynamic balancing), subject to
 // `cap` (partial rows of the statistics epilogues must fit the scratch buffer and stay <= 1024).
-static int row_blocks(int rows, int other_blocks, size_t cap = 1u << 30, int slots = 1024, int max_gx = 1024) {
+static int row_blocks(int rows, int other_blocks, size_t cap, int slots, int max_gx = 1024) {
     const int nrt = cdiv(rows, 128);
     const int other = other_blocks > 0 ? other_blocks : 1;
     int lim = nrt;
@@ -1201,33 +1212,6 @@ static int row_blocks(int rows, int other_blocks, size_t cap = 1u << 30, int slo
         }
     }
     return best;
-}
-int gemm_mode();
-static inline int gemm_slots(int nt, int mode = -1) { return 256 * gemm_lb(nt, mode < 0 ? gemm_mode() : mode); }
-// ragged mid widths (mc % 4 != 0 after the elasticity re-masking): the split-bf16 instantiations only have the aligned weight
-// loaders (the guarded ones cost ~50 registers, i.e. a resident workgroup), such launches keep the fp32 loop
-// the launch's arithmetic: the descriptor's own mode (TFNAS_GEMM_EXPLICIT) or the process default
-static inline int gemm_mode_for(const TfnasCellDesc& d) {
-    for (int g = 0; g < d.G; ++g)
-        if (d.g[g].mc & 3) return 0;
-    if (d.gemm_mode & TFNAS_GEMM_EXPLICIT) return d.gemm_mode & 7;
-    return gemm_mode();
-}
-static inline bool gemm_everywhere(const TfnasCellDesc& d) {
-    return (d.gemm_mode & TFNAS_GEMM_EXPLICIT) ? (d.gemm_mode & TFNAS_GEMM_EVERYWHERE) != 0 : g_gemm_everywhere != 0;
-}
-// The data-gradient GEMMs gain little from the bf16 pipe (their K loops are bound by the BN3-backward transform / the chunk ->
-// group bookkeeping and, with one candidate or large images, by bytes): measured per cell at B = 128 (DESIGN.md section 4c), split-bf16
-// vs fp32 MFMA: all-candidate launches of the 14x14 / 7x7 cells 0.94-0.98x, 28x28 up to 1.19x, one-candidate launches 0.9-1.8x.
-// They keep the fp32 loop except where they won.
-static inline int gemm_mode_dgrad(const TfnasCellDesc& d) {
-    const int m = gemm_mode_for(d);
-    if (m == 0 || gemm_everywhere(d)) return m;
-    if (m == 1) return m;                                  // plain bf16 is a reduced-precision MODE, not a policy: everywhere
-    return (d.G > 1 && d.Ho * d.Wo <= 196) ? m : 0;
-}
-static inline int gemm_mode_fwd(const TfnasCellDesc& d, int /*hw*/) {
-    return gemm_mode_for(d);
 }
 
 // Column-tile width of the GEMMs whose N extent is the mid channels of EVERY group (tiles cannot straddle groups): the
@@ -1252,237 +1236,270 @@ static int pick_nt_groups(const TfnasCellDesc& d) {
     }
     return best;
 }
+// sums over the groups: tiles of `width` mid channels, widest group, floats of a [mc][n] weight per group
+static int group_tiles(const TfnasCellDesc& d, int width, int last_extra = 0) {
+    int t = 0;
+    for (int g = 0; g < d.G; ++g) t += cdiv(d.g[g].mcp + (g == d.G - 1 ? last_extra : 0), width);
+    return t;
+}
+static int max_mcp(const TfnasCellDesc& d) {
+    int m = 0;
+    for (int g = 0; g < d.G; ++g) m = d.g[g].mcp > m ? d.g[g].mcp : m;
+    return m;
+}
+static size_t mid_floats(const TfnasCellDesc& d, int n) {
+    size_t f = 0;
+    for (int g = 0; g < d.G; ++g) f += (size_t)d.g[g].mc * n;
+    return f;
+}
+// a plan whose N extent is a channel count (ic / oc): the width that pads it least
+static GemmPlan plan_cols(int n) {
+    GemmPlan p{};
+    p.nt = pick_nt(n, kNtSmall, 6);
+    p.tiles = cdiv(n, 16 * p.nt);
+    return p;
+}
+
+GemmPlan gemm_plan_expand_fwd(const TfnasCellDesc& d) {
+    GemmPlan p{};
+    p.var = d.mode == TFNAS_MODE_STEM ? GEMM_STEM : GEMM_PLAIN;
+    // stem: 32 output channels -> 32-wide tiles (a 64-wide tile would be half empty)
+    p.nt = p.var == GEMM_STEM ? (d.g[0].mcp <= 32 ? 2 : 4) : pick_nt_groups(d);
+    p.mm = gemm_arith(d, false);
+    p.tiles = group_tiles(d, 16 * p.nt);
+    p.grid = dim3(row_blocks(d.N * d.H * d.W, p.tiles, stats_row_cap(2 * (size_t)d.M), gemm_slots(p.nt, p.mm)), p.tiles);
+    return p;
+}
 
 int launch_expand_fwd(const TfnasCellDesc& d, const float* x, float* E, double* stats1, float* part,
                       hipStream_t s) {
     ProfScope _prof(TK_EXPAND_FWD, s);
-    // stem: 32 output channels -> 32-wide tiles (a 64-wide tile would be half empty)
-    const int nt = d.mode == TFNAS_MODE_STEM ? (d.g[0].mcp <= 32 ? 2 : 4) : pick_nt_groups(d);
-    int tiles = 0;
-    for (int g = 0; g < d.G; ++g) tiles += cdiv(d.g[g].mcp, 16 * nt);
-    const int mm = gemm_mode_fwd(d, d.H * d.W);
-    dim3 grid(row_blocks(d.N * d.H * d.W, tiles, stats_row_cap(2 * (size_t)d.M), gemm_slots(nt, mm)), tiles);
-    DISPATCH_MM_(mm, {
-        if (d.mode == TFNAS_MODE_STEM) {
-            if (nt == 2) hipLaunchKernelGGL((k_expand_fwd<2, true, MM>), grid, dim3(256), 0, s, d, x, E, part);
-            else hipLaunchKernelGGL((k_expand_fwd<4, true, MM>), grid, dim3(256), 0, s, d, x, E, part);
-        } else {
-            switch (nt) {
-                case 5: hipLaunchKernelGGL((k_expand_fwd<5, false, MM>), grid, dim3(256), 0, s, d, x, E, part); break;
-                case 7: hipLaunchKernelGGL((k_expand_fwd<7, false, MM>), grid, dim3(256), 0, s, d, x, E, part); break;
-                default: hipLaunchKernelGGL((k_expand_fwd<4, false, MM>), grid, dim3(256), 0, s, d, x, E, part); break;
-            }
-        }
+    const GemmPlan p = gemm_plan_expand_fwd(d);
+    DISPATCH_MM(p.mm, {
+        if (p.var == GEMM_STEM)
+            hipLaunchKernelGGL((p.nt == 2 ? k_expand_fwd<2, true, MM> : k_expand_fwd<4, true, MM>), p.grid, dim3(256), 0, s, d, x, E, part);
+        else
+            DISPATCH_NT_GROUPS(p.nt, { hipLaunchKernelGGL((k_expand_fwd<NT, false, MM>), p.grid, dim3(256), 0, s, d, x, E, part); })
     })
     _prof.stop();
-    return launch_reduce_rows(part, grid.x, 2 * d.M, 2 * (size_t)d.M, stats1, nullptr, s);
+    return launch_reduce_rows(part, p.grid.x, 2 * d.M, 2 * (size_t)d.M, stats1, nullptr, s);
 }
 
+// caps of the K-splits of the w-step's one-candidate launches (see gemm_plan_expand_dgrad); build flags, tools/README.md
 #ifndef TFNAS_WSPLIT_DGRAD
 #define TFNAS_WSPLIT_DGRAD 2
 #endif
 #ifndef TFNAS_WSPLIT_PFWD
 #define TFNAS_WSPLIT_PFWD 2
 #endif
-int launch_project_fwd(const TfnasCellDesc& d, const float* D, const float* gate, const double* stats2,
-                       float* Pr, double* stats3, float* part, hipStream_t s) {
-    ProfScope _prof(TK_PROJECT_FWD, s);
-    const int nt = pick_nt(d.oc, kNtSmall, 6), mm = gemm_mode_fwd(d, d.Ho * d.Wo);
-    int mcp_max = 0;
-    for (int g = 0; g < d.G; ++g) mcp_max = d.g[g].mcp > mcp_max ? d.g[g].mcp : mcp_max;
-    const int tiles = cdiv(d.oc, 16 * nt);
-    const int ncols2 = 2 * d.G * d.oc;
+GemmPlan gemm_plan_project_fwd(const TfnasCellDesc& d) {
+    GemmPlan p = plan_cols(d.oc);
+    p.mm = gemm_arith(d, false);
+    const int mcp_max = max_mcp(d), ncols2 = 2 * d.G * d.oc;
     const int Po = d.N * d.Ho * d.Wo, nrt = cdiv(Po, 128);
+    p.shm = (kGtLdsFloats[p.nt] + 2 * ((mcp_max + 15) & ~15)) * sizeof(float);
     // K-split for under-filled launches (sampled mode on the 14x14 / 7x7 cells: 150-400 workgroups walking 30-72
     // K-chunks back to back at ~2 us per chunk -- one workgroup per CU cannot hide the load latency)
     int nsplit = 1;
-    const int wgs = nrt * tiles * d.G, kch = cdiv(mcp_max, 16);
+    const int wgs = nrt * p.tiles * d.G, kch = cdiv(mcp_max, 16);
     if (wgs < 512 && kch >= 16 && (d.oc & 3) == 0 && d.oc <= 1024) {
         nsplit = cdiv(1024, wgs);
         if (nsplit > 4) nsplit = 4;
         if (nsplit > kch / 8) nsplit = kch / 8;
-        if (d.need_wgrad && d.G == 1 && nsplit > TFNAS_WSPLIT_PFWD) nsplit = TFNAS_WSPLIT_PFWD;      // (see expand_dgrad_splits)
+        if (d.need_wgrad && d.G == 1 && nsplit > TFNAS_WSPLIT_PFWD) nsplit = TFNAS_WSPLIT_PFWD;      // (see gemm_plan_expand_dgrad)
         const size_t per = (size_t)d.G * Po * d.oc, rows2 = 256 * (size_t)ncols2;
         while (nsplit > 1 && (nsplit - 1) * per + rows2 > TFNAS_PART_FLOATS) --nsplit;
     }
-    if (nsplit > 1) {
-        float* prp = part;
-        float* part2 = part + (size_t)(nsplit - 1) * d.G * Po * d.oc;
-        dim3 grid(nrt, tiles, d.G * nsplit);
-        DISPATCH_MM_(mm, DISPATCH_NT(nt, DISPATCH_ACT(d.act, {
-            const size_t shm = (GT<NT>::LDS_FLOATS + 2 * ((mcp_max + 15) & ~15)) * sizeof(float);
-            hipLaunchKernelGGL((k_project_fwd<NT, ACT, MM>), grid, dim3(256), shm, s, d, D, gate, stats2, Pr, part, nsplit, prp);
-        })))
-        int gx2 = cdiv(Po, 64);
-        if (gx2 > 256) gx2 = 256;
-        const int rps = cdiv(Po, gx2);
-        gx2 = cdiv(Po, rps);
-        hipLaunchKernelGGL(k_pr_reduce, dim3(gx2, d.G), dim3(256), 0, s, Pr, prp, nsplit - 1, d.G, Po, d.oc, rps, part2);
-        _prof.stop();
-        return launch_reduce_rows(part2, gx2, ncols2, (size_t)ncols2, stats3, nullptr, s);
-    }
-    dim3 grid(row_blocks(Po, tiles * d.G, stats_row_cap((size_t)ncols2), gemm_slots(nt, mm)), tiles, d.G);
-    DISPATCH_MM_(mm, DISPATCH_NT(nt, DISPATCH_ACT(d.act, {
-        const size_t shm = (GT<NT>::LDS_FLOATS + 2 * ((mcp_max + 15) & ~15)) * sizeof(float);
-        hipLaunchKernelGGL((k_project_fwd<NT, ACT, MM>), grid, dim3(256), shm, s, d, D, gate, stats2, Pr, part, 1,
-                           (float*)nullptr);
-    })))
-    _prof.stop();
-    return launch_reduce_rows(part, grid.x, ncols2, (size_t)ncols2, stats3, nullptr, s);
+    p.splits = nsplit;
+    p.parts = nsplit - 1;
+    // split: every split takes all row tiles; k_pr_reduce adds the partial products and writes the statistics rows
+    if (p.parts) p.grid = dim3(nrt, p.tiles, d.G * nsplit);
+    else p.grid = dim3(row_blocks(Po, p.tiles * d.G, stats_row_cap((size_t)ncols2), gemm_slots(p.nt, p.mm)), p.tiles, d.G);
+    int gx2 = cdiv(Po, 64);
+    if (gx2 > 256) gx2 = 256;
+    p.rps = cdiv(Po, gx2);
+    p.grid2 = dim3(cdiv(Po, p.rps), d.G);
+    return p;
 }
 
-#define TFNAS_FOLD_LAUNCH(NT_)                                                                                           \
-    hipLaunchKernelGGL((k_project_dgrad<NT_, MM, true>), grid, dim3(256),                                               \
-                       (GT<NT_>::LDS_FLOATS + 4 * ((d.oc + 15) & ~15)) * sizeof(float), s, d, dout, Pr, stats3, red3, wmix, dZ, \
-                       D, stats2, rec)
+int launch_project_fwd(const TfnasCellDesc& d, const float* D, const float* gate, const double* stats2,
+                       float* Pr, double* stats3, float* part, hipStream_t s) {
+    ProfScope _prof(TK_PROJECT_FWD, s);
+    const GemmPlan p = gemm_plan_project_fwd(d);
+    const int ncols2 = 2 * d.G * d.oc, Po = d.N * d.Ho * d.Wo;
+    // split: the partial products of splits 1.. go to prp = `part`, the statistics rows of k_pr_reduce behind them
+    float* prp = p.parts ? part : nullptr;
+    float* rows = part + (size_t)p.parts * d.G * Po * d.oc;
+    DISPATCH_MM(p.mm, DISPATCH_NT(p.nt, DISPATCH_ACT(d.act, {
+        hipLaunchKernelGGL((k_project_fwd<NT, ACT, MM>), p.grid, dim3(256), p.shm, s, d, D, gate, stats2, Pr, part, p.splits, prp);
+    })))
+    if (p.parts) hipLaunchKernelGGL(k_pr_reduce, p.grid2, dim3(256), 0, s, Pr, prp, p.parts, d.G, Po, d.oc, p.rps, rows);
+    _prof.stop();
+    return launch_reduce_rows(rows, p.parts ? p.grid2.x : p.grid.x, ncols2, (size_t)ncols2, stats3, nullptr, s);
+}
+
+GemmPlan gemm_plan_project_dgrad(const TfnasCellDesc& d, bool fold) {
+    GemmPlan p{};
+    p.var = fold ? GEMM_FOLD : GEMM_PLAIN;
+    p.nt = pick_nt_groups(d);
+    p.mm = gemm_arith(d, true);
+    p.tiles = group_tiles(d, 16 * p.nt);
+    p.grid = dim3(row_blocks(d.N * d.Ho * d.Wo, p.tiles, 1u << 30, gemm_slots(p.nt, p.mm)), p.tiles);
+    p.shm = (kGtLdsFloats[p.nt] + 4 * ((d.oc + 15) & ~15)) * sizeof(float);
+    return p;
+}
+
 int launch_project_dgrad(const TfnasCellDesc& d, const float* dout, const float* Pr, const double* stats3,
                          const double* red3, const float* wmix, float* dZ, hipStream_t s, const float* D,
                          const double* stats2, float* rec) {
     ProfScope _prof(TK_PROJECT_DGRAD, s);
-    const int nt = pick_nt_groups(d), mm = gemm_mode_dgrad(d);
-    int tiles = 0;
-    for (int g = 0; g < d.G; ++g) tiles += cdiv(d.g[g].mcp, 16 * nt);
-    dim3 grid(row_blocks(d.N * d.Ho * d.Wo, tiles, 1u << 30, gemm_slots(nt, mm)), tiles);
-    if (rec) {
-        if (!D || !stats2) return TFNAS_ENULL;
-        DISPATCH_MM_(mm, {
-            switch (nt) {                                   // (pick_nt_groups only returns 4, 5 or 7)
-                case 5: TFNAS_FOLD_LAUNCH(5); break;
-                case 7: TFNAS_FOLD_LAUNCH(7); break;
-                default: TFNAS_FOLD_LAUNCH(4); break;
-            }
-        })
-        return (int)hipGetLastError();
-    }
-    DISPATCH_MM_(mm, DISPATCH_NT(nt, {
-        const size_t shm = (GT<NT>::LDS_FLOATS + 4 * ((d.oc + 15) & ~15)) * sizeof(float);
-        hipLaunchKernelGGL((k_project_dgrad<NT, MM>), grid, dim3(256), shm, s, d, dout, Pr, stats3, red3, wmix, dZ);
+    if (rec && (!D || !stats2)) return TFNAS_ENULL;
+    const GemmPlan p = gemm_plan_project_dgrad(d, rec != nullptr);
+    DISPATCH_MM(p.mm, DISPATCH_NT_GROUPS(p.nt, {
+        if (p.var == GEMM_FOLD)
+            hipLaunchKernelGGL((k_project_dgrad<NT, MM, true>), p.grid, dim3(256), p.shm, s, d, dout, Pr, stats3, red3, wmix, dZ,
+                               D, stats2, rec);
+        else
+            hipLaunchKernelGGL((k_project_dgrad<NT, MM>), p.grid, dim3(256), p.shm, s, d, dout, Pr, stats3, red3, wmix, dZ);
     }))
     return (int)hipGetLastError();
 }
 
-static int pick_rows_per_split(int rows, int out_tiles, size_t out_size, int nt, size_t scratch = TFNAS_PART_FLOATS) {
+// K-splits of a weight-gradient plan (nt, tiles, out set): grid = (splits, mtiles, ztiles), `scratch` floats for the partial tiles
+static void plan_row_splits(GemmPlan& p, int rows, int mtiles, int ztiles, size_t scratch) {
     // ONE resident round: as many workgroups as the chip holds of this variant (256 CUs x wgrad_lb), never a second, mostly
     // empty round (cell 10: 55 splits x 6 tiles = 330 workgroups on 256 slots ran 2 x 65 us); at least 128 rows (8 K-chunks)
     // per split; partial tiles must fit the scratch
-    const int target = 256 * wgrad_lb(nt), min_rows = 128;
+    const int target = 256 * wgrad_lb(p.nt), min_rows = 128, out_tiles = mtiles * ztiles;
     int splits = target / (out_tiles > 0 ? out_tiles : 1);
-    const size_t cap = scratch / (out_size > 0 ? out_size : 1);
+    const size_t cap = scratch / (p.out > 0 ? p.out : 1);
     if ((size_t)splits > cap) splits = (int)cap;
     if (splits < 1) splits = 1;
     int rps = cdiv(rows, splits);
     if (rps < min_rows) rps = min_rows;
-    return ((rps + 15) / 16) * 16;
+    p.rps = ((rps + 15) / 16) * 16;
+    p.splits = cdiv(rows, p.rps);
+    p.grid = dim3(p.splits, mtiles, ztiles);
+}
+// the splits' partial weight gradients of every group -> its `dst` ([mc][n] floats per group, rows of p.out floats)
+static int reduce_group_wgrads(const TfnasCellDesc& d, const GemmPlan& p, const float* part, int n, float* TfnasGroup::*dst,
+                               hipStream_t s) {
+    size_t poff = 0;
+    for (int g = 0; g < d.G; ++g) {
+        const int cols = d.g[g].mc * n;
+        int rc = launch_reduce_rows(part + poff, p.splits, cols, p.out, nullptr, d.g[g].*dst, s, wgrad_accum(d));
+        if (rc) return rc;
+        poff += cols;
+    }
+    return (int)hipGetLastError();
+}
+
+GemmPlan gemm_plan_project_wgrad(const TfnasCellDesc& d) {
+    GemmPlan p = plan_cols(d.oc);
+    p.out = mid_floats(d, d.oc);
+    plan_row_splits(p, d.N * d.Ho * d.Wo, cdiv(max_mcp(d), 128), p.tiles * d.G, TFNAS_PART_FLOATS);
+    p.shm = (kGtLdsFloats[p.nt] + 5 * ((d.oc + 15) & ~15)) * sizeof(float);
+    return p;
 }
 
 int launch_project_wgrad(const TfnasCellDesc& d, const float* dout, const float* Pr, const float* D,
                          const float* gate, const double* stats2, const double* stats3, const double* red3,
                          const float* wmix, float* part, hipStream_t s) {
     ProfScope _prof(TK_PROJECT_WGRAD, s);
-    const int nt = pick_nt(d.oc, kNtSmall, 6);
-    const int Po = d.N * d.Ho * d.Wo;
-    int mcp_max = 0;
-    for (int g = 0; g < d.G; ++g) mcp_max = d.g[g].mcp > mcp_max ? d.g[g].mcp : mcp_max;
-    const int mtiles = cdiv(mcp_max, 128), ntiles = cdiv(d.oc, 16 * nt);
-    size_t out_size = 0;
-    for (int g = 0; g < d.G; ++g) out_size += (size_t)d.g[g].mc * d.oc;
-    const int rps = pick_rows_per_split(Po, mtiles * ntiles * d.G, out_size, nt);
-    dim3 grid(cdiv(Po, rps), mtiles, ntiles * d.G);
-    DISPATCH_NT(nt, DISPATCH_ACT(d.act, {
-        size_t shm = (GT<NT>::LDS_FLOATS + 5 * ((d.oc + 15) & ~15)) * sizeof(float);
-        hipLaunchKernelGGL((k_project_wgrad<NT, ACT>), grid, dim3(256), shm, s, d, dout, Pr, D, gate, stats2,
-                           stats3, red3, wmix, rps, ntiles, part, out_size);
+    const GemmPlan p = gemm_plan_project_wgrad(d);
+    DISPATCH_NT(p.nt, DISPATCH_ACT(d.act, {
+        hipLaunchKernelGGL((k_project_wgrad<NT, ACT>), p.grid, dim3(256), p.shm, s, d, dout, Pr, D, gate, stats2,
+                           stats3, red3, wmix, p.rps, p.tiles, part, p.out);
     }))
     _prof.stop();
-    size_t poff = 0;
-    for (int g = 0; g < d.G; ++g) {
-        const int n = d.g[g].mc * d.oc;
-        int rc = launch_reduce_rows(part + poff, grid.x, n, out_size, nullptr, d.g[g].g_proj, s, 1, 0, 0, wgrad_accum(d));
-        if (rc) return rc;
-        poff += n;
-    }
-    return (int)hipGetLastError();
-}
-
-// K-splits of expand dgrad: only when the (row tile x column tile) grid cannot fill the chip
-int expand_dgrad_splits(const TfnasCellDesc& d) {
-    const int nt = pick_nt(d.ic, kNtSmall, 6);
-    const int tiles = cdiv(d.N * d.H * d.W, 128) * cdiv(d.ic, 16 * nt);
-    if (tiles >= 512) return 1;
-    int nchunks = 0;
-    for (int g = 0; g < d.G; ++g) nchunks += cdiv(d.g[g].mcp, 16);
-    int ns = cdiv(1024, tiles);
-    if (ns > 16) ns = 16;
-    if (ns > nchunks / 4) ns = nchunks / 4;      // at least 4 K-chunks per split
-    // one-candidate launches of the weight step run beside three other queues: the chip is full anyway, and every extra split is
-    // one more [P][ic] partial written, read back and summed (k_dx_reduce).  Capped at 2 (round 6, four alternating bench pairs on
-    // one box: w-step 16.55 -> 16.37 ms; a cap of 1 loses: the 196-tile launches of the 14 x 14 cells then walk 40+ K-chunks each)
-    if (d.need_wgrad && d.G == 1 && ns > TFNAS_WSPLIT_DGRAD) ns = TFNAS_WSPLIT_DGRAD;
-    return ns < 1 ? 1 : ns;
+    return reduce_group_wgrads(d, p, part, d.oc, &TfnasGroup::g_proj, s);
 }
 
 // floats of the correction operator G | b
 size_t expand_gram_floats(const TfnasCellDesc& d) { return (size_t)(d.ic + 4) * d.ic; }
+static int mid_chunks(const TfnasCellDesc& d) { return group_tiles(d, 16); }      // K-chunks over all mid channels of all groups
+
+GemmPlan gemm_plan_expand_gram(const TfnasCellDesc& d, size_t scratch_floats) {
+    GemmPlan p{};
+    // policy (measured, B = 128, alternating bench runs): with the K of ONE candidate (the sampled launches of the w-step, the head)
+    // the single launch wins; with all eight candidates' K (4 000 mid channels: 8 dependent load rounds per wave) it is at best equal
+    // to the split-K GEMM + reduction (a 4-wave version: alpha-step +0.3 ms), which stays for those launches
+    if (!(d.route & TFNAS_ROUTE_GRAM2) && mid_floats(d, 1) <= GRAM1_MAX_K) {
+        // one launch, no K-split partials, no reduction (k_gram1); the scratch is not used
+        p.var = GEMM_GRAM1;
+        p.grid = dim3(cdiv(d.ic, 32), cdiv(d.ic + 1, 16));
+        return p;
+    }
+    p = plan_cols(d.ic);
+    const size_t gsz = expand_gram_floats(d);
+    const int mchunks = mid_chunks(d), mtiles = cdiv(d.ic + 1, 128);
+    int splits = cdiv(512, mtiles * p.tiles);
+    if (splits > mchunks / 4) splits = mchunks / 4;               // at least 4 K-chunks per split
+    if ((size_t)splits > scratch_floats / gsz) splits = (int)(scratch_floats / gsz);
+    if (splits < 1) splits = 1;
+    p.rps = cdiv(mchunks, splits);
+    p.splits = cdiv(mchunks, p.rps);
+    p.grid = dim3(p.splits, mtiles, p.tiles);
+    return p;
+}
 
 // G | b -> gram ([ic+4][ic] floats); `scratch` holds the K-split partials (scratch_floats available)
 int launch_expand_gram(const TfnasCellDesc& d, const float* cb1, float* scratch, size_t scratch_floats, float* gram,
                        hipStream_t s) {
     ProfScope _prof(TK_SMALL, s);
-    int mtot = 0;
-    for (int g = 0; g < d.G; ++g) mtot += d.g[g].mc;
-    // policy (measured, B = 128, alternating bench runs): with the K of ONE candidate (the sampled launches of the w-step, the head)
-    // the single launch wins; with all eight candidates' K (4 000 mid channels: 8 dependent load rounds per wave) it is at best equal
-    // to the split-K GEMM + reduction (a 4-wave version: alpha-step +0.3 ms), which stays for those launches
-    if (!(d.route & TFNAS_ROUTE_GRAM2) && mtot <= GRAM1_MAX_K) {
-        // one launch, no K-split partials, no reduction (k_gram1); `scratch` is not used
+    const GemmPlan p = gemm_plan_expand_gram(d, scratch_floats);
+    if (p.var == GEMM_GRAM1) {
         for (int g = 0; g < d.G; ++g)
             if (d.g[g].mc < 1) return TFNAS_EINVAL;
-        const dim3 grid(cdiv(d.ic, 32), cdiv(d.ic + 1, 16));
-        if (d.mode == TFNAS_MODE_HEAD) hipLaunchKernelGGL(k_gram1<16>, grid, dim3(1024), 0, s, d, cb1, gram);
-        else hipLaunchKernelGGL(k_gram1<4>, grid, dim3(256), 0, s, d, cb1, gram);
+        if (d.mode == TFNAS_MODE_HEAD) hipLaunchKernelGGL(k_gram1<16>, p.grid, dim3(1024), 0, s, d, cb1, gram);
+        else hipLaunchKernelGGL(k_gram1<4>, p.grid, dim3(256), 0, s, d, cb1, gram);
         return (int)hipGetLastError();
     }
-    const int nt = pick_nt(d.ic, kNtSmall, 6);
-    const int ng = 1;
-    const size_t gsz = (size_t)(d.ic + 4) * d.ic;
-    int mchunks = 0;                                              // K-chunks of the operator
-    for (int g = 0; g < d.G; ++g) mchunks += cdiv(d.g[g].mcp, 16);
-    const int mtiles = cdiv(d.ic + 1, 128), ntiles = cdiv(d.ic, 16 * nt);
-    int splits = cdiv(512, mtiles * ntiles * ng);
-    if (splits > mchunks / 4) splits = mchunks / 4;               // at least 4 K-chunks per split
-    if ((size_t)splits * ng > scratch_floats / gsz) splits = (int)(scratch_floats / gsz / ng);
-    if (splits < 1) splits = 1;
-    if (scratch_floats < gsz * ng) return TFNAS_ERANGE;
-    const int cps = cdiv(mchunks, splits);
-    splits = cdiv(mchunks, cps);
-    dim3 grid(splits * ng, mtiles, ntiles);
-    DISPATCH_NT(nt, { hipLaunchKernelGGL(k_expand_gram<NT>, grid, dim3(256), 0, s, d, cb1, cps, splits, scratch); })
+    const size_t gsz = expand_gram_floats(d);
+    if (scratch_floats < gsz) return TFNAS_ERANGE;
+    DISPATCH_NT(p.nt, { hipLaunchKernelGGL(k_expand_gram<NT>, p.grid, dim3(256), 0, s, d, cb1, p.rps, p.splits, scratch); })
     _prof.stop();
-    return launch_reduce_rows(scratch, splits, (int)gsz, gsz, nullptr, gram, s, ng, (size_t)splits * gsz, gsz);
+    return launch_reduce_rows(scratch, p.splits, (int)gsz, gsz, nullptr, gram, s);
+}
+
+GemmPlan gemm_plan_expand_dgrad(const TfnasCellDesc& d, bool split, int nsl) {
+    GemmPlan p = plan_cols(d.ic);
+    p.mm = gemm_arith(d, true);
+    const int P = d.N * d.H * d.W, out_tiles = cdiv(P, 128) * p.tiles;
+    // K-splits: only when the (row tile x column tile) grid cannot fill the chip
+    p.splits = 1;
+    if (split && nsl < 0 && out_tiles < 512) {
+        const int mchunks = mid_chunks(d);
+        int ns = cdiv(1024, out_tiles);
+        if (ns > 16) ns = 16;
+        if (ns > mchunks / 4) ns = mchunks / 4;      // at least 4 K-chunks per split
+        // one-candidate launches of the weight step run beside three other queues: the chip is full anyway, and every extra split is
+        // one more [P][ic] partial written, read back and summed (k_dx_reduce).  Capped at 2 (round 6, four alternating bench pairs on
+        // one box: w-step 16.55 -> 16.37 ms; a cap of 1 loses: the 196-tile launches of the 14 x 14 cells then walk 40+ K-chunks each)
+        if (d.need_wgrad && d.G == 1 && ns > TFNAS_WSPLIT_DGRAD) ns = TFNAS_WSPLIT_DGRAD;
+        p.splits = ns < 1 ? 1 : ns;
+    }
+    p.grid = dim3(row_blocks(P, p.tiles * p.splits, 1u << 30, gemm_slots(p.nt, p.mm), 4096), p.tiles, p.splits);
+    p.parts = nsl >= 0 ? nsl + 1 : (p.splits > 1 ? p.splits : 0);
+    size_t blocks = cdiv64((size_t)P * d.ic / 4, 256 * 2);
+    p.grid2 = dim3((unsigned)(blocks > 2048 ? 2048 : blocks));
+    return p;
 }
 
 int launch_expand_dgrad(const TfnasCellDesc& d, const float* dEh, const float* x, const float* cb1, const float* gram,
                         const float* dout, const float* wmix, float* dx, float* dxp, hipStream_t s,
-                        const float* add_src, const float* add_scale) {
-    ProfScope _prof(TK_EXPAND_DGRAD, s);
-    const int nt = pick_nt(d.ic, kNtSmall, 6);
-    const int tiles = cdiv(d.ic, 16 * nt);
-    const int nsplit = dxp ? expand_dgrad_splits(d) : 1;
-    const int ng = 1;
-    const int mm = gemm_mode_dgrad(d);
-    dim3 grid(row_blocks(d.N * d.H * d.W, tiles * nsplit * ng, 1u << 30, gemm_slots(nt, mm), 4096), tiles, nsplit * ng);
-    DISPATCH_MM_(mm, DISPATCH_NT(nt, {
-        hipLaunchKernelGGL((k_expand_dgrad<NT, MM>), grid, dim3(256), 0, s, d, dEh, x, cb1, gram, dout, wmix, dx, dxp, nsplit,
-                           add_src, add_scale);
-    }))
-    _prof.stop();
-    if (nsplit > 1) {
+                        const float* add_src, const float* add_scale, int nsl) {
+    const GemmPlan p = gemm_plan_expand_dgrad(d, dxp != nullptr, nsl);
+    {
+        ProfScope _prof(TK_EXPAND_DGRAD, s);
+        DISPATCH_MM(p.mm, DISPATCH_NT(p.nt, {
+            hipLaunchKernelGGL((k_expand_dgrad<NT, MM>), p.grid, dim3(256), 0, s, d, dEh, x, cb1, gram, dout, wmix, dx, dxp, p.splits,
+                               add_src, add_scale, nsl);
+        }))
+    }
+    if (p.parts) {
         ProfScope _p2(TK_SMALL, s);
-        const size_t n4 = (size_t)d.N * d.H * d.W * d.ic / 4;
-        size_t blocks = cdiv64(n4, 256 * 2);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(k_dx_reduce, dim3((unsigned)blocks, ng), dim3(256), 0, s, d, dxp, nsplit, gram, dout, wmix, dx,
-                           add_src, add_scale);
+        hipLaunchKernelGGL(k_dx_reduce, p.grid2, dim3(256), 0, s, d, dxp, p.parts, gram, dout, wmix, dx, add_src, add_scale);
     }
     return (int)hipGetLastError();
 }
@@ -1492,84 +1509,49 @@ int launch_expand_dgrad(const TfnasCellDesc& d, const float* dEh, const float* x
 int launch_expand_dgrad_x(const TfnasCellDesc& d, const float* x, const float* cb1, const float* gram, const float* dout,
                           const float* wmix, float* dx, float* dxp, int nsl, hipStream_t s, const float* add_src,
                           const float* add_scale) {
-    {
-        ProfScope _prof(TK_EXPAND_DGRAD, s);
-        const int nt = pick_nt(d.ic, kNtSmall, 6);
-        const int tiles = cdiv(d.ic, 16 * nt);
-        const int mm = gemm_mode_dgrad(d);
-        dim3 grid(row_blocks(d.N * d.H * d.W, tiles, 1u << 30, gemm_slots(nt, mm), 4096), tiles, 1);
-        DISPATCH_MM_(mm, DISPATCH_NT(nt, {
-            hipLaunchKernelGGL((k_expand_dgrad<NT, MM>), grid, dim3(256), 0, s, d, (const float*)nullptr, x, cb1, gram, dout, wmix,
-                               dx, dxp, 1, add_src, add_scale, nsl);
-        }))
-    }
-    ProfScope _p2(TK_SMALL, s);
-    const size_t n4 = (size_t)d.N * d.H * d.W * d.ic / 4;
-    size_t blocks = cdiv64(n4, 256 * 2);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_dx_reduce, dim3((unsigned)blocks, 1), dim3(256), 0, s, d, dxp, nsl + 1, gram, dout, wmix, dx, add_src,
-                       add_scale);
-    return (int)hipGetLastError();
+    return launch_expand_dgrad(d, nullptr, x, cb1, gram, dout, wmix, dx, dxp, s, add_src, add_scale, nsl);
 }
 
-// Expand weight gradient without reading E (Gram form, k_expand_wgrad<XG>) where E is at least 100 MB (measured alone at
-// B = 128, DESIGN.md section 4d: cell 0 0.33 -> 0.24 ms, cells 1 / 2 equal; from 28 x 28 on E comes from the last-level cache and the
-// extension rows + the fix-up launch cost more than the second stream: cell 10 0.08 -> 0.11 ms); TFNAS_ROUTE_XG_OFF: never,
-// TFNAS_ROUTE_XG_ALL: wherever the shape allows (tests); every choice is compared with the oracle (tests/test_gpu_cell.py)
-static bool expand_wgrad_xg(const TfnasCellDesc& d) {
-    if ((d.route & TFNAS_ROUTE_XG_OFF) || d.mode == TFNAS_MODE_STEM || (d.ic & 3) != 0) return false;
-    return (d.route & TFNAS_ROUTE_XG_ALL) || (size_t)d.N * d.H * d.W * d.M * sizeof(float) >= ((size_t)100 << 20);
-}
+// XG: the double sums of the splits live in the top of `part` (2 floats per element, 16-byte aligned)
+static size_t xg_red_floats(const GemmPlan& p) { return p.var == GEMM_XG ? 2 * p.out + 4 : 0; }
 
-static int launch_expand_wgrad_fix(const TfnasCellDesc& d, const float* cb1, const double* red, size_t out_main, hipStream_t s) {
-    ProfScope _p2(TK_EXPAND_WGRAD, s);
-    hipLaunchKernelGGL(k_expand_wgrad_fix, dim3((unsigned)cdiv64(out_main, 64)), dim3(256), 0, s, d, cb1, red, out_main);
-    return (int)hipGetLastError();
+GemmPlan gemm_plan_expand_wgrad(const TfnasCellDesc& d) {
+    GemmPlan p = plan_cols(d.ic);
+    // Expand weight gradient without reading E (Gram form, k_expand_wgrad<XG>) where E is at least 100 MB (measured alone at
+    // B = 128, DESIGN.md section 4d: cell 0 0.33 -> 0.24 ms, cells 1 / 2 equal; from 28 x 28 on E comes from the last-level cache and the
+    // extension rows + the fix-up launch cost more than the second stream: cell 10 0.08 -> 0.11 ms); TFNAS_ROUTE_XG_OFF: never,
+    // TFNAS_ROUTE_XG_ALL: wherever the shape allows (tests); every choice is compared with the oracle (tests/test_gpu_cell.py)
+    const int P = d.N * d.H * d.W;
+    if (d.mode == TFNAS_MODE_STEM) p.var = GEMM_STEM;
+    else if (!(d.route & TFNAS_ROUTE_XG_OFF) && (d.ic & 3) == 0 &&
+             ((d.route & TFNAS_ROUTE_XG_ALL) || (size_t)P * d.M * sizeof(float) >= ((size_t)100 << 20)))
+        p.var = GEMM_XG;
+    const int next = p.var == GEMM_XG ? d.ic + 1 : 0;               // extension rows behind the last group's
+    p.out_main = mid_floats(d, d.ic);
+    p.out = p.out_main + (size_t)next * d.ic;
+    plan_row_splits(p, P, group_tiles(d, 128, next), p.tiles, TFNAS_PART_FLOATS - xg_red_floats(p));
+    return p;
 }
 
 int launch_expand_wgrad(const TfnasCellDesc& d, const float* dEh, const float* E, const float* cb1,
                         const float* x, float* part, hipStream_t s) {
     ProfScope _prof(TK_EXPAND_WGRAD, s);
-    const int nt = pick_nt(d.ic, kNtSmall, 6);
-    const int P = d.N * d.H * d.W;
-    const bool xg = expand_wgrad_xg(d);
-    if (!xg && !E) return TFNAS_ENULL;
-    const int next = xg ? d.ic + 1 : 0;                             // extension rows behind the last group's
-    int mtiles = 0;
-    for (int g = 0; g < d.G; ++g) mtiles += cdiv(d.g[g].mcp + (g == d.G - 1 ? next : 0), 128);
-    const int ntiles = cdiv(d.ic, 16 * nt);
-    size_t out_main = 0;
-    for (int g = 0; g < d.G; ++g) out_main += (size_t)d.g[g].mc * d.ic;
-    const size_t out_size = out_main + (size_t)next * d.ic;
-    // XG: the double sums of the splits live in the top of `part` (2 floats per element, 16-byte aligned)
-    const size_t red_floats = xg ? 2 * out_size + 4 : 0;
-    if (red_floats + out_size > TFNAS_PART_FLOATS) return TFNAS_ERANGE;
-    const int rps = pick_rows_per_split(P, mtiles * ntiles, out_size, nt, TFNAS_PART_FLOATS - red_floats);
-    dim3 grid(cdiv(P, rps), mtiles, ntiles);
-    DISPATCH_NT(nt, {
-        if (d.mode == TFNAS_MODE_STEM)
-            hipLaunchKernelGGL((k_expand_wgrad<NT, true, false>), grid, dim3(256), 0, s, d, dEh, E, cb1, x, rps, part, out_size,
-                               out_main);
-        else if (xg)
-            hipLaunchKernelGGL((k_expand_wgrad<NT, false, true>), grid, dim3(256), 0, s, d, dEh, E, cb1, x, rps, part, out_size,
-                               out_main);
-        else
-            hipLaunchKernelGGL((k_expand_wgrad<NT, false, false>), grid, dim3(256), 0, s, d, dEh, E, cb1, x, rps, part, out_size,
-                               out_main);
+    const GemmPlan p = gemm_plan_expand_wgrad(d);
+    const size_t red_floats = xg_red_floats(p);
+    if (p.var != GEMM_XG && !E) return TFNAS_ENULL;
+    if (red_floats + p.out > TFNAS_PART_FLOATS) return TFNAS_ERANGE;
+    if (p.var == GEMM_STEM && p.nt != 2) return TFNAS_EINVAL;      // ic = 27 (tfnas_cell_plan): plan_cols gives the stem 2
+    DISPATCH_NT(p.nt, {
+        auto k = p.var == GEMM_XG ? k_expand_wgrad<NT, false, true> : k_expand_wgrad<NT, false, false>;
+        if (p.var == GEMM_STEM) k = k_expand_wgrad<2, true, false>;
+        hipLaunchKernelGGL(k, p.grid, dim3(256), 0, s, d, dEh, E, cb1, x, p.rps, part, p.out, p.out_main);
     })
     _prof.stop();
-    if (xg) {
-        double* red = reinterpret_cast<double*>((uintptr_t)(part + TFNAS_PART_FLOATS - red_floats + 3) & ~(uintptr_t)15);
-        int rc = launch_reduce_rows(part, grid.x, (int)out_size, out_size, red, nullptr, s);
-        if (rc) return rc;
-        return launch_expand_wgrad_fix(d, cb1, red, out_main, s);
-    }
-    size_t poff = 0;
-    for (int g = 0; g < d.G; ++g) {
-        const int n = d.g[g].mc * d.ic;
-        int rc = launch_reduce_rows(part + poff, grid.x, n, out_size, nullptr, d.g[g].g_expand, s, 1, 0, 0, wgrad_accum(d));
-        if (rc) return rc;
-        poff += n;
-    }
+    if (p.var != GEMM_XG) return reduce_group_wgrads(d, p, part, d.ic, &TfnasGroup::g_expand, s);
+    double* red = reinterpret_cast<double*>((uintptr_t)(part + TFNAS_PART_FLOATS - red_floats + 3) & ~(uintptr_t)15);
+    int rc = launch_reduce_rows(part, p.splits, (int)p.out, p.out, red, nullptr, s);
+    if (rc) return rc;
+    ProfScope _p2(TK_EXPAND_WGRAD, s);
+    hipLaunchKernelGGL(k_expand_wgrad_fix, dim3((unsigned)cdiv64(p.out_main, 64)), dim3(256), 0, s, d, cb1, red, p.out_main);
     return (int)hipGetLastError();
 }

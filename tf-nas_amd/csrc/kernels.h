@@ -33,8 +33,34 @@ static inline bool route_side(const TfnasCellDesc& d) { return !(d.route & TFNAS
 static inline int wgrad_accum(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_ACCUM_WGRAD) ? 1 : 0; }
 
 // gemm_kernels.hip
-int gemm_mode();            // arithmetic of the row-tiled GEMMs (tfnas_hip.h: TFNAS_GEMM_*)
+int gemm_mode();            // arithmetic of the row-tiled GEMMs (tfnas_hip.h: TFNAS_GEMM_*): the process default ...
 int set_gemm_mode(int m);
+int gemm_mode_of(const TfnasCellDesc& d);   // ... and the descriptor's own (TFNAS_GEMM_EXPLICIT), else that default
+// What one 1x1-convolution GEMM family launches, chosen once by the family's planner (gemm_plan_*: a pure function of the
+// descriptor and the few facts the launcher gets from its arguments); the launcher carries it out: one dispatch, then the reductions.
+enum GemmVariant { GEMM_PLAIN, GEMM_STEM, GEMM_XG, GEMM_FOLD, GEMM_GRAM1 };
+struct GemmPlan {
+    GemmVariant var;        // stem im2col operand / Gram-form expand wgrad / FOLD epilogue / one-launch Gram operator
+    int mm;                 // arithmetic of this launch (TFNAS_GEMM_*; the families with the fp32 loop only: 0)
+    int nt, tiles;          // column-tile width in 16-column MFMA tiles, column tiles of the N extent
+    int splits;             // K-splits of the GEMM launch (1: none)
+    int rps;                // K extent of a split: rows (weight gradients), 16-channel chunks (expand_gram); project_fwd: rows per
+                            // k_pr_reduce workgroup
+    int parts;              // partial tiles the family's own reduction kernel sums (k_pr_reduce, k_dx_reduce); 0: not launched
+    dim3 grid, grid2;       // of the GEMM, of that reduction kernel
+    size_t shm;             // dynamic LDS bytes of the GEMM
+    size_t out, out_main;   // weight gradients: floats of one split's partial output; of which the groups' own gradients (the
+                            // rest: the extension rows of GEMM_XG)
+};
+GemmPlan gemm_plan_expand_fwd(const TfnasCellDesc& d);
+GemmPlan gemm_plan_project_fwd(const TfnasCellDesc& d);
+GemmPlan gemm_plan_project_dgrad(const TfnasCellDesc& d, bool fold);       // fold: rec is given
+GemmPlan gemm_plan_project_wgrad(const TfnasCellDesc& d);
+GemmPlan gemm_plan_expand_gram(const TfnasCellDesc& d, size_t scratch_floats);
+// split: dxp is given (room for the K-split partials; tfnas_cell_ws sizes it from this plan's `splits`).  nsl >= 0: the fused
+// per-image route -- dxp[0 .. nsl) already hold partial sums, the GEMM adds one more partial tile and is never split
+GemmPlan gemm_plan_expand_dgrad(const TfnasCellDesc& d, bool split, int nsl = -1);
+GemmPlan gemm_plan_expand_wgrad(const TfnasCellDesc& d);
 int launch_expand_fwd(const TfnasCellDesc& d, const float* x, float* E, double* stats1, float* part,
                       hipStream_t s);
 int launch_project_fwd(const TfnasCellDesc& d, const float* D, const float* gate, const double* stats2,
@@ -56,11 +82,10 @@ int launch_project_wgrad(const TfnasCellDesc& d, const float* dout, const float*
 size_t expand_gram_floats(const TfnasCellDesc& d);
 int launch_expand_gram(const TfnasCellDesc& d, const float* cb1, float* scratch, size_t scratch_floats, float* gram,
                        hipStream_t s);
+// (nsl >= 0: the fused route's form, dEh unused -- launch_expand_dgrad_x below)
 int launch_expand_dgrad(const TfnasCellDesc& d, const float* dEh, const float* x, const float* cb1, const float* gram,
                         const float* dout, const float* wmix, float* dx, float* dxp, hipStream_t s,
-                        const float* add_src = nullptr, const float* add_scale = nullptr);
-int expand_dgrad_splits(const TfnasCellDesc& d);
-
+                        const float* add_src = nullptr, const float* add_scale = nullptr, int nsl = -1);
 int launch_expand_dgrad_x(const TfnasCellDesc& d, const float* x, const float* cb1, const float* gram, const float* dout,
                           const float* wmix, float* dx, float* dxp, int nsl, hipStream_t s, const float* add_src = nullptr,
                           const float* add_scale = nullptr);
@@ -166,11 +191,10 @@ int launch_head_pool(const TfnasCellDesc& d, const float* E, const double* stats
 int launch_head_bwd(const TfnasCellDesc& d, const float* E, const double* stats1, const float* dpooled, float* dEh,
                     double* red1, float* part, hipStream_t s);
 // out[c] = sum_{b<nb} part[b*stride + c]  (double and/or float output); the deterministic replacement of atomics
-// nbatch > 1: `nbatch` independent reductions in one launch (blockIdx.y): batch b reads part + b*in_stride and writes
-// out + b*out_stride.  accum != 0: the float output is added to what out_f already holds (out_f[c] += (float)sum: the
+// accum != 0: the float output is added to what out_f already holds (out_f[c] += (float)sum: the
 // weight-gradient outputs of a TFNAS_CELL_ACCUM_WGRAD launch; the double output is always overwritten)
 int launch_reduce_rows(const float* part, int nb, int ncols, size_t stride, double* out_d, float* out_f,
-                       hipStream_t s, int nbatch = 1, size_t in_stride = 0, size_t out_stride = 0, int accum = 0);
+                       hipStream_t s, int accum = 0);
 /* One `part` scratch region = TFNAS_PART_ALLOC floats (16 MiB): TFNAS_PART_FLOATS for per-workgroup partial rows / split-K
    tiles; the last TFNAS_TAIL_SLOTS words are reserved (they held the ticket counters of the removed "last workgroup reduces"
    epilogues; the size of the region is part of the workspace ABI and stays). */

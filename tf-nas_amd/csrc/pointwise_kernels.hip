@@ -723,21 +723,22 @@ int launch_reduce_bn1(const TfnasCellDesc& d, const float* part, int nb, const d
 }
 
 int launch_reduce_rows(const float* part, int nb, int ncols, size_t stride, double* out_d, float* out_f,
-                       hipStream_t s, int nbatch, size_t in_stride, size_t out_stride, int accum) {
+                       hipStream_t s, int accum) {
     ProfScope _prof(TK_REDUCE_ROWS, s);
-    const bool al4 = (ncols & 3) == 0 && (stride & 3) == 0 && ((uintptr_t)part & 15) == 0 && (in_stride & 3) == 0;
-    const unsigned nby = nbatch > 1 ? (unsigned)nbatch : 1u;
+    // (one reduction per launch: the kernels' batch index blockIdx.y and their batch strides stay 0)
+    const bool al4 = (ncols & 3) == 0 && (stride & 3) == 0 && ((uintptr_t)part & 15) == 0;
+    const size_t in_stride = 0, out_stride = 0;
     if (al4 && nb <= 128 && ncols >= 1024)
-        hipLaunchKernelGGL(k_reduce_rows_wide, dim3(cdiv(ncols, 128), nby), dim3(256), 0, s, part, nb, ncols, stride, out_d,
+        hipLaunchKernelGGL(k_reduce_rows_wide, dim3(cdiv(ncols, 128), 1), dim3(256), 0, s, part, nb, ncols, stride, out_d,
                            out_f, in_stride, out_stride, accum);
     else if (al4 && nb > 64)
-        hipLaunchKernelGGL(k_reduce_rows_q<4>, dim3(cdiv(ncols, 16), nby), dim3(256), 0, s, part, nb, ncols, stride, out_d, out_f,
+        hipLaunchKernelGGL(k_reduce_rows_q<4>, dim3(cdiv(ncols, 16), 1), dim3(256), 0, s, part, nb, ncols, stride, out_d, out_f,
                            in_stride, out_stride, accum);
     else if (ncols <= 2048 && nb > 256)
-        hipLaunchKernelGGL(k_reduce_rows<4>, dim3(cdiv(ncols, 4), nby), dim3(256), 0, s, part, nb, ncols, stride, out_d, out_f,
+        hipLaunchKernelGGL(k_reduce_rows<4>, dim3(cdiv(ncols, 4), 1), dim3(256), 0, s, part, nb, ncols, stride, out_d, out_f,
                            in_stride, out_stride, accum);
     else
-        hipLaunchKernelGGL(k_reduce_rows<8>, dim3(cdiv(ncols, 8), nby), dim3(256), 0, s, part, nb, ncols, stride, out_d, out_f,
+        hipLaunchKernelGGL(k_reduce_rows<8>, dim3(cdiv(ncols, 8), 1), dim3(256), 0, s, part, nb, ncols, stride, out_d, out_f,
                            in_stride, out_stride, accum);
     return (int)hipGetLastError();
 }
