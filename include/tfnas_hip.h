@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-/* 4, additive: TFNAS_CELL_ACCUM_WGRAD (weight gradients added to their destinations, per launch) and tfnas_path_set_wgrad_accum.
+/* 4, additive: tfnas_cls_ce_ex / tfnas_cls_reduce (the derived network's retrain tail: label smoothing, rank, forward-only form,
+ * device-side upstream gradient, running meter).
+ * 4, additive: TFNAS_CELL_ACCUM_WGRAD (weight gradients added to their destinations, per launch) and tfnas_path_set_wgrad_accum.
  * 4 (round 6): every route switch of a launch lives in its descriptor (TfnasCellDesc.route: TFNAS_ROUTE_*); the library reads no
  * environment variable at launch time (the TFNAS_* variables only seed the Python-side defaults, functions.route_from_env).
  * tfnas_cell_route() + TfnasCellDesc.fwd_route: a backward refuses a descriptor whose route differs from the forward's.
@@ -334,6 +336,33 @@ int tfnas_cls_ce(int N, int C, int K, const float *pooled, const float *W, const
                  float *logits, float *loss_n, float *dlogits, float *dpooled, void *stream);
 int tfnas_cls_wgrad(int npath, int N, int C, int K, const float *const *pooled, const float *const *dlogits,
                     const float *const *loss_n, float loss_scale, float *dW, float *db, float *loss, void *stream);
+/* The same tail for the derived network's retrain path (train_eval.py:228-293 with CrossEntropyLabelSmooth, :72-85,126), again one
+ * launch per image-wise part and one per reduction, for ONE path.
+ * tfnas_cls_ce_ex = tfnas_cls_ce with a label-smoothing factor eps in [0, 1) (num_classes == K) and the target's rank:
+ *   loss_n[n]     = lse - (1 - eps) logits[n][t] - (eps / K) sum_k logits[n][k]            (t = target[n], lse = logsumexp_k logits[n])
+ *   dlogits[n][k] = scale * (softmax(logits[n])[k] - (1 - eps) [k == t] - eps / K);   dpooled[n][c] = sum_k dlogits[n][k] W[k][c]
+ *   rank[n]       = #{k: logits[n][k] > logits[n][t]} + #{k < t: logits[n][k] == logits[n][t]}
+ * so top-1 is rank < 1 and top-5 is rank < 5 without a topk.  TIE RULE: among equal logits the lower class index ranks first (exactly
+ * one class has rank 0); torch.topk promises no order among ties, so the two can differ on a row whose target logit is tied.
+ * eps == 0 gives logits, loss_n, dlogits and dpooled bit-identical to tfnas_cls_ce.  A target outside [0, K) (compared on all 64
+ * bits) is FLAGGED, not skipped: loss_n[n] = NaN, rank[n] = -1, that image's dlogits and dpooled rows are zero, and no load or store
+ * is indexed by it.  dlogits == NULL && dpooled == NULL is the forward-only form (validation): the gradient phase and its LDS are
+ * skipped; exactly one of them NULL is TFNAS_EINVAL, as is eps outside [0, 1).  Limits as tfnas_cls_ce: C % 4 == 0, 4 <= C <= 4096,
+ * K <= 4096, LDS (C + K + KG * C floats, KG = min(8, K, 1024 / (C / 4)), 0 when forward-only) <= 64 KiB else TFNAS_ERANGE.
+ * tfnas_cls_reduce, everything that sums over the N images of that launch:
+ *   dW[k][c] (=|+=) g * sum_n dlogits[n][k] pooled[n][c];   db[k] (=|+=) g * sum_n dlogits[n][k]
+ *   g = *gscale, a DEVICE scalar -- the upstream d loss of a backward pass, no host read -- or 1 when gscale is NULL;
+ *   accumulate = 1 adds to what dW / db hold, 0 overwrites.  dW == NULL && db == NULL: metrics only (pooled / dlogits unused).
+ *   out[4]   = {mean loss_n, #(rank < 1), #(rank < 5), #(rank < 0: invalid targets)} as floats (NULL: not wanted)
+ *   meter[5] += {sum loss_n, #(rank < 1), #(rank < 5), N, #invalid} in double (NULL: none): a running epoch meter, added by one
+ *   thread in a fixed order with ordinary loads and stores -- launches that share a meter must be ordered by their stream, and the
+ *   host reads it once per epoch.  An invalid target makes the mean and the meter's loss sum NaN.
+ * TFNAS_ENULL: loss_n / rank missing, only some of (dW, db, pooled, dlogits) given, or no destination at all.  Fixed summation
+ * orders, no atomics. */
+int tfnas_cls_ce_ex(int N, int C, int K, const float *pooled, const float *W, const float *bias, const int64_t *target, float scale,
+                    float eps, float *logits, float *loss_n, int32_t *rank, float *dlogits, float *dpooled, void *stream);
+int tfnas_cls_reduce(int N, int C, int K, const float *pooled, const float *dlogits, const float *loss_n, const int32_t *rank,
+                     const float *gscale, int accumulate, float *dW, float *db, float *out, double *meter, void *stream);
 /* dst[i] += src[i], count floats (a multiple of 4): the second path's share of a shared parameter's gradient. */
 int tfnas_add_into(float *dst, const float *src, uint64_t count, void *stream);
 

@@ -7,6 +7,11 @@
 // and the start of their backward, when nothing else is on the chip.  Here: ONE launch per path for everything that depends on one
 // image (logits, loss, d logits, d pooled) and ONE launch for what sums over images and paths (dW, db, the loss scalar).
 // Deterministic: fixed summation orders, no atomics.
+//
+// The derived network's retrain path (reference: train_eval.py:228-293 with CrossEntropyLabelSmooth, :72-85,126) runs the same two
+// bodies in their EX form: label smoothing, the target's rank (top-1 / top-5 without a topk), NaN / rank -1 on an out-of-range label,
+// a forward-only form for validation, and a reduction that scales by a device-resident upstream gradient, can accumulate, and keeps
+// an epoch's running sums on the device (k_cls_ce_ex, k_cls_reduce).  The search step's instantiations are unchanged.
 #include "tfnas_dev.h"
 #include "kernels.h"
 #include "prof.h"
@@ -16,12 +21,20 @@
 // in LDS; wave w takes classes w, w + 16, ... in batches of CB with every W load of a batch in flight before the first FMA, lanes
 // stride the C features in float4 pieces; softmax / loss in one wave; then d pooled = d logits . W with the K classes split over
 // KG thread groups (a thread owns four feature columns x one class range, partial sums combined through LDS in group order).
+//
+// EX (the retrain tail): smoothing factor eps, loss_n = lse - (1 - eps) l_t - (eps / K) sum_k l_k and d logits = scale (softmax -
+// (1 - eps) [k == t] - eps / K), both written as the hard-target value plus an eps term that is skipped when eps == 0 (bit-identical
+// to the plain form then); rank[n] = #{k: l_k > l_t} + #{k < t: l_k == l_t} (ties go to the lower class index, so exactly one class
+// has rank 0) from the same single-wave pass as the sum of exp, sum_k l_k from the pass that takes the max; a target outside [0, K)
+// gives loss_n = NaN, rank = -1 and zero gradient rows, and nothing is ever indexed by it; d pooled == NULL (then d logits is too):
+// forward only, the kernel ends after the softmax wave and the launch asks for no [KG][C] LDS.
 constexpr int CLS_CB = 4, CLS_T = 1024;
-__global__ __launch_bounds__(CLS_T) void k_cls_ce(int C, int K, int KG, const float* __restrict__ pooled, const float* __restrict__ W,
-                                                  const float* __restrict__ bias, const int64_t* __restrict__ target, float scale,
-                                                  float* __restrict__ logits, float* __restrict__ loss_n,
-                                                  float* __restrict__ dlogits, float* __restrict__ dpooled) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
+template <bool EX>
+__device__ __forceinline__ void cls_ce_body(float* sm, int C, int K, int KG, const float* __restrict__ pooled,
+                                            const float* __restrict__ W, const float* __restrict__ bias,
+                                            const int64_t* __restrict__ target, float scale, float eps, float* __restrict__ logits,
+                                            float* __restrict__ loss_n, int32_t* __restrict__ rank, float* __restrict__ dlogits,
+                                            float* __restrict__ dpooled) {
     float* xs = sm;                          // [C]
     float* lg = sm + C;                      // [K rounded up to 4] logits, then d logits
     float* pp = lg + ((K + 3) & ~3);         // [KG][C] partial d pooled
@@ -65,25 +78,62 @@ __global__ __launch_bounds__(CLS_T) void k_cls_ce(int C, int K, int KG, const fl
     __syncthreads();
     if (wave == 0) {
         // log-softmax over K classes in one wave: max, sum of exp, in a fixed (lane-strided, then butterfly) order
-        float m = -INFINITY;
-        for (int k = lane; k < K; k += 64) m = fmaxf(m, lg[k]);
+        float m = -INFINITY, sl = 0.f;
+        for (int k = lane; k < K; k += 64) {
+            m = fmaxf(m, lg[k]);
+            if constexpr (EX) sl += lg[k];
+        }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        const int64_t tl = target[n];
+        int t = (int)tl;
+        bool tok = t >= 0 && t < K;                          // (ignore_index-style targets contribute nothing; the reference has none)
+        float lt = 0.f;
+        int rk = 0;
+        if constexpr (EX) {
+            sl = wave_sum(sl);
+            tok = tl >= 0 && tl < (int64_t)K;                // (on all 64 bits: 2^32 + 3 is not class 3)
+            t = tok ? (int)tl : -1;
+            if (tok) lt = lg[t];
+        }
         float s = 0.f;
-        for (int k = lane; k < K; k += 64) s += expf(lg[k] - m);
+        for (int k = lane; k < K; k += 64) {
+            s += expf(lg[k] - m);
+            if constexpr (EX) rk += (lg[k] > lt || (lg[k] == lt && k < t)) ? 1 : 0;
+        }
         s = wave_sum(s);
         const float lse = m + logf(s);
-        const int t = (int)target[n];
-        const bool tok = t >= 0 && t < K;                    // (ignore_index-style targets contribute nothing; the reference has none)
-        if (lane == 0) loss_n[n] = tok ? lse - lg[t] : 0.f;
+        if constexpr (EX) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) rk += __shfl_xor(rk, o, 64);
+            if (lane == 0) {
+                float v = lse - lt;
+                if (eps != 0.f) v += eps * (lt - sl * (1.f / (float)K));
+                loss_n[n] = tok ? v : NAN;
+                rank[n] = tok ? rk : -1;
+            }
+        } else {
+            if (lane == 0) loss_n[n] = tok ? lse - lg[t] : 0.f;
+        }
         const float inv = 1.f / s;
+        const bool bwd = !EX || dpooled != nullptr;
+        const float epsk = eps / (float)K;
         for (int k = lane; k < K; k += 64) {
             const float l = lg[k];
             logits[(size_t)n * K + k] = l;
-            const float g = tok ? scale * (expf(l - m) * inv - (k == t ? 1.f : 0.f)) : 0.f;
-            dlogits[(size_t)n * K + k] = g;
-            lg[k] = g;
+            if (bwd) {
+                float d = expf(l - m) * inv - (k == t ? 1.f : 0.f);
+                if constexpr (EX) {
+                    if (eps != 0.f) d += (k == t ? eps : 0.f) - epsk;
+                }
+                const float g = tok ? scale * d : 0.f;
+                dlogits[(size_t)n * K + k] = g;
+                lg[k] = g;
+            }
         }
+    }
+    if constexpr (EX) {
+        if (!dpooled) return;                                // (a kernel argument: the whole workgroup leaves together)
     }
     __syncthreads();
     const int nq = C >> 2, kper = (K + KG - 1) / KG;
@@ -120,6 +170,23 @@ __global__ __launch_bounds__(CLS_T) void k_cls_ce(int C, int K, int KG, const fl
     }
 }
 
+__global__ __launch_bounds__(CLS_T) void k_cls_ce(int C, int K, int KG, const float* __restrict__ pooled, const float* __restrict__ W,
+                                                  const float* __restrict__ bias, const int64_t* __restrict__ target, float scale,
+                                                  float* __restrict__ logits, float* __restrict__ loss_n,
+                                                  float* __restrict__ dlogits, float* __restrict__ dpooled) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    cls_ce_body<false>(sm, C, K, KG, pooled, W, bias, target, scale, 0.f, logits, loss_n, nullptr, dlogits, dpooled);
+}
+
+__global__ __launch_bounds__(CLS_T) void k_cls_ce_ex(int C, int K, int KG, const float* __restrict__ pooled,
+                                                     const float* __restrict__ W, const float* __restrict__ bias,
+                                                     const int64_t* __restrict__ target, float scale, float eps,
+                                                     float* __restrict__ logits, float* __restrict__ loss_n, int32_t* __restrict__ rank,
+                                                     float* __restrict__ dlogits, float* __restrict__ dpooled) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    cls_ce_body<true>(sm, C, K, KG, pooled, W, bias, target, scale, eps, logits, loss_n, rank, dlogits, dpooled);
+}
+
 struct ClsPaths {
     const float* pooled[2];
     const float* dlogits[2];
@@ -128,29 +195,33 @@ struct ClsPaths {
 
 // dW[k][c] = sum over paths and images of d logits[n][k] * pooled[n][c]  (blockIdx.y < ceil(K / 4): four classes x 256 features per
 // workgroup, image loop unrolled by 8);  the last blockIdx.y row: db[k] = sum d logits[.][k] and loss = scale * sum loss_n.
-__global__ __launch_bounds__(256) void k_cls_wgrad(int npath, int N, int C, int K, ClsPaths P, float loss_scale,
-                                                   float* __restrict__ dW, float* __restrict__ db, float* __restrict__ loss) {
-    __shared__ float dl[256][4];
-    const int tid = threadIdx.x;
-    const int kgroups = (K + 3) >> 2;
-    if ((int)blockIdx.y == kgroups) {
-        if (blockIdx.x != 0) return;
-        for (int k = tid; k < K; k += 256) {
-            double s = 0.0;
-            for (int p = 0; p < npath; ++p)
-                for (int n = 0; n < N; ++n) s += (double)P.dlogits[p][(size_t)n * K + k];
-            db[k] = (float)s;
-        }
-        if (tid < 64) {
-            double s = 0.0;
-            for (int p = 0; p < npath; ++p)
-                for (int n = tid; n < N; n += 64) s += (double)P.loss_n[p][n];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-            if (tid == 0 && loss) loss[0] = (float)(s * (double)loss_scale);
-        }
-        return;
+// EX (k_cls_reduce): every sum is multiplied by gs (the upstream d loss, read from the device) and stored or, with acc, added to
+// what the destination holds.
+template <bool EX>
+__device__ __forceinline__ void cls_put(float* dst, float v, float gs, int acc) {
+    if constexpr (EX) {
+        v *= gs;
+        if (acc) v += *dst;
     }
+    *dst = v;
+}
+
+// db[k] = sum over paths and images of d logits[n][k], one thread per class, images in order, in double
+template <bool EX>
+__device__ __forceinline__ void cls_db_row(int npath, int N, int K, const ClsPaths& P, float gs, int acc, float* __restrict__ db) {
+    for (int k = threadIdx.x; k < K; k += 256) {
+        double s = 0.0;
+        for (int p = 0; p < npath; ++p)
+            for (int n = 0; n < N; ++n) s += (double)P.dlogits[p][(size_t)n * K + k];
+        cls_put<EX>(db + k, (float)s, gs, acc);
+    }
+}
+
+// the four-class x 256-feature tile of dW of workgroup (blockIdx.x, blockIdx.y)
+template <bool EX>
+__device__ __forceinline__ void cls_dw_tile(float (*dl)[4], int npath, int N, int C, int K, const ClsPaths& P, float gs, int acc,
+                                            float* __restrict__ dW) {
+    const int tid = threadIdx.x;
     const int k0 = blockIdx.y * 4, c = blockIdx.x * 256 + tid;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     for (int p = 0; p < npath; ++p) {
@@ -190,11 +261,85 @@ __global__ __launch_bounds__(256) void k_cls_wgrad(int npath, int N, int C, int 
         }
     }
     if (c < C) {
-        if (k0 + 0 < K) dW[(size_t)(k0 + 0) * C + c] = a0;
-        if (k0 + 1 < K) dW[(size_t)(k0 + 1) * C + c] = a1;
-        if (k0 + 2 < K) dW[(size_t)(k0 + 2) * C + c] = a2;
-        if (k0 + 3 < K) dW[(size_t)(k0 + 3) * C + c] = a3;
+        if (k0 + 0 < K) cls_put<EX>(dW + (size_t)(k0 + 0) * C + c, a0, gs, acc);
+        if (k0 + 1 < K) cls_put<EX>(dW + (size_t)(k0 + 1) * C + c, a1, gs, acc);
+        if (k0 + 2 < K) cls_put<EX>(dW + (size_t)(k0 + 2) * C + c, a2, gs, acc);
+        if (k0 + 3 < K) cls_put<EX>(dW + (size_t)(k0 + 3) * C + c, a3, gs, acc);
     }
+}
+
+__global__ __launch_bounds__(256) void k_cls_wgrad(int npath, int N, int C, int K, ClsPaths P, float loss_scale,
+                                                   float* __restrict__ dW, float* __restrict__ db, float* __restrict__ loss) {
+    __shared__ float dl[256][4];
+    const int tid = threadIdx.x;
+    const int kgroups = (K + 3) >> 2;
+    if ((int)blockIdx.y == kgroups) {
+        if (blockIdx.x != 0) return;
+        cls_db_row<false>(npath, N, K, P, 1.f, 0, db);
+        if (tid < 64) {
+            double s = 0.0;
+            for (int p = 0; p < npath; ++p)
+                for (int n = tid; n < N; n += 64) s += (double)P.loss_n[p][n];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (tid == 0 && loss) loss[0] = (float)(s * (double)loss_scale);
+        }
+        return;
+    }
+    cls_dw_tile<false>(dl, npath, N, C, K, P, 1.f, 0, dW);
+}
+
+// The retrain tail's reduction over the images of ONE path.  With dW / db: the same grid and tiles as k_cls_wgrad (blockIdx.y <
+// ceil(K / 4)) plus the last row; without (metrics only): that row alone, one workgroup.  The row's first wave sums loss_n in double
+// and counts rank < 1, rank < 5 and rank < 0 (lane-strided, then butterfly: a fixed order), and its first thread writes out[4] =
+// {mean loss, top-1 count, top-5 count, invalid count} and adds {sum loss_n, top-1, top-5, N, invalid} to the running meter with
+// ordinary loads and stores -- launches that share a meter are ordered by their stream.
+__global__ __launch_bounds__(256) void k_cls_reduce(int N, int C, int K, ClsPaths P, const int32_t* __restrict__ rank,
+                                                    const float* __restrict__ gscale, int acc, float* __restrict__ dW,
+                                                    float* __restrict__ db, float* __restrict__ out, double* __restrict__ meter) {
+    __shared__ float dl[256][4];
+    const int tid = threadIdx.x;
+    const int kgroups = dW ? (K + 3) >> 2 : 0;
+    const float gs = gscale ? gscale[0] : 1.f;
+    if ((int)blockIdx.y == kgroups) {
+        if (blockIdx.x != 0) return;
+        if (db) cls_db_row<true>(1, N, K, P, gs, acc, db);
+        if (tid < 64 && (out || meter)) {
+            double s = 0.0;
+            int c1 = 0, c5 = 0, bad = 0;
+            for (int n = tid; n < N; n += 64) {
+                s += (double)P.loss_n[0][n];
+                const int r = rank[n];
+                bad += r < 0 ? 1 : 0;
+                c1 += (r >= 0 && r < 1) ? 1 : 0;
+                c5 += (r >= 0 && r < 5) ? 1 : 0;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                s += __shfl_xor(s, o, 64);
+                c1 += __shfl_xor(c1, o, 64);
+                c5 += __shfl_xor(c5, o, 64);
+                bad += __shfl_xor(bad, o, 64);
+            }
+            if (tid == 0) {
+                if (out) {
+                    out[0] = (float)(s / (double)N);
+                    out[1] = (float)c1;
+                    out[2] = (float)c5;
+                    out[3] = (float)bad;
+                }
+                if (meter) {
+                    meter[0] += s;
+                    meter[1] += (double)c1;
+                    meter[2] += (double)c5;
+                    meter[3] += (double)N;
+                    meter[4] += (double)bad;
+                }
+            }
+        }
+        return;
+    }
+    cls_dw_tile<true>(dl, 1, N, C, K, P, gs, acc, dW);
 }
 
 // dst += src (n floats, a multiple of 4): the second bi-sampling path's share of a shared parameter's gradient
@@ -223,6 +368,50 @@ extern "C" int tfnas_cls_ce(int N, int C, int K, const float* pooled, const floa
     if (shm > 64 * 1024) return TFNAS_ERANGE;
     hipLaunchKernelGGL(k_cls_ce, dim3(N), dim3(CLS_T), shm, s, C, K, KG, pooled, W, bias, target, scale, logits, loss_n, dlogits,
                        dpooled);
+    return (int)hipGetLastError();
+}
+
+extern "C" int tfnas_cls_ce_ex(int N, int C, int K, const float* pooled, const float* W, const float* bias, const int64_t* target,
+                               float scale, float eps, float* logits, float* loss_n, int32_t* rank, float* dlogits, float* dpooled,
+                               void* stream) {
+    if (!pooled || !W || !target || !logits || !loss_n || !rank) return TFNAS_ENULL;
+    if (N < 1 || K < 1 || K > 4096 || C < 4 || C > 4096) return TFNAS_ERANGE;
+    if (C & 3) return TFNAS_EINVAL;
+    if ((dlogits == nullptr) != (dpooled == nullptr)) return TFNAS_EINVAL;       // both (training) or neither (forward only)
+    if (!(eps >= 0.f && eps < 1.f)) return TFNAS_EINVAL;
+    int KG = 0;
+    if (dpooled) {                                           // (as tfnas_cls_ce)
+        KG = CLS_T / (C >> 2);
+        if (KG < 1) KG = 1;
+        if (KG > 8) KG = 8;
+        if (KG > K) KG = K;
+    }
+    const size_t shm = ((size_t)C + ((K + 3) & ~3) + (size_t)KG * C) * sizeof(float);
+    if (shm > 64 * 1024) return TFNAS_ERANGE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    ProfScope _prof(TK_SMALL, s);
+    hipLaunchKernelGGL(k_cls_ce_ex, dim3(N), dim3(CLS_T), shm, s, C, K, KG, pooled, W, bias, target, scale, eps, logits, loss_n, rank,
+                       dlogits, dpooled);
+    return (int)hipGetLastError();
+}
+
+extern "C" int tfnas_cls_reduce(int N, int C, int K, const float* pooled, const float* dlogits, const float* loss_n,
+                                const int32_t* rank, const float* gscale, int accumulate, float* dW, float* db, float* out,
+                                double* meter, void* stream) {
+    const bool grads = dW || db;
+    if (!loss_n || !rank) return TFNAS_ENULL;
+    if (grads && (!dW || !db || !pooled || !dlogits)) return TFNAS_ENULL;
+    if (!grads && !out && !meter) return TFNAS_ENULL;        // nothing to write
+    if (N < 1 || K < 1 || K > 4096 || C < 1 || C > 4096) return TFNAS_ERANGE;
+    if (accumulate != 0 && accumulate != 1) return TFNAS_EINVAL;
+    ClsPaths P = {};
+    P.pooled[0] = pooled;
+    P.dlogits[0] = dlogits;
+    P.loss_n[0] = loss_n;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    ProfScope _prof(TK_SMALL, s);
+    const dim3 grid = grads ? dim3(cdiv(C, 256), cdiv(K, 4) + 1) : dim3(1, 1);
+    hipLaunchKernelGGL(k_cls_reduce, grid, dim3(256), 0, s, N, C, K, P, rank, gscale, accumulate, dW, db, out, meter);
     return (int)hipGetLastError();
 }
 

@@ -6,8 +6,10 @@
 keys identical, incl. BatchNorm running statistics), ``forward(x) -> logits``, ``get_lookup_latency(x)`` and ``config``.  Every
 block -- stems, MBConv blocks with AFFINE BatchNorm, running statistics in train / eval mode and drop-connect, the feature-mix
 head -- runs on the HIP kernels of the search path (``tfnas_mbconv_fwd/bwd``, ``tfnas_head_affine_fwd/bwd``: the affine part is
-folded into the per-channel statistics tables, csrc/bn_affine.hip); dropout, the classifier GEMM and the loss are torch ops.
-``CrossEntropyLabelSmooth`` and ``train_step`` / ``validate`` restate train_eval.py:72-85, 228-293.
+folded into the per-channel statistics tables, csrc/bn_affine.hip); dropout is a torch op, and so are the classifier GEMM and
+the loss inside ``forward``.  ``CrossEntropyLabelSmooth`` and ``train_step`` / ``validate`` restate train_eval.py:72-85, 228-293;
+there the classifier, the (label-smoothed) loss, their gradients and top-1 / top-5 are the retrain tail's HIP launches
+(tail.RetrainTailFn, ``FUSED_TAIL``) whenever ``fused_tail_eligible`` says the model and the criterion are what those compute.
 """
 import os
 
@@ -79,7 +81,8 @@ class _DerivedBase(nn.Module):
             self._head_plan = CellPlan(fm.in_channels, 4, 1, fm.act_func, [_HeadBlock(fm)], mode=_lib.MODE_HEAD, modes=self.hip_modes)
         return HeadAffineFn.apply(self._head_plan, x, fm.bn, self.training, fm.conv.weight, fm.bn.weight, fm.bn.bias)
 
-    def forward(self, x):
+    def features(self, x):
+        """Everything in front of the classifier: stem -> stages -> head -> dropout, [N, 1280]."""
         x = self._stem(x)
         for stage in self._stages():
             for block in stage:
@@ -87,7 +90,10 @@ class _DerivedBase(nn.Module):
         x = self._head(x)                                   # feature_mix_layer + global_avg_pooling, [N, 1280]
         if self.dropout_rate > 0.0:
             x = F.dropout(x, p=self.dropout_rate, training=self.training)
-        return self.classifier(x)
+        return x
+
+    def forward(self, x):
+        return self.classifier(self.features(x))
 
     def get_lookup_latency(self, x):
         """Sum of the looked-up block latencies (model_eval.py:133-212); ``x`` only provides the input resolution."""
@@ -206,6 +212,67 @@ DIRECT_GRADS = True          # (tests flip these two module flags to compare wit
 LAZY_JOIN = True
 
 
+# the classifier + loss + top-k tail of train_step / validate on the HIP launches of tail.RetrainTailFn (tests flip it to compare with
+# the torch route)
+FUSED_TAIL = True
+
+
+def _has_hooks(m):
+    return bool(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, '_backward_pre_hooks', None))
+
+
+def _fused_tail_plan(model, criterion, validating=False):
+    """(derived network, eps) when the fused retrain tail computes exactly what ``criterion(model(x), target)`` would, else None."""
+    core = model
+    if not isinstance(core, _DerivedBase):
+        # a wrapper's own forward is skipped by the fused route (features + tail are called on the network itself): only look
+        # through one whose forward is nothing but ``self.module(x)`` -- nn.DataParallel on at most one device
+        core = getattr(model, 'module', None)
+        if not (isinstance(core, _DerivedBase) and isinstance(model, nn.DataParallel) and len(model.device_ids) <= 1):
+            return None
+    lin = core.classifier.linear
+    W, b = lin.weight, lin.bias
+    if b is None or any(_has_hooks(m) for m in (model, core, core.classifier, lin)):
+        return None
+    for p in (W, b):
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.device != W.device:
+            return None
+    trainable = W.requires_grad and b.requires_grad
+    frozen = not W.requires_grad and not b.requires_grad
+    if not (trainable or (validating and frozen)):
+        return None
+    from .tail import cls_shapes_ok
+    K = lin.out_features
+    if not cls_shapes_ok(lin.in_features, K):
+        return None
+    if isinstance(criterion, CrossEntropyLabelSmooth):
+        if type(criterion) is not CrossEntropyLabelSmooth or criterion.num_classes != K or _has_hooks(criterion):
+            return None
+        eps = criterion.epsilon
+    elif type(criterion) is nn.CrossEntropyLoss:
+        if criterion.weight is not None or criterion.ignore_index != -100 or criterion.reduction != 'mean' or _has_hooks(criterion):
+            return None
+        eps = criterion.label_smoothing
+    elif validating and (criterion is None or criterion is F.cross_entropy):
+        eps = 0.0
+    else:
+        return None
+    eps = float(eps)
+    if not 0.0 <= eps < 1.0:
+        return None
+    return core, eps
+
+
+def fused_tail_eligible(model, criterion, validating=False):
+    """True when train_step (``validating``: validate) may run classifier + loss + top-k on the retrain tail's HIP launches:
+    the model is a derived network (or nn.DataParallel on one device around one) without forward / backward hooks on the way;
+    classifier weight and bias are contiguous CUDA fp32 and both trainable (validate: or both frozen); in_features % 4 == 0,
+    in_features and num_classes <= 4096, LDS <= 64 KiB; and the criterion is ``CrossEntropyLabelSmooth`` with num_classes == K,
+    or ``nn.CrossEntropyLoss`` with no class weights, the default ignore_index and mean reduction (eps = its label_smoothing),
+    or -- validate only -- None / ``F.cross_entropy``.  Anything else takes the torch route untouched."""
+    return _fused_tail_plan(model, criterion, validating) is not None
+
+
 class RetrainState:
     """Flat weight / gradient / momentum arenas of the derived network (path.WeightArena) + the fused step tail of the search
     path: ``.grad`` of every parameter is a view into ONE gradient buffer (autograd accumulates in place), so a data-parallel
@@ -318,13 +385,15 @@ class RetrainState:
         opt._opt_called = True
 
 
-def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None, fused=True):
+def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None, fused=True, meter=None):
     """One iteration of train_eval.py:228-252 (forward, label-smoothed loss, backward, clip, SGD); with a process group the
     gradients are averaged with ONE all-reduce of the flat gradient arena before clipping (one process per GPU instead of apex
     DDP).  ``fused`` (GPU models with a plain torch.optim.SGD): RetrainState -- gradient arena + tfnas_sgd_clip_step; otherwise
-    torch's clip_grad_norm_ + optimizer.step()."""
+    torch's clip_grad_norm_ + optimizer.step().  Classifier + loss run on the fused retrain tail when ``FUSED_TAIL`` and
+    ``fused_tail_eligible``; ``meter`` (a tail.DeviceMeter) collects loss / top-1 / top-5 of the step on the device."""
     import torch.distributed as dist
     model.train()
+    tail_plan = _fused_tail_plan(model, criterion) if FUSED_TAIL and x.is_cuda else None
     st = None
     if fused and x.is_cuda and RetrainState.fusable(optimizer, model):
         st = getattr(model, '_retrain_state', None)
@@ -333,8 +402,16 @@ def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None
             object.__setattr__(model, '_retrain_state', st)         # (not a submodule / buffer: stays out of state_dict)
         st.begin()
     try:
-        logits = model(x)
-        loss = criterion(logits, target)
+        if tail_plan is not None:
+            from .tail import RetrainTailFn
+            core, eps = tail_plan
+            lin = core.classifier.linear
+            loss, logits, _ = RetrainTailFn.apply(core.features(x), lin.weight, lin.bias, target, eps, core.hip_modes, meter)
+        else:
+            logits = model(x)
+            loss = criterion(logits, target)
+            if meter is not None:
+                meter.add(loss, logits, target)
         if st is None:
             optimizer.zero_grad()
         loss.backward()
@@ -359,23 +436,26 @@ def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None
 
 def validate(model, val_queue, criterion=None):
     """train_eval.py:271-293: eval mode (running statistics), top-1 / top-5 / loss."""
-    from .search import AverageMeter, accuracy
-    criterion = criterion or F.cross_entropy
-    objs, top1, top5 = AverageMeter(), AverageMeter(), AverageMeter()
+    from .tail import DeviceMeter, retrain_tail_forward
     model.eval()
     dev = next(model.parameters()).device
+    tail_plan = _fused_tail_plan(model, criterion, validating=True) if FUSED_TAIL and dev.type == 'cuda' else None
+    criterion = criterion or F.cross_entropy
+    meter = DeviceMeter(dev)                                # ONE device -> host copy after the loop instead of one per batch
     for x, target in val_queue:
         x, target = x.to(dev, non_blocking=True), target.to(dev, non_blocking=True)
         with torch.no_grad():
-            logits = model(x)
-            loss = criterion(logits, target)
-        p1, p5 = accuracy(logits, target, topk=(1, 5))
-        vals = torch.stack([loss.float(), p1, p5]).tolist()
-        n = x.size(0)
-        objs.update(vals[0], n)
-        top1.update(vals[1], n)
-        top5.update(vals[2], n)
-    return top1.avg, top5.avg, objs.avg
+            if tail_plan is not None:
+                core, eps = tail_plan
+                lin = core.classifier.linear
+                retrain_tail_forward(core.features(x), lin.weight, lin.bias, target, eps, meter)
+            else:
+                logits = model(x)
+                meter.add(criterion(logits, target), logits, target)
+    obj, top1, top5, _, bad = meter.read()
+    if bad:
+        raise ValueError('validate: %d target(s) outside [0, num_classes)' % bad)
+    return top1, top5, obj
 
 
 def build_derived_network(num_classes, model_path=None, config_path=None, dropout_rate=0.2, drop_connect_rate=0.2):
@@ -404,7 +484,7 @@ def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250
     import math
     import os
     import shutil
-    from .search import AverageMeter, accuracy
+    from .tail import DeviceMeter
     os.makedirs(save_dir, exist_ok=True)
     dev = torch.device(device)
     model = model.to(dev)
@@ -421,19 +501,19 @@ def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250
         model.load_state_dict({k[len('module.'):] if k.startswith('module.') else k: v for k, v in ck['state_dict'].items()})
         opt.load_state_dict(ck['optimizer'])
     history = []
+    meter = DeviceMeter(dev)
     for epoch in range(start, epochs):
         cur = 0.5 * lr * (1.0 + math.cos(math.pi * epoch / float(epochs)))          # CosineAnnealingLR(T_max=epochs).get_lr()
         warm = epoch < 5 and batch_size > 256
         for g in opt.param_groups:
             g['lr'] = cur * (epoch + 1) / 5.0 if warm else cur
-        objs, top1 = AverageMeter(), AverageMeter()
+        meter.reset()
         for x, y in make_train_queue(epoch):
             x, y = x.to(dev, non_blocking=True), y.to(dev, non_blocking=True)
-            loss, logits = train_step(model, x, y, crit_smooth, opt, grad_clip, group)
-            p1, = accuracy(logits, y, topk=(1,))
-            vals = torch.stack([loss.float(), p1]).tolist()
-            objs.update(vals[0], x.size(0))
-            top1.update(vals[1], x.size(0))
+            train_step(model, x, y, crit_smooth, opt, grad_clip, group, meter=meter)
+        train_obj, train_acc, _, _, bad = meter.read()      # the epoch's only device -> host copy of the training loop
+        if bad:
+            raise ValueError('run_retrain: epoch %d saw %d training target(s) outside [0, %d)' % (epoch, bad, num_classes))
         v1, v5, vobj = validate(model, make_val_queue(epoch))
         is_best = v1 > best1
         if is_best:
@@ -444,7 +524,7 @@ def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250
         torch.save(state, path)
         if is_best:
             shutil.copyfile(path, os.path.join(save_dir, 'model_best.pth.tar'))
-        history.append(dict(epoch=epoch, lr=opt.param_groups[0]['lr'], train_acc=top1.avg, train_obj=objs.avg, val_top1=v1,
+        history.append(dict(epoch=epoch, lr=opt.param_groups[0]['lr'], train_acc=train_acc, train_obj=train_obj, val_top1=v1,
                             val_top5=v5, val_obj=vobj))
-        log('Epoch %d lr %e train_acc %f val_top1 %f val_top5 %f' % (epoch, opt.param_groups[0]['lr'], top1.avg, v1, v5))
+        log('Epoch %d lr %e train_acc %f val_top1 %f val_top5 %f' % (epoch, opt.param_groups[0]['lr'], train_acc, v1, v5))
     return history

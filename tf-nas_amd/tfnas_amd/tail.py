@@ -15,6 +15,11 @@ WeightArena (no AccumulateGrad, no zero-fill + two adds).
 
 Private to ``search._w_step_paths``: the backward of ``BiTailFn`` hands out gradients computed in its forward under the assumption
 that the loss it returned is differentiated with gradient 1 -- ``loss.backward()``, which is what the weight step does.
+
+The derived network's retrain path (model_eval.train_step / validate; reference train_eval.py:228-293) has a general-purpose tail
+of its own below: ``RetrainTailFn`` (label-smoothed loss, logits and the target's rank, correct under any upstream gradient),
+``retrain_tail_forward`` (the forward-only kernel for validation) and ``DeviceMeter`` (an epoch's loss / top-1 / top-5 sums kept on
+the device and read once).
 """
 import ctypes as C
 
@@ -22,6 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import TfnasCellDesc, check, ptr
+from . import functions
 from .functions import _nhwc, _on
 
 
@@ -194,6 +200,135 @@ def frozen_classifier_loss(model, pooled, target):
     if lin.weight.dtype != torch.float32 or (lin.in_features & 3) or lin.in_features > 4096 or lin.out_features > 4096:
         return None
     return ClsCeFn.apply(pooled, lin.weight.detach(), lin.bias.detach(), target)
+
+
+def cls_shapes_ok(Cf, K):
+    """The limits of tfnas_cls_ce / tfnas_cls_ce_ex (include/tfnas_hip.h): C % 4 == 0, 4 <= C <= 4096, K <= 4096, LDS <= 64 KiB."""
+    if Cf < 4 or (Cf & 3) or Cf > 4096 or K < 1 or K > 4096:
+        return False
+    kg = max(1, min(8, K, 1024 // (Cf >> 2)))
+    return 4 * (Cf + ((K + 3) & ~3) + kg * Cf) <= 64 * 1024
+
+
+def _cls_ce_ex(pooled, W, b, target, eps, grads):
+    """One tfnas_cls_ce_ex launch on the current stream -> (pooled, logits, loss_n, rank, dlogits, dpooled); the last two are None in
+    the forward-only form.  dlogits carries the 1 / N of the mean reduction."""
+    pooled = pooled.contiguous()
+    N, Cf = pooled.shape
+    K = W.shape[0]
+    dev = pooled.device
+    if target.dtype != torch.int64 or not target.is_contiguous():
+        target = target.long().contiguous()
+    f32 = torch.float32
+    logits = torch.empty((N, K), device=dev, dtype=f32)
+    loss_n = torch.empty(N, device=dev, dtype=f32)
+    rank = torch.empty(N, device=dev, dtype=torch.int32)
+    dlogits = torch.empty((N, K), device=dev, dtype=f32) if grads else None
+    dpooled = torch.empty((N, Cf), device=dev, dtype=f32) if grads else None
+    with _on(dev):
+        check(_lib.lib().tfnas_cls_ce_ex(N, Cf, K, ptr(pooled), ptr(W), ptr(b), ptr(target), 1.0 / N, float(eps), ptr(logits),
+                                         ptr(loss_n), ptr(rank), ptr(dlogits), ptr(dpooled), functions._stream(dev)),
+              'tfnas_cls_ce_ex')
+    return pooled, logits, loss_n, rank, dlogits, dpooled
+
+
+def _cls_metrics(loss_n, rank, K, meter):
+    """The metrics-only tfnas_cls_reduce: out[4] = {mean loss, top-1 count, top-5 count, invalid count}, and the meter's sums."""
+    dev = loss_n.device
+    out = torch.empty(4, device=dev, dtype=torch.float32)
+    buf = meter.buf if isinstance(meter, DeviceMeter) else meter
+    with _on(dev):
+        check(_lib.lib().tfnas_cls_reduce(loss_n.numel(), 4, K, None, None, ptr(loss_n), ptr(rank), None, 0, None, None, ptr(out),
+                                          ptr(buf), functions._stream(dev)), 'tfnas_cls_reduce')
+    return out
+
+
+class DeviceMeter:
+    """Running {sum of per-image losses, top-1 hits, top-5 hits, images, invalid targets} of an epoch as five doubles ON THE DEVICE:
+    the retrain tail's reduction launch adds to them (tfnas_cls_reduce), the torch route adds with torch ops (``add``), and ``read``
+    is the only device -> host copy -- once per epoch instead of a ``.tolist()`` per step (train_eval.py:246-250,287-291 keep
+    AverageMeters on the host).  Every update is enqueued on the caller's current stream."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(5, device=device, dtype=torch.float64)
+
+    def reset(self):
+        self.buf.zero_()
+
+    def add(self, loss, logits, target):
+        """What the fused tail adds, from a mean loss and logits computed by torch ops (no host sync either)."""
+        n = target.size(0)
+        hit = logits.topk(min(5, logits.size(1)), 1, True, True)[1].eq(target.view(-1, 1))
+        f64 = torch.float64
+        vals = [loss.detach().to(f64) * n, hit[:, :1].sum().to(f64), hit.sum().to(f64)]
+        self.buf[:3] += torch.stack(vals)
+        self.buf[3] += n
+
+    def read(self):
+        """(loss average, top-1 %, top-5 %, images, invalid targets)"""
+        s, c1, c5, cnt, bad = self.buf.tolist()
+        if cnt == 0:
+            return 0.0, 0.0, 0.0, 0, 0
+        return s / cnt, 100.0 * c1 / cnt, 100.0 * c5 / cnt, int(cnt), int(bad)
+
+
+def retrain_tail_forward(pooled, W, b, target, eps=0.0, meter=None):
+    """(loss, logits, rank) without gradients: the forward-only kernel (no d logits / d pooled phase) + the metrics launch."""
+    _, logits, loss_n, rank, _, _ = _cls_ce_ex(pooled, W, b, target, eps, False)
+    out = _cls_metrics(loss_n, rank, W.shape[0], meter)
+    return out[0], logits, rank
+
+
+class RetrainTailFn(torch.autograd.Function):
+    """(loss, logits, rank) = f(pooled, W, b, target, eps[, modes, meter]): classifier + label-smoothed cross-entropy (mean
+    reduction; train_eval.py:72-85 with num_classes == K) + the target's rank (top-k is ``rank < k``; ties go to the lower class
+    index, -1 marks a target outside [0, K), whose loss is NaN and whose gradient rows are zero) -- include/tfnas_hip.h:
+    tfnas_cls_ce_ex / tfnas_cls_reduce.  Forward: the per-image launch + the metrics launch (which feeds ``meter``, a DeviceMeter).
+    Backward, correct for ANY upstream d loss with no host read: the weight-gradient launch takes it as a device scalar, d pooled
+    is scaled by it.  ``modes`` (a functions.HipModes, default functions.DEFAULT_MODES) is honoured like MBConvAffineFn does: with
+    ``direct_grads`` and usable ``.grad`` views dW / db are written in place and None is returned for them; with ``lazy_join`` as
+    well that launch rides the weight-gradient side stream (joined once per step by RetrainState).  logits and rank carry no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, pooled, W, b, target, eps, modes=None, meter=None):
+        modes = functions.DEFAULT_MODES if modes is None else modes
+        pooled, logits, loss_n, rank, dlogits, dpooled = _cls_ce_ex(pooled, W, b, target, eps, True)
+        out = _cls_metrics(loss_n, rank, W.shape[0], meter)
+        ctx.modes = modes
+        ctx.direct = functions._direct_targets([W, b], modes) if W.requires_grad and b.requires_grad else None
+        ctx.save_for_backward(pooled, dlogits, dpooled, loss_n, rank, W, b)
+        ctx.mark_non_differentiable(logits, rank)
+        return out[0], logits, rank
+
+    @staticmethod
+    def backward(ctx, gloss, glogits, grank):
+        pooled, dlogits, dpooled, loss_n, rank, W, b = ctx.saved_tensors
+        dev = pooled.device
+        N, Cf = pooled.shape
+        K = W.shape[0]
+        gs = gloss.to(torch.float32).contiguous()
+        gW = gb = None
+        direct = ctx.direct
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            if direct is not None:
+                gW, gb = direct
+            else:
+                gW, gb = torch.empty_like(W), torch.empty_like(b)
+            side = functions._side_stream(dev) if ctx.modes.lazy_join and direct is not None else None
+            if side is not None:
+                side.wait_stream(torch.cuda.current_stream(dev))
+            stream = functions._stream(dev) if side is None else C.c_void_p(side.cuda_stream)
+            with _on(dev):
+                check(_lib.lib().tfnas_cls_reduce(N, Cf, K, ptr(pooled), ptr(dlogits), ptr(loss_n), ptr(rank), ptr(gs), 0, ptr(gW),
+                                                  ptr(gb), None, None, stream), 'tfnas_cls_reduce')
+            if side is not None:                 # the launch still reads these when this function returns
+                for t in (pooled, dlogits, loss_n, rank, gs):
+                    t.record_stream(side)
+            if direct is not None:
+                gW = gb = None
+        dpo = dpooled * gs if ctx.needs_input_grad[0] else None
+        return (dpo, gW if ctx.needs_input_grad[1] else None, gb if ctx.needs_input_grad[2] else None, None, None, None, None)
 
 
 def _clone_on(t, stream):
