@@ -484,7 +484,9 @@ int tfnas_paths_fwd(int npath, void *const *ctx, const float *const *x0, const f
 /* Backward of the same.  dout[p]: gradient of out[p];  dout_lat[p]: device float[nstage] or NULL;
  * produces dx0[p] (if need_dx0), dwmix[p] float[ncell][8] and dcell_lat[p] float[ncell] (soft mode), stage dbetas, and the
  * cells' weight gradients at the g_* pointers of the planned descriptors (need_wgrad cells).
- * On return every path's side stream has been joined to its stream.
+ * On return every path's side stream has been joined to its stream, also on an error return.
+ * The context remembers the route word (tfnas_cell_route) of every cell's last tfnas_paths_fwd; a cell whose backward would take
+ * another route (the process-default GEMM mode or the statistics hook changed in between) returns TFNAS_EINVAL before it launches.
  * stage_begin / stage_end: walk only the stages [stage_begin, stage_end) (in reverse order; stage_end = -1: to the last one).
  * A backward may be issued as consecutive segments, last stages first -- (k, -1) then (0, k) -- so that the caller can start
  * reducing the late stages' weight gradients (89 % of the parameters) across ranks while the early stages are still running. */

@@ -220,3 +220,41 @@ def test_segmented_backward_and_stream_picker(lut):
         res.append([p.detach().clone() for p in m.weight_parameters()])
     for a, b in zip(*res):
         assert torch.equal(a, b)
+
+
+def test_path_backward_refuses_a_route_that_differs_from_the_forwards(lut):
+    """Path-level twin of tests/test_gpu_cell.py::test_backward_refuses_a_route_that_differs_from_the_forwards (ADVICE r6,
+    fx_kernels.hip): the fused per-image route of the late cells leaves ehat = BN1(E) in the E buffer and exists in the x3 arithmetic
+    only, so a change of the process-default GEMM mode between a path forward and its backward changes what the backward would take
+    the E buffer for.  tfnas_paths_fwd records each cell's route in the path context; tfnas_paths_bwd returns TFNAS_EINVAL before the
+    first such cell launches anything (an error return, not a fault), and the context stays usable."""
+    import ctypes as C
+    from tfnas_amd import _lib, search
+    lib = _lib.lib()
+    old_mode, old_paths, old_tail = lib.tfnas_gemm_mode(), search.USE_PATHS, search.FUSED_TAIL
+    search.USE_PATHS, search.FUSED_TAIL = True, False
+    try:
+        m = _model(lut)
+        st = search.SearchState(m)
+        assert st.runner is not None
+        _, oa = search.make_optimizers(m)
+        noise = search.NoiseSource(7)
+        gen = torch.Generator(device='cuda').manual_seed(9)
+        x = torch.randn(4, 3, 224, 224, device='cuda', generator=gen)
+        y = torch.randint(0, 100, (4,), device='cuda', generator=gen)
+        st.require(False, True)
+        logits, lat = search._a_forward_paths(st, x, noise.exp('cuda'))
+        pd = st.runner._slots['soft'].pd
+        routes = [lib.tfnas_cell_route(C.byref(pd.cell[i])) for i in range(pd.ncell)]
+        assert any(r & _lib.ROUTE_TAKEN_FX for r in routes), routes       # the forward took the fused route somewhere
+        assert lib.tfnas_set_gemm_mode(0) == 0                             # fp32: the fused route is off from here on
+        assert not any(lib.tfnas_cell_route(C.byref(pd.cell[i])) & _lib.ROUTE_TAKEN_FX for i in range(pd.ncell))
+        with pytest.raises(RuntimeError, match='tfnas_paths_bwd failed with code -1'):
+            (torch.nn.functional.cross_entropy(logits, y) + lat).backward()
+        assert lib.tfnas_set_gemm_mode(old_mode) == 0
+        loss_a, loss_l, lat2, _ = search.a_step(st, x, y, oa, 15.0, 0.1, 5.0, noise.exp('cuda'))    # same mode both ways: fine
+        torch.cuda.synchronize()
+        assert torch.isfinite(loss_a) and torch.isfinite(loss_l) and torch.isfinite(lat2)
+    finally:
+        assert lib.tfnas_set_gemm_mode(old_mode) == 0
+        search.USE_PATHS, search.FUSED_TAIL = old_paths, old_tail

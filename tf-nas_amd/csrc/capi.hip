@@ -9,8 +9,6 @@
 #include <mutex>
 #include <vector>
 
-static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // ---------------------------------------------------------------------------------------------------------------
 // Weight-gradient side stream.  The weight-gradient kernels of a cell are leaves of the backward dependency chain
 // (nothing downstream in the same call consumes them), and like most kernels of the sampled w-step they are
@@ -44,13 +42,6 @@ static SideCtx* side_for(hipStream_t s) {
     g_side.push_back(c);
     return c;
 }
-// make `side` wait for everything enqueued on `main` so far; returns the stream to launch on
-static hipStream_t side_fork(SideCtx* c, int k, hipStream_t main) {
-    if (!c) return main;
-    if (hipEventRecord(c->fork[k], main) != hipSuccess || hipStreamWaitEvent(c->side, c->fork[k], 0) != hipSuccess)
-        return main;
-    return c->side;
-}
 static int side_join(SideCtx* c, hipStream_t main) {
     if (!c) return 0;
     hipError_t e = hipEventRecord(c->join, c->side);
@@ -58,7 +49,7 @@ static int side_join(SideCtx* c, hipStream_t main) {
     return (int)e;
 }
 
-// Joins the side stream on every exit path of tfnas_mixedop_bwd: an early error return must not leave weight-gradient
+// Joins the side stream on every exit path of a cell backward (cell_bwd_entry): an early error return must not leave weight-gradient
 // kernels running on buffers the caller is about to free.
 struct SideJoinGuard {
     SideCtx* c = nullptr;
@@ -157,12 +148,6 @@ extern "C" uint64_t tfnas_sizeof(int which) {
         default: return 0;
     }
 }
-
-#define TRY(call)               \
-    do {                        \
-        int _r = (call);        \
-        if (_r != 0) return _r; \
-    } while (0)
 
 // the per-launch modes of a descriptor (callers may change them between tfnas_cell_plan and a launch: every entry point re-checks)
 static int check_modes(const TfnasCellDesc* d) {
@@ -268,9 +253,8 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
 }
 
 extern "C" int tfnas_efree_supported(const TfnasCellDesc* dp) { return (dp && efree_supported(*dp)) ? 1 : 0; }
-extern "C" int tfnas_fx_supported(const TfnasCellDesc* dp) {
-    return (dp && dp->mode == TFNAS_MODE_CELL && !dp->need_wgrad && !efree_ic_ok(dp->ic) && fx_supported(*dp)) ? 1 : 0;
-}
+// (fx_plan refuses every mode but TFNAS_MODE_CELL, need_wgrad and ic < 64 -- the E-free widths 16 / 24 / 40 -- by itself)
+extern "C" int tfnas_fx_supported(const TfnasCellDesc* dp) { return (dp && fx_supported(*dp)) ? 1 : 0; }
 // what a forward of this descriptor leaves in the saved buffers (tfnas_hip.h): the one decision of cell_fwd_impl that changes
 // their MEANING is the fused per-image route (ehat instead of E); affine / eval BatchNorm launches (tfnas_mbconv_*) never take it
 static int route_taken(const TfnasCellDesc& d, bool affine) {
@@ -295,7 +279,7 @@ static int bn_fwd_fix(const TfnasCellDesc& d, const TfnasBnAffine* bn, int site,
                              bn->running_var[site], bn->momentum, bn->eval, s, stats_world(d));   // (sync-stats: global batch)
 }
 
-int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdBufs& b, hipStream_t s) {
+int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdBufs& b, hipStream_t s, int* route) {
     double* stats1 = b.stats + ws.off_stats1;
     double* stats2 = b.stats + ws.off_stats2;
     double* stats3 = b.stats + ws.off_stats3;
@@ -310,7 +294,10 @@ int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdB
     const TfnasCellDesc& d = dc;
     // E-free late cells (14 x 14 / 7 x 7 images, 64..192 input channels): the fused per-image route (fx_kernels.hip)
     // (frozen weights only: fx_supported refuses need_wgrad; with E the forward leaves ehat there for the backward)
-    const bool fx = !bn && fx_supported(d);
+    // The launch's ONE route decision; the path level keeps the word for its backward (`route`).
+    const int taken = route_taken(d0, bn != nullptr);
+    if (route) *route = taken;
+    const bool fx = (taken & TFNAS_ROUTE_TAKEN_FX) != 0;
     if (fx) TRY(launch_fx_stats(d, b.x, stats1, b.part, s));                  // BN1 statistics from the Gram matrix of x
     else if (b.E) TRY(launch_expand_fwd(d, b.x, b.E, stats1, b.part, s));     // 1x1 expand (all groups) + BN1 statistics
     else TRY(launch_expand_stats_gram(d, b.x, stats1, b.part, s));            // E-free: BN1 statistics from the Gram matrix of x
@@ -356,18 +343,32 @@ static int bn_bwd_fix(const TfnasCellDesc& d, const TfnasBnAffine* bn, int site,
     return 0;
 }
 
+// dx = de W_expand (+ residual, + sink gradient) without reading E: the BN1-backward correction operator G | b goes to the top
+// of `part`, then the expand dgrad (nsl >= 0: the fused route's form, launch_expand_dgrad)
+static int expand_dx(const TfnasCellDesc& d, const float* dEh, const float* x, const float* cb1, float* part, const float* dout,
+                     const float* wmix, float* dx, float* dxp, hipStream_t s, const float* add_src = nullptr,
+                     const float* add_scale = nullptr, int nsl = -1) {
+    const size_t room = TFNAS_PART_FLOATS - expand_gram_floats(d);
+    float* gram = part + room;
+    TRY(launch_expand_gram(d, cb1, part, room, gram, s));
+    return launch_expand_dgrad(d, dEh, x, cb1, gram, dout, wmix, dx, dxp, s, add_src, add_scale, nsl);
+}
+
 // TFNAS_ROUTE_FOLD_OFF: BN2-backward tables in their own pass (k_bn2_pool) instead of the epilogue of k_project_dgrad; both
 // are compared with the oracle (tests/test_gpu_cell.py::test_variant_against_oracle)
 
-int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdBufs& b0, hipStream_t s, const CellSide* so) {
+int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdBufs& b0, hipStream_t s, const CellSide* so,
+                  int fwd_route) {
     const TfnasBnAffine* bn = b0.bn;
     TfnasCellDesc dc = d0;
     if (bn) dc.eps = -1.f;
     const TfnasCellDesc& d = dc;
     CellBwdBufs b = b0;
-    // the forward's route, when the caller recorded it (tfnas_cell_route -> fwd_route): a backward that would read the E buffer
-    // differently from how the forward wrote it (need_wgrad or the sync hook changed in between) refuses
-    if ((d0.fwd_route & TFNAS_ROUTE_TAKEN_VALID) && route_taken(d0, bn != nullptr) != d0.fwd_route) return TFNAS_EINVAL;
+    // The launch's ONE route decision, against the forward's when the caller recorded it (per cell: tfnas_cell_route ->
+    // TfnasCellDesc.fwd_route; path level: PathCtx): a backward that would read the E buffer differently from how the forward
+    // wrote it (need_wgrad, the sync hook or the process-default GEMM mode changed in between) refuses before it launches anything
+    const int taken = route_taken(d0, bn != nullptr);
+    if ((fwd_route & TFNAS_ROUTE_TAKEN_VALID) && taken != fwd_route) return TFNAS_EINVAL;
     const float* dout_res = b0.dout;                       // the residual branch sees the unscaled gradient
     if (b0.drop_scale && d.has_res) {
         if (!b0.dout_s) return TFNAS_ENULL;
@@ -382,7 +383,6 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
     const float* hpre = b.fsmall + ws.off_hpre;
     float* dgate = b.bsmall + ws.off_dgate;
     float* dpooled = b.bsmall + ws.off_dpooled;
-    float* dgl = b.bsmall + ws.off_dgl;
     float* dhpre = b.bsmall + ws.off_dhpre;
     float* cb1 = b.bsmall + ws.off_cb1;
     double* red3 = b.red + ws.off_red3;
@@ -426,21 +426,17 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
         else TRY(launch_se_bwd_reduce(d, b.dZ, b.D, stats2, dgate, s));         // SE groups: d gate
     }
     // (K-split partials of the SE backward go through dEh, which is only written by the depthwise dgrad further down)
-    TRY(launch_se_fc_bwd(d, dgate, gate, hpre, dgl, dhpre, dpooled, b.dEh, (size_t)ws.dEh, s));
+    TRY(launch_se_fc_bwd(d, dgate, gate, hpre, dhpre, dpooled, b.dEh, (size_t)ws.dEh, s));
     if (fused2) TRY(launch_bn2_finish(d, part, gate, dpooled, red2, s));      // BN2 backward sums
     else TRY(launch_bn2_bwd(d, b.dZ, b.D, stats2, gate, dpooled, red2, part, s));
     TRY(stats_sync(d, red2, 2 * (size_t)d.M, s));
     if (bn) TRY(bn_bwd_fix(d0, bn, 1, red2, s));
-    if (!bn && fx_supported(d)) {
+    if (taken & TFNAS_ROUTE_TAKEN_FX) {
         // fused per-image route: depthwise dgrad + act' + the dE (rstd . W1) term of the expand dgrad in one kernel (dE never
         // materialised; partial sums per channel slice in the dEh buffer), then the BN1-backward correction -x G + b
         int nsl = 0;
         TRY(launch_fx_bwd(d, b.x, b.E, stats1, stats2, red2, b.dZ, b.D, gate, dpooled, b.dEh, (size_t)ws.dEh, red1, cb1, part, &nsl, s));
-        if (b.dx) {
-            float* gram = part + TFNAS_PART_FLOATS - expand_gram_floats(d);
-            TRY(launch_expand_gram(d, cb1, part, TFNAS_PART_FLOATS - expand_gram_floats(d), gram, s));
-            TRY(launch_expand_dgrad_x(d, b.x, cb1, gram, dout_res, b.wmix, b.dx, b.dEh, nsl, s, b.add_src, b.add_scale));
-        }
+        if (b.dx) TRY(expand_dx(d, nullptr, b.x, cb1, part, dout_res, b.wmix, b.dx, b.dEh, s, b.add_src, b.add_scale, nsl));
         return 0;
     }
     // the depthwise backward-data pass below, planned once; on the stride-1 ring cells and the stride-2 register-window cells
@@ -467,12 +463,8 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
         TRY(launch_dw_bwd_data(dw_bwd, d, b.dZ, gate, dpooled, b.D, stats2, red2, b.E, b.x, stats1, b.dEh, red1, part, s, cb1));
     }
     if (d.need_wgrad) TRY(launch_expand_wgrad(d, b.dEh, b.E, cb1, b.x, part_w2, fork_to(so, 2, s)));
-    if (b.dx && d.mode != TFNAS_MODE_STEM) {
-        // dx = de W_expand (+ residual) without reading E: BN1-backward correction operator G | b in the top of `part`
-        float* gram = part + TFNAS_PART_FLOATS - expand_gram_floats(d);
-        TRY(launch_expand_gram(d, cb1, part, TFNAS_PART_FLOATS - expand_gram_floats(d), gram, s));
-        TRY(launch_expand_dgrad(d, b.dEh, b.x, cb1, gram, dout_res, b.wmix, b.dx, b.dxp, s, b.add_src, b.add_scale));
-    }
+    if (b.dx && d.mode != TFNAS_MODE_STEM)
+        TRY(expand_dx(d, b.dEh, b.x, cb1, part, dout_res, b.wmix, b.dx, b.dxp, s, b.add_src, b.add_scale));
     return 0;
 }
 
@@ -489,6 +481,38 @@ extern "C" int tfnas_mixedop_fwd(const TfnasCellDesc* dp, const float* x, const 
     return cell_fwd_impl(d, ws, b, S(stream));
 }
 
+// What the two cell-backward entry points share: the library's side stream for the weight-gradient kernels (see SideCtx;
+// scratch = the second piece of `part`), its join on every exit path, the launch sequence.  wgrad_stream: the caller-owned
+// streams of the forks (tfnas_mixedop_bwd; NULL: none); lazy: leave the library's side stream unjoined (tfnas_mbconv_bwd)
+static int cell_bwd_entry(const TfnasCellDesc& d, CellBwdBufs b, hipStream_t s, void* const* wgrad_stream, bool lazy) {
+    TfnasCellWs ws;
+    TRY(tfnas_cell_ws(&d, &ws));
+    SideCtx* sc = (d.need_wgrad && route_side(d)) ? side_for(s) : nullptr;
+    SideJoinGuard guard;
+    guard.c = sc;
+    guard.main = s;
+    CellSide so = {};
+    if (sc) {
+        for (int i = 0; i < 3; ++i) {
+            hipStream_t own = (wgrad_stream && wgrad_stream[i]) ? S(wgrad_stream[i]) : nullptr;
+            so.side[i] = own ? own : sc->side;
+            guard.extra[i] = own;
+            so.fork[i] = sc->fork[i];
+            if (own) {
+                // forks on different streams run concurrently: one scratch piece each (tfnas_hip.h: `part` then holds FOUR pieces)
+                b.part_w1 = b.part + 2 * TFNAS_PART_ALLOC;
+                b.part_w2 = b.part + 3 * TFNAS_PART_ALLOC;
+            }
+        }
+    }
+    TRY(cell_bwd_impl(d, ws, b, s, sc ? &so : nullptr, d.fwd_route));
+    if (lazy) {                                  // the caller joins later (tfnas_side_join)
+        guard.joined = true;
+        return guard.join_extra();               // (caller-owned streams of THIS launch are always joined here)
+    }
+    return guard.join();
+}
+
 extern "C" int tfnas_mixedop_bwd(const TfnasCellDesc* dp, const float* x, const float* wmix, const float* E,
                                  const float* D, const float* Pr, const float* fsmall, const double* stats,
                                  const float* dout, float* dZ, float* dEh, float* bsmall, double* red, float* part,
@@ -499,31 +523,9 @@ extern "C" int tfnas_mixedop_bwd(const TfnasCellDesc* dp, const float* x, const 
     if (d.mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     if (!E && !efree_supported(d)) return TFNAS_ENULL;
     TRY(check_modes(dp));
-    TfnasCellWs ws;
-    TRY(tfnas_cell_ws(dp, &ws));
-    hipStream_t s = S(stream);
-    // weight gradients: on the library's side stream (see SideCtx), scratch = second half of `part`
-    SideCtx* sc = (d.need_wgrad && route_side(d)) ? side_for(s) : nullptr;
-    SideJoinGuard guard;
-    guard.c = sc;
-    guard.main = s;
-    CellSide so = {};
-    if (sc) {
-        for (int i = 0; i < 3; ++i) {
-            so.side[i] = d.wgrad_stream[i] ? S(d.wgrad_stream[i]) : sc->side;
-            guard.extra[i] = d.wgrad_stream[i] ? S(d.wgrad_stream[i]) : nullptr;
-            so.fork[i] = sc->fork[i];
-        }
-    }
     CellBwdBufs b = {x, wmix, E, D, Pr, fsmall, stats, dout, dZ, dEh, bsmall, red, part, part + TFNAS_PART_ALLOC,
                      dx, dxp, dwmix, nullptr, nullptr};
-    if (sc && (d.wgrad_stream[0] || d.wgrad_stream[1] || d.wgrad_stream[2])) {
-        // forks on different streams run concurrently: one scratch piece each (tfnas_hip.h: `part` then holds FOUR pieces)
-        b.part_w1 = part + 2 * TFNAS_PART_ALLOC;
-        b.part_w2 = part + 3 * TFNAS_PART_ALLOC;
-    }
-    TRY(cell_bwd_impl(d, ws, b, s, sc ? &so : nullptr));
-    return guard.join();
+    return cell_bwd_entry(d, b, S(stream), d.wgrad_stream, false);
 }
 
 extern "C" int tfnas_mbconv_fwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn, const float* drop_scale, const float* x,
@@ -551,102 +553,72 @@ extern "C" int tfnas_mbconv_bwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn
     if (d.mode == TFNAS_MODE_HEAD || d.G != 1) return TFNAS_EINVAL;
     if (d.wgrad_stream[0] || d.wgrad_stream[1] || d.wgrad_stream[2]) return TFNAS_EINVAL;     // (tfnas_mixedop_bwd only)
     TRY(check_modes(dp));
-    TfnasCellWs ws;
-    TRY(tfnas_cell_ws(dp, &ws));
-    hipStream_t s = S(stream);
-    SideCtx* sc = (d.need_wgrad && route_side(d)) ? side_for(s) : nullptr;
-    SideJoinGuard guard;
-    guard.c = sc;
-    guard.main = s;
-    CellSide so = {};
-    if (sc) {
-        for (int i = 0; i < 3; ++i) {
-            so.side[i] = d.wgrad_stream[i] ? S(d.wgrad_stream[i]) : sc->side;
-            guard.extra[i] = d.wgrad_stream[i] ? S(d.wgrad_stream[i]) : nullptr;
-            so.fork[i] = sc->fork[i];
-        }
-    }
     CellBwdBufs b = {x, nullptr, E, D, Pr, fsmall, stats, dout, dZ, dEh, bsmall, red, part, part + TFNAS_PART_ALLOC,
                      dx, dxp, nullptr, nullptr, nullptr};
     b.bn = bn;
     b.drop_scale = drop_scale;
     b.dout_s = dout_s;
-    TRY(cell_bwd_impl(d, ws, b, s, sc ? &so : nullptr));
-    if (g_lazy_join || (d.flags & TFNAS_CELL_LAZY_JOIN)) {              // the caller joins later (tfnas_side_join)
-        guard.joined = true;
-        return guard.join_extra();               // (caller-owned streams of THIS launch are always joined here)
-    }
-    return guard.join();
+    return cell_bwd_entry(d, b, S(stream), nullptr, g_lazy_join || (d.flags & TFNAS_CELL_LAZY_JOIN));
+}
+
+// The head (1x1 conv 320->1280 + BN + swish + global average pool), forward / backward; bn != NULL: affine / eval BatchNorm,
+// handled like site 0 of a cell (cell_fwd_impl)
+static int head_fwd_impl(const TfnasCellDesc& d0, const TfnasBnAffine* bn, const float* x, float* E, double* stats, float* part,
+                         float* pooled, hipStream_t s) {
+    TfnasCellDesc dc = d0;
+    if (bn) dc.eps = -1.f;
+    const TfnasCellDesc& d = dc;
+    TRY(launch_expand_fwd(d, x, E, stats, part, s));          // 1x1 conv 320->1280 + BN statistics
+    TRY(stats_sync(d, stats, 2 * (size_t)d.M, s));
+    if (bn) TRY(bn_fwd_fix(d0, bn, 0, stats, s));
+    return launch_head_pool(d, E, stats, pooled, s);           // BN + swish + global average pool
+}
+
+static int head_bwd_impl(const TfnasCellDesc& d0, const TfnasBnAffine* bn, const float* x, const float* E, const double* stats,
+                         const float* dpooled, float* dEh, float* cb1, double* red, float* part, float* dx, float* dxp,
+                         hipStream_t s) {
+    TfnasCellDesc dc = d0;
+    if (bn) dc.eps = -1.f;
+    const TfnasCellDesc& d = dc;
+    TRY(launch_head_bwd(d, E, stats, dpooled, dEh, red, part, s));       // pool + swish backward, BN-backward sums
+    TRY(stats_sync(d, red, 2 * (size_t)d.M, s));
+    if (bn) TRY(bn_bwd_fix(d0, bn, 0, red, s));
+    TRY(launch_bn1_consts(d, stats, red, cb1, s));
+    TRY(expand_dx(d, dEh, x, cb1, part, nullptr, nullptr, dx, dxp, s));
+    if (d.need_wgrad) TRY(launch_expand_wgrad(d, dEh, E, cb1, x, part, s));
+    return 0;
 }
 
 extern "C" int tfnas_head_affine_fwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn, const float* x, float* E, double* stats,
                                      float* part, float* pooled, void* stream) {
     if (!dp || !bn || !x || !E || !stats || !part || !pooled) return TFNAS_ENULL;
-    const TfnasCellDesc& d0 = *dp;
-    if (d0.mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    hipStream_t s = S(stream);
-    TfnasCellDesc d = d0;
-    d.eps = -1.f;
-    TRY(launch_expand_fwd(d, x, E, stats, part, s));
-    TRY(stats_sync(d, stats, 2 * (size_t)d.M, s));
-    TRY(launch_bn_fwd_fix(stats, d0.g[0].mc, (uint64_t)d0.N * d0.H * d0.W, d0.eps, bn->weight[0], bn->bias[0],
-                          bn->running_mean[0], bn->running_var[0], bn->momentum, bn->eval, s, stats_world(d0)));
-    TRY(launch_head_pool(d, E, stats, pooled, s));
-    return 0;
+    if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    return head_fwd_impl(*dp, bn, x, E, stats, part, pooled, S(stream));
 }
 
 extern "C" int tfnas_head_affine_bwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn, const float* x, const float* E,
                                      const double* stats, const float* dpooled, float* dEh, float* cb1, double* red,
                                      float* part, float* dx, float* dxp, void* stream) {
     if (!dp || !bn || !x || !E || !stats || !dpooled || !dEh || !cb1 || !red || !part || !dx) return TFNAS_ENULL;
-    const TfnasCellDesc& d0 = *dp;
-    if (d0.mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    if (d0.need_wgrad && !d0.g[0].g_expand) return TFNAS_ENULL;
-    hipStream_t s = S(stream);
-    TfnasCellDesc d = d0;
-    d.eps = -1.f;
-    const uint64_t cnt = (uint64_t)d0.N * d0.H * d0.W;
-    TRY(launch_head_bwd(d, E, stats, dpooled, dEh, red, part, s));
-    TRY(stats_sync(d, red, 2 * (size_t)d.M, s));
-    TRY(launch_bn_bwd_fix(red, d0.g[0].mc, cnt, bn->weight[0], bn->bias[0], bn->g_weight[0], bn->g_bias[0], s,
-                          wgrad_accum(d0)));
-    if (bn->eval) HIP_TRY(hipMemsetAsync(red, 0, sizeof(double) * 2 * (size_t)d0.g[0].mc, s));
-    TRY(launch_bn1_consts(d, stats, red, cb1, s));
-    float* gram = part + TFNAS_PART_FLOATS - expand_gram_floats(d);
-    TRY(launch_expand_gram(d, cb1, part, TFNAS_PART_FLOATS - expand_gram_floats(d), gram, s));
-    TRY(launch_expand_dgrad(d, dEh, x, cb1, gram, nullptr, nullptr, dx, dxp, s));
-    if (d.need_wgrad) TRY(launch_expand_wgrad(d, dEh, E, cb1, x, part, s));
-    return 0;
+    if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
+    return head_bwd_impl(*dp, bn, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
 
 extern "C" int tfnas_head_fwd(const TfnasCellDesc* dp, const float* x, float* E, double* stats, float* part,
                               float* pooled, void* stream) {
     if (!dp || !x || !E || !stats || !part || !pooled) return TFNAS_ENULL;
-    const TfnasCellDesc& d = *dp;
-    if (d.mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    hipStream_t s = S(stream);
-    TRY(launch_expand_fwd(d, x, E, stats, part, s));          // 1x1 conv 320->1280 + BN statistics
-    TRY(stats_sync(d, stats, 2 * (size_t)d.M, s));
-    TRY(launch_head_pool(d, E, stats, pooled, s));            // BN + swish + global average pool
-    return 0;
+    if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    return head_fwd_impl(*dp, nullptr, x, E, stats, part, pooled, S(stream));
 }
 
 extern "C" int tfnas_head_bwd(const TfnasCellDesc* dp, const float* x, const float* E, const double* stats,
                               const float* dpooled, float* dEh, float* cb1, double* red, float* part, float* dx,
                               float* dxp, void* stream) {
     if (!dp || !x || !E || !stats || !dpooled || !dEh || !cb1 || !red || !part || !dx) return TFNAS_ENULL;
-    const TfnasCellDesc& d = *dp;
-    if (d.mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    if (d.need_wgrad && !d.g[0].g_expand) return TFNAS_ENULL;
-    hipStream_t s = S(stream);
-    TRY(launch_head_bwd(d, E, stats, dpooled, dEh, red, part, s));       // pool + swish backward, BN-backward sums
-    TRY(stats_sync(d, red, 2 * (size_t)d.M, s));
-    TRY(launch_bn1_consts(d, stats, red, cb1, s));
-    float* gram = part + TFNAS_PART_FLOATS - expand_gram_floats(d);
-    TRY(launch_expand_gram(d, cb1, part, TFNAS_PART_FLOATS - expand_gram_floats(d), gram, s));
-    TRY(launch_expand_dgrad(d, dEh, x, cb1, gram, nullptr, nullptr, dx, dxp, s));
-    if (d.need_wgrad) TRY(launch_expand_wgrad(d, dEh, E, cb1, x, part, s));
-    return 0;
+    if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
+    return head_bwd_impl(*dp, nullptr, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
 
 extern "C" int tfnas_head_wgrad(const TfnasCellDesc* dp, const float* x, const float* E, const float* dEh, const float* cb1,

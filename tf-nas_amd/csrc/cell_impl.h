@@ -3,6 +3,14 @@
 #include <hip/hip_runtime.h>
 #include "tfnas_hip.h"
 
+static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+#define TRY(call)               \
+    do {                        \
+        int _r = (call);        \
+        if (_r != 0) return _r; \
+    } while (0)
+
 struct CellFwdBufs {
     const float* x;
     const float* wmix;
@@ -39,5 +47,9 @@ struct CellSide {
     hipEvent_t fork[3];
 };
 
-int cell_fwd_impl(const TfnasCellDesc& d, const TfnasCellWs& ws, const CellFwdBufs& b, hipStream_t s);
-int cell_bwd_impl(const TfnasCellDesc& d, const TfnasCellWs& ws, const CellBwdBufs& b, hipStream_t s, const CellSide* so);
+// Each launch decides its route ONCE (capi.hip: route_taken -- TFNAS_ROUTE_TAKEN_VALID | the routes that change what the saved
+// buffers MEAN).  route != NULL: the forward stores that word there; fwd_route: the word of the forward whose buffers this backward
+// reads (0: not recorded) -- a backward whose own word differs returns TFNAS_EINVAL before it launches anything.
+int cell_fwd_impl(const TfnasCellDesc& d, const TfnasCellWs& ws, const CellFwdBufs& b, hipStream_t s, int* route = nullptr);
+int cell_bwd_impl(const TfnasCellDesc& d, const TfnasCellWs& ws, const CellBwdBufs& b, hipStream_t s, const CellSide* so,
+                  int fwd_route);

@@ -620,7 +620,7 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_project_wgrad(TfnasCellDe
         const f32x4 v = (k_a3[i] * r.a - k_ab[i]) - (r.b - k_mean[i]) * k_s[i];
         return (bok[i] && r0 + c * 16 + kl < r1) ? v : zero4();
     };
-    gemm_mainloop2<NT, false, false, false, false>(la, xa, lb, xb, nchunks, acc, lds);
+    gemm_mainloop2<NT, false, false, false>(la, xa, lb, xb, nchunks, acc, lds);
     // The gradient is [oc][mc] (mid channel fastest) and a lane's accumulator quad is 4 consecutive mid channels of one
     // output channel: one 16-byte store per quad (the four lane groups of an output channel then cover 64 contiguous
     // bytes) instead of four 4-byte stores that each scatter a wave over 64 different cache lines.
@@ -1061,7 +1061,7 @@ __global__ __launch_bounds__(256, wgrad_lb(NT)) void k_expand_wgrad(TfnasCellDes
         if (STEM) return r;
         return (bok[i] && r0 + c * 16 + kl < r1) ? r : zero4();
     };
-    gemm_mainloop2<NT, false, false, false, false>(la, xa, lb, xb, nchunks, acc, lds);
+    gemm_mainloop2<NT, false, false, false>(la, xa, lb, xb, nchunks, acc, lds);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1486,6 +1486,8 @@ GemmPlan gemm_plan_expand_dgrad(const TfnasCellDesc& d, bool split, int nsl) {
     return p;
 }
 
+// nsl >= 0, the fused per-image route (fx_kernels.hip): dxp[0 .. nsl) hold the partial sums of dE (rstd . W1); this adds the
+// BN1-backward correction -x G (one more partial tile, MFMA) and sums everything (+ b, + residual, + sink gradient) into dx
 int launch_expand_dgrad(const TfnasCellDesc& d, const float* dEh, const float* x, const float* cb1, const float* gram,
                         const float* dout, const float* wmix, float* dx, float* dxp, hipStream_t s,
                         const float* add_src, const float* add_scale, int nsl) {
@@ -1502,14 +1504,6 @@ int launch_expand_dgrad(const TfnasCellDesc& d, const float* dEh, const float* x
         hipLaunchKernelGGL(k_dx_reduce, p.grid2, dim3(256), 0, s, d, dxp, p.parts, gram, dout, wmix, dx, add_src, add_scale);
     }
     return (int)hipGetLastError();
-}
-
-// fused per-image route (fx_kernels.hip): dxp[0 .. nsl) hold the partial sums of dE (rstd . W1); this adds the BN1-backward
-// correction -x G (one more partial tile, MFMA) and sums everything (+ b, + residual, + sink gradient) into dx
-int launch_expand_dgrad_x(const TfnasCellDesc& d, const float* x, const float* cb1, const float* gram, const float* dout,
-                          const float* wmix, float* dx, float* dxp, int nsl, hipStream_t s, const float* add_src,
-                          const float* add_scale) {
-    return launch_expand_dgrad(d, nullptr, x, cb1, gram, dout, wmix, dx, dxp, s, add_src, add_scale, nsl);
 }
 
 // XG: the double sums of the splits live in the top of `part` (2 floats per element, 16-byte aligned)

@@ -31,6 +31,10 @@ static inline int route_se(const TfnasCellDesc& d) { return (d.route & TFNAS_ROU
 static inline bool route_side(const TfnasCellDesc& d) { return !(d.route & TFNAS_ROUTE_WGRAD_INLINE); }
 // TFNAS_CELL_ACCUM_WGRAD: every weight-gradient store of the launch adds to its destination (g <- g + v)
 static inline int wgrad_accum(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_ACCUM_WGRAD) ? 1 : 0; }
+// the ReLU / Swish fork of a launcher: the statements run with ACT = the launch's activation as a compile-time constant
+#define ACT_DISPATCH(act, ...)                                                          \
+    if ((act) == TFNAS_ACT_RELU) { constexpr int ACT = TFNAS_ACT_RELU; __VA_ARGS__; }   \
+    else { constexpr int ACT = TFNAS_ACT_SWISH; __VA_ARGS__; }
 
 // gemm_kernels.hip
 int gemm_mode();            // arithmetic of the row-tiled GEMMs (tfnas_hip.h: TFNAS_GEMM_*): the process default ...
@@ -82,13 +86,10 @@ int launch_project_wgrad(const TfnasCellDesc& d, const float* dout, const float*
 size_t expand_gram_floats(const TfnasCellDesc& d);
 int launch_expand_gram(const TfnasCellDesc& d, const float* cb1, float* scratch, size_t scratch_floats, float* gram,
                        hipStream_t s);
-// (nsl >= 0: the fused route's form, dEh unused -- launch_expand_dgrad_x below)
+// (nsl >= 0: the fused route's form -- dEh unused, dxp[0 .. nsl) hold launch_fx_bwd's partial sums)
 int launch_expand_dgrad(const TfnasCellDesc& d, const float* dEh, const float* x, const float* cb1, const float* gram,
                         const float* dout, const float* wmix, float* dx, float* dxp, hipStream_t s,
                         const float* add_src = nullptr, const float* add_scale = nullptr, int nsl = -1);
-int launch_expand_dgrad_x(const TfnasCellDesc& d, const float* x, const float* cb1, const float* gram, const float* dout,
-                          const float* wmix, float* dx, float* dxp, int nsl, hipStream_t s, const float* add_src = nullptr,
-                          const float* add_scale = nullptr);
 int launch_expand_wgrad(const TfnasCellDesc& d, const float* dEh, const float* E, const float* cb1,
                         const float* x, float* part, hipStream_t s);
 
@@ -148,7 +149,7 @@ int launch_fx_stats(const TfnasCellDesc& d, const float* x, double* stats1, floa
 int launch_fx_fwd(const TfnasCellDesc& d, const float* x, const double* stats1, float* E, float* D, double* stats2,
                   float* part, hipStream_t s);
 // backward: the partial sums of dE (rstd . W1) into scratch[0 .. nsl * P * ic) (nsl returned), the BN1-backward sums into
-// red1 and the cb1 table; the caller finishes with launch_expand_gram + launch_expand_dgrad_x(scratch, nsl)
+// red1 and the cb1 table; the caller finishes with launch_expand_gram + launch_expand_dgrad(dxp = scratch, nsl)
 int launch_fx_bwd(const TfnasCellDesc& d, const float* x, const float* Eh, const double* stats1, const double* stats2,
                   const double* red2, const float* dZ, const float* D, const float* gate, const float* dpooled, float* scratch,
                   size_t scratch_floats, double* red1, float* cb1, float* part, int* nsl, hipStream_t s);
@@ -175,8 +176,8 @@ int launch_mix_bwd_stats(const TfnasCellDesc& d, const float* dout, const float*
 int launch_mix_dw(const TfnasCellDesc& d, const double* red3, const double* resdot, float* dwmix, hipStream_t s);
 int launch_se_bwd_reduce(const TfnasCellDesc& d, const float* dZ, const float* D, const double* stats2,
                          float* dgate, hipStream_t s);
-int launch_se_fc_bwd(const TfnasCellDesc& d, const float* dgate, const float* gate, const float* hpre,
-                     float* dgl, float* dhpre, float* dpooled, float* scratch, size_t scratch_floats, hipStream_t s);
+int launch_se_fc_bwd(const TfnasCellDesc& d, const float* dgate, const float* gate, const float* hpre, float* dhpre,
+                     float* dpooled, float* scratch, size_t scratch_floats, hipStream_t s);
 int launch_se_wgrad(const TfnasCellDesc& d, const float* dgate, const float* gate, const float* dhpre,
                     const float* hpre, const float* pooled, hipStream_t s);
 bool bn2_fused_fits(const TfnasCellDesc& d);

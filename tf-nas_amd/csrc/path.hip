@@ -49,20 +49,14 @@ struct PathCtx {
     hipEvent_t wdone[TFNAS_MAX_CELLS];
     hipEvent_t join = nullptr;
     bool events_ok = false;
+    int fwd_route[TFNAS_MAX_CELLS] = {};   // the route word each cell's last forward took (cell_impl.h; 0: none since the plan)
 };
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-#define TRY(call)               \
-    do {                        \
-        int _r = (call);        \
-        if (_r != 0) return _r; \
-    } while (0)
 
 int plan_path(PathCtx& c, const TfnasPathDesc& in, TfnasPathWs* out) {
     if (in.ncell < 1 || in.ncell > TFNAS_MAX_CELLS || in.nstage < 1 || in.nstage > TFNAS_MAX_STAGES) return TFNAS_ERANGE;
     c.planned = false;
     c.pd = in;
+    memset(c.fwd_route, 0, sizeof(c.fwd_route));
     TfnasPathDesc& pd = c.pd;
     // stages: first_cell / nres, every cell belongs to exactly one stage
     int nc = 0;
@@ -198,7 +192,7 @@ int fwd_cell(PathCtx& c, int i, const float* x0, const float* wmix, float* arena
     b.stats = reinterpret_cast<double*>(arena + o.stats);
     b.part = arena + c.set[0].part;
     b.out = arena + o.out;
-    return cell_fwd_impl(pd.cell[i], c.cws[i], b, s);
+    return cell_fwd_impl(pd.cell[i], c.cws[i], b, s, &c.fwd_route[i]);
 }
 
 // res pointers of a stage's sink (model_search.py:200-204: res_list[start_res:])
@@ -435,7 +429,7 @@ int bwd_cell(BwdRun& r, int i) {
             so.fork[k] = c.fork[i][k];
         }
     }
-    TRY(cell_bwd_impl(pd.cell[i], c.cws[i], b, r.s, side ? &so : nullptr));
+    TRY(cell_bwd_impl(pd.cell[i], c.cws[i], b, r.s, side ? &so : nullptr, c.fwd_route[i]));
     if (side) HIP_TRY(hipEventRecord(c.wdone[i], c.side));
     return 0;
 }

@@ -744,10 +744,6 @@ int launch_reduce_rows(const float* part, int nb, int ncols, size_t stride, doub
 }
 
 // ============================================================================ host launchers
-#define ACT_DISPATCH(act, ...)                                                          \
-    if ((act) == TFNAS_ACT_RELU) { constexpr int ACT = TFNAS_ACT_RELU; __VA_ARGS__; }   \
-    else { constexpr int ACT = TFNAS_ACT_SWISH; __VA_ARGS__; }
-
 int launch_se_pool(const TfnasCellDesc& d, const float* D, const double* stats2, float* pooled, hipStream_t s) {
     ProfScope _prof(TK_SE_POOL, s);
     const int chunks = chunk_count(d, 64, true);

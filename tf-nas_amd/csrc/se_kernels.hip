@@ -15,10 +15,6 @@
 #include "kernels.h"
 #include "prof.h"
 
-#ifndef TFNAS_SE_PF2
-#define TFNAS_SE_PF2 false     /* prefetch distance 2 in the K loop (gemm_core.h); measured: no gain (A/B switch) */
-#endif
-
 struct SeArgs {
     const float* pooled;   // [N][M]
     const float* gate;     // [N][M]
@@ -83,7 +79,7 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
             return (n0 + nn < se && (cbase + c) * 16 + kl < mc) ? v : zero4();
         };
         const int tot = (mcp + 15) >> 4;
-        gemm_mainloop2<NT, true, true, true, TFNAS_SE_PF2>(la, xa, lb, xb, split ? max(0, min(cps, tot - cbase)) : tot, acc, lds);
+        gemm_mainloop2<NT, true, true, true>(la, xa, lb, xb, split ? max(0, min(cps, tot - cbase)) : tot, acc, lds);
     } else if (MODE == 1) {
         if (r0 >= N || n0 >= mcp) return;
         auto la = [&](int c, int, int row, int kl) -> f32x4 {
@@ -100,7 +96,7 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
         auto xb = [&](f32x4 v, int c, int, int nn, int kl) -> f32x4 {
             return (n0 + nn < mc && c * 16 + kl < se) ? v : zero4();
         };
-        gemm_mainloop2<NT, true, true, true, TFNAS_SE_PF2>(la, xa, lb, xb, (se + 15) >> 4, acc, lds);
+        gemm_mainloop2<NT, true, true, true>(la, xa, lb, xb, (se + 15) >> 4, acc, lds);
     } else if (MODE == 2) {
         if (r0 >= N || n0 >= se) return;
         auto la = [&](int c, int, int row, int kl) -> Pair {
@@ -121,7 +117,7 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
             return ((cbase + c) * 16 + kl < mc && n0 + nn < se) ? v : zero4();
         };
         const int tot = (mcp + 15) >> 4;
-        gemm_mainloop2<NT, true, false, true, TFNAS_SE_PF2>(la, xa, lb, xb, split ? max(0, min(cps, tot - cbase)) : tot, acc, lds);
+        gemm_mainloop2<NT, true, false, true>(la, xa, lb, xb, split ? max(0, min(cps, tot - cbase)) : tot, acc, lds);
     } else if (MODE == 3) {
         if (r0 >= N || n0 >= mcp) return;
         auto la = [&](int c, int, int row, int kl) -> f32x4 {
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
             if (!mc_al) return v;
             return (c * 16 + kl < se && n0 + nn < mc) ? v : zero4();
         };
-        gemm_mainloop2<NT, true, false, true, TFNAS_SE_PF2>(la, xa, lb, xb, (se + 15) >> 4, acc, lds);
+        gemm_mainloop2<NT, true, false, true>(la, xa, lb, xb, (se + 15) >> 4, acc, lds);
     } else {   // MODE 4 / 5: rows = mid channels, cols = se, K = batch
         if (r0 >= mcp || n0 >= se) return;
         auto la = [&](int c, int, int kl, int m) -> Pair {
@@ -167,7 +163,7 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
             const f32x4 w = MODE == 4 ? act_f4<ACT>(v) : v;
             return (c * 16 + kl < N && n0 + nn < se) ? w : zero4();
         };
-        gemm_mainloop2<NT, false, false, true, TFNAS_SE_PF2>(la, xa, lb, xb, (N + 15) >> 4, acc, lds);
+        gemm_mainloop2<NT, false, false, true>(la, xa, lb, xb, (N + 15) >> 4, acc, lds);
     }
     (void)id;
 
@@ -584,145 +580,107 @@ __global__ __launch_bounds__(256) void k_se_nn(TfnasCellDesc d, SeArgs a) {
     }
 }
 
-// the wave-level kernels need aligned float4 rows of W_r / the gradients: every SE group's mid width a multiple of 4
-// TfnasCellDesc.route, TFNAS_ROUTE_SE_*: 0 wave-level MFMA kernels where the shapes allow | 1 per-image kernels | 2 LDS-tiled GEMMs:
-// the three formulations of the excite FCs, every one compared with the oracle (tests/test_gpu_cell.py::test_variant_against_oracle)
-static inline int se_variant(const TfnasCellDesc& d) { return route_se(d); }
-static bool se_wave_ok(const TfnasCellDesc& d) {
-    if (se_variant(d) != 0) return false;
-    for (int g = 0; g < d.G; ++g)
-        if (d.g[g].se > 0 && ((d.g[g].mc & 3) || (d.g[g].se & 3) || d.g[g].mc < 4)) return false;
-    return true;
-}
-#define SEW_LAUNCH(KERNEL, MODE_, GRID)                                                                   \
-    {                                                                                                    \
-        if (d.act == TFNAS_ACT_RELU)                                                                     \
-            hipLaunchKernelGGL((KERNEL<MODE_, TFNAS_ACT_RELU>), GRID, dim3(256), 0, s, d, a);            \
-        else                                                                                             \
-            hipLaunchKernelGGL((KERNEL<MODE_, TFNAS_ACT_SWISH>), GRID, dim3(256), 0, s, d, a);           \
-    }
-
 // ============================================================================ host launchers
-static int se_count(const TfnasCellDesc& d, int& mcp_max, int& se_max) {
-    int t = 0;
-    mcp_max = se_max = 0;
-    for (int g = 0; g < d.G; ++g)
-        if (d.g[g].se > 0) {
-            ++t;
-            if (d.g[g].mcp > mcp_max) mcp_max = d.g[g].mcp;
-            if (d.g[g].se > se_max) se_max = d.g[g].se;
-        }
-    return t;
-}
-
-// K-splits of MODE 0 / 2: >= 4 chunks of 16 channels per split, <= 16 splits, partials must fit `cap` floats
-static int se_ksplit(const TfnasCellDesc& d, int mcp_max, size_t cap) {
-    int ks = ((mcp_max + 15) / 16) / 4;
-    if (ks > 16) ks = 16;
+// What the excite launchers launch, chosen once from the descriptor (TfnasCellDesc.route, TFNAS_ROUTE_SE_*: 0 wave-level MFMA
+// kernels where the shapes allow | 1 per-image kernels | 2 LDS-tiled GEMMs: the three formulations of the excite FCs, every one
+// compared with the oracle, tests/test_gpu_cell.py::test_variant_against_oracle); the launchers carry it out.
+enum SeVariant { SE_WAVE, SE_IMAGE, SE_TILED };
+struct SePlan {
+    SeVariant var;
+    int ng;                 // SE groups of the launch (0: nothing is launched)
+    int mcp_max, se_max;    // widest padded mid / hidden width among them
+    int ksplit;             // SE_TILED: K-splits of MODE 0 / 2
+    size_t shm;             // SE_IMAGE: dynamic LDS bytes
+};
+static SePlan se_plan(const TfnasCellDesc& d, size_t scratch_floats) {
+    SePlan p = {SE_TILED, 0, 0, 0, 1, 0};
+    // the wave-level kernels need aligned float4 rows of W_r / the gradients: every SE group's mid width a multiple of 4
+    bool wave = route_se(d) == 0;
+    for (int g = 0; g < d.G; ++g) {
+        const TfnasGroup& gr = d.g[g];
+        if (gr.se <= 0) continue;
+        ++p.ng;
+        if (gr.mcp > p.mcp_max) p.mcp_max = gr.mcp;
+        if (gr.se > p.se_max) p.se_max = gr.se;
+        if ((gr.mc & 3) || (gr.se & 3) || gr.mc < 4) wave = false;
+    }
+    // the per-image kernels need the pooled row + hidden vectors in LDS
+    p.shm = (size_t)(((p.mcp_max + 3) & ~3) + ((p.se_max + 3) & ~3) + 256 + SE_CH * (p.se_max | 1)) * sizeof(float);
+    if (wave) p.var = SE_WAVE;
+    else if (route_se(d) != 2 && p.se_max <= 256 && p.shm <= 60 * 1024) p.var = SE_IMAGE;
+    // K-splits of MODE 0 / 2: >= 4 chunks of 16 channels per split, <= 16 splits, partials must fit the scratch
+    p.ksplit = ((p.mcp_max + 15) / 16) / 4;
+    if (p.ksplit > 16) p.ksplit = 16;
     const size_t per = (size_t)d.N * d.SE;
-    if (per && (size_t)ks > cap / per) ks = (int)(cap / per);
-    return ks < 1 ? 1 : ks;
+    if (per && (size_t)p.ksplit > scratch_floats / per) p.ksplit = (int)(scratch_floats / per);
+    if (p.ksplit < 1) p.ksplit = 1;
+    return p;
 }
 
-// the fused per-image kernels need the pooled row + hidden vectors in LDS
-static size_t se_fused_lds(int mcp_max, int se_max) {
-    return (size_t)(((mcp_max + 3) & ~3) + ((se_max + 3) & ~3) + 256 + SE_CH * (se_max | 1)) * sizeof(float);
-}
-static bool se_fused_ok(const TfnasCellDesc& d, int mcp_max, int se_max) {
-    if (se_variant(d) == 2) return false;
-    return se_max <= 256 && se_fused_lds(mcp_max, se_max) <= 60 * 1024;
-}
-
-#define SE_FINISH(MODE_)                                                                                 \
-    if (a.ksplit > 1) {                                                                                  \
-        dim3 fgrid(cdiv(d.N * d.SE, 256));                                                               \
-        if (d.act == TFNAS_ACT_RELU)                                                                     \
-            hipLaunchKernelGGL((k_se_finish<MODE_, TFNAS_ACT_RELU>), fgrid, dim3(256), 0, s, d, a);      \
-        else                                                                                             \
-            hipLaunchKernelGGL((k_se_finish<MODE_, TFNAS_ACT_SWISH>), fgrid, dim3(256), 0, s, d, a);     \
+template <int MODE>
+static void se_gemm(const TfnasCellDesc& d, const SeArgs& a, int rows, int cols, int ng, hipStream_t s) {
+    dim3 grid(cdiv(rows, 128) * ((MODE == 0 || MODE == 2) ? a.ksplit : 1), cdiv(cols, 64), ng);
+    ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_gemm<MODE, ACT>), grid, dim3(256), 0, s, d, a); })
+    if constexpr (MODE == 0 || MODE == 2) {      // (their K-split partials)
+        if (a.ksplit > 1)
+            ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_finish<MODE, ACT>), dim3(cdiv(d.N * d.SE, 256)), dim3(256), 0, s, d, a); })
     }
-
-#define SE_LAUNCH(MODE_, rows, cols)                                                                     \
-    {                                                                                                    \
-        dim3 grid(cdiv((rows), 128) * (((MODE_) == 0 || (MODE_) == 2) ? a.ksplit : 1), cdiv((cols), 64), ng); \
-        if (d.act == TFNAS_ACT_RELU)                                                                     \
-            hipLaunchKernelGGL((k_se_gemm<MODE_, TFNAS_ACT_RELU>), grid, dim3(256), 0, s, d, a);         \
-        else                                                                                             \
-            hipLaunchKernelGGL((k_se_gemm<MODE_, TFNAS_ACT_SWISH>), grid, dim3(256), 0, s, d, a);        \
-    }
+}
 
 int launch_se_fc_fwd(const TfnasCellDesc& d, const float* pooled, float* hpre, float* gate, float* scratch,
                      size_t scratch_floats, hipStream_t s) {
     ProfScope _prof(TK_SE_FC_FWD, s);
-    int mcp_max, se_max;
-    const int ng = se_count(d, mcp_max, se_max);
-    if (!ng) return 0;
-    if (se_wave_ok(d)) {
-        SeArgs a = {pooled, gate, hpre, nullptr, nullptr, hpre, nullptr, 1};
-        SEW_LAUNCH(k_se_nt, 0, dim3(cdiv(d.N, 16), cdiv(se_max, 16), ng))
+    const SePlan p = se_plan(d, scratch ? scratch_floats : 0);
+    if (!p.ng) return 0;
+    SeArgs a = {pooled, gate, hpre, nullptr, nullptr, hpre, nullptr, 1};
+    if (p.var == SE_TILED) a.scratch = scratch, a.ksplit = p.ksplit;
+    if (p.var == SE_WAVE) {
+        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_nt<0, ACT>), dim3(cdiv(d.N, 16), cdiv(p.se_max, 16), p.ng), dim3(256), 0, s, d, a); })
         a.out0 = gate;
-        SEW_LAUNCH(k_se_nt, 1, dim3(cdiv(d.N, 16), cdiv(mcp_max, 64), ng))
-        return (int)hipGetLastError();
+        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_nt<1, ACT>), dim3(cdiv(d.N, 16), cdiv(p.mcp_max, 64), p.ng), dim3(256), 0, s, d, a); })
+    } else if (p.var == SE_IMAGE) {
+        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_fused_fwd<ACT>), dim3(d.N, p.ng), dim3(256), p.shm, s, d, pooled, hpre, gate); })
+    } else {
+        se_gemm<0>(d, a, d.N, p.se_max, p.ng, s);
+        a.out0 = gate;
+        se_gemm<1>(d, a, d.N, p.mcp_max, p.ng, s);
     }
-    if (se_fused_ok(d, mcp_max, se_max)) {
-        const size_t shm = se_fused_lds(mcp_max, se_max);
-        if (d.act == TFNAS_ACT_RELU)
-            hipLaunchKernelGGL((k_se_fused_fwd<TFNAS_ACT_RELU>), dim3(d.N, ng), dim3(256), shm, s, d, pooled, hpre, gate);
-        else
-            hipLaunchKernelGGL((k_se_fused_fwd<TFNAS_ACT_SWISH>), dim3(d.N, ng), dim3(256), shm, s, d, pooled, hpre, gate);
-        return (int)hipGetLastError();
-    }
-    SeArgs a = {pooled, gate, hpre, nullptr, nullptr, hpre, scratch, se_ksplit(d, mcp_max, scratch ? scratch_floats : 0)};
-    SE_LAUNCH(0, d.N, se_max)
-    SE_FINISH(0)
-    a.out0 = gate;
-    SE_LAUNCH(1, d.N, mcp_max)
     return (int)hipGetLastError();
 }
 
-int launch_se_fc_bwd(const TfnasCellDesc& d, const float* dgate, const float* gate, const float* hpre,
-                     float* dgl, float* dhpre, float* dpooled, float* scratch, size_t scratch_floats, hipStream_t s) {
+int launch_se_fc_bwd(const TfnasCellDesc& d, const float* dgate, const float* gate, const float* hpre, float* dhpre,
+                     float* dpooled, float* scratch, size_t scratch_floats, hipStream_t s) {
     ProfScope _prof(TK_SE_FC_BWD, s);
-    (void)dgl;
-    int mcp_max, se_max;
-    const int ng = se_count(d, mcp_max, se_max);
-    if (!ng) return 0;
-    if (se_wave_ok(d)) {
-        SeArgs a = {nullptr, gate, hpre, dgate, dhpre, dhpre, nullptr, 1};
-        SEW_LAUNCH(k_se_nn, 2, dim3(cdiv(d.N, 16), cdiv(se_max, 64), ng))
+    const SePlan p = se_plan(d, scratch ? scratch_floats : 0);
+    if (!p.ng) return 0;
+    SeArgs a = {nullptr, gate, hpre, dgate, dhpre, dhpre, nullptr, 1};
+    if (p.var == SE_TILED) a.scratch = scratch, a.ksplit = p.ksplit;
+    if (p.var == SE_WAVE) {
+        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_nn<2, ACT>), dim3(cdiv(d.N, 16), cdiv(p.se_max, 64), p.ng), dim3(256), 0, s, d, a); })
         a.out0 = dpooled;
-        SEW_LAUNCH(k_se_nn, 3, dim3(cdiv(d.N, 16), cdiv(mcp_max, 256), ng))
-        return (int)hipGetLastError();
+        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_nn<3, ACT>), dim3(cdiv(d.N, 16), cdiv(p.mcp_max, 256), p.ng), dim3(256), 0, s, d, a); })
+    } else if (p.var == SE_IMAGE) {
+        ACT_DISPATCH(d.act, {
+            hipLaunchKernelGGL((k_se_fused_bwd<ACT>), dim3(d.N, p.ng), dim3(256), p.shm, s, d, dgate, gate, hpre, dhpre, dpooled);
+        })
+    } else {
+        se_gemm<2>(d, a, d.N, p.se_max, p.ng, s);
+        a.out0 = dpooled;
+        se_gemm<3>(d, a, d.N, p.mcp_max, p.ng, s);
     }
-    if (se_fused_ok(d, mcp_max, se_max)) {
-        const size_t shm = se_fused_lds(mcp_max, se_max);
-        if (d.act == TFNAS_ACT_RELU)
-            hipLaunchKernelGGL((k_se_fused_bwd<TFNAS_ACT_RELU>), dim3(d.N, ng), dim3(256), shm, s, d, dgate, gate, hpre,
-                               dhpre, dpooled);
-        else
-            hipLaunchKernelGGL((k_se_fused_bwd<TFNAS_ACT_SWISH>), dim3(d.N, ng), dim3(256), shm, s, d, dgate, gate, hpre,
-                               dhpre, dpooled);
-        return (int)hipGetLastError();
-    }
-    SeArgs a = {nullptr, gate, hpre, dgate, dhpre, dhpre, scratch, se_ksplit(d, mcp_max, scratch ? scratch_floats : 0)};
-    SE_LAUNCH(2, d.N, se_max)
-    SE_FINISH(2)
-    a.out0 = dpooled;
-    SE_LAUNCH(3, d.N, mcp_max)
     return (int)hipGetLastError();
 }
 
 int launch_se_wgrad(const TfnasCellDesc& d, const float* dgate, const float* gate, const float* dhpre,
                     const float* hpre, const float* pooled, hipStream_t s) {
     ProfScope _prof(TK_SE_WGRAD, s);
-    int mcp_max, se_max;
-    const int ng = se_count(d, mcp_max, se_max);
-    if (!ng) return 0;
+    const SePlan p = se_plan(d, 0);
+    if (!p.ng) return 0;
     SeArgs a = {pooled, gate, hpre, dgate, dhpre, nullptr, nullptr, 1};
     // (a wave-level TN formulation of these two, K = batch = 128 images, was built and measured: 51 instead of 36 us per cell
-    //  for the three launches -- ~100 waves walking 32 dependent K-steps each; the LDS-tiled GEMMs stay)
-    SE_LAUNCH(4, mcp_max, se_max)
-    SE_LAUNCH(5, mcp_max, se_max)
-    hipLaunchKernelGGL(k_se_bias_grad, dim3(cdiv(mcp_max + se_max, 64), ng), dim3(256), 0, s, d, a);
+    //  for the three launches -- ~100 waves walking 32 dependent K-steps each; the LDS-tiled GEMMs stay in every variant)
+    se_gemm<4>(d, a, p.mcp_max, p.se_max, p.ng, s);
+    se_gemm<5>(d, a, p.mcp_max, p.se_max, p.ng, s);
+    hipLaunchKernelGGL(k_se_bias_grad, dim3(cdiv(p.mcp_max + p.se_max, 64), p.ng), dim3(256), 0, s, d, a);
     return (int)hipGetLastError();
 }
