@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-/* 4, additive: tfnas_cls_ce_ex / tfnas_cls_reduce (the derived network's retrain tail: label smoothing, rank, forward-only form,
+/* 4, additive: tfnas_cls_wgrad_ex (tfnas_cls_wgrad + the search epoch's running loss / top-1 / top-5 / invalid-target meter).
+ * 4, additive: tfnas_cls_ce_ex / tfnas_cls_reduce (the derived network's retrain tail: label smoothing, rank, forward-only form,
  * device-side upstream gradient, running meter).
  * 4, additive: TFNAS_CELL_ACCUM_WGRAD (weight gradients added to their destinations, per launch) and tfnas_path_set_wgrad_accum.
  * 4 (round 6): every route switch of a launch lives in its descriptor (TfnasCellDesc.route: TFNAS_ROUTE_*); the library reads no
@@ -363,6 +364,24 @@ int tfnas_cls_ce_ex(int N, int C, int K, const float *pooled, const float *W, co
                     float eps, float *logits, float *loss_n, int32_t *rank, float *dlogits, float *dpooled, void *stream);
 int tfnas_cls_reduce(int N, int C, int K, const float *pooled, const float *dlogits, const float *loss_n, const int32_t *rank,
                      const float *gscale, int accumulate, float *dW, float *db, float *out, double *meter, void *stream);
+/* tfnas_cls_wgrad_ex = tfnas_cls_wgrad + the running meter of a search epoch (train_search.py:387-391: objs_w.update(loss_w, n),
+ * top1 / top5 of the GUMBEL path's logits), folded into the same launch: same grid, tiles and summation orders, so dW, db and loss
+ * are bit-identical to tfnas_cls_wgrad on the same inputs, with or without a meter.
+ *   npath (1 or 2), N, C, K, pooled / dlogits / loss_n (npath device pointers each), loss_scale, dW [K][C], db [K], loss (or NULL):
+ *     as tfnas_cls_wgrad.
+ *   rank0  int32 [N]: rank[] of path 0 as tfnas_cls_ce_ex wrote it for the launch that produced dlogits[0] / loss_n[0] (rank < k is a
+ *     top-k hit, ties go to the lower class index, -1 marks a target outside [0, K)).  Read only when meter is given.
+ *   meter  5 doubles on the device, the tfnas_cls_reduce layout, or NULL (then the call equals tfnas_cls_wgrad and rank0 is ignored):
+ *     meter[0] += sum_p sum_n loss_n_p[n]   (ALL npath paths: N * (loss_g + loss_r) of the mean-reduced losses, in double)
+ *     meter[1] += #(0 <= rank0 < 1);  meter[2] += #(0 <= rank0 < 5);  meter[3] += N;  meter[4] += #(rank0 < 0)
+ *     added by one thread in that order with ordinary loads and stores, no atomics: launches that share a meter (this one,
+ *     tfnas_cls_reduce) must be ordered by their stream; the host zeroes it and reads it, e.g. once per epoch.
+ * An invalid target carries over from the per-image launch: tfnas_cls_ce_ex gives loss_n = NaN for it, so meter[0] (and loss) become
+ * NaN while meter[4] counts it -- the retrain meter's semantics; tfnas_cls_ce gives 0, so a path computed by it contributes nothing.
+ * TFNAS_ENULL: meter without rank0, or what tfnas_cls_wgrad rejects; TFNAS_ERANGE as tfnas_cls_wgrad. */
+int tfnas_cls_wgrad_ex(int npath, int N, int C, int K, const float *const *pooled, const float *const *dlogits,
+                       const float *const *loss_n, const int32_t *rank0, float loss_scale, float *dW, float *db, float *loss,
+                       double *meter, void *stream);
 /* dst[i] += src[i], count floats (a multiple of 4): the second path's share of a shared parameter's gradient. */
 int tfnas_add_into(float *dst, const float *src, uint64_t count, void *stream);
 

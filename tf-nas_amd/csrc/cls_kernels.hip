@@ -268,22 +268,70 @@ __device__ __forceinline__ void cls_dw_tile(float (*dl)[4], int npath, int N, in
     }
 }
 
+// The last blockIdx.y row of the weight step's summation launch: db, then the first wave sums loss_n of every path in double
+// (lane-strided, then butterfly: a fixed order) and its first thread stores loss.  METER (k_cls_wgrad_ex): the same wave counts
+// rank < 1, rank < 5 and rank < 0 of path 0 and the thread adds {sum loss_n, top-1, top-5, N, invalid} to the running meter with
+// ordinary loads and stores, like k_cls_reduce -- launches that share a meter are ordered by their stream.
+template <bool METER>
+__device__ __forceinline__ void cls_wgrad_row(int npath, int N, int K, const ClsPaths& P, const int32_t* __restrict__ rank0,
+                                              float loss_scale, float* __restrict__ db, float* __restrict__ loss,
+                                              double* __restrict__ meter) {
+    const int tid = threadIdx.x;
+    cls_db_row<false>(npath, N, K, P, 1.f, 0, db);
+    if (tid < 64) {
+        double s = 0.0;
+        for (int p = 0; p < npath; ++p)
+            for (int n = tid; n < N; n += 64) s += (double)P.loss_n[p][n];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (tid == 0 && loss) loss[0] = (float)(s * (double)loss_scale);
+        if constexpr (METER) {
+            if (!meter) return;                              // (a kernel argument: the whole wave leaves together)
+            int c1 = 0, c5 = 0, bad = 0;
+            for (int n = tid; n < N; n += 64) {
+                const int r = rank0[n];
+                bad += r < 0 ? 1 : 0;
+                c1 += (r >= 0 && r < 1) ? 1 : 0;
+                c5 += (r >= 0 && r < 5) ? 1 : 0;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                c1 += __shfl_xor(c1, o, 64);
+                c5 += __shfl_xor(c5, o, 64);
+                bad += __shfl_xor(bad, o, 64);
+            }
+            if (tid == 0) {
+                meter[0] += s;
+                meter[1] += (double)c1;
+                meter[2] += (double)c5;
+                meter[3] += (double)N;
+                meter[4] += (double)bad;
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_cls_wgrad(int npath, int N, int C, int K, ClsPaths P, float loss_scale,
                                                    float* __restrict__ dW, float* __restrict__ db, float* __restrict__ loss) {
     __shared__ float dl[256][4];
-    const int tid = threadIdx.x;
     const int kgroups = (K + 3) >> 2;
     if ((int)blockIdx.y == kgroups) {
         if (blockIdx.x != 0) return;
-        cls_db_row<false>(npath, N, K, P, 1.f, 0, db);
-        if (tid < 64) {
-            double s = 0.0;
-            for (int p = 0; p < npath; ++p)
-                for (int n = tid; n < N; n += 64) s += (double)P.loss_n[p][n];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-            if (tid == 0 && loss) loss[0] = (float)(s * (double)loss_scale);
-        }
+        cls_wgrad_row<false>(npath, N, K, P, nullptr, loss_scale, db, loss, nullptr);
+        return;
+    }
+    cls_dw_tile<false>(dl, npath, N, C, K, P, 1.f, 0, dW);
+}
+
+// k_cls_wgrad + the search epoch's running meter (the w block of tail.SearchMeter): same grid, tiles and summation orders.
+__global__ __launch_bounds__(256) void k_cls_wgrad_ex(int npath, int N, int C, int K, ClsPaths P, const int32_t* __restrict__ rank0,
+                                                      float loss_scale, float* __restrict__ dW, float* __restrict__ db,
+                                                      float* __restrict__ loss, double* __restrict__ meter) {
+    __shared__ float dl[256][4];
+    const int kgroups = (K + 3) >> 2;
+    if ((int)blockIdx.y == kgroups) {
+        if (blockIdx.x != 0) return;
+        cls_wgrad_row<true>(npath, N, K, P, rank0, loss_scale, db, loss, meter);
         return;
     }
     cls_dw_tile<false>(dl, npath, N, C, K, P, 1.f, 0, dW);
@@ -415,9 +463,11 @@ extern "C" int tfnas_cls_reduce(int N, int C, int K, const float* pooled, const 
     return (int)hipGetLastError();
 }
 
-extern "C" int tfnas_cls_wgrad(int npath, int N, int C, int K, const float* const* pooled, const float* const* dlogits,
-                               const float* const* loss_n, float loss_scale, float* dW, float* db, float* loss, void* stream) {
+static int cls_wgrad_launch(int npath, int N, int C, int K, const float* const* pooled, const float* const* dlogits,
+                            const float* const* loss_n, const int32_t* rank0, float loss_scale, float* dW, float* db, float* loss,
+                            double* meter, bool ex, void* stream) {
     if (!pooled || !dlogits || !loss_n || !dW || !db) return TFNAS_ENULL;
+    if (meter && !rank0) return TFNAS_ENULL;
     if (npath < 1 || npath > 2 || N < 1 || K < 1 || C < 1) return TFNAS_ERANGE;
     ClsPaths P = {};
     for (int p = 0; p < npath; ++p) {
@@ -428,8 +478,24 @@ extern "C" int tfnas_cls_wgrad(int npath, int N, int C, int K, const float* cons
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ProfScope _prof(TK_SMALL, s);
-    hipLaunchKernelGGL(k_cls_wgrad, dim3(cdiv(C, 256), cdiv(K, 4) + 1), dim3(256), 0, s, npath, N, C, K, P, loss_scale, dW, db, loss);
+    const dim3 grid(cdiv(C, 256), cdiv(K, 4) + 1);
+    if (ex)
+        hipLaunchKernelGGL(k_cls_wgrad_ex, grid, dim3(256), 0, s, npath, N, C, K, P, rank0, loss_scale, dW, db, loss, meter);
+    else
+        hipLaunchKernelGGL(k_cls_wgrad, grid, dim3(256), 0, s, npath, N, C, K, P, loss_scale, dW, db, loss);
     return (int)hipGetLastError();
+}
+
+extern "C" int tfnas_cls_wgrad(int npath, int N, int C, int K, const float* const* pooled, const float* const* dlogits,
+                               const float* const* loss_n, float loss_scale, float* dW, float* db, float* loss, void* stream) {
+    return cls_wgrad_launch(npath, N, C, K, pooled, dlogits, loss_n, nullptr, loss_scale, dW, db, loss, nullptr, false, stream);
+}
+
+extern "C" int tfnas_cls_wgrad_ex(int npath, int N, int C, int K, const float* const* pooled, const float* const* dlogits,
+                                  const float* const* loss_n, const int32_t* rank0, float loss_scale, float* dW, float* db,
+                                  float* loss, double* meter, void* stream) {
+    return cls_wgrad_launch(npath, N, C, K, pooled, dlogits, loss_n, meter ? rank0 : nullptr, loss_scale, dW, db, loss, meter, true,
+                            stream);
 }
 
 extern "C" int tfnas_add_into(float* dst, const float* src, uint64_t count, void* stream) {

@@ -96,6 +96,7 @@ _PROTOS = {
     'tfnas_head_wgrad': (C.c_int, [C.POINTER(TfnasCellDesc)] + [_P] * 6),
     'tfnas_cls_ce': (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
     'tfnas_cls_wgrad': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _PP, _PP, _PP, C.c_float, _P, _P, _P, _P]),
+    'tfnas_cls_wgrad_ex': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _PP, _PP, _PP, _P, C.c_float, _P, _P, _P, _P, _P]),
     'tfnas_cls_ce_ex': (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P]),
     'tfnas_cls_reduce': (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     'tfnas_add_into': (C.c_int, [_P, _P, C.c_uint64, _P]),

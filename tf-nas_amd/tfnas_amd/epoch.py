@@ -201,14 +201,35 @@ def cosine_lr_list(w_lr, epochs):
     return [0.5 * w_lr * (1.0 + math.cos(math.pi * e / float(epochs))) for e in range(epochs)]
 
 
+def train_stats(stats, m, epoch, arch_epoch, num_classes):
+    """Fill an epoch's training statistics from a SearchMeter.read() dict ``m`` -- what train_wo_arch / train_w_arch report
+    (train_search.py:345-354, 387-432) -- after refusing an epoch that trained on out-of-range targets: the classifier kernels flag
+    them and give them no gradient, the meter counts them (as run_retrain does for the retrain loop)."""
+    if m['invalid'] > 0:
+        raise ValueError('search_epoch: epoch %d saw %d target(s) outside [0, %d)' % (epoch, m['invalid'], num_classes))
+    stats['train_top1'], stats['train_top5'], stats['train_objs_w'] = m['top1'], m['top5'], m['objs_w']
+    if arch_epoch:
+        stats['train_objs_a'], stats['train_objs_l'] = m['objs_a'], m['objs_l']
+    return stats
+
+
 def search_epoch(epoch, state_dict, mc_mask_dddict, lat_lookup, train_queue, val_queue, *, num_classes=100, epochs=100,
                  lr=0.025, T=5.0, w_mom=0.9, w_wd=1e-5, a_lr=0.01, a_wd=5e-4, a_betas=(0.5, 0.999), grad_clip=5.0,
-                 target_lat=15.0, lambda_lat=0.1, warmup_epochs=10, noise=None, device='cuda', group=None, log=None):
+                 target_lat=15.0, lambda_lat=0.1, warmup_epochs=10, noise=None, device='cuda', group=None, log=None,
+                 print_freq=100):
     """One epoch of the reference's main loop (train_search.py:155-307) on the HIP model.  ``state_dict`` / ``mc_mask_dddict``
     are updated in place and returned together with the epoch's statistics.  ``train_queue`` / ``val_queue``: iterables of
-    (x, target) batches (the weight-sharing / arch-step queues of train_w_arch)."""
+    (x, target) batches (the weight-sharing / arch-step queues of train_w_arch).
+
+    The training loss / top-1 / top-5 of the epoch (the reference's AverageMeters) are summed on the device by the steps themselves
+    (tail.SearchMeter) and read once after the loop -- summed over the ranks of ``group`` first -- into ``stats['train_top1']``,
+    ``['train_top5']``, ``['train_objs_w']`` and, in architecture epochs, ``['train_objs_a']``, ``['train_objs_l']``.  With a ``log``
+    the reference's TRAIN lines are logged every ``print_freq`` steps from this rank's running sums: one more read, i.e. one host
+    synchronisation, per ``print_freq`` steps, and none without a ``log``."""
     from . import search
+    from .tail import SearchMeter
     from .model_search import Network
+    step_log = log                                                 # (None: no per-step lines, hence no read inside the loop)
     log = log or (lambda *a: None)
     lat_keys = geometry.make_lat_lookup_key_dddict()
     mc_max = geometry.get_mc_num_dddict(mc_mask_dddict, is_max=True)
@@ -221,14 +242,16 @@ def search_epoch(epoch, state_dict, mc_mask_dddict, lat_lookup, train_queue, val
     noise = noise or search.NoiseSource(1000 + epoch)
     dev = torch.device(device)
     stats = dict(epoch=epoch, lr=lr, T=T, steps=0)
+    arch_epoch = epoch >= warmup_epochs
+    meter = SearchMeter(dev)
     val_iter = iter(val_queue) if val_queue is not None else None
     try:
         for step, (x_w, t_w) in enumerate(train_queue):
             x_w, t_w = x_w.to(dev, non_blocking=True), t_w.to(dev, non_blocking=True)
-            if epoch < warmup_epochs:                              # train_wo_arch (train_search.py:318-354)
-                search.w_step(state, x_w, t_w, opt_w, grad_clip, noise.exp(dev), bi_sampling=False, group=group)
+            if not arch_epoch:                                     # train_wo_arch (train_search.py:318-354)
+                search.w_step(state, x_w, t_w, opt_w, grad_clip, noise.exp(dev), bi_sampling=False, group=group, meter=meter)
             else:                                                  # train_w_arch (train_search.py:357-432)
-                search.w_step(state, x_w, t_w, opt_w, grad_clip, noise.exp(dev), noise.rand_pos(), group=group)
+                search.w_step(state, x_w, t_w, opt_w, grad_clip, noise.exp(dev), noise.rand_pos(), group=group, meter=meter)
                 if step % 2 == 0:
                     try:
                         x_a, t_a = next(val_iter)
@@ -236,11 +259,20 @@ def search_epoch(epoch, state_dict, mc_mask_dddict, lat_lookup, train_queue, val
                         val_iter = iter(val_queue)
                         x_a, t_a = next(val_iter)
                     la, ll, lat, _ = search.a_step(state, x_a.to(dev, non_blocking=True), t_a.to(dev, non_blocking=True), opt_a,
-                                                   target_lat, lambda_lat, grad_clip, noise.exp(dev), group=group)
+                                                   target_lat, lambda_lat, grad_clip, noise.exp(dev), group=group, meter=meter)
                     stats['last_lat'] = lat
+            if step_log is not None and step % print_freq == 0:    # train_search.py:351-352, 428-430
+                m = meter.read()
+                if arch_epoch:
+                    log('TRAIN w_Arch Step: %04d Objs_W: %f R1: %f R5: %f Objs_A: %f Objs_L: %f'
+                        % (step, m['objs_w'], m['top1'], m['top5'], m['objs_a'], m['objs_l']))
+                else:
+                    log('TRAIN wo_Arch Step: %04d Objs: %f R1: %f R5: %f' % (step, m['objs_w'], m['top1'], m['top5']))
             stats['steps'] = step + 1
         if 'last_lat' in stats:
             stats['last_lat'] = float(stats['last_lat'])
+        meter.reduce_(group)
+        train_stats(stats, meter.read(), epoch, arch_epoch, num_classes)
         if epochs - epoch < 5 and val_queue is not None:           # validation for the last 5 epochs (train_search.py:229-231)
             stats['val_top1'], stats['val_top5'], stats['val_loss'] = search.validate(state, val_queue, noise=noise)
         torch.cuda.synchronize(dev) if dev.type == 'cuda' else None
@@ -293,5 +325,7 @@ def run_search(save_dir, lat_lookup, make_train_queue, make_val_queue, *, num_cl
         if epoch >= warmup_epochs:
             T *= T_decay
         save_search_checkpoint(save_dir, epoch + 1, state_dict, mc_mask)
+        if log is not None:
+            log('Train_acc %f' % stats['train_top1'])              # train_search.py:225
         history.append(stats)
     return history

@@ -687,13 +687,17 @@ def host_gumbel_positions(log_alphas, exp_noise, T):
 
 
 def w_step(state, x, target, opt_w, grad_clip=5.0, noise_g=None, rand_pos=None, bi_sampling=True, group=None,
-           overlap_paths=True):
+           overlap_paths=True, meter=None):
     """Weight step: CE(gumbel path) [+ CE(random path)] -> backward -> (all-reduce) -> clip -> SGD.
 
     The two sampled paths of bi-sampling are independent sub-graphs (different candidates, same input) whose
     kernels are too small to fill 256 CUs at 128 images; with ``overlap_paths`` the 'random' path is enqueued on a
     second HIP stream, so its forward -- and, because autograd replays every node on its forward stream, its
-    backward -- runs concurrently with the 'gumbel' path.  Same arithmetic, same results."""
+    backward -- runs concurrently with the 'gumbel' path.  Same arithmetic, same results.
+
+    ``meter`` (a tail.SearchMeter): the step's n * loss and the gumbel path's top-1 / top-5 hits (train_search.py:345-349,
+    387-391) are added to it on the device, without a host read -- by the fused tail's own launches where it runs, by torch ops
+    (SearchMeter.add_w) on every other route.  With ``meter=None`` every route enqueues exactly what it did without the argument."""
     model = state.model
     state.throttle(x.device)
     state.require(True, False)
@@ -703,7 +707,7 @@ def w_step(state, x, target, opt_w, grad_clip=5.0, noise_g=None, rand_pos=None, 
     overlap = bi_sampling and overlap_paths and x.is_cuda
     host_e = getattr(noise_g, '_tfnas_host', None) if HOST_SAMPLING else None
     if state.runner is not None and USE_PATHS and overlap_paths and (not bi_sampling or rand_pos is not None):
-        return _w_step_paths(state, x, target, opt_w, grad_clip, noise_g, host_e, rand_pos, bi_sampling, group)
+        return _w_step_paths(state, x, target, opt_w, grad_clip, noise_g, host_e, rand_pos, bi_sampling, group, meter)
     if INTERLEAVE_PATHS and overlap and host_e is not None and rand_pos is not None and hasattr(model, 'forward_bisample'):
         # fast path: positions known on the host -> both paths in one interleaved sweep (see forward_bisample)
         cur = torch.cuda.current_stream(x.device)
@@ -723,6 +727,8 @@ def w_step(state, x, target, opt_w, grad_clip=5.0, noise_g=None, rand_pos=None, 
         if grad_clip > 0:
             nn.utils.clip_grad_norm_(state.weights, grad_clip)
         opt_w.step()
+        if meter is not None:
+            meter.add_w(loss, logits_g, target)
         state.mark_step(x.device)
         return loss.detach(), logits_g.detach()
     kw, feat, leaf = {}, None, None
@@ -773,11 +779,13 @@ def w_step(state, x, target, opt_w, grad_clip=5.0, noise_g=None, rand_pos=None, 
     if grad_clip > 0:
         nn.utils.clip_grad_norm_(state.weights, grad_clip)
     opt_w.step()
+    if meter is not None:
+        meter.add_w(loss, logits_g, target)
     state.mark_step(x.device)
     return loss.detach(), logits_g.detach()
 
 
-def _w_step_paths(state, x, target, opt_w, grad_clip, noise_g, host_e, rand_pos, bi_sampling, group):
+def _w_step_paths(state, x, target, opt_w, grad_clip, noise_g, host_e, rand_pos, bi_sampling, group, meter=None):
     """w_step on the path level: stems -> ONE node for the sampled path(s) -> head(s); weight gradients of the cells land
     in the WeightArena, everything else is unchanged (same kernels, same clip / SGD)."""
     model, runner = state.model, state.runner
@@ -825,7 +833,8 @@ def _w_step_paths(state, x, target, opt_w, grad_clip, noise_g, host_e, rand_pos,
         oa, ob = runner.bisampled(feat, idx_a, idx_b, side)
         tail = state.bitail()
         wmap = runner.wgrad_streams
-        loss, logits_g = BiTailFn.apply(tail, model, oa, ob, target, side, [wmap['A'], wmap['B']] if len(wmap) == 2 else None)
+        loss, logits_g = BiTailFn.apply(tail, model, oa, ob, target, side, [wmap['A'], wmap['B']] if len(wmap) == 2 else None,
+                                        meter)
     elif bi_sampling:
         cur = torch.cuda.current_stream(dev)
         side = state.side_stream(dev)
@@ -860,6 +869,8 @@ def _w_step_paths(state, x, target, opt_w, grad_clip, noise_g, host_e, rand_pos,
         if grad_clip > 0:
             nn.utils.clip_grad_norm_(state.weights, grad_clip)
         opt_w.step()
+    if meter is not None and tail is None:      # (the fused tail's summation launch has added this step already)
+        meter.add_w(loss, logits_g, target)
     state.mark_step(dev)
     return loss.detach(), logits_g.detach()
 
@@ -877,21 +888,26 @@ def _a_forward_paths(state, x, noise):
 
 
 def a_step(state, x, target, opt_a, target_lat=15.0, lambda_lat=0.1, grad_clip=5.0, noise=None, group=None,
-           return_grads=False):
+           return_grads=False, meter=None):
     """Architecture step: CE + lambda*|lat/target-1| -> backward -> (all-reduce) -> clip -> Adam -> log-softmax
-    projection of alphas AND betas (train_search.py:421-422)."""
+    projection of alphas AND betas (train_search.py:421-422).
+
+    ``meter`` (a tail.SearchMeter): n * loss_a, n * loss_l and the step's top-1 / top-5 hits are added to it on the device
+    (train_search.py:424-426 keeps the two losses) -- loss_a and the hits by one metrics-only launch behind the fused classifier
+    tail where it runs, by torch ops (SearchMeter.add_a) otherwise."""
     model = state.model
     state.throttle(x.device)
     state.require(False, True)
-    loss_a = None
+    loss_a, metered = None, False
     if state.runner is not None and USE_PATHS:
         logits, lat = _a_forward_paths(state, x, noise)
         if FUSED_TAIL:                               # (`logits` is the pooled feature vector here)
             from .tail import frozen_classifier_loss
             pooled = logits
-            res = frozen_classifier_loss(model, pooled, target)
+            res = frozen_classifier_loss(model, pooled, target, meter)
             if res is not None:
                 loss_a, logits = res
+                metered = meter is not None
             else:
                 logits = model.classifier(pooled)
     else:
@@ -900,6 +916,11 @@ def a_step(state, x, target, opt_a, target_lat=15.0, lambda_lat=0.1, grad_clip=5
         loss_a = F.cross_entropy(logits, target)
     loss_l = torch.abs(lat / target_lat - 1.) * lambda_lat
     loss = loss_a + loss_l
+    if meter is not None:
+        if metered:
+            meter.add_a(None, loss_l, target.size(0))
+        else:
+            meter.add_a(loss_a, loss_l, target.size(0), logits, target)
     opt_a.zero_grad()
     loss.backward()
     fused = (FUSED_OPT and state.runner is not None and isinstance(opt_a, torch.optim.Adam) and len(opt_a.param_groups) == 1

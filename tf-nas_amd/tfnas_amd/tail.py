@@ -20,6 +20,11 @@ The derived network's retrain path (model_eval.train_step / validate; reference 
 of its own below: ``RetrainTailFn`` (label-smoothed loss, logits and the target's rank, correct under any upstream gradient),
 ``retrain_tail_forward`` (the forward-only kernel for validation) and ``DeviceMeter`` (an epoch's loss / top-1 / top-5 sums kept on
 the device and read once).
+
+``SearchMeter`` is the search loop's counterpart (train_search.py:318-432 keeps AverageMeters on the host and pays a ``.item()`` per
+value and step): the fused tails feed it from launches they make anyway -- ``BiTail.run(meter=...)`` swaps path A's per-image launch
+for its rank-producing form and the summation launch for ``tfnas_cls_wgrad_ex``; ``ClsCeFn`` adds one metrics-only reduction -- and
+every other route adds with torch ops.
 """
 import ctypes as C
 
@@ -63,6 +68,7 @@ class _PathTail:
         self.dlogits = torch.empty((N, K), device=dev, dtype=f32)
         self.logits = torch.empty((N, K), device=dev, dtype=f32)          # (path B's logits: nobody reads them)
         self.loss_n = torch.empty(N, device=dev, dtype=f32)
+        self.rank = torch.empty(N, device=dev, dtype=torch.int32)        # (path A with a meter: the target's rank)
         self.gw = torch.empty(mc * plan.ic, device=dev, dtype=f32) if own_grad else None     # path B's share of d W_feature_mix
 
 
@@ -90,8 +96,10 @@ class BiTail:
         self.loss = torch.zeros((), device=dev, dtype=torch.float32)
         self._key = key
 
-    def run(self, model, oa, ob, target, side, wgrad_streams):
-        """Enqueue both tails; returns (loss 0-dim tensor, logits of path A, d oa, d ob) -- NHWC gradient buffers."""
+    def run(self, model, oa, ob, target, side, wgrad_streams, meter=None):
+        """Enqueue both tails; returns (loss 0-dim tensor, logits of path A, d oa, d ob) -- NHWC gradient buffers.
+        ``meter`` (a SearchMeter): path A's per-image launch becomes tfnas_cls_ce_ex(eps = 0) -- bit-identical outputs plus the
+        target's rank -- and the summation launch tfnas_cls_wgrad_ex, which adds the step to the meter's w block; no launch more."""
         lib = _lib.lib()
         xa, xb = _nhwc(oa), _nhwc(ob)
         dev = xa.device
@@ -118,8 +126,12 @@ class BiTail:
                 t.d.need_wgrad, t.d.g[0].g_expand = 0, None
                 t.dw.need_wgrad, t.dw.g[0].g_expand = 1, gdst
                 check(lib.tfnas_head_fwd(C.byref(t.d), ptr(x), ptr(t.E), ptr(t.stats), ptr(t.part), ptr(t.pooled), s), 'tfnas_head_fwd')
-                check(lib.tfnas_cls_ce(N, Cf, K, ptr(t.pooled), ptr(w_cls), ptr(b_cls), ptr(target), 1.0 / N, ptr(lg), ptr(t.loss_n),
-                                       ptr(t.dlogits), ptr(t.dpooled), s), 'tfnas_cls_ce')
+                if meter is not None and t is self.a:
+                    check(lib.tfnas_cls_ce_ex(N, Cf, K, ptr(t.pooled), ptr(w_cls), ptr(b_cls), ptr(target), 1.0 / N, 0.0, ptr(lg),
+                                              ptr(t.loss_n), ptr(t.rank), ptr(t.dlogits), ptr(t.dpooled), s), 'tfnas_cls_ce_ex')
+                else:
+                    check(lib.tfnas_cls_ce(N, Cf, K, ptr(t.pooled), ptr(w_cls), ptr(b_cls), ptr(target), 1.0 / N, ptr(lg),
+                                           ptr(t.loss_n), ptr(t.dlogits), ptr(t.dpooled), s), 'tfnas_cls_ce')
                 check(lib.tfnas_head_bwd(C.byref(t.d), ptr(x), ptr(t.E), ptr(t.stats), ptr(t.dpooled), ptr(t.dEh), ptr(t.cb1),
                                          ptr(t.red), ptr(t.part), ptr(t.dx), ptr(t.dxp), s), 'tfnas_head_bwd')
                 # the head's weight gradient: a leaf, on the path's weight-gradient stream (joined by tfnas_paths_bwd / w_step)
@@ -134,9 +146,16 @@ class BiTail:
                 if other is not None and other is not w:
                     w.wait_stream(other)
             P = lambda ts: _lib.raw_array([t.data_ptr() for t in ts])
-            check(lib.tfnas_cls_wgrad(2, N, Cf, K, P([self.a.pooled, self.b.pooled]), P([self.a.dlogits, self.b.dlogits]),
-                                      P([self.a.loss_n, self.b.loss_n]), 1.0 / N, C.c_void_p(arena.grad_ptr(w_cls)),
-                                      C.c_void_p(arena.grad_ptr(b_cls)), ptr(self.loss), C.c_void_p(w.cuda_stream)), 'tfnas_cls_wgrad')
+            if meter is not None:
+                check(lib.tfnas_cls_wgrad_ex(2, N, Cf, K, P([self.a.pooled, self.b.pooled]), P([self.a.dlogits, self.b.dlogits]),
+                                             P([self.a.loss_n, self.b.loss_n]), ptr(self.a.rank), 1.0 / N,
+                                             C.c_void_p(arena.grad_ptr(w_cls)), C.c_void_p(arena.grad_ptr(b_cls)), ptr(self.loss),
+                                             meter.w_ptr(dev), C.c_void_p(w.cuda_stream)), 'tfnas_cls_wgrad_ex')
+            else:
+                check(lib.tfnas_cls_wgrad(2, N, Cf, K, P([self.a.pooled, self.b.pooled]), P([self.a.dlogits, self.b.dlogits]),
+                                          P([self.a.loss_n, self.b.loss_n]), 1.0 / N, C.c_void_p(arena.grad_ptr(w_cls)),
+                                          C.c_void_p(arena.grad_ptr(b_cls)), ptr(self.loss), C.c_void_p(w.cuda_stream)),
+                      'tfnas_cls_wgrad')
             check(lib.tfnas_add_into(C.c_void_p(arena.grad_ptr(w_fm)), ptr(self.b.gw), w_fm.numel(), C.c_void_p(w.cuda_stream)),
                   'tfnas_add_into')
         self.join_stream = w if w is not cur else None
@@ -147,8 +166,8 @@ class BiTailFn(torch.autograd.Function):
     """(loss, logits_g) = CE(classifier(head(oa))) + CE(classifier(head(ob))); see the module docstring for the contract."""
 
     @staticmethod
-    def forward(ctx, tail, model, oa, ob, target, side, wgrad_streams):
-        loss, logits, dxa, dxb = tail.run(model, oa, ob, target, side, wgrad_streams)
+    def forward(ctx, tail, model, oa, ob, target, side, wgrad_streams, meter=None):
+        loss, logits, dxa, dxb = tail.run(model, oa, ob, target, side, wgrad_streams, meter)
         ctx.dxa, ctx.dxb = dxa, dxb
         ctx.mark_non_differentiable(logits)
         # (a fresh 0-dim tensor per step: the persistent one is overwritten by the next step)
@@ -157,17 +176,19 @@ class BiTailFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gloss, glogits):
-        return None, None, ctx.dxa.permute(0, 3, 1, 2), ctx.dxb.permute(0, 3, 1, 2), None, None, None
+        return None, None, ctx.dxa.permute(0, 3, 1, 2), ctx.dxb.permute(0, 3, 1, 2), None, None, None, None
 
 
 class ClsCeFn(torch.autograd.Function):
     """(loss, logits) = cross_entropy(linear(pooled, W, b), target), mean reduction, for FROZEN classifier weights (the architecture
     step, ``validate``): ONE launch forward (tfnas_cls_ce: logits, per-image loss, d logits, d pooled) + a 128-element sum, one
     scaling launch backward -- instead of eight stock torch launches (GEMM, log-softmax, nll and their backward kernels).
-    Reference: models/model_search.py:301-303 + train_search.py:107,410."""
+    Reference: models/model_search.py:301-303 + train_search.py:107,410.
+    ``meter`` (a SearchMeter): the launch is tfnas_cls_ce_ex(eps = 0) -- bit-identical outputs plus the target's rank -- followed by
+    one metrics-only tfnas_cls_reduce into the meter's a block: loss sum, top-1 / top-5, images, invalid targets."""
 
     @staticmethod
-    def forward(ctx, pooled, W, b, target):
+    def forward(ctx, pooled, W, b, target, meter=None):
         lib = _lib.lib()
         pooled = pooled.contiguous()
         N, Cf = pooled.shape
@@ -179,9 +200,17 @@ class ClsCeFn(torch.autograd.Function):
         loss_n = torch.empty(N, device=dev, dtype=torch.float32)
         dlogits = torch.empty((N, K), device=dev, dtype=torch.float32)
         dpooled = torch.empty((N, Cf), device=dev, dtype=torch.float32)
+        s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with _on(dev):
-            check(lib.tfnas_cls_ce(N, Cf, K, ptr(pooled), ptr(W), ptr(b), ptr(target), 1.0 / N, ptr(logits), ptr(loss_n),
-                                   ptr(dlogits), ptr(dpooled), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'tfnas_cls_ce')
+            if meter is not None:
+                rank = torch.empty(N, device=dev, dtype=torch.int32)
+                check(lib.tfnas_cls_ce_ex(N, Cf, K, ptr(pooled), ptr(W), ptr(b), ptr(target), 1.0 / N, 0.0, ptr(logits), ptr(loss_n),
+                                          ptr(rank), ptr(dlogits), ptr(dpooled), s), 'tfnas_cls_ce_ex')
+                check(lib.tfnas_cls_reduce(N, Cf, K, None, None, ptr(loss_n), ptr(rank), None, 0, None, None, None,
+                                           meter.a_ptr(dev), s), 'tfnas_cls_reduce')
+            else:
+                check(lib.tfnas_cls_ce(N, Cf, K, ptr(pooled), ptr(W), ptr(b), ptr(target), 1.0 / N, ptr(logits), ptr(loss_n),
+                                       ptr(dlogits), ptr(dpooled), s), 'tfnas_cls_ce')
         ctx.save_for_backward(dpooled)
         ctx.mark_non_differentiable(logits)
         return loss_n.sum() * (1.0 / N), logits
@@ -189,17 +218,20 @@ class ClsCeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, glogits):
         dpooled, = ctx.saved_tensors
-        return dpooled * gloss, None, None, None
+        return dpooled * gloss, None, None, None, None
 
 
-def frozen_classifier_loss(model, pooled, target):
-    """loss, logits through ClsCeFn when the classifier's parameters are frozen CUDA fp32 tensors; None otherwise."""
+def frozen_classifier_loss(model, pooled, target, meter=None):
+    """loss, logits through ClsCeFn when the classifier's parameters are frozen CUDA fp32 tensors; None otherwise (then nothing
+    was added to ``meter`` either)."""
     lin = getattr(getattr(model, 'classifier', None), 'linear', None)
     if lin is None or lin.bias is None or lin.weight.requires_grad or lin.bias.requires_grad or not pooled.is_cuda:
         return None
     if lin.weight.dtype != torch.float32 or (lin.in_features & 3) or lin.in_features > 4096 or lin.out_features > 4096:
         return None
-    return ClsCeFn.apply(pooled, lin.weight.detach(), lin.bias.detach(), target)
+    if meter is None:
+        return ClsCeFn.apply(pooled, lin.weight.detach(), lin.bias.detach(), target)
+    return ClsCeFn.apply(pooled, lin.weight.detach(), lin.bias.detach(), target, meter)
 
 
 def cls_shapes_ok(Cf, K):
@@ -270,6 +302,84 @@ class DeviceMeter:
         if cnt == 0:
             return 0.0, 0.0, 0.0, 0, 0
         return s / cnt, 100.0 * c1 / cnt, 100.0 * c5 / cnt, int(cnt), int(bad)
+
+
+def target_rank(logits, target):
+    """(rank, valid) of every row's target by the rule of tfnas_cls_ce_ex (include/tfnas_hip.h), as torch ops on any device:
+    rank = #{k: l_k > l_t} + #{k < t: l_k == l_t} -- ties go to the lower class index, where torch.topk promises no order -- and
+    -1 where the target is outside [0, K).  Nothing is indexed by an invalid target."""
+    K = logits.size(1)
+    t = target.view(-1, 1).long()
+    valid = (t >= 0) & (t < K)
+    lt = logits.gather(1, t.clamp(0, K - 1))
+    ks = torch.arange(K, device=logits.device).view(1, -1)
+    rank = ((logits > lt) | ((logits == lt) & (ks < t))).sum(1, keepdim=True)
+    return torch.where(valid, rank, torch.full_like(rank, -1)).view(-1), valid.view(-1)
+
+
+class SearchMeter:
+    """A search epoch's running sums (train_search.py:318-432: the AverageMeters objs_w, top1, top5, objs_a, objs_l) as eleven
+    doubles ON THE DEVICE: two blocks of the DeviceMeter / tfnas_cls_reduce layout {sum of per-image losses, top-1 hits, top-5 hits,
+    images, invalid targets} -- ``w`` for the weight steps (loss = loss_g + loss_r, hits of the gumbel path), ``a`` for the
+    architecture steps -- and sum n * loss_l.  The fused tails add to the blocks from their own launches (tfnas_cls_wgrad_ex,
+    tfnas_cls_reduce); ``add_w`` / ``add_a`` are the same sums as torch ops for the routes without a fused tail and for host
+    tensors.  Nothing here synchronises with the host except ``read``.  Updates are ordered by the steps' streams: every step
+    joins its side streams into the caller's stream before it returns."""
+    W, A, L, SIZE = 0, 5, 10, 11
+
+    def __init__(self, device):
+        self.buf = torch.zeros(self.SIZE, device=device, dtype=torch.float64)
+
+    def reset(self):
+        self.buf.zero_()
+
+    def _block_ptr(self, first, dev):
+        if self.buf.device != dev:
+            raise RuntimeError('tfnas_amd: the SearchMeter lives on %s, the step runs on %s' % (self.buf.device, dev))
+        return C.c_void_p(self.buf.data_ptr() + 8 * first)
+
+    def w_ptr(self, dev):
+        return self._block_ptr(self.W, dev)
+
+    def a_ptr(self, dev):
+        return self._block_ptr(self.A, dev)
+
+    def _add(self, first, loss, n, logits, target):
+        f64 = torch.float64
+        s = loss.detach().to(f64) * n
+        cnt = torch.full((), float(n), dtype=f64, device=s.device)
+        if logits is None:
+            vals = [s, torch.zeros_like(s), torch.zeros_like(s), cnt]
+        else:
+            rank, valid = target_rank(logits.detach(), target)
+            vals = [s, (valid & (rank < 1)).sum().to(f64), (valid & (rank < 5)).sum().to(f64), cnt, (~valid).sum().to(f64)]
+        self.buf[first:first + len(vals)].add_(torch.stack(vals))
+
+    def add_w(self, loss, logits, target):
+        """One weight step from its returned mean loss (both paths' sum under bi-sampling) and the gumbel path's logits."""
+        self._add(self.W, loss, target.size(0), logits, target)
+
+    def add_a(self, loss_a, loss_l, n, logits=None, target=None):
+        """One architecture step: n * loss_l always; n * loss_a, the images and -- with logits / target -- the hits unless
+        ``loss_a`` is None (the fused classifier tail has added its block from its own launch)."""
+        if loss_a is not None:
+            self._add(self.A, loss_a, n, logits, target)
+        self.buf[self.L:self.L + 1].add_(loss_l.detach().to(torch.float64).view(1) * n)
+
+    def reduce_(self, group=None):
+        """Sum the buffer over the ranks of ``group`` with one all-reduce (nothing when not distributed)."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            dist.all_reduce(self.buf, op=dist.ReduceOp.SUM, group=group)
+
+    def read(self):
+        """The only device -> host copy: the reference's averages (losses per image, top-k in percent) and the counts."""
+        v = self.buf.tolist()
+        w, a = v[self.W:self.W + 5], v[self.A:self.A + 5]
+        nw, na = w[3] or 1.0, a[3] or 1.0
+        return dict(objs_w=w[0] / nw, top1=100.0 * w[1] / nw, top5=100.0 * w[2] / nw, images_w=int(w[3]),
+                    objs_a=a[0] / na, objs_l=v[self.L] / na, top1_a=100.0 * a[1] / na, top5_a=100.0 * a[2] / na,
+                    images_a=int(a[3]), invalid=int(w[4] + a[4]))
 
 
 def retrain_tail_forward(pooled, W, b, target, eps=0.0, meter=None):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Median time of the two step kinds in SEPARATE loops (w-steps only, then alpha-steps only), so that a timing-only build with
 wrong numerics (TFNAS_LIB=...) cannot feed NaN architecture parameters into
-the sampler of the next w-step.  usage: steps_split.py [B] [iters]   -- runs on the GPU box"""
+the sampler of the next w-step.  usage: steps_split.py [B] [iters]   -- runs on the GPU box
+STEPS_METER=1: every step feeds a tail.SearchMeter (what epoch.search_epoch does), to price the meter against a run without."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tf-nas_amd'))
@@ -33,7 +34,11 @@ def med(f):
     return ts[len(ts) // 2], ts[0]
 
 
+mkw = {}
+if os.environ.get('STEPS_METER', '0') == '1':
+    from tfnas_amd.tail import SearchMeter
+    mkw = dict(meter=SearchMeter(dev))
 only = os.environ.get('STEPS_ONLY', '')          # 'w' / 'a': one loop only (a rocprofv3 --stats run of one step kind)
-w = med(lambda: search.w_step(state, x, y, opt_w, 5.0, noise.exp(dev), noise.rand_pos())) if only != 'a' else (0., 0.)
-a = med(lambda: search.a_step(state, x, y, opt_a, 15.0, 0.1, 5.0, noise.exp(dev))) if only != 'w' else (0., 0.)
+w = med(lambda: search.w_step(state, x, y, opt_w, 5.0, noise.exp(dev), noise.rand_pos(), **mkw)) if only != 'a' else (0., 0.)
+a = med(lambda: search.a_step(state, x, y, opt_a, 15.0, 0.1, 5.0, noise.exp(dev), **mkw)) if only != 'w' else (0., 0.)
 print('w_step median %.2f ms (min %.2f) | a_step median %.2f ms (min %.2f)' % (w[0], w[1], a[0], a[1]), flush=True)
