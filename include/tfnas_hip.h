@@ -324,21 +324,16 @@ int tfnas_head_wgrad(const TfnasCellDesc *d, const float *x, const float *E, con
                      void *stream);
 
 /* ---- classifier + cross-entropy tail (models/model_search.py:301-303 `self.classifier(x)`; train_search.py:107 nn.CrossEntropyLoss
- * as called at :333, :376-379, :410, and their autograd) ---------------------------------------------------------------------------
- * tfnas_cls_ce, one launch, everything that depends on ONE image:
+ * as called at :333, :376-379, :410, and their autograd; train_eval.py:228-293 with CrossEntropyLabelSmooth, :72-85,126) -------------
+ * Every route makes TWO launches: one for everything that depends on ONE image, one for everything that sums over images.  Each has
+ * a plain form (the weight step's critical chain carries nothing optional) and a form with the optional parts.  pooled [N][C], W
+ * [K][C], bias [K] or NULL, target int64 [N]; fixed summation orders, no atomics.
+ *
+ * The per-image launch.  tfnas_cls_ce:
  *   logits[n][k] = bias[k] + sum_c pooled[n][c] W[k][c];  loss_n[n] = logsumexp_k logits[n] - logits[n][target[n]]
  *   dlogits[n][k] = scale * (softmax(logits[n])[k] - [k == target[n]])   (scale = 1 / N: the mean reduction of CrossEntropyLoss)
  *   dpooled[n][c] = sum_k dlogits[n][k] W[k][c]
- * pooled [N][C] (C a multiple of 4), W [K][C], bias [K] or NULL, target int64 [N].
- * tfnas_cls_wgrad, one launch, everything that sums over images -- and over the npath <= 2 bi-sampling paths of a weight step:
- *   dW[k][c] = sum_p sum_n dlogits_p[n][k] pooled_p[n][c];  db[k] = sum_p sum_n dlogits_p[n][k];  loss = loss_scale * sum_p sum_n loss_n_p[n]
- * (overwritten, not accumulated; loss may be NULL: sum further micro-batches with tfnas_add_into).  Fixed summation orders, no atomics. */
-int tfnas_cls_ce(int N, int C, int K, const float *pooled, const float *W, const float *bias, const int64_t *target, float scale,
-                 float *logits, float *loss_n, float *dlogits, float *dpooled, void *stream);
-int tfnas_cls_wgrad(int npath, int N, int C, int K, const float *const *pooled, const float *const *dlogits,
-                    const float *const *loss_n, float loss_scale, float *dW, float *db, float *loss, void *stream);
-/* The same tail for the derived network's retrain path (train_eval.py:228-293 with CrossEntropyLabelSmooth, :72-85,126), again one
- * launch per image-wise part and one per reduction, for ONE path.
+ * and a target outside [0, K) contributes nothing (loss_n = 0, zero gradient rows).
  * tfnas_cls_ce_ex = tfnas_cls_ce with a label-smoothing factor eps in [0, 1) (num_classes == K) and the target's rank:
  *   loss_n[n]     = lse - (1 - eps) logits[n][t] - (eps / K) sum_k logits[n][k]            (t = target[n], lse = logsumexp_k logits[n])
  *   dlogits[n][k] = scale * (softmax(logits[n])[k] - (1 - eps) [k == t] - eps / K);   dpooled[n][c] = sum_k dlogits[n][k] W[k][c]
@@ -348,40 +343,46 @@ int tfnas_cls_wgrad(int npath, int N, int C, int K, const float *const *pooled, 
  * eps == 0 gives logits, loss_n, dlogits and dpooled bit-identical to tfnas_cls_ce.  A target outside [0, K) (compared on all 64
  * bits) is FLAGGED, not skipped: loss_n[n] = NaN, rank[n] = -1, that image's dlogits and dpooled rows are zero, and no load or store
  * is indexed by it.  dlogits == NULL && dpooled == NULL is the forward-only form (validation): the gradient phase and its LDS are
- * skipped; exactly one of them NULL is TFNAS_EINVAL, as is eps outside [0, 1).  Limits as tfnas_cls_ce: C % 4 == 0, 4 <= C <= 4096,
- * K <= 4096, LDS (C + K + KG * C floats, KG = min(8, K, 1024 / (C / 4)), 0 when forward-only) <= 64 KiB else TFNAS_ERANGE.
- * tfnas_cls_reduce, everything that sums over the N images of that launch:
- *   dW[k][c] (=|+=) g * sum_n dlogits[n][k] pooled[n][c];   db[k] (=|+=) g * sum_n dlogits[n][k]
- *   g = *gscale, a DEVICE scalar -- the upstream d loss of a backward pass, no host read -- or 1 when gscale is NULL;
- *   accumulate = 1 adds to what dW / db hold, 0 overwrites.  dW == NULL && db == NULL: metrics only (pooled / dlogits unused).
- *   out[4]   = {mean loss_n, #(rank < 1), #(rank < 5), #(rank < 0: invalid targets)} as floats (NULL: not wanted)
- *   meter[5] += {sum loss_n, #(rank < 1), #(rank < 5), N, #invalid} in double (NULL: none): a running epoch meter, added by one
- *   thread in a fixed order with ordinary loads and stores -- launches that share a meter must be ordered by their stream, and the
- *   host reads it once per epoch.  An invalid target makes the mean and the meter's loss sum NaN.
- * TFNAS_ENULL: loss_n / rank missing, only some of (dW, db, pooled, dlogits) given, or no destination at all.  Fixed summation
- * orders, no atomics. */
-int tfnas_cls_ce_ex(int N, int C, int K, const float *pooled, const float *W, const float *bias, const int64_t *target, float scale,
-                    float eps, float *logits, float *loss_n, int32_t *rank, float *dlogits, float *dpooled, void *stream);
-int tfnas_cls_reduce(int N, int C, int K, const float *pooled, const float *dlogits, const float *loss_n, const int32_t *rank,
-                     const float *gscale, int accumulate, float *dW, float *db, float *out, double *meter, void *stream);
-/* tfnas_cls_wgrad_ex = tfnas_cls_wgrad + the running meter of a search epoch (train_search.py:387-391: objs_w.update(loss_w, n),
+ * skipped; exactly one of them NULL is TFNAS_EINVAL, as is eps outside [0, 1).
+ * Limits of both: C % 4 == 0 (else TFNAS_EINVAL), 4 <= C <= 4096, K <= 4096, LDS (C + K + KG * C floats, KG = min(8, K,
+ * 1024 / (C / 4)), 0 when forward-only) <= 64 KiB else TFNAS_ERANGE.
+ *
+ * The summation launch: one workgroup per 4-class x 256-feature tile of dW, and one that sums db, the loss and the counts.
+ * tfnas_cls_wgrad, over the npath <= 2 bi-sampling paths of a weight step (npath device pointers each):
+ *   dW[k][c] = sum_p sum_n dlogits_p[n][k] pooled_p[n][c];  db[k] = sum_p sum_n dlogits_p[n][k];  loss = loss_scale * sum_p sum_n loss_n_p[n]
+ * (overwritten, not accumulated; loss may be NULL: sum further micro-batches with tfnas_add_into).
+ * tfnas_cls_wgrad_ex = tfnas_cls_wgrad + the running meter of a search epoch (train_search.py:387-391: objs_w.update(loss_w, n),
  * top1 / top5 of the GUMBEL path's logits), folded into the same launch: same grid, tiles and summation orders, so dW, db and loss
  * are bit-identical to tfnas_cls_wgrad on the same inputs, with or without a meter.
- *   npath (1 or 2), N, C, K, pooled / dlogits / loss_n (npath device pointers each), loss_scale, dW [K][C], db [K], loss (or NULL):
- *     as tfnas_cls_wgrad.
- *   rank0  int32 [N]: rank[] of path 0 as tfnas_cls_ce_ex wrote it for the launch that produced dlogits[0] / loss_n[0] (rank < k is a
- *     top-k hit, ties go to the lower class index, -1 marks a target outside [0, K)).  Read only when meter is given.
- *   meter  5 doubles on the device, the tfnas_cls_reduce layout, or NULL (then the call equals tfnas_cls_wgrad and rank0 is ignored):
- *     meter[0] += sum_p sum_n loss_n_p[n]   (ALL npath paths: N * (loss_g + loss_r) of the mean-reduced losses, in double)
- *     meter[1] += #(0 <= rank0 < 1);  meter[2] += #(0 <= rank0 < 5);  meter[3] += N;  meter[4] += #(rank0 < 0)
- *     added by one thread in that order with ordinary loads and stores, no atomics: launches that share a meter (this one,
- *     tfnas_cls_reduce) must be ordered by their stream; the host zeroes it and reads it, e.g. once per epoch.
- * An invalid target carries over from the per-image launch: tfnas_cls_ce_ex gives loss_n = NaN for it, so meter[0] (and loss) become
- * NaN while meter[4] counts it -- the retrain meter's semantics; tfnas_cls_ce gives 0, so a path computed by it contributes nothing.
- * TFNAS_ENULL: meter without rank0, or what tfnas_cls_wgrad rejects; TFNAS_ERANGE as tfnas_cls_wgrad. */
+ *   rank0  int32 [N]: rank[] of path 0 as tfnas_cls_ce_ex wrote it for the launch that produced dlogits[0] / loss_n[0].  Read only
+ *     when meter is given; meter == NULL makes the call equal tfnas_cls_wgrad.
+ *   meter[0] += sum_p sum_n loss_n_p[n]   (ALL npath paths: N * (loss_g + loss_r) of the mean-reduced losses); the counts are path 0's.
+ * TFNAS_ENULL: meter without rank0, or a missing array, path pointer, dW or db; TFNAS_ERANGE: npath outside 1..2, N, C or K < 1.
+ * tfnas_cls_reduce, over the N images of ONE path, for a backward pass under any upstream gradient:
+ *   dW[k][c] (=|+=) g * sum_n dlogits[n][k] pooled[n][c];   db[k] (=|+=) g * sum_n dlogits[n][k]
+ *   g = *gscale, a DEVICE scalar -- the upstream d loss of a backward pass, no host read -- or 1 when gscale is NULL;
+ *   accumulate = 1 adds to what dW / db hold, 0 overwrites.  dW == NULL && db == NULL: metrics only (pooled / dlogits unused, one
+ *   workgroup).  With gscale == NULL and accumulate == 0 dW and db are bit-identical to tfnas_cls_wgrad_ex(npath = 1).
+ *   out[4]   = {mean loss_n, #(rank < 1), #(rank < 5), #(rank < 0: invalid targets)} as floats (NULL: not wanted)
+ * TFNAS_ENULL: loss_n / rank missing, only some of (dW, db, pooled, dlogits) given, or no destination at all; C, K <= 4096.
+ *
+ * The meter of both _ex summation forms, 5 doubles on the device (NULL: none):
+ *   meter[5] += {sum loss_n, #(0 <= rank < 1), #(0 <= rank < 5), N, #(rank < 0)}, i.e. meter[0] .. meter[4], in double,
+ * added by one thread in that order with ordinary loads and stores, no atomics: launches that share a meter must be
+ * ordered by their stream; the host zeroes it and reads it, e.g. once per epoch.  An invalid target carries over from the per-image
+ * launch: tfnas_cls_ce_ex gives loss_n = NaN for it, so meter[0] (and loss / out[0]) become NaN while meter[4] counts it;
+ * tfnas_cls_ce gives 0, so a path computed by it contributes nothing. */
+int tfnas_cls_ce(int N, int C, int K, const float *pooled, const float *W, const float *bias, const int64_t *target, float scale,
+                 float *logits, float *loss_n, float *dlogits, float *dpooled, void *stream);
+int tfnas_cls_ce_ex(int N, int C, int K, const float *pooled, const float *W, const float *bias, const int64_t *target, float scale,
+                    float eps, float *logits, float *loss_n, int32_t *rank, float *dlogits, float *dpooled, void *stream);
+int tfnas_cls_wgrad(int npath, int N, int C, int K, const float *const *pooled, const float *const *dlogits,
+                    const float *const *loss_n, float loss_scale, float *dW, float *db, float *loss, void *stream);
 int tfnas_cls_wgrad_ex(int npath, int N, int C, int K, const float *const *pooled, const float *const *dlogits,
                        const float *const *loss_n, const int32_t *rank0, float loss_scale, float *dW, float *db, float *loss,
                        double *meter, void *stream);
+int tfnas_cls_reduce(int N, int C, int K, const float *pooled, const float *dlogits, const float *loss_n, const int32_t *rank,
+                     const float *gscale, int accumulate, float *dW, float *db, float *out, double *meter, void *stream);
 /* dst[i] += src[i], count floats (a multiple of 4): the second path's share of a shared parameter's gradient. */
 int tfnas_add_into(float *dst, const float *src, uint64_t count, void *stream);
 

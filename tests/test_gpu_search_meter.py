@@ -128,6 +128,38 @@ def test_wgrad_ex_flags_invalid_targets_like_the_retrain_meter():
     assert bool(torch.isfinite(dW).all()) and bool(torch.isfinite(db).all())      # (invalid rows carry zero gradient)
 
 
+@pytest.mark.parametrize('invalid', [False, True])
+@pytest.mark.parametrize('Cf,K', [(4, 1), (260, 3), (64, 6)])
+@pytest.mark.parametrize('N', [1, 63, 65, 130])
+def test_reduce_and_wgrad_ex_of_one_path_share_their_sums_bit_for_bit(N, Cf, K, invalid):
+    """The three summation kernels call ONE row and ONE tile: for a single path tfnas_cls_reduce(gscale = NULL, accumulate = 0) and
+    tfnas_cls_wgrad_ex(npath = 1) on the same pooled / dlogits / loss_n / rank store bit-identical dW and db and, from the same
+    meter contents, leave bit-identical five doubles (compared as bit patterns: with an out-of-range label the loss sum is NaN).
+    N: a partial wave, just over one wave, more than two lane strides; (C, K): the minimum, a ragged feature tile with K % 4 != 0,
+    K > 5."""
+    from tfnas_amd import _lib
+    g = torch.Generator().manual_seed(31 * N + K)
+    target = torch.randint(0, K, (N,), generator=g)
+    if invalid:
+        target[N // 2] = K
+    paths, rank, _ = _tail_inputs(N, Cf, K, 1, 500 * N + K, target=target)
+    start = torch.tensor([0.5, 3.0, 7.0, 11.0, 2.0], device='cuda', dtype=torch.float64)
+    m_w, m_r = start.clone(), start.clone()
+    rc, dW_w, db_w, _loss = _wgrad(paths, N, Cf, K, rank=rank, meter=m_w)
+    assert rc == 0
+    p = paths[0]
+    dW_r, db_r = torch.full((K, Cf), float('nan'), device='cuda'), torch.full((K,), float('nan'), device='cuda')
+    rc = _lib.lib().tfnas_cls_reduce(N, Cf, K, _lib.ptr(p['pooled']), _lib.ptr(p['dlogits']), _lib.ptr(p['loss_n']), _lib.ptr(rank),
+                                     None, 0, _lib.ptr(dW_r), _lib.ptr(db_r), None, _lib.ptr(m_r), _stream())
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert torch.equal(dW_r, dW_w) and torch.equal(db_r, db_w) and bool(torch.isfinite(dW_r).all())
+    assert torch.equal(m_r.view(torch.int64), m_w.view(torch.int64)), (m_r.tolist(), m_w.tolist())
+    got = m_r.tolist()
+    assert [v - s for v, s in zip(got[1:], start.tolist()[1:])] == _counts(rank.cpu().numpy(), N)
+    assert got[4] == 2.0 + int(invalid) and (got[0] != got[0]) == invalid
+
+
 def test_wgrad_ex_counts_tied_rows_by_the_lower_index_rule():
     """W = 0: every row's logits are the bias, with ties.  Expected counts from the header's formula: among equal logits the lower
     class index ranks first."""

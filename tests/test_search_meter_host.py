@@ -91,6 +91,27 @@ def test_search_meter_equals_a_hand_written_average_meter_loop():
     assert meter.read()['images_w'] == 0 and float(meter.buf.abs().sum()) == 0.0
 
 
+def test_device_meter_and_search_meter_share_one_block_arithmetic():
+    """DeviceMeter.add and SearchMeter.add_w fed the same (loss, logits, target) leave the same five numbers, with hits by the
+    rank rule: a target tied with a LOWER-indexed class misses top-1, one tied with a HIGHER-indexed class hits, and a target equal
+    to K is counted as invalid (and is no hit)."""
+    from tfnas_amd.tail import DeviceMeter, SearchMeter
+    logits = torch.tensor([[1., 0., 1., 0., -1., -2., -3.],       # target 2 tied with class 0: rank 1
+                           [0., 2., 0., 2., -1., -2., -3.],       # target 1 tied with class 3: rank 0
+                           [3., 2., 1., 0., -1., -2., -3.],       # target 7 == K
+                           [6., 5., 4., 3., 2., 1., 0.]])         # target 5: rank 5, outside the top 5
+    target = torch.tensor([2, 1, 7, 5])
+    loss = torch.tensor(0.75)
+    dm, sm = DeviceMeter('cpu'), SearchMeter('cpu')
+    dm.add(loss, logits, target)
+    sm.add_w(loss, logits, target)
+    assert dm.buf.tolist() == [3.0, 1.0, 2.0, 4.0, 1.0]            # {n * loss, top-1, top-5, images, invalid}
+    assert torch.equal(dm.buf, sm.buf[SearchMeter.W:SearchMeter.W + 5]) and float(sm.buf[5:].abs().sum()) == 0.0
+    assert dm.read() == (0.75, 25.0, 50.0, 4, 1)
+    m = sm.read()
+    assert (m['objs_w'], m['top1'], m['top5'], m['images_w'], m['invalid']) == dm.read()
+
+
 def test_epoch_end_check_raises_on_invalid_targets_and_fills_the_stats():
     from tfnas_amd.epoch import train_stats
     from tfnas_amd.tail import SearchMeter

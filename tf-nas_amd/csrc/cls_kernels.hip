@@ -8,10 +8,11 @@
 // image (logits, loss, d logits, d pooled) and ONE launch for what sums over images and paths (dW, db, the loss scalar).
 // Deterministic: fixed summation orders, no atomics.
 //
-// The derived network's retrain path (reference: train_eval.py:228-293 with CrossEntropyLabelSmooth, :72-85,126) runs the same two
-// bodies in their EX form: label smoothing, the target's rank (top-1 / top-5 without a topk), NaN / rank -1 on an out-of-range label,
-// a forward-only form for validation, and a reduction that scales by a device-resident upstream gradient, can accumulate, and keeps
-// an epoch's running sums on the device (k_cls_ce_ex, k_cls_reduce).  The search step's instantiations are unchanged.
+// Both launches have their optional parts compiled out of the weight step's kernels (k_cls_ce, k_cls_wgrad) and in their other
+// forms: k_cls_ce_ex -- label smoothing, the target's rank (top-1 / top-5 without a topk), NaN / rank -1 on an out-of-range label, a
+// forward-only form (the retrain path, reference: train_eval.py:228-293 with CrossEntropyLabelSmooth, :72-85,126; the metered search
+// steps); k_cls_wgrad_ex -- an epoch's running sums on the device; k_cls_reduce -- those, one path, a device-resident upstream
+// gradient and accumulation.  What the forms share is written once: cls_ce_body, cls_dw_tile, cls_db_row, cls_sum_row.
 #include "tfnas_dev.h"
 #include "kernels.h"
 #include "prof.h"
@@ -268,123 +269,106 @@ __device__ __forceinline__ void cls_dw_tile(float (*dl)[4], int npath, int N, in
     }
 }
 
-// The last blockIdx.y row of the weight step's summation launch: db, then the first wave sums loss_n of every path in double
-// (lane-strided, then butterfly: a fixed order) and its first thread stores loss.  METER (k_cls_wgrad_ex): the same wave counts
-// rank < 1, rank < 5 and rank < 0 of path 0 and the thread adds {sum loss_n, top-1, top-5, N, invalid} to the running meter with
-// ordinary loads and stores, like k_cls_reduce -- launches that share a meter are ordered by their stream.
-template <bool METER>
-__device__ __forceinline__ void cls_wgrad_row(int npath, int N, int K, const ClsPaths& P, const int32_t* __restrict__ rank0,
-                                              float loss_scale, float* __restrict__ db, float* __restrict__ loss,
-                                              double* __restrict__ meter) {
-    const int tid = threadIdx.x;
-    cls_db_row<false>(npath, N, K, P, 1.f, 0, db);
-    if (tid < 64) {
-        double s = 0.0;
-        for (int p = 0; p < npath; ++p)
-            for (int n = tid; n < N; n += 64) s += (double)P.loss_n[p][n];
+// The first wave of the last blockIdx.y row, for all three summation kernels: sum of loss_n over npath paths in double (paths outer,
+// images lane-strided, then the xor butterfly: a fixed order) and, with RANKS and a rank array, the counts rank < 1, rank < 5 and
+// rank < 0 of those images.  Every lane returns the totals; without RANKS the counts are compiled out (k_cls_wgrad).
+struct ClsRowSum {
+    double s;
+    int c1, c5, bad;
+};
+template <bool RANKS>
+__device__ __forceinline__ ClsRowSum cls_sum_row(int npath, int N, const ClsPaths& P, const int32_t* __restrict__ rank) {
+    const int lane = threadIdx.x;
+    ClsRowSum r = {0.0, 0, 0, 0};
+    for (int p = 0; p < npath; ++p)
+        for (int n = lane; n < N; n += 64) r.s += (double)P.loss_n[p][n];
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (tid == 0 && loss) loss[0] = (float)(s * (double)loss_scale);
-        if constexpr (METER) {
-            if (!meter) return;                              // (a kernel argument: the whole wave leaves together)
-            int c1 = 0, c5 = 0, bad = 0;
-            for (int n = tid; n < N; n += 64) {
-                const int r = rank0[n];
-                bad += r < 0 ? 1 : 0;
-                c1 += (r >= 0 && r < 1) ? 1 : 0;
-                c5 += (r >= 0 && r < 5) ? 1 : 0;
-            }
+    for (int o = 32; o > 0; o >>= 1) r.s += __shfl_xor(r.s, o, 64);
+    if constexpr (RANKS) {
+        if (!rank) return r;                                 // (a kernel argument: the whole wave takes the same side)
+        for (int n = lane; n < N; n += 64) {
+            const int k = rank[n];
+            r.bad += k < 0 ? 1 : 0;
+            r.c1 += (k >= 0 && k < 1) ? 1 : 0;
+            r.c5 += (k >= 0 && k < 5) ? 1 : 0;
+        }
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                c1 += __shfl_xor(c1, o, 64);
-                c5 += __shfl_xor(c5, o, 64);
-                bad += __shfl_xor(bad, o, 64);
-            }
-            if (tid == 0) {
-                meter[0] += s;
-                meter[1] += (double)c1;
-                meter[2] += (double)c5;
-                meter[3] += (double)N;
-                meter[4] += (double)bad;
-            }
+        for (int o = 32; o > 0; o >>= 1) {
+            r.c1 += __shfl_xor(r.c1, o, 64);
+            r.c5 += __shfl_xor(r.c5, o, 64);
+            r.bad += __shfl_xor(r.bad, o, 64);
         }
     }
+    return r;
 }
 
+// meter += {sum loss_n, top-1, top-5, N, invalid}: one thread, ordinary loads and stores -- launches that share a meter are ordered
+// by their stream
+__device__ __forceinline__ void cls_meter_add(double* __restrict__ meter, const ClsRowSum& r, int N) {
+    meter[0] += r.s;
+    meter[1] += (double)r.c1;
+    meter[2] += (double)r.c5;
+    meter[3] += (double)N;
+    meter[4] += (double)r.bad;
+}
+
+// The three summation kernels share one shape: blockIdx.y < ceil(K / 4) is a dW tile; workgroup (0, last row) does db, then its first
+// wave calls cls_sum_row and thread 0 stores what that kernel owes.  k_cls_wgrad: loss[0] alone, no rank or meter code.
 __global__ __launch_bounds__(256) void k_cls_wgrad(int npath, int N, int C, int K, ClsPaths P, float loss_scale,
                                                    float* __restrict__ dW, float* __restrict__ db, float* __restrict__ loss) {
     __shared__ float dl[256][4];
-    const int kgroups = (K + 3) >> 2;
-    if ((int)blockIdx.y == kgroups) {
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.y == (K + 3) >> 2) {
         if (blockIdx.x != 0) return;
-        cls_wgrad_row<false>(npath, N, K, P, nullptr, loss_scale, db, loss, nullptr);
+        cls_db_row<false>(npath, N, K, P, 1.f, 0, db);
+        if (tid >= 64) return;
+        const ClsRowSum r = cls_sum_row<false>(npath, N, P, nullptr);
+        if (tid == 0 && loss) loss[0] = (float)(r.s * (double)loss_scale);
         return;
     }
     cls_dw_tile<false>(dl, npath, N, C, K, P, 1.f, 0, dW);
 }
 
-// k_cls_wgrad + the search epoch's running meter (the w block of tail.SearchMeter): same grid, tiles and summation orders.
+// k_cls_wgrad + the search epoch's running meter (the w block of tail.SearchMeter): the loss sum of ALL paths, the counts of path
+// 0's rank0 (the host passes NULL without a meter).
 __global__ __launch_bounds__(256) void k_cls_wgrad_ex(int npath, int N, int C, int K, ClsPaths P, const int32_t* __restrict__ rank0,
                                                       float loss_scale, float* __restrict__ dW, float* __restrict__ db,
                                                       float* __restrict__ loss, double* __restrict__ meter) {
     __shared__ float dl[256][4];
-    const int kgroups = (K + 3) >> 2;
-    if ((int)blockIdx.y == kgroups) {
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.y == (K + 3) >> 2) {
         if (blockIdx.x != 0) return;
-        cls_wgrad_row<true>(npath, N, K, P, rank0, loss_scale, db, loss, meter);
+        cls_db_row<false>(npath, N, K, P, 1.f, 0, db);
+        if (tid >= 64) return;
+        const ClsRowSum r = cls_sum_row<true>(npath, N, P, rank0);
+        if (tid == 0 && loss) loss[0] = (float)(r.s * (double)loss_scale);
+        if (tid == 0 && meter) cls_meter_add(meter, r, N);
         return;
     }
     cls_dw_tile<false>(dl, npath, N, C, K, P, 1.f, 0, dW);
 }
 
-// The retrain tail's reduction over the images of ONE path.  With dW / db: the same grid and tiles as k_cls_wgrad (blockIdx.y <
-// ceil(K / 4)) plus the last row; without (metrics only): that row alone, one workgroup.  The row's first wave sums loss_n in double
-// and counts rank < 1, rank < 5 and rank < 0 (lane-strided, then butterfly: a fixed order), and its first thread writes out[4] =
-// {mean loss, top-1 count, top-5 count, invalid count} and adds {sum loss_n, top-1, top-5, N, invalid} to the running meter with
-// ordinary loads and stores -- launches that share a meter are ordered by their stream.
+// The retrain tail's reduction over the images of ONE path: every dW / db sum is multiplied by gs (the upstream d loss, read from the
+// device) and stored or, with acc, added.  Without dW / db (metrics only) the grid is the row's one workgroup.  Thread 0 writes
+// out[4] = {mean loss, top-1 count, top-5 count, invalid count} and adds to the meter.
 __global__ __launch_bounds__(256) void k_cls_reduce(int N, int C, int K, ClsPaths P, const int32_t* __restrict__ rank,
                                                     const float* __restrict__ gscale, int acc, float* __restrict__ dW,
                                                     float* __restrict__ db, float* __restrict__ out, double* __restrict__ meter) {
     __shared__ float dl[256][4];
     const int tid = threadIdx.x;
-    const int kgroups = dW ? (K + 3) >> 2 : 0;
     const float gs = gscale ? gscale[0] : 1.f;
-    if ((int)blockIdx.y == kgroups) {
+    if ((int)blockIdx.y == (dW ? (K + 3) >> 2 : 0)) {
         if (blockIdx.x != 0) return;
         if (db) cls_db_row<true>(1, N, K, P, gs, acc, db);
-        if (tid < 64 && (out || meter)) {
-            double s = 0.0;
-            int c1 = 0, c5 = 0, bad = 0;
-            for (int n = tid; n < N; n += 64) {
-                s += (double)P.loss_n[0][n];
-                const int r = rank[n];
-                bad += r < 0 ? 1 : 0;
-                c1 += (r >= 0 && r < 1) ? 1 : 0;
-                c5 += (r >= 0 && r < 5) ? 1 : 0;
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                s += __shfl_xor(s, o, 64);
-                c1 += __shfl_xor(c1, o, 64);
-                c5 += __shfl_xor(c5, o, 64);
-                bad += __shfl_xor(bad, o, 64);
-            }
-            if (tid == 0) {
-                if (out) {
-                    out[0] = (float)(s / (double)N);
-                    out[1] = (float)c1;
-                    out[2] = (float)c5;
-                    out[3] = (float)bad;
-                }
-                if (meter) {
-                    meter[0] += s;
-                    meter[1] += (double)c1;
-                    meter[2] += (double)c5;
-                    meter[3] += (double)N;
-                    meter[4] += (double)bad;
-                }
-            }
+        if (tid >= 64 || !(out || meter)) return;
+        const ClsRowSum r = cls_sum_row<true>(1, N, P, rank);
+        if (tid == 0 && out) {
+            out[0] = (float)(r.s / (double)N);
+            out[1] = (float)r.c1;
+            out[2] = (float)r.c5;
+            out[3] = (float)r.bad;
         }
+        if (tid == 0 && meter) cls_meter_add(meter, r, N);
         return;
     }
     cls_dw_tile<true>(dl, 1, N, C, K, P, gs, acc, dW);
@@ -400,23 +384,37 @@ __global__ __launch_bounds__(256) void k_add_into(float* __restrict__ dst, const
     }
 }
 
+// The per-image launch of both forms.  KG, the class groups of the d pooled phase: as many as fill the 1024 threads with (four
+// feature columns x class range) items; none, and no [KG][C] LDS, in the forward-only form.
+static int cls_ce_launch(bool ex, int N, int C, int K, const float* pooled, const float* W, const float* bias, const int64_t* target,
+                         float scale, float eps, float* logits, float* loss_n, int32_t* rank, float* dlogits, float* dpooled,
+                         void* stream) {
+    int KG = 0;
+    if (dpooled) {
+        KG = CLS_T / (C >> 2);
+        if (KG < 1) KG = 1;
+        if (KG > 8) KG = 8;
+        if (KG > K) KG = K;
+    }
+    const size_t shm = ((size_t)C + ((K + 3) & ~3) + (size_t)KG * C) * sizeof(float);
+    if (shm > 64 * 1024) return TFNAS_ERANGE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    ProfScope _prof(TK_SMALL, s);
+    if (ex)
+        hipLaunchKernelGGL(k_cls_ce_ex, dim3(N), dim3(CLS_T), shm, s, C, K, KG, pooled, W, bias, target, scale, eps, logits, loss_n,
+                           rank, dlogits, dpooled);
+    else
+        hipLaunchKernelGGL(k_cls_ce, dim3(N), dim3(CLS_T), shm, s, C, K, KG, pooled, W, bias, target, scale, logits, loss_n, dlogits,
+                           dpooled);
+    return (int)hipGetLastError();
+}
+
 extern "C" int tfnas_cls_ce(int N, int C, int K, const float* pooled, const float* W, const float* bias, const int64_t* target,
                             float scale, float* logits, float* loss_n, float* dlogits, float* dpooled, void* stream) {
     if (!pooled || !W || !target || !logits || !loss_n || !dlogits || !dpooled) return TFNAS_ENULL;
     if (N < 1 || K < 1 || K > 4096 || C < 4 || C > 4096) return TFNAS_ERANGE;
     if (C & 3) return TFNAS_EINVAL;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    ProfScope _prof(TK_SMALL, s);
-    // class groups of the d pooled phase: as many as fill the 1024 threads with (four feature columns x class range) items
-    int KG = CLS_T / (C >> 2);
-    if (KG < 1) KG = 1;
-    if (KG > 8) KG = 8;
-    if (KG > K) KG = K;
-    const size_t shm = ((size_t)C + ((K + 3) & ~3) + (size_t)KG * C) * sizeof(float);
-    if (shm > 64 * 1024) return TFNAS_ERANGE;
-    hipLaunchKernelGGL(k_cls_ce, dim3(N), dim3(CLS_T), shm, s, C, K, KG, pooled, W, bias, target, scale, logits, loss_n, dlogits,
-                       dpooled);
-    return (int)hipGetLastError();
+    return cls_ce_launch(false, N, C, K, pooled, W, bias, target, scale, 0.f, logits, loss_n, nullptr, dlogits, dpooled, stream);
 }
 
 extern "C" int tfnas_cls_ce_ex(int N, int C, int K, const float* pooled, const float* W, const float* bias, const int64_t* target,
@@ -427,19 +425,30 @@ extern "C" int tfnas_cls_ce_ex(int N, int C, int K, const float* pooled, const f
     if (C & 3) return TFNAS_EINVAL;
     if ((dlogits == nullptr) != (dpooled == nullptr)) return TFNAS_EINVAL;       // both (training) or neither (forward only)
     if (!(eps >= 0.f && eps < 1.f)) return TFNAS_EINVAL;
-    int KG = 0;
-    if (dpooled) {                                           // (as tfnas_cls_ce)
-        KG = CLS_T / (C >> 2);
-        if (KG < 1) KG = 1;
-        if (KG > 8) KG = 8;
-        if (KG > K) KG = K;
+    return cls_ce_launch(true, N, C, K, pooled, W, bias, target, scale, eps, logits, loss_n, rank, dlogits, dpooled, stream);
+}
+
+// The summation launch of all three forms: packs the npath paths' pointers, one workgroup per dW tile plus the last row -- that row
+// alone without dW (tfnas_cls_reduce, metrics only).  `dst` is loss (the wgrad forms) or out[4] (REDUCE).
+enum ClsSum { CLS_WGRAD, CLS_WGRAD_EX, CLS_REDUCE };
+static int cls_sum_launch(ClsSum form, int npath, int N, int C, int K, const float* const* pooled, const float* const* dlogits,
+                          const float* const* loss_n, const int32_t* rank, float loss_scale, const float* gscale, int acc, float* dW,
+                          float* db, float* dst, double* meter, void* stream) {
+    ClsPaths P = {};
+    for (int p = 0; p < npath; ++p) {
+        P.pooled[p] = pooled[p];
+        P.dlogits[p] = dlogits[p];
+        P.loss_n[p] = loss_n[p];
     }
-    const size_t shm = ((size_t)C + ((K + 3) & ~3) + (size_t)KG * C) * sizeof(float);
-    if (shm > 64 * 1024) return TFNAS_ERANGE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ProfScope _prof(TK_SMALL, s);
-    hipLaunchKernelGGL(k_cls_ce_ex, dim3(N), dim3(CLS_T), shm, s, C, K, KG, pooled, W, bias, target, scale, eps, logits, loss_n, rank,
-                       dlogits, dpooled);
+    const dim3 grid = dW ? dim3(cdiv(C, 256), cdiv(K, 4) + 1) : dim3(1, 1);
+    if (form == CLS_WGRAD)
+        hipLaunchKernelGGL(k_cls_wgrad, grid, dim3(256), 0, s, npath, N, C, K, P, loss_scale, dW, db, dst);
+    else if (form == CLS_WGRAD_EX)
+        hipLaunchKernelGGL(k_cls_wgrad_ex, grid, dim3(256), 0, s, npath, N, C, K, P, rank, loss_scale, dW, db, dst, meter);
+    else
+        hipLaunchKernelGGL(k_cls_reduce, grid, dim3(256), 0, s, N, C, K, P, rank, gscale, acc, dW, db, dst, meter);
     return (int)hipGetLastError();
 }
 
@@ -452,50 +461,32 @@ extern "C" int tfnas_cls_reduce(int N, int C, int K, const float* pooled, const 
     if (!grads && !out && !meter) return TFNAS_ENULL;        // nothing to write
     if (N < 1 || K < 1 || K > 4096 || C < 1 || C > 4096) return TFNAS_ERANGE;
     if (accumulate != 0 && accumulate != 1) return TFNAS_EINVAL;
-    ClsPaths P = {};
-    P.pooled[0] = pooled;
-    P.dlogits[0] = dlogits;
-    P.loss_n[0] = loss_n;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    ProfScope _prof(TK_SMALL, s);
-    const dim3 grid = grads ? dim3(cdiv(C, 256), cdiv(K, 4) + 1) : dim3(1, 1);
-    hipLaunchKernelGGL(k_cls_reduce, grid, dim3(256), 0, s, N, C, K, P, rank, gscale, accumulate, dW, db, out, meter);
-    return (int)hipGetLastError();
+    return cls_sum_launch(CLS_REDUCE, 1, N, C, K, &pooled, &dlogits, &loss_n, rank, 1.f, gscale, accumulate, dW, db, out, meter,
+                          stream);
 }
 
-static int cls_wgrad_launch(int npath, int N, int C, int K, const float* const* pooled, const float* const* dlogits,
-                            const float* const* loss_n, const int32_t* rank0, float loss_scale, float* dW, float* db, float* loss,
-                            double* meter, bool ex, void* stream) {
+// the checks of tfnas_cls_wgrad and tfnas_cls_wgrad_ex, then the launch
+static int cls_wgrad(ClsSum form, int npath, int N, int C, int K, const float* const* pooled, const float* const* dlogits,
+                     const float* const* loss_n, const int32_t* rank0, float loss_scale, float* dW, float* db, float* loss,
+                     double* meter, void* stream) {
     if (!pooled || !dlogits || !loss_n || !dW || !db) return TFNAS_ENULL;
     if (meter && !rank0) return TFNAS_ENULL;
     if (npath < 1 || npath > 2 || N < 1 || K < 1 || C < 1) return TFNAS_ERANGE;
-    ClsPaths P = {};
-    for (int p = 0; p < npath; ++p) {
+    for (int p = 0; p < npath; ++p)
         if (!pooled[p] || !dlogits[p] || !loss_n[p]) return TFNAS_ENULL;
-        P.pooled[p] = pooled[p];
-        P.dlogits[p] = dlogits[p];
-        P.loss_n[p] = loss_n[p];
-    }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    ProfScope _prof(TK_SMALL, s);
-    const dim3 grid(cdiv(C, 256), cdiv(K, 4) + 1);
-    if (ex)
-        hipLaunchKernelGGL(k_cls_wgrad_ex, grid, dim3(256), 0, s, npath, N, C, K, P, rank0, loss_scale, dW, db, loss, meter);
-    else
-        hipLaunchKernelGGL(k_cls_wgrad, grid, dim3(256), 0, s, npath, N, C, K, P, loss_scale, dW, db, loss);
-    return (int)hipGetLastError();
+    return cls_sum_launch(form, npath, N, C, K, pooled, dlogits, loss_n, meter ? rank0 : nullptr, loss_scale, nullptr, 0, dW, db, loss,
+                          meter, stream);
 }
 
 extern "C" int tfnas_cls_wgrad(int npath, int N, int C, int K, const float* const* pooled, const float* const* dlogits,
                                const float* const* loss_n, float loss_scale, float* dW, float* db, float* loss, void* stream) {
-    return cls_wgrad_launch(npath, N, C, K, pooled, dlogits, loss_n, nullptr, loss_scale, dW, db, loss, nullptr, false, stream);
+    return cls_wgrad(CLS_WGRAD, npath, N, C, K, pooled, dlogits, loss_n, nullptr, loss_scale, dW, db, loss, nullptr, stream);
 }
 
 extern "C" int tfnas_cls_wgrad_ex(int npath, int N, int C, int K, const float* const* pooled, const float* const* dlogits,
                                   const float* const* loss_n, const int32_t* rank0, float loss_scale, float* dW, float* db,
                                   float* loss, double* meter, void* stream) {
-    return cls_wgrad_launch(npath, N, C, K, pooled, dlogits, loss_n, meter ? rank0 : nullptr, loss_scale, dW, db, loss, meter, true,
-                            stream);
+    return cls_wgrad(CLS_WGRAD_EX, npath, N, C, K, pooled, dlogits, loss_n, rank0, loss_scale, dW, db, loss, meter, stream);
 }
 
 extern "C" int tfnas_add_into(float* dst, const float* src, uint64_t count, void* stream) {

@@ -16,15 +16,12 @@ WeightArena (no AccumulateGrad, no zero-fill + two adds).
 Private to ``search._w_step_paths``: the backward of ``BiTailFn`` hands out gradients computed in its forward under the assumption
 that the loss it returned is differentiated with gradient 1 -- ``loss.backward()``, which is what the weight step does.
 
-The derived network's retrain path (model_eval.train_step / validate; reference train_eval.py:228-293) has a general-purpose tail
-of its own below: ``RetrainTailFn`` (label-smoothed loss, logits and the target's rank, correct under any upstream gradient),
-``retrain_tail_forward`` (the forward-only kernel for validation) and ``DeviceMeter`` (an epoch's loss / top-1 / top-5 sums kept on
-the device and read once).
-
-``SearchMeter`` is the search loop's counterpart (train_search.py:318-432 keeps AverageMeters on the host and pays a ``.item()`` per
-value and step): the fused tails feed it from launches they make anyway -- ``BiTail.run(meter=...)`` swaps path A's per-image launch
-for its rank-producing form and the summation launch for ``tfnas_cls_wgrad_ex``; ``ClsCeFn`` adds one metrics-only reduction -- and
-every other route adds with torch ops.
+Every route makes the same two launches (include/tfnas_hip.h): the per-image one (``_cls_ce``) and one that sums over images
+(``_cls_wgrad`` for both paths of a weight step, tfnas_cls_reduce for one path).  The derived network's retrain path
+(model_eval.train_step / validate; train_eval.py:228-293) reaches them through ``RetrainTailFn`` (label-smoothed loss, logits and
+the target's rank, correct under any upstream gradient) and ``retrain_tail_forward`` (forward only).  An epoch's loss / top-1 /
+top-5 sums stay on the device in ``MeterBlock``s, fed by the summation launches (by torch ops on the routes without one) and read
+once: ``DeviceMeter`` (retrain) is one block, ``SearchMeter`` (train_search.py:318-432) two and the latency loss.
 """
 import ctypes as C
 
@@ -109,10 +106,10 @@ class BiTail:
         arena = self.state.arena
         K, Cf = lin.out_features, lin.in_features
         cur = torch.cuda.current_stream(dev)
-        if target.dtype != torch.int64 or not target.is_contiguous():
-            target = target.long().contiguous()
+        t64 = _int64(target)
+        if t64 is not target:
             side.wait_stream(cur)                        # (made on the current stream just now; path B reads it on `side`)
-            target.record_stream(side)
+            t64.record_stream(side)
         wsa, wsb = (wgrad_streams + [None, None])[:2] if wgrad_streams else (None, None)
         logits = [torch.empty((N, K), device=dev, dtype=torch.float32), self.b.logits]
         w_fm, w_cls, b_cls = fm.conv.weight, lin.weight, lin.bias
@@ -126,12 +123,8 @@ class BiTail:
                 t.d.need_wgrad, t.d.g[0].g_expand = 0, None
                 t.dw.need_wgrad, t.dw.g[0].g_expand = 1, gdst
                 check(lib.tfnas_head_fwd(C.byref(t.d), ptr(x), ptr(t.E), ptr(t.stats), ptr(t.part), ptr(t.pooled), s), 'tfnas_head_fwd')
-                if meter is not None and t is self.a:
-                    check(lib.tfnas_cls_ce_ex(N, Cf, K, ptr(t.pooled), ptr(w_cls), ptr(b_cls), ptr(target), 1.0 / N, 0.0, ptr(lg),
-                                              ptr(t.loss_n), ptr(t.rank), ptr(t.dlogits), ptr(t.dpooled), s), 'tfnas_cls_ce_ex')
-                else:
-                    check(lib.tfnas_cls_ce(N, Cf, K, ptr(t.pooled), ptr(w_cls), ptr(b_cls), ptr(target), 1.0 / N, ptr(lg),
-                                           ptr(t.loss_n), ptr(t.dlogits), ptr(t.dpooled), s), 'tfnas_cls_ce')
+                _cls_ce(t.pooled, w_cls, b_cls, t64, s, rank=meter is not None and t is self.a,
+                        out=dict(logits=lg, loss_n=t.loss_n, rank=t.rank, dlogits=t.dlogits, dpooled=t.dpooled))
                 check(lib.tfnas_head_bwd(C.byref(t.d), ptr(x), ptr(t.E), ptr(t.stats), ptr(t.dpooled), ptr(t.dEh), ptr(t.cb1),
                                          ptr(t.red), ptr(t.part), ptr(t.dx), ptr(t.dxp), s), 'tfnas_head_bwd')
                 # the head's weight gradient: a leaf, on the path's weight-gradient stream (joined by tfnas_paths_bwd / w_step)
@@ -145,17 +138,8 @@ class BiTail:
             for other in (cur, side, wsb):
                 if other is not None and other is not w:
                     w.wait_stream(other)
-            P = lambda ts: _lib.raw_array([t.data_ptr() for t in ts])
-            if meter is not None:
-                check(lib.tfnas_cls_wgrad_ex(2, N, Cf, K, P([self.a.pooled, self.b.pooled]), P([self.a.dlogits, self.b.dlogits]),
-                                             P([self.a.loss_n, self.b.loss_n]), ptr(self.a.rank), 1.0 / N,
-                                             C.c_void_p(arena.grad_ptr(w_cls)), C.c_void_p(arena.grad_ptr(b_cls)), ptr(self.loss),
-                                             meter.w_ptr(dev), C.c_void_p(w.cuda_stream)), 'tfnas_cls_wgrad_ex')
-            else:
-                check(lib.tfnas_cls_wgrad(2, N, Cf, K, P([self.a.pooled, self.b.pooled]), P([self.a.dlogits, self.b.dlogits]),
-                                          P([self.a.loss_n, self.b.loss_n]), 1.0 / N, C.c_void_p(arena.grad_ptr(w_cls)),
-                                          C.c_void_p(arena.grad_ptr(b_cls)), ptr(self.loss), C.c_void_p(w.cuda_stream)),
-                      'tfnas_cls_wgrad')
+            _cls_wgrad((self.a, self.b), N, Cf, K, C.c_void_p(arena.grad_ptr(w_cls)), C.c_void_p(arena.grad_ptr(b_cls)), self.loss,
+                       C.c_void_p(w.cuda_stream), None if meter is None else meter.w.ptr(dev))
             check(lib.tfnas_add_into(C.c_void_p(arena.grad_ptr(w_fm)), ptr(self.b.gw), w_fm.numel(), C.c_void_p(w.cuda_stream)),
                   'tfnas_add_into')
         self.join_stream = w if w is not cur else None
@@ -189,28 +173,11 @@ class ClsCeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pooled, W, b, target, meter=None):
-        lib = _lib.lib()
-        pooled = pooled.contiguous()
-        N, Cf = pooled.shape
-        K = W.shape[0]
-        dev = pooled.device
-        if target.dtype != torch.int64 or not target.is_contiguous():
-            target = target.long().contiguous()
-        logits = torch.empty((N, K), device=dev, dtype=torch.float32)
-        loss_n = torch.empty(N, device=dev, dtype=torch.float32)
-        dlogits = torch.empty((N, K), device=dev, dtype=torch.float32)
-        dpooled = torch.empty((N, Cf), device=dev, dtype=torch.float32)
-        s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with _on(dev):
-            if meter is not None:
-                rank = torch.empty(N, device=dev, dtype=torch.int32)
-                check(lib.tfnas_cls_ce_ex(N, Cf, K, ptr(pooled), ptr(W), ptr(b), ptr(target), 1.0 / N, 0.0, ptr(logits), ptr(loss_n),
-                                          ptr(rank), ptr(dlogits), ptr(dpooled), s), 'tfnas_cls_ce_ex')
-                check(lib.tfnas_cls_reduce(N, Cf, K, None, None, ptr(loss_n), ptr(rank), None, 0, None, None, None,
-                                           meter.a_ptr(dev), s), 'tfnas_cls_reduce')
-            else:
-                check(lib.tfnas_cls_ce(N, Cf, K, ptr(pooled), ptr(W), ptr(b), ptr(target), 1.0 / N, ptr(logits), ptr(loss_n),
-                                       ptr(dlogits), ptr(dpooled), s), 'tfnas_cls_ce')
+        dev, N = pooled.device, pooled.size(0)
+        s = functions._stream(dev)
+        _, logits, loss_n, rank, _, dpooled = _cls_ce(pooled, W, b, target, s, rank=meter is not None)
+        if meter is not None:
+            _cls_metrics(loss_n, rank, W.shape[0], meter.a.ptr(dev), s, want_out=False)
         ctx.save_for_backward(dpooled)
         ctx.mark_non_differentiable(logits)
         return loss_n.sum() * (1.0 / N), logits
@@ -227,10 +194,10 @@ def frozen_classifier_loss(model, pooled, target, meter=None):
     lin = getattr(getattr(model, 'classifier', None), 'linear', None)
     if lin is None or lin.bias is None or lin.weight.requires_grad or lin.bias.requires_grad or not pooled.is_cuda:
         return None
-    if lin.weight.dtype != torch.float32 or (lin.in_features & 3) or lin.in_features > 4096 or lin.out_features > 4096:
+    # (the limits of the launch, stated once: for C, K <= 4096 the LDS term of cls_shapes_ok never binds -- C + K + KG * C is at most
+    # 3 * 4096 floats, 48 KiB -- so this is the C % 4, C <= 4096, K <= 4096 this function has always asked for)
+    if lin.weight.dtype != torch.float32 or not cls_shapes_ok(lin.in_features, lin.out_features):
         return None
-    if meter is None:
-        return ClsCeFn.apply(pooled, lin.weight.detach(), lin.bias.detach(), target)
     return ClsCeFn.apply(pooled, lin.weight.detach(), lin.bias.detach(), target, meter)
 
 
@@ -242,66 +209,60 @@ def cls_shapes_ok(Cf, K):
     return 4 * (Cf + ((K + 3) & ~3) + kg * Cf) <= 64 * 1024
 
 
-def _cls_ce_ex(pooled, W, b, target, eps, grads):
-    """One tfnas_cls_ce_ex launch on the current stream -> (pooled, logits, loss_n, rank, dlogits, dpooled); the last two are None in
-    the forward-only form.  dlogits carries the 1 / N of the mean reduction."""
-    pooled = pooled.contiguous()
-    N, Cf = pooled.shape
-    K = W.shape[0]
-    dev = pooled.device
-    if target.dtype != torch.int64 or not target.is_contiguous():
-        target = target.long().contiguous()
-    f32 = torch.float32
-    logits = torch.empty((N, K), device=dev, dtype=f32)
-    loss_n = torch.empty(N, device=dev, dtype=f32)
-    rank = torch.empty(N, device=dev, dtype=torch.int32)
-    dlogits = torch.empty((N, K), device=dev, dtype=f32) if grads else None
-    dpooled = torch.empty((N, Cf), device=dev, dtype=f32) if grads else None
+def _int64(target):
+    """The targets as the kernels read them: contiguous int64 (the same tensor when they already are)."""
+    return target if target.dtype == torch.int64 and target.is_contiguous() else target.long().contiguous()
+
+
+def _cls_ce(pooled, W, b, target, stream, eps=0.0, rank=False, grads=True, out=None):
+    """THE per-image launch, on ``stream`` (a launch pointer) -> (pooled, logits, loss_n, rank, dlogits, dpooled), into the buffers of
+    ``out`` (by those names) where it has them and fresh ones otherwise.  tfnas_cls_ce unless something only tfnas_cls_ce_ex has is
+    asked for -- the target's ``rank``, ``eps`` != 0, or the forward-only form (``grads`` False: no dlogits / dpooled) -- so a step
+    without a meter launches what it always did, and an invalid target there gives loss 0, not NaN.  Without ``rank`` the
+    returned rank is None.  dlogits carries the 1 / N of the mean reduction."""
+    pooled, target = pooled.contiguous(), _int64(target)
+    (N, Cf), K, dev = pooled.shape, W.shape[0], pooled.device
+    ex = bool(rank) or eps != 0 or not grads
+    out = out or {}
+
+    def buf(name, shape, dtype=torch.float32):
+        t = out.get(name)
+        return torch.empty(shape, device=dev, dtype=dtype) if t is None else t
+    logits, loss_n = buf('logits', (N, K)), buf('loss_n', N)
+    rk = buf('rank', N, torch.int32) if ex else None
+    dlogits, dpooled = (buf('dlogits', (N, K)), buf('dpooled', (N, Cf))) if grads else (None, None)
+    lib = _lib.lib()
     with _on(dev):
-        check(_lib.lib().tfnas_cls_ce_ex(N, Cf, K, ptr(pooled), ptr(W), ptr(b), ptr(target), 1.0 / N, float(eps), ptr(logits),
-                                         ptr(loss_n), ptr(rank), ptr(dlogits), ptr(dpooled), functions._stream(dev)),
-              'tfnas_cls_ce_ex')
-    return pooled, logits, loss_n, rank, dlogits, dpooled
+        if ex:
+            check(lib.tfnas_cls_ce_ex(N, Cf, K, ptr(pooled), ptr(W), ptr(b), ptr(target), 1.0 / N, float(eps), ptr(logits),
+                                      ptr(loss_n), ptr(rk), ptr(dlogits), ptr(dpooled), stream), 'tfnas_cls_ce_ex')
+        else:
+            check(lib.tfnas_cls_ce(N, Cf, K, ptr(pooled), ptr(W), ptr(b), ptr(target), 1.0 / N, ptr(logits), ptr(loss_n),
+                                   ptr(dlogits), ptr(dpooled), stream), 'tfnas_cls_ce')
+    return pooled, logits, loss_n, rk, dlogits, dpooled
 
 
-def _cls_metrics(loss_n, rank, K, meter):
-    """The metrics-only tfnas_cls_reduce: out[4] = {mean loss, top-1 count, top-5 count, invalid count}, and the meter's sums."""
+def _cls_wgrad(paths, N, Cf, K, dW, db, loss, stream, meter=None):
+    """THE summation launch of a weight step over ``paths`` (_PathTail): tfnas_cls_wgrad, or with ``meter`` (a launch pointer to
+    a meter block) tfnas_cls_wgrad_ex with the rank of paths[0].  dW / db / stream are launch pointers."""
+    lib = _lib.lib()
+    P = lambda name: _lib.raw_array([getattr(t, name).data_ptr() for t in paths])
+    head = (len(paths), N, Cf, K, P('pooled'), P('dlogits'), P('loss_n'))
+    if meter is None:
+        check(lib.tfnas_cls_wgrad(*head, 1.0 / N, dW, db, ptr(loss), stream), 'tfnas_cls_wgrad')
+    else:
+        check(lib.tfnas_cls_wgrad_ex(*head, ptr(paths[0].rank), 1.0 / N, dW, db, ptr(loss), meter, stream), 'tfnas_cls_wgrad_ex')
+
+
+def _cls_metrics(loss_n, rank, K, meter, stream, want_out=True):
+    """The metrics-only tfnas_cls_reduce: out[4] = {mean loss, top-1 count, top-5 count, invalid count} (returned; None without
+    ``want_out``), and the sums of ``meter`` (a launch pointer to a meter block, or None)."""
     dev = loss_n.device
-    out = torch.empty(4, device=dev, dtype=torch.float32)
-    buf = meter.buf if isinstance(meter, DeviceMeter) else meter
+    out = torch.empty(4, device=dev, dtype=torch.float32) if want_out else None
     with _on(dev):
         check(_lib.lib().tfnas_cls_reduce(loss_n.numel(), 4, K, None, None, ptr(loss_n), ptr(rank), None, 0, None, None, ptr(out),
-                                          ptr(buf), functions._stream(dev)), 'tfnas_cls_reduce')
+                                          meter, stream), 'tfnas_cls_reduce')
     return out
-
-
-class DeviceMeter:
-    """Running {sum of per-image losses, top-1 hits, top-5 hits, images, invalid targets} of an epoch as five doubles ON THE DEVICE:
-    the retrain tail's reduction launch adds to them (tfnas_cls_reduce), the torch route adds with torch ops (``add``), and ``read``
-    is the only device -> host copy -- once per epoch instead of a ``.tolist()`` per step (train_eval.py:246-250,287-291 keep
-    AverageMeters on the host).  Every update is enqueued on the caller's current stream."""
-
-    def __init__(self, device):
-        self.buf = torch.zeros(5, device=device, dtype=torch.float64)
-
-    def reset(self):
-        self.buf.zero_()
-
-    def add(self, loss, logits, target):
-        """What the fused tail adds, from a mean loss and logits computed by torch ops (no host sync either)."""
-        n = target.size(0)
-        hit = logits.topk(min(5, logits.size(1)), 1, True, True)[1].eq(target.view(-1, 1))
-        f64 = torch.float64
-        vals = [loss.detach().to(f64) * n, hit[:, :1].sum().to(f64), hit.sum().to(f64)]
-        self.buf[:3] += torch.stack(vals)
-        self.buf[3] += n
-
-    def read(self):
-        """(loss average, top-1 %, top-5 %, images, invalid targets)"""
-        s, c1, c5, cnt, bad = self.buf.tolist()
-        if cnt == 0:
-            return 0.0, 0.0, 0.0, 0, 0
-        return s / cnt, 100.0 * c1 / cnt, 100.0 * c5 / cnt, int(cnt), int(bad)
 
 
 def target_rank(logits, target):
@@ -317,34 +278,23 @@ def target_rank(logits, target):
     return torch.where(valid, rank, torch.full_like(rank, -1)).view(-1), valid.view(-1)
 
 
-class SearchMeter:
-    """A search epoch's running sums (train_search.py:318-432: the AverageMeters objs_w, top1, top5, objs_a, objs_l) as eleven
-    doubles ON THE DEVICE: two blocks of the DeviceMeter / tfnas_cls_reduce layout {sum of per-image losses, top-1 hits, top-5 hits,
-    images, invalid targets} -- ``w`` for the weight steps (loss = loss_g + loss_r, hits of the gumbel path), ``a`` for the
-    architecture steps -- and sum n * loss_l.  The fused tails add to the blocks from their own launches (tfnas_cls_wgrad_ex,
-    tfnas_cls_reduce); ``add_w`` / ``add_a`` are the same sums as torch ops for the routes without a fused tail and for host
-    tensors.  Nothing here synchronises with the host except ``read``.  Updates are ordered by the steps' streams: every step
-    joins its side streams into the caller's stream before it returns."""
-    W, A, L, SIZE = 0, 5, 10, 11
+class MeterBlock:
+    """THE meter layout of include/tfnas_hip.h -- five doubles {sum of per-image losses, top-1 hits, top-5 hits, images, invalid
+    targets} -- on ``buf[first:first + 5]`` of its owner's buffer: what a launch adds to (``ptr``), the same sums as torch ops
+    (``add``) and the averages of five host numbers (``averages``).  Nothing here synchronises with the host."""
 
-    def __init__(self, device):
-        self.buf = torch.zeros(self.SIZE, device=device, dtype=torch.float64)
+    def __init__(self, buf, first=0):
+        self.buf = buf[first:first + 5]                  # (a view: the owner zeroes, reduces and reads the whole buffer)
 
-    def reset(self):
-        self.buf.zero_()
-
-    def _block_ptr(self, first, dev):
+    def ptr(self, dev):
+        """The block as a launch argument of a step on ``dev``."""
         if self.buf.device != dev:
-            raise RuntimeError('tfnas_amd: the SearchMeter lives on %s, the step runs on %s' % (self.buf.device, dev))
-        return C.c_void_p(self.buf.data_ptr() + 8 * first)
+            raise RuntimeError('tfnas_amd: the meter lives on %s, the step runs on %s' % (self.buf.device, dev))
+        return C.c_void_p(self.buf.data_ptr())
 
-    def w_ptr(self, dev):
-        return self._block_ptr(self.W, dev)
-
-    def a_ptr(self, dev):
-        return self._block_ptr(self.A, dev)
-
-    def _add(self, first, loss, n, logits, target):
+    def add(self, loss, n, logits=None, target=None):
+        """What the fused tails add, from a mean loss over ``n`` images and -- for the hits and the invalid count, by
+        ``target_rank`` -- logits and targets."""
         f64 = torch.float64
         s = loss.detach().to(f64) * n
         cnt = torch.full((), float(n), dtype=f64, device=s.device)
@@ -353,17 +303,65 @@ class SearchMeter:
         else:
             rank, valid = target_rank(logits.detach(), target)
             vals = [s, (valid & (rank < 1)).sum().to(f64), (valid & (rank < 5)).sum().to(f64), cnt, (~valid).sum().to(f64)]
-        self.buf[first:first + len(vals)].add_(torch.stack(vals))
+        self.buf[:len(vals)].add_(torch.stack(vals))
+
+    @staticmethod
+    def averages(v):
+        """(loss average, top-1 %, top-5 %, images, invalid targets) of a block's five numbers on the host; zeros when empty."""
+        s, c1, c5, cnt, bad = v
+        n = cnt or 1.0
+        return s / n, 100.0 * c1 / n, 100.0 * c5 / n, int(cnt), int(bad)
+
+
+class DeviceMeter:
+    """An epoch's running sums of the retrain path as ONE MeterBlock on the device: the retrain tail's reduction launch adds to it
+    (tfnas_cls_reduce), the torch route adds with torch ops (``add``), and ``read`` is the only device -> host copy -- once per
+    epoch instead of a ``.tolist()`` per step (train_eval.py:246-250,287-291 keep AverageMeters on the host).  Every update is
+    enqueued on the caller's current stream."""
+
+    def __init__(self, device):
+        self.buf = torch.zeros(5, device=device, dtype=torch.float64)
+        self.block = MeterBlock(self.buf)
+
+    def reset(self):
+        self.buf.zero_()
+
+    def add(self, loss, logits, target):
+        """What the fused tail adds, from a mean loss and logits computed by torch ops (no host sync either).  Hits are counted by
+        ``target_rank`` -- the kernels' tie rule: a target logit exactly tied with another class's is a hit only against higher
+        class indices, where torch.topk promised no order -- and the fifth slot counts the targets outside [0, K)."""
+        self.block.add(loss, target.size(0), logits, target)
+
+    def read(self):
+        """(loss average, top-1 %, top-5 %, images, invalid targets)"""
+        return MeterBlock.averages(self.buf.tolist())
+
+
+class SearchMeter:
+    """A search epoch's running sums (train_search.py:318-432: the AverageMeters objs_w, top1, top5, objs_a, objs_l) as eleven
+    doubles ON THE DEVICE: two MeterBlocks -- ``w`` for the weight steps (loss = loss_g + loss_r, hits of the gumbel path), ``a``
+    for the architecture steps -- and sum n * loss_l.  The fused tails add to the blocks from their own launches
+    (tfnas_cls_wgrad_ex, tfnas_cls_reduce); ``add_w`` / ``add_a`` are the same sums as torch ops for the routes without a fused
+    tail and for host tensors.  Nothing here synchronises with the host except ``read``.  Updates are ordered by the steps'
+    streams: every step joins its side streams into the caller's stream before it returns."""
+    W, A, L, SIZE = 0, 5, 10, 11
+
+    def __init__(self, device):
+        self.buf = torch.zeros(self.SIZE, device=device, dtype=torch.float64)
+        self.w, self.a = MeterBlock(self.buf, self.W), MeterBlock(self.buf, self.A)
+
+    def reset(self):
+        self.buf.zero_()
 
     def add_w(self, loss, logits, target):
         """One weight step from its returned mean loss (both paths' sum under bi-sampling) and the gumbel path's logits."""
-        self._add(self.W, loss, target.size(0), logits, target)
+        self.w.add(loss, target.size(0), logits, target)
 
     def add_a(self, loss_a, loss_l, n, logits=None, target=None):
         """One architecture step: n * loss_l always; n * loss_a, the images and -- with logits / target -- the hits unless
         ``loss_a`` is None (the fused classifier tail has added its block from its own launch)."""
         if loss_a is not None:
-            self._add(self.A, loss_a, n, logits, target)
+            self.a.add(loss_a, n, logits, target)
         self.buf[self.L:self.L + 1].add_(loss_l.detach().to(torch.float64).view(1) * n)
 
     def reduce_(self, group=None):
@@ -375,17 +373,16 @@ class SearchMeter:
     def read(self):
         """The only device -> host copy: the reference's averages (losses per image, top-k in percent) and the counts."""
         v = self.buf.tolist()
-        w, a = v[self.W:self.W + 5], v[self.A:self.A + 5]
-        nw, na = w[3] or 1.0, a[3] or 1.0
-        return dict(objs_w=w[0] / nw, top1=100.0 * w[1] / nw, top5=100.0 * w[2] / nw, images_w=int(w[3]),
-                    objs_a=a[0] / na, objs_l=v[self.L] / na, top1_a=100.0 * a[1] / na, top5_a=100.0 * a[2] / na,
-                    images_a=int(a[3]), invalid=int(w[4] + a[4]))
+        w, a = MeterBlock.averages(v[self.W:self.W + 5]), MeterBlock.averages(v[self.A:self.A + 5])
+        return dict(objs_w=w[0], top1=w[1], top5=w[2], images_w=w[3], objs_a=a[0], objs_l=v[self.L] / (a[3] or 1.0), top1_a=a[1],
+                    top5_a=a[2], images_a=a[3], invalid=w[4] + a[4])
 
 
 def retrain_tail_forward(pooled, W, b, target, eps=0.0, meter=None):
     """(loss, logits, rank) without gradients: the forward-only kernel (no d logits / d pooled phase) + the metrics launch."""
-    _, logits, loss_n, rank, _, _ = _cls_ce_ex(pooled, W, b, target, eps, False)
-    out = _cls_metrics(loss_n, rank, W.shape[0], meter)
+    s = functions._stream(pooled.device)
+    _, logits, loss_n, rank, _, _ = _cls_ce(pooled, W, b, target, s, eps, rank=True, grads=False)
+    out = _cls_metrics(loss_n, rank, W.shape[0], meter and meter.block.ptr(pooled.device), s)
     return out[0], logits, rank
 
 
@@ -403,8 +400,9 @@ class RetrainTailFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pooled, W, b, target, eps, modes=None, meter=None):
         modes = functions.DEFAULT_MODES if modes is None else modes
-        pooled, logits, loss_n, rank, dlogits, dpooled = _cls_ce_ex(pooled, W, b, target, eps, True)
-        out = _cls_metrics(loss_n, rank, W.shape[0], meter)
+        s = functions._stream(pooled.device)
+        pooled, logits, loss_n, rank, dlogits, dpooled = _cls_ce(pooled, W, b, target, s, eps, rank=True)
+        out = _cls_metrics(loss_n, rank, W.shape[0], meter and meter.block.ptr(pooled.device), s)
         ctx.modes = modes
         ctx.direct = functions._direct_targets([W, b], modes) if W.requires_grad and b.requires_grad else None
         ctx.save_for_backward(pooled, dlogits, dpooled, loss_n, rank, W, b)
