@@ -77,10 +77,16 @@ extern "C" {
  *   w_proj   [oc][mc]      point_linear.conv.weight         [oc,mc,1,1]
  *   w_se_r   [se][mc], b_se_r [se]   squeeze_excite.conv_reduce.{weight,bias}
  *   w_se_e   [mc][se], b_se_e [mc]   squeeze_excite.conv_expand.{weight,bias}
- * g_* are the matching gradient outputs (same shapes), only read/written when need_wgrad != 0. */
+ * g_* are the matching gradient outputs (same shapes), only read/written when need_wgrad != 0.
+ * k: 3, 5 or -- in a descriptor whose flags carry TFNAS_CELL_K7 -- 7 (pad k / 2); any other value, and 7 without the bit, is
+ * TFNAS_EINVAL.  A cell with a 7 x 7 group runs its depthwise passes on the LDS tile
+ * kernels whatever TFNAS_ROUTE_DW_* asks (the register-window and ring kernels are built for 3 and 5), keeps the depthwise weight
+ * gradient in its own launch, and always materialises E: tfnas_efree_supported and tfnas_fx_supported return 0 for it.  The groups'
+ * depthwise weight gradients share one row of partial sums: sum of mc * k * k above 4 Mi - 1024 floats is TFNAS_ERANGE
+ * (tfnas_cell_plan, tfnas_cell_ws); eight 7 x 7 groups of 1536 channels fit. */
 typedef struct TfnasGroup {
     int32_t mc;       /* mid channels (any integer > 0, e.g. 53)            [in]  */
-    int32_t k;        /* depthwise kernel size: 3 or 5                      [in]  */
+    int32_t k;        /* depthwise kernel size: 3 or 5; 7 with TFNAS_CELL_K7 [in]  */
     int32_t se;       /* squeeze-excite width (a multiple of 4), 0 = no SE   [in]  */
     int32_t mcp;      /* mc rounded up to a multiple of 4                   [plan] */
     int32_t off;      /* first column of this group in the [.][M] tensors (multiple of 32) [plan] */
@@ -112,7 +118,8 @@ typedef struct TfnasCellDesc {
                                  modes: an fp32-exact search net beside a bf16-GEMM derived net)                      [in] */
     int32_t flags;            /* TFNAS_CELL_LAZY_JOIN: tfnas_mbconv_bwd returns without joining its weight-gradient side
                                  stream (see tfnas_set_lazy_join, which sets the default for descriptors without the bit);
-                                 TFNAS_CELL_ACCUM_WGRAD: the backward adds its weight gradients to their destinations   [in]
+                                 TFNAS_CELL_ACCUM_WGRAD: the backward adds its weight gradients to their destinations;
+                                 TFNAS_CELL_K7: groups may have depthwise kernel size 7                                 [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -152,6 +159,13 @@ typedef struct TfnasCellDesc {
  * of an earlier launch, and the other bi-sampling path of tfnas_paths_bwd (two paths never share a gradient range).
  * (0x2, 0x4, 0x8 are undefined; 0x10 was TFNAS_CELL_FXP, retired: all are refused.) */
 #define TFNAS_CELL_ACCUM_WGRAD 0x20
+/* TfnasCellDesc.flags: the caller knows depthwise kernel size 7 (TfnasGroup.k).  Additive like TFNAS_CELL_ACCUM_WGRAD: without the
+ * bit every descriptor is accepted or refused exactly as before it existed (k = 7 is TFNAS_EINVAL: callers that probe
+ * tfnas_cell_plan for what the library can run, and fall back otherwise, keep seeing that); with it, groups may have k = 7 and
+ * nothing else changes -- a descriptor of 3 x 3 / 5 x 5 groups plans, routes and launches the same with or without the bit.  Checked
+ * by tfnas_cell_plan and again by every entry point (the descriptor's modes may change between the two).  The Python mirror sets it
+ * for every descriptor that holds a 7 x 7 group (functions.HipModes.apply). */
+#define TFNAS_CELL_K7 0x80
 /* TfnasCellDesc.route (ABI 4; rounds 2-5 read these from TFNAS_* environment variables latched once per process) */
 #define TFNAS_ROUTE_FX_OFF 0x1        /* frozen-weight launches of the 14 x 14 / 7 x 7 cells through the materialised route instead
                                          of the fused per-image kernels (csrc/fx_kernels.hip)                                   */
@@ -163,7 +177,7 @@ typedef struct TfnasCellDesc {
 #define TFNAS_ROUTE_XG_OFF 0x10       /* expand weight gradient never in Gram form                                              */
 #define TFNAS_ROUTE_XG_ALL 0x20       /* ... in Gram form wherever the shape allows (default: where E >= 100 MB)                */
 #define TFNAS_ROUTE_DW_SHIFT 6        /* 2 bits: 0 per-launch policy, 1 register-window kernels wherever the geometry allows,   */
-#define TFNAS_ROUTE_DW_MASK 0xc0      /*         2 LDS ring / tile kernels only, 3 tile kernels only                            */
+#define TFNAS_ROUTE_DW_MASK 0xc0      /*         2 LDS ring / tile kernels only, 3 tile kernels only (7 x 7 cells: always 3)    */
 #define TFNAS_ROUTE_SE_SHIFT 8        /* 2 bits: 0 wave-level MFMA kernels for the excite FCs, 1 one fused per-image kernel,    */
 #define TFNAS_ROUTE_SE_MASK 0x300     /*         2 LDS-tiled GEMMs                                                              */
 #define TFNAS_ROUTE_WGRAD_INLINE 0x400 /* weight-gradient kernels on the caller's stream (no side stream)                       */
@@ -235,7 +249,7 @@ int tfnas_cell_ws(const TfnasCellDesc *d, TfnasCellWs *ws);
 /* 1 when the cell can run without the expanded tensor E ("E-free" mode: pass E = NULL to tfnas_mixedop_fwd AND to the
  * matching tfnas_mixedop_bwd; the depthwise kernels then recompute act(BN1(x W_expand^T)) from the narrow cell input,
  * and BN1's batch statistics come from the ic x ic Gram matrix of x).  Currently: TFNAS_MODE_CELL, need_wgrad = 0
- * (the alpha-step: frozen weights), ic in {16, 24, 40}.  Same arithmetic contract as the E path (fp32, <= 1e-3). */
+ * (the alpha-step: frozen weights), ic in {16, 24, 40}, kernel sizes 3 / 5.  Same arithmetic contract as the E path (fp32, <= 1e-3). */
 int tfnas_efree_supported(const TfnasCellDesc *d);
 /* What a forward of the (planned) descriptor does with the saved buffers -- a pure function of the descriptor (geometry,
  * need_wgrad, route, sync hook): TFNAS_ROUTE_TAKEN_VALID | TFNAS_ROUTE_TAKEN_*.  Callers that plan the backward with a descriptor
@@ -246,7 +260,7 @@ int tfnas_cell_route(const TfnasCellDesc *d);
  * most 14 x 14 pixels, 64 <= ic <= 192 (a multiple of 16), frozen weights -- the supernet's cells at 14 x 14 and 7 x 7.  One kernel
  * per direction runs expand 1x1 + BN1 + activation + depthwise k x k (models/layers.py:542-552) for a group of whole images x a
  * slice of mid channels; neither E nor its gradient is ever written (the dEh buffer of tfnas_mixedop_bwd is used as scratch for
- * partial sums of dx).  Implies tfnas_efree_supported. */
+ * partial sums of dx).  Implies tfnas_efree_supported (so: 0 for a cell with a 7 x 7 group). */
 int tfnas_fx_supported(const TfnasCellDesc *d);
 
 /* MixedOP forward.

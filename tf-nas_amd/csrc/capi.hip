@@ -155,7 +155,11 @@ static int check_modes(const TfnasCellDesc* d) {
         const int gm = d->gemm_mode & ~(TFNAS_GEMM_EXPLICIT | TFNAS_GEMM_EVERYWHERE);
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
-    if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD)) return TFNAS_EINVAL;
+    if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7)) return TFNAS_EINVAL;
+    if (!(d->flags & TFNAS_CELL_K7)) {            // kernel size 7 is opt-in: without the bit it is refused as it always was
+        for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g)
+            if (d->g[g].k == 7) return TFNAS_EINVAL;
+    }
     if (d->route & ~TFNAS_ROUTE_ALL) return TFNAS_EINVAL;
     if ((d->route & TFNAS_ROUTE_XG_OFF) && (d->route & TFNAS_ROUTE_XG_ALL)) return TFNAS_EINVAL;
     if ((d->route & TFNAS_ROUTE_SE_MASK) == TFNAS_ROUTE_SE_MASK) return TFNAS_EINVAL;     // (3 is not an excite-FC variant)
@@ -184,13 +188,14 @@ extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
     if (d->act != TFNAS_ACT_RELU && d->act != TFNAS_ACT_SWISH) return TFNAS_EINVAL;
     if (d->has_res && (d->ic != d->oc || d->stride != 1)) return TFNAS_EINVAL;
     TRY(check_modes(d));
-    // conv output size with pad = k/2 (same for k = 3 and 5)
+    // conv output size with pad = k/2 (same for k = 3, 5 and 7)
     d->Ho = (d->H - 1) / d->stride + 1;
     d->Wo = (d->W - 1) / d->stride + 1;
     int off = 0, se_off = 0;
     for (int g = 0; g < d->G; ++g) {
         TfnasGroup& gr = d->g[g];
-        if (gr.mc < 1 || (gr.k != 3 && gr.k != 5) || gr.se < 0) return TFNAS_EINVAL;
+        if (gr.mc < 1 || (gr.k != 3 && gr.k != 5 && gr.k != 7) ||      // (7: with TFNAS_CELL_K7 only, check_modes)
+            gr.se < 0) return TFNAS_EINVAL;
         if (gr.se & 3) return TFNAS_EINVAL;       // SE widths are in_channels x {1, 2} in the search space; the excite
                                                   // GEMMs move hidden units in quads
         gr.mcp = (gr.mc + 3) & ~3;
@@ -209,12 +214,14 @@ extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
     d->M = off;
     d->SE = se_off;
     if ((double)d->N * d->H * d->W >= 2147483647.0) return TFNAS_ERANGE;   // row indices are int, offsets size_t
+    if (!dw_wgrad_row_fits(*d)) return TFNAS_ERANGE;     // one row of depthwise weight-gradient partials (sum of mc * k * k)
     return 0;
 }
 
 extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     if (!d || !ws) return TFNAS_ENULL;
     memset(ws, 0, sizeof(*ws));
+    if (!dw_wgrad_row_fits(*d)) return TFNAS_ERANGE;
     const uint64_t P = (uint64_t)d->N * d->H * d->W, Po = (uint64_t)d->N * d->Ho * d->Wo;
     const uint64_t M = d->M, N = d->N, SE = d->SE, G = d->G, oc = d->oc;
     // the four stream tensors: P*M / Po*M fp32 elements

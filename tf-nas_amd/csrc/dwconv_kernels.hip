@@ -441,13 +441,18 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
 // ============================================================================ weight gradient
 // part[bx][poff_g + c*K*K + ky*K + kx] = sum over this workgroup's tiles of dd[n][ho][wo][c] * a1[n][ho*S+ky-p][wo*S+kx-p][c]
 // (a1 = act(BN1(E))); k_reduce_rows sums the workgroups into g_dw
-template <int K, int S, int ACT>
-__global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const float* __restrict__ dZ,
-                                                     const float* __restrict__ gate, const float* __restrict__ dpooled,
-                                                     const float* __restrict__ D, const double* __restrict__ stats2,
-                                                     const double* __restrict__ red2, const float* __restrict__ E,
-                                                     const double* __restrict__ stats1, float* __restrict__ part,
-                                                     size_t out_size, DwGeom gm) {
+// KR: tap rows of one workgroup.  KR = K (3 x 3, 5 x 5): all of them.  7 x 7: 49 float4 accumulators are 196 registers before the
+// 13-wide window and the operands, past the 256 that two workgroups per CU leave a thread, so the rows are split over blockIdx.z
+// (KR = 4: rows 0-3 and 4-6, 28 and 21 accumulators); each part stages the tile itself and writes its own K * KR-float slice of
+// every channel's K * K block of the partial row.
+// (KY0, KR as template arguments: tap rows [KY0, KY0 + KR) with every accumulator index a compile-time constant)
+template <int K, int S, int ACT, int KY0, int KR>
+__device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const float* __restrict__ dZ,
+                                              const float* __restrict__ gate, const float* __restrict__ dpooled,
+                                              const float* __restrict__ D, const double* __restrict__ stats2,
+                                              const double* __restrict__ red2, const float* __restrict__ E,
+                                              const double* __restrict__ stats1, float* __restrict__ part,
+                                              size_t out_size, const DwGeom& gm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int g, c0;
     if (!dw_locate<K>(d, blockIdx.y, gm.CC, g, c0)) return;
@@ -460,7 +465,7 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
     const int tid = threadIdx.x;
     const int IH = gm.L0, IW = gm.L1;
 
-    const int tile_floats = max(IH * IW * CC, 4 * K * K * CC);
+    const int tile_floats = max(IH * IW * CC, 4 * KR * K * CC);
     float* in_tile = lds;
     f32x4* cst2 = reinterpret_cast<f32x4*>(lds + tile_floats);
     float2* cst1 = reinterpret_cast<float2*>(cst2 + CC);
@@ -474,9 +479,9 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
     const int nsw = TW >> 2, nstrips = TH * nsw;
     const bool has_se = d.g[g].se > 0;
     const float inv_hw = 1.f / (float)(Ho * Wo);
-    f32x4 wacc[K * K];
+    f32x4 wacc[KR * K];
 #pragma unroll
-    for (int u = 0; u < K * K; ++u) wacc[u] = zero4();
+    for (int u = 0; u < KR * K; ++u) wacc[u] = zero4();
     for (int t = xcd_first_tile(); t < gm.ntiles; t += gridDim.x) {
         const int tw = t % gm.tilesW, th = (t / gm.tilesW) % gm.tilesH, n = t / (gm.tilesW * gm.tilesH);
         const int ho0 = th * TH, wo0 = tw * TW;
@@ -504,9 +509,13 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
                 dv[j] = ok[j] ? ld4_nt(D + a) : zero4();
             }
         };
-        f32x4 pdd[4], pdv[4];
+        // (KR < K: the accumulators leave no registers to hold them across the staging)
+        constexpr bool PF = KR == K;       // (one part)
+        f32x4 pdd[PF ? 4 : 1], pdv[PF ? 4 : 1];
         bool pok[4] = {false, false, false, false};
-        if (tid < nitems) item_ops(tid, pdd, pdv, pok);
+        if constexpr (PF) {
+            if (tid < nitems) item_ops(tid, pdd, pdv, pok);
+        }
         __syncthreads();
         load_tile(in_tile, IH, IW, CC, gm.cq_shift, E,
                   [&](int r, int c, int cq, size_t& a) {
@@ -528,12 +537,16 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
             const int oh = st / nsw, ow0 = (st - oh * nsw) * 4;
             f32x4 dd[4], dv[4];
             bool ok[4];
-            if (item == tid) {
+            if constexpr (PF) {
+                if (item == tid) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dd[j] = pdd[j];
-                    dv[j] = pdv[j];
-                    ok[j] = pok[j];
+                    for (int j = 0; j < 4; ++j) {
+                        dd[j] = pdd[j];
+                        dv[j] = pdv[j];
+                        ok[j] = pok[j];
+                    }
+                } else {
+                    item_ops(item, dd, dv, ok);
                 }
             } else {
                 item_ops(item, dd, dv, ok);
@@ -541,42 +554,58 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
 #pragma unroll
             for (int j = 0; j < 4; ++j) dd[j] = ok[j] ? bn2_dd<ACT>(cst2, 4 * cq, dd[j], dv[j], has_se, g4, dp4) : zero4();
 #pragma unroll
-            for (int ky = 0; ky < K; ++ky) {
-                const float* rowp = in_tile + ((oh * S + ky) * IW + ow0 * S) * CC + 4 * cq;
+            for (int r = 0; r < KR; ++r) {
+                const float* rowp = in_tile + ((oh * S + KY0 + r) * IW + ow0 * S) * CC + 4 * cq;
                 f32x4 win[WIN];
 #pragma unroll
                 for (int u = 0; u < WIN; ++u) win[u] = ld4(rowp + u * CC);
 #pragma unroll
                 for (int kx = 0; kx < K; ++kx)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) wacc[ky * K + kx] += dd[j] * win[j * S + kx];
+                    for (int j = 0; j < 4; ++j) wacc[r * K + kx] += dd[j] * win[j * S + kx];
             }
         }
     }
     // reduce over the threads sharing a channel quad: first inside the wave, then across the 4 waves
     for (int o = CQ; o < 64; o <<= 1) {
 #pragma unroll
-        for (int u = 0; u < K * K; ++u) {
+        for (int u = 0; u < KR * K; ++u) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) wacc[u][q] += __shfl_xor(wacc[u][q], o, 64);
         }
     }
     __syncthreads();
-    float* wred = in_tile;   // [4 waves][K*K][CC]
+    float* wred = in_tile;   // [4 waves][KR*K][CC]
     const int lane = tid & 63, wv = tid >> 6;
     if (lane < CQ) {
 #pragma unroll
-        for (int u = 0; u < K * K; ++u) st4(wred + (wv * K * K + u) * CC + 4 * lane, wacc[u]);
+        for (int u = 0; u < KR * K; ++u) st4(wred + (wv * KR * K + u) * CC + 4 * lane, wacc[u]);
     }
     __syncthreads();
-    for (int idx = tid; idx < K * K * CC; idx += 256) {
+    for (int idx = tid; idx < KR * K * CC; idx += 256) {
         const int cl = idx % CC, u = idx / CC;
         if (c0 + cl < mc) {
             float s = 0.f;
 #pragma unroll
-            for (int ww = 0; ww < 4; ++ww) s += wred[(ww * K * K + u) * CC + cl];
-            gw[(size_t)(c0 + cl) * (K * K) + u] = s;
+            for (int ww = 0; ww < 4; ++ww) s += wred[(ww * KR * K + u) * CC + cl];
+            gw[(size_t)(c0 + cl) * (K * K) + KY0 * K + u] = s;
         }
+    }
+}
+template <int K, int S, int ACT, int KR = K>
+__global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const float* __restrict__ dZ,
+                                                     const float* __restrict__ gate, const float* __restrict__ dpooled,
+                                                     const float* __restrict__ D, const double* __restrict__ stats2,
+                                                     const double* __restrict__ red2, const float* __restrict__ E,
+                                                     const double* __restrict__ stats1, float* __restrict__ part,
+                                                     size_t out_size, DwGeom gm) {
+    static_assert(KR == K || (KR < K && 2 * KR >= K), "one part, or two over blockIdx.z");
+    if constexpr (KR == K) {
+        dw_wgrad_rows<K, S, ACT, 0, K>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
+    } else if (blockIdx.z == 0) {
+        dw_wgrad_rows<K, S, ACT, 0, KR>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
+    } else {
+        dw_wgrad_rows<K, S, ACT, KR, K - KR>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
     }
 }
 
@@ -607,6 +636,19 @@ static size_t dw_wout_size(const TfnasCellDesc& d) {
     for (int g = 0; g < d.G; ++g) n += (size_t)d.g[g].mc * d.g[g].k * d.g[g].k;
     return n;
 }
+
+// a group with a kernel size other than 3 / 5 (that is 7: tfnas_cell_plan).  The register-window and the ring kernels hold K x K
+// taps or accumulators in registers and are built for 3 and 5 only: such a cell takes the tile kernels in every pass, whatever
+// TFNAS_ROUTE_DW_* asks, never fuses the weight gradient into the backward-data pass, and always has E (efree_supported).
+static bool dw_has_k7(const TfnasCellDesc& d) {
+    for (int g = 0; g < d.G; ++g)
+        if (d.g[g].k != 3 && d.g[g].k != 5) return true;
+    return false;
+}
+// the weight-gradient partial row (with 7 x 7 groups up to mc x 49 floats each) must fit the partials region at least once:
+// otherwise the descriptor is refused (tfnas_cell_plan, tfnas_cell_ws, launch_dw_wgrad).  Eight groups of 1536 channels at
+// 7 x 7 -- the elasticity bound -- are 602 112 floats: 6 rows.
+bool dw_wgrad_row_fits(const TfnasCellDesc& d) { return dw_wout_size(d) <= TFNAS_PART_FLOATS; }
 
 // every group has kernel size 3 (or 5 where k5 is set)
 static bool dw_groups_k(const TfnasCellDesc& d, bool k5) {
@@ -649,12 +691,12 @@ static int dw_grid_x(const DwGeom& gm, int chunks, int target_blocks) {
     return gx < 1 ? 1 : gx;
 }
 
-// Tiles of Th x Tw (outputs for fwd_like, inputs otherwise).  Both kernel-size launches of one pass share grid.x so that they
-// fill the same rows of the partials matrix.
+// Tiles of Th x Tw (outputs for fwd_like, inputs otherwise).  The kernel-size launches (3, 5, 7) of one pass share grid.x so that
+// they fill the same rows of the partials matrix.
 static void dw_tile_plan(const TfnasCellDesc& d, int Th, int Tw, bool fwd_like, int target_blocks, size_t row_floats,
                          bool force32, DwPlan& p) {
     int gx = 1 << 30;
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < DW_NK; ++i) {
         pick_tile(d.N, Th, Tw, 3 + 2 * i, d.stride, fwd_like, p.tile[i], force32);
         p.chunks[i] = dw_chunks(d, 3 + 2 * i, p.tile[i].CC);
         if (!p.chunks[i]) continue;
@@ -672,6 +714,7 @@ static void dw_tile_plan(const TfnasCellDesc& d, int Th, int Tw, bool fwd_like, 
 // ---------------------------------------------------------------------------------------------------- ring kernels
 // geometry of the ring kernels for d.H x d.W images (stride 1): false if unsupported
 static bool pick_slide(const TfnasCellDesc& d, int K, DwSlide& gm) {
+    if (K != 3 && K != 5) return false;   // (dw_has_k7)
     const int ws_min = 14;                // (7-wide images: only the weight gradient gained, and the register-window kernel has it)
     if (d.stride != 1 || d.W > 56 || d.W < ws_min) return false;
     if ((size_t)d.N * d.H * d.W * d.M >= ((size_t)1 << 30)) return false;     // 32-bit element offsets
@@ -696,7 +739,7 @@ static bool pick_slide(const TfnasCellDesc& d, int K, DwSlide& gm) {
 
 // the ring kernels for both kernel sizes, one image lane (= partial row) count: false if the route or a geometry rules them out
 static bool dws_plan(const TfnasCellDesc& d, size_t row_floats, DwPlan& p) {
-    if (route_dw(d) == 3) return false;
+    if (route_dw(d) == 3 || dw_has_k7(d)) return false;
     int gx = d.N;
     for (int i = 0; i < 2; ++i) {
         if (!pick_slide(d, 3 + 2 * i, p.ring[i])) return false;
@@ -755,6 +798,7 @@ static int dwd_jw(const TfnasCellDesc& d) {
 static bool dwd_plan(const TfnasCellDesc& d, size_t row_floats, int jw, int kind, DwPlan& p) {
     constexpr int lpp = 16;                                  // lanes per pixel of the k_dwd_* kernels (2 channels each)
     if (d.stride != 1 && d.stride != 2) return false;
+    if (dw_has_k7(d)) return false;
     if ((size_t)d.N * d.H * d.W * d.M >= ((size_t)1 << 30)) return false;                 // 32-bit element offsets
     for (int g = 0; g < d.G; ++g)
         if (d.g[g].mc & 1) return false;
@@ -863,11 +907,12 @@ static DwPlan dw_plan_wgrad(const TfnasCellDesc& d) {
 }
 
 // ---------------------------------------------------------------------------------------------------- launchers
-// Template arguments of a launch from its runtime kernel size (3 | 5), stride (1 | 2), activation (ReLU -> 0, swish -> 1)
-// and variant (one of Vs): calls f(K, S, ACT, V) with std::integral_constant arguments.  False if the variant is not one of Vs.
-// (Every combination is instantiated: a kernel without a stride or variant parameter ignores that argument.)
-template <int... Vs, class F>
-static bool dw_dispatch(int k, int stride, int act, int v, F&& f) {
+// Template arguments of a launch from its runtime kernel size (3 | 5, and 7 where K7), stride (1 | 2), activation (ReLU -> 0,
+// swish -> 1) and variant (one of Vs): calls f(K, S, ACT, V) with std::integral_constant arguments.  False if the kernel size or
+// the variant is not among them.  (Every combination is instantiated: a kernel without a stride or variant parameter ignores that
+// argument.)  dw_dispatch: the register-window and ring launches (3 | 5); dw_tile_dispatch: the tile launches (3 | 5 | 7).
+template <bool K7, int... Vs, class F>
+static bool dw_dispatch_k(int k, int stride, int act, int v, F&& f) {
     bool hit = false;
     auto with_v = [&](auto K, auto S, auto A) {
         ((v == Vs ? (f(K, S, A, std::integral_constant<int, Vs>{}), hit = true) : false) || ...);
@@ -881,8 +926,19 @@ static bool dw_dispatch(int k, int stride, int act, int v, F&& f) {
         else with_a(K, std::integral_constant<int, 2>{});
     };
     if (k == 3) with_s(std::integral_constant<int, 3>{});
-    else with_s(std::integral_constant<int, 5>{});
+    else if (k == 5) with_s(std::integral_constant<int, 5>{});
+    else if constexpr (K7) {
+        if (k == 7) with_s(std::integral_constant<int, 7>{});
+    }
     return hit;
+}
+template <int... Vs, class F>
+static bool dw_dispatch(int k, int stride, int act, int v, F&& f) {
+    return dw_dispatch_k<false, Vs...>(k, stride, act, v, f);
+}
+template <int... Vs, class F>
+static bool dw_tile_dispatch(int k, int stride, int act, int v, F&& f) {
+    return dw_dispatch_k<true, Vs...>(k, stride, act, v, f);
 }
 // variant of the launches with the weight gradient fused into the backward-data pass (k_dwd_bwd<.., WG>, k_dws_bwd<.., WGR>)
 constexpr int DW_WG = -1;
@@ -903,13 +959,14 @@ static int dw_reduce_wgrad(const TfnasCellDesc& d, const float* wpart, int rows,
 
 int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const double* stats1, float* D,
                   double* stats2, float* part, hipStream_t s) {
-    if (!E && !efree_ic_ok(d.ic)) return TFNAS_EINVAL;
+    if (!E && (!efree_ic_ok(d.ic) || dw_has_k7(d))) return TFNAS_EINVAL;
     const DwPlan p = dw_plan_fwd(d, E == nullptr, x != nullptr);
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < DW_NK; ++i) {
         if (!p.chunks[i]) continue;
         const int kk = 3 + 2 * i;
         ProfScope _prof(TK_DW_FWD, s, d.G > 2);
         bool ok = false;
+        if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_has_k7)
         if (p.fam == DW_DIRECT) {
             const DwDirect gm = p.direct[i];
             ok = dw_dispatch<2, 4>(kk, d.stride, d.act, p.jw, [&](auto K, auto S, auto A, auto JW) {
@@ -927,9 +984,10 @@ int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const 
             const int tile = gm.L0 * gm.L1 * gm.CC > 2048 ? gm.L0 * gm.L1 * gm.CC : 2048;
             const size_t shm = (size_t)(tile + kk * kk * gm.CC + 2 * gm.CC) * sizeof(float);
             if (shm > 64 * 1024) return TFNAS_ERANGE;
-            ok = dw_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
-                hipLaunchKernelGGL((k_dw_fwd<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, E, x, stats1, D,
-                                   part, gm);
+            ok = dw_tile_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
+                if constexpr (K != 7 || KQ == 0)              // (no E-free 7 x 7 kernels: refused above)
+                    hipLaunchKernelGGL((k_dw_fwd<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, E, x, stats1, D,
+                                       part, gm);
             });
         }
         if (!ok) return TFNAS_EINVAL;
@@ -940,14 +998,15 @@ int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const 
 int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
                        const float* D, const double* stats2, const double* red2, const float* E, const float* x,
                        const double* stats1, float* dEh, double* red1, float* part, hipStream_t s, float* cb1) {
-    if (!E && !efree_ic_ok(d.ic)) return TFNAS_EINVAL;
+    if (!E && (!efree_ic_ok(d.ic) || dw_has_k7(d))) return TFNAS_EINVAL;
     const size_t wout = dw_wout_size(d);
     float* wpart = part + (((size_t)p.rows * 2 * d.M + 63) & ~(size_t)63);    // (fuse_wgrad: behind the statistics partials)
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < DW_NK; ++i) {
         if (!p.chunks[i]) continue;
         const int kk = 3 + 2 * i;
         ProfScope _prof(TK_DW_BWD_DATA, s, d.G > 2);
         bool ok = false;
+        if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_has_k7)
         if (p.fam == DW_DIRECT) {
             const DwDirect gm = p.direct[i];
             ok = dw_dispatch<2, 4, DW_WG>(kk, d.stride, d.act, p.fuse_wgrad ? DW_WG : p.jw, [&](auto K, auto S, auto A, auto V) {
@@ -980,9 +1039,10 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
             const size_t shm = (size_t)(tile + kk * kk * gm.CC + 4 * gm.CC + 2 * gm.CC + (p.kq ? gm.T0 * gm.T1 * gm.CC : 0)) *
                                sizeof(float);
             if (shm > 64 * 1024) return TFNAS_ERANGE;
-            ok = dw_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
-                hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate,
-                                   dpooled, D, stats2, red2, E, x, stats1, dEh, part, gm);
+            ok = dw_tile_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
+                if constexpr (K != 7 || KQ == 0)
+                    hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate,
+                                       dpooled, D, stats2, red2, E, x, stats1, dEh, part, gm);
             });
         }
         if (!ok) return TFNAS_EINVAL;
@@ -999,12 +1059,14 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
 int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
                     const double* stats2, const double* red2, const float* E, const double* stats1, float* part,
                     hipStream_t s) {
+    if (!dw_wgrad_row_fits(d)) return TFNAS_ERANGE;
     const DwPlan p = dw_plan_wgrad(d);
     const size_t wout = dw_wout_size(d);
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < DW_NK; ++i) {
         if (!p.chunks[i]) continue;
         const int kk = 3 + 2 * i;
         ProfScope _prof(TK_DW_WGRAD, s);
+        if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_has_k7)
         if (p.fam == DW_DIRECT) {
             const DwDirect gm = p.direct[i];
             dw_dispatch<2, 4>(kk, d.stride, d.act, p.jw, [&](auto K, auto S, auto A, auto JW) {
@@ -1022,12 +1084,15 @@ int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, 
             });
         } else {
             const DwGeom gm = p.tile[i];
+            const int kr = kk == 7 ? 4 : kk;       // tap rows per workgroup (k_dw_wgrad: KR), parts over blockIdx.z
             int tile = gm.L0 * gm.L1 * gm.CC;
-            if (tile < 4 * kk * kk * gm.CC) tile = 4 * kk * kk * gm.CC;
+            if (tile < 4 * kr * kk * gm.CC) tile = 4 * kr * kk * gm.CC;
             const size_t shm = (size_t)(tile + 4 * gm.CC + 2 * gm.CC) * sizeof(float);
-            dw_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
-                hipLaunchKernelGGL((k_dw_wgrad<K, S, A>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate, dpooled, D,
-                                   stats2, red2, E, stats1, part, wout, gm);
+            if (shm > 64 * 1024) return TFNAS_ERANGE;
+            dw_tile_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
+                constexpr int KR = K == 7 ? 4 : (int)K;
+                hipLaunchKernelGGL((k_dw_wgrad<K, S, A, KR>), dim3(p.rows, p.chunks[i], (K + KR - 1) / KR), dim3(256), shm, s, d,
+                                   dZ, gate, dpooled, D, stats2, red2, E, stats1, part, wout, gm);
             });
         }
     }

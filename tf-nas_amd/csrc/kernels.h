@@ -93,8 +93,9 @@ int launch_expand_dgrad(const TfnasCellDesc& d, const float* dEh, const float* x
 int launch_expand_wgrad(const TfnasCellDesc& d, const float* dEh, const float* E, const float* cb1,
                         const float* x, float* part, hipStream_t s);
 
-// dwconv_kernels.hip: the depthwise k x k convolution (k = 3 | 5) in three kernel families, each with the geometry struct its
-// kernels take by value.  Register-window kernels (dw_direct.inc):
+// dwconv_kernels.hip: the depthwise k x k convolution in three kernel families, each with the geometry struct its kernels take by
+// value: k = 3 | 5 in all of them, k = 7 in the LDS tile kernels only (a cell with a 7 x 7 group is planned onto those in every
+// pass).  Register-window kernels (dw_direct.inc):
 struct DwDirect {
     int chunks;      // 32-channel chunks of the groups with this kernel size
     int ncg;         // column groups per image: ceil(Wo / (4 * JW))
@@ -119,16 +120,17 @@ struct DwGeom {
     int L0, L1;        // LDS tile extent (rows, cols)
 };
 // What one depthwise pass launches, chosen once by the pass's planner from the descriptor (route bits included), whether E is
-// present and whether x is given; the launcher carries it out: the k = 3 launch, the k = 5 launch, then the reductions of
-// the `rows` partial rows.
+// present and whether x is given; the launcher carries it out: the k = 3 launch, the k = 5 launch, the k = 7 launch (DW_TILE
+// only), then the reductions of the `rows` partial rows.
 enum DwFamily { DW_DIRECT, DW_RING, DW_TILE };
+constexpr int DW_NK = 3;  // kernel sizes 3 + 2 * i of a pass
 struct DwPlan {
     DwFamily fam;
     int rows;             // partial rows of the pass
-    int chunks[2];        // channel chunks of the k = 3 / k = 5 launch (0: not launched)
+    int chunks[DW_NK];    // channel chunks of the k = 3 / k = 5 / k = 7 launch (0: not launched)
     DwDirect direct[2];   // geometry of the k = 3 / k = 5 launch: the planned family's member
     DwSlide ring[2];
-    DwGeom tile[2];
+    DwGeom tile[DW_NK];
     int jw;               // DW_DIRECT: output columns per lane (JW)
     bool pipe;            // DW_RING: the register-prefetch variant (PIPE)
     int kq;               // E-free: ic / 4 of the expand recomputed from x (KQ); 0: E is read
@@ -153,6 +155,7 @@ int launch_fx_fwd(const TfnasCellDesc& d, const float* x, const double* stats1, 
 int launch_fx_bwd(const TfnasCellDesc& d, const float* x, const float* Eh, const double* stats1, const double* stats2,
                   const double* red2, const float* dZ, const float* D, const float* gate, const float* dpooled, float* scratch,
                   size_t scratch_floats, double* red1, float* cb1, float* part, int* nsl, hipStream_t s);
+bool dw_wgrad_row_fits(const TfnasCellDesc& d);     // the depthwise weight-gradient partial row fits the partials region
 DwPlan dw_plan_bwd_data(const TfnasCellDesc& d, bool efree, bool has_x);
 // p = dw_plan_bwd_data(d, E == nullptr, x != nullptr); cb1: also fill the BN1 table
 int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,

@@ -134,6 +134,8 @@ class HipModes:
         d.gemm_mode = 0 if self.gemm is None else (_lib.GEMM_EXPLICIT | _lib.GEMM_MODES[self.gemm]
                                                    | (_lib.GEMM_EVERYWHERE if self.everywhere else 0))
         d.flags = _lib.CELL_LAZY_JOIN if self.lazy_join else 0
+        if any(d.g[g].k == 7 for g in range(min(d.G, _lib.MAX_GROUPS))):
+            d.flags |= _lib.CELL_K7                    # (the library takes 7 x 7 groups only from callers that say they know them)
         d.route = ENV_ROUTE if self.route is None else int(self.route)
         if self.sync is None:
             d.sync_fn, d.sync_user, d.sync_world = None, None, 0

@@ -55,6 +55,7 @@ class _BlockTimer:
         d.mode, d.act, d.G, d.need_wgrad, d.eps = _lib.MODE_CELL, _lib.ACT[act], 1, 0, BN_EPS
         d.has_res = int(ic == oc and stride == 1)
         d.g[0].mc, d.g[0].k, d.g[0].se = mc, k, se
+        d.flags = _lib.CELL_K7 if k == 7 else 0
         _lib.check(lib.tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
         ws = _lib.TfnasCellWs()
         _lib.check(lib.tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
@@ -109,6 +110,9 @@ class _BlockTimer:
             e1.synchronize()
             times.append(e0.elapsed_time(e1) / iters)
         return float(np.median(times))
+
+
+Measurer = _BlockTimer          # public name: Measurer(device).measure(ic, mc, se, oc, k, stride, act, size, ...), k in {3, 5, 7}
 
 
 def lut_keys():

@@ -1,0 +1,63 @@
+#!/usr/bin/env python3
+"""Depthwise launches of a sampled candidate by kernel size (GPU box): forward, data gradient and weight gradient of one MBConv
+candidate with k = 5 (default route, and tile kernels only) and k = 7 (tile kernels) at two benchmark geometries, HIP-event time per
+launch from the library's tfnas_prof_* timers.  Weight gradients run on the caller's stream (route bit) so that no launch overlaps
+another; the variants alternate and the median over the rounds is printed (DESIGN.md section 4, 7 x 7 table).
+   python tools/dw_k_compare.py [batch] [rounds]"""
+import ctypes as C
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'tf-nas_amd'))
+import torch  # noqa: E402
+from tfnas_amd import _lib, functions as F  # noqa: E402
+from tfnas_amd.layers import MBInvertedResBlock  # noqa: E402
+
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
+ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 7
+GEOMS = [('56 x 56 x 144', 24, 144, 24, 1, 'relu', 56), ('14 x 14 x 672', 112, 672, 112, 1, 'swish', 14)]
+VARIANTS = [('k5 default route', 5, {}), ('k5 tile kernels', 5, dict(dw='tiled', dwwg=False)), ('k7 tile kernels', 7, {})]
+FAMS = ('k_dw_fwd', 'k_dw_bwd_data', 'k_dw_wgrad')
+
+lib = _lib.lib()
+ids = {lib.tfnas_prof_name(i).decode(): i for i in range(lib.tfnas_prof_count())}
+dev = torch.device('cuda', 0)
+
+
+def collect(fam):
+    n, ms = C.c_uint64(), C.c_double()
+    _lib.check(lib.tfnas_prof_collect(ids[fam], C.byref(n), C.byref(ms)), 'tfnas_prof_collect')
+    return ms.value / max(1, n.value)
+
+
+for name, ic, mc, oc, s, act, hw in GEOMS:
+    torch.manual_seed(1)
+    x = torch.randn(B, ic, hw, hw, device=dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    blocks = []
+    for label, k, route in VARIANTS:
+        blk = MBInvertedResBlock(ic, mc, 0, oc, k, s, affine=False, act_func=act).to(dev)
+        F.adopt_modes(blk, F.HipModes(route=F.route_bits(wgrad_stream=False, **route)))
+        blocks.append(blk)
+
+    def step(blk):
+        out = blk(x)
+        out.backward(out)
+        torch.cuda.synchronize()
+        blk.zero_grad()
+        x.grad = None
+
+    for blk in blocks:            # warm-up
+        step(blk)
+    times = [{f: [] for f in FAMS} for _ in blocks]
+    for _ in range(ROUNDS):
+        for i, blk in enumerate(blocks):
+            lib.tfnas_prof_enable(sum(1 << ids[f] for f in FAMS))
+            step(blk)
+            lib.tfnas_prof_enable(0)
+            for f in FAMS:
+                times[i][f].append(collect(f))
+    print('%s, B = %d, median of %d alternating rounds (ms per launch)' % (name, B, ROUNDS))
+    for (label, k, route), t in zip(VARIANTS, times):
+        print('  %-18s' % label + '  '.join('%s %.3f' % (f, statistics.median(t[f])) for f in FAMS))
