@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-/* 4, additive: tfnas_cls_wgrad_ex (tfnas_cls_wgrad + the search epoch's running loss / top-1 / top-5 / invalid-target meter).
+/* 4, additive: TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH in a descriptor whose flags carry TFNAS_CELL_ACTS (cells, affine blocks, head;
+ * materialised route and LDS tile depthwise kernels only).
+ * 4, additive: tfnas_cls_wgrad_ex (tfnas_cls_wgrad + the search epoch's running loss / top-1 / top-5 / invalid-target meter).
  * 4, additive: tfnas_cls_ce_ex / tfnas_cls_reduce (the derived network's retrain tail: label smoothing, rank, forward-only form,
  * device-side upstream gradient, running meter).
  * 4, additive: TFNAS_CELL_ACCUM_WGRAD (weight gradients added to their destinations, per launch) and tfnas_path_set_wgrad_accum.
@@ -65,6 +67,16 @@ extern "C" {
 
 #define TFNAS_ACT_RELU 0
 #define TFNAS_ACT_SWISH 1
+/* The reference's other two (models/layers.py:38-47), accepted only from a descriptor whose flags carry TFNAS_CELL_ACTS, in
+ * TFNAS_MODE_CELL (tfnas_mixedop_*, tfnas_mbconv_*, the path level) and TFNAS_MODE_HEAD; TFNAS_MODE_STEM refuses them.
+ * With z the BatchNorm output, at all three sites (after BN1, after BN2, the SE hidden layer; the SE gate stays a sigmoid):
+ *   RELU6   min(max(z, 0), 6);           derivative 1 where 0 < z < 6 (strict), else 0
+ *   HSWISH  z * min(max(z + 3, 0), 6) / 6; derivative (2 z + 3) / 6 where -3 < z < 3 (strict), 1 where z >= 3, 0 where z <= -3
+ * A cell with one of them always materialises E (tfnas_efree_supported and tfnas_fx_supported return 0) and runs its depthwise
+ * passes on the LDS tile kernels whatever TfnasCellDesc.route asks, the depthwise weight gradient in its own launch: the ring,
+ * register-window, E-free and fused per-image kernels exist for ReLU and Swish only. */
+#define TFNAS_ACT_RELU6 2
+#define TFNAS_ACT_HSWISH 3
 
 #define TFNAS_EINVAL (-1)   /* bad geometry / alignment (ic, oc must be multiples of 4) */
 #define TFNAS_ENULL (-2)    /* required pointer is NULL */
@@ -119,7 +131,8 @@ typedef struct TfnasCellDesc {
     int32_t flags;            /* TFNAS_CELL_LAZY_JOIN: tfnas_mbconv_bwd returns without joining its weight-gradient side
                                  stream (see tfnas_set_lazy_join, which sets the default for descriptors without the bit);
                                  TFNAS_CELL_ACCUM_WGRAD: the backward adds its weight gradients to their destinations;
-                                 TFNAS_CELL_K7: groups may have depthwise kernel size 7                                 [in]
+                                 TFNAS_CELL_K7: groups may have depthwise kernel size 7;
+                                 TFNAS_CELL_ACTS: act may be TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH                         [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -166,6 +179,11 @@ typedef struct TfnasCellDesc {
  * by tfnas_cell_plan and again by every entry point (the descriptor's modes may change between the two).  The Python mirror sets it
  * for every descriptor that holds a 7 x 7 group (functions.HipModes.apply). */
 #define TFNAS_CELL_K7 0x80
+/* TfnasCellDesc.flags: the caller knows the activations TFNAS_ACT_RELU6 and TFNAS_ACT_HSWISH.  Additive in the same way: without
+ * the bit act = 2, 3 stay TFNAS_EINVAL; with it a ReLU / Swish descriptor plans, routes and launches the same, and act may also be
+ * 2 or 3 (any other value is TFNAS_EINVAL either way).  Checked by tfnas_cell_plan and again by every entry point.  The Python
+ * mirror sets it for every descriptor with one of the two (functions.HipModes.apply). */
+#define TFNAS_CELL_ACTS 0x100
 /* TfnasCellDesc.route (ABI 4; rounds 2-5 read these from TFNAS_* environment variables latched once per process) */
 #define TFNAS_ROUTE_FX_OFF 0x1        /* frozen-weight launches of the 14 x 14 / 7 x 7 cells through the materialised route instead
                                          of the fused per-image kernels (csrc/fx_kernels.hip)                                   */
@@ -177,7 +195,8 @@ typedef struct TfnasCellDesc {
 #define TFNAS_ROUTE_XG_OFF 0x10       /* expand weight gradient never in Gram form                                              */
 #define TFNAS_ROUTE_XG_ALL 0x20       /* ... in Gram form wherever the shape allows (default: where E >= 100 MB)                */
 #define TFNAS_ROUTE_DW_SHIFT 6        /* 2 bits: 0 per-launch policy, 1 register-window kernels wherever the geometry allows,   */
-#define TFNAS_ROUTE_DW_MASK 0xc0      /*         2 LDS ring / tile kernels only, 3 tile kernels only (7 x 7 cells: always 3)    */
+#define TFNAS_ROUTE_DW_MASK 0xc0      /*         2 LDS ring / tile kernels only, 3 tile kernels only (7 x 7 cells and
+                                         TFNAS_ACT_RELU6 / _HSWISH cells: always 3)                                             */
 #define TFNAS_ROUTE_SE_SHIFT 8        /* 2 bits: 0 wave-level MFMA kernels for the excite FCs, 1 one fused per-image kernel,    */
 #define TFNAS_ROUTE_SE_MASK 0x300     /*         2 LDS-tiled GEMMs                                                              */
 #define TFNAS_ROUTE_WGRAD_INLINE 0x400 /* weight-gradient kernels on the caller's stream (no side stream)                       */
@@ -249,7 +268,7 @@ int tfnas_cell_ws(const TfnasCellDesc *d, TfnasCellWs *ws);
 /* 1 when the cell can run without the expanded tensor E ("E-free" mode: pass E = NULL to tfnas_mixedop_fwd AND to the
  * matching tfnas_mixedop_bwd; the depthwise kernels then recompute act(BN1(x W_expand^T)) from the narrow cell input,
  * and BN1's batch statistics come from the ic x ic Gram matrix of x).  Currently: TFNAS_MODE_CELL, need_wgrad = 0
- * (the alpha-step: frozen weights), ic in {16, 24, 40}, kernel sizes 3 / 5.  Same arithmetic contract as the E path (fp32, <= 1e-3). */
+ * (the alpha-step: frozen weights), ic in {16, 24, 40}, kernel sizes 3 / 5, ReLU / Swish.  Same arithmetic contract as the E path (fp32, <= 1e-3). */
 int tfnas_efree_supported(const TfnasCellDesc *d);
 /* What a forward of the (planned) descriptor does with the saved buffers -- a pure function of the descriptor (geometry,
  * need_wgrad, route, sync hook): TFNAS_ROUTE_TAKEN_VALID | TFNAS_ROUTE_TAKEN_*.  Callers that plan the backward with a descriptor
@@ -260,7 +279,7 @@ int tfnas_cell_route(const TfnasCellDesc *d);
  * most 14 x 14 pixels, 64 <= ic <= 192 (a multiple of 16), frozen weights -- the supernet's cells at 14 x 14 and 7 x 7.  One kernel
  * per direction runs expand 1x1 + BN1 + activation + depthwise k x k (models/layers.py:542-552) for a group of whole images x a
  * slice of mid channels; neither E nor its gradient is ever written (the dEh buffer of tfnas_mixedop_bwd is used as scratch for
- * partial sums of dx).  Implies tfnas_efree_supported (so: 0 for a cell with a 7 x 7 group). */
+ * partial sums of dx).  Implies tfnas_efree_supported (so: 0 for a cell with a 7 x 7 group or with TFNAS_ACT_RELU6 / _HSWISH). */
 int tfnas_fx_supported(const TfnasCellDesc *d);
 
 /* MixedOP forward.

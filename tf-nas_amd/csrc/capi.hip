@@ -149,13 +149,22 @@ extern "C" uint64_t tfnas_sizeof(int which) {
     }
 }
 
+// the activation of a descriptor: ReLU / Swish; ReLU6 / hard-swish from a caller that set TFNAS_CELL_ACTS, never in a stem
+static int check_act(const TfnasCellDesc* d) {
+    if (d->act == TFNAS_ACT_RELU || d->act == TFNAS_ACT_SWISH) return 0;
+    if (d->act != TFNAS_ACT_RELU6 && d->act != TFNAS_ACT_HSWISH) return TFNAS_EINVAL;
+    if (!(d->flags & TFNAS_CELL_ACTS) || d->mode == TFNAS_MODE_STEM) return TFNAS_EINVAL;
+    return 0;
+}
+
 // the per-launch modes of a descriptor (callers may change them between tfnas_cell_plan and a launch: every entry point re-checks)
 static int check_modes(const TfnasCellDesc* d) {
+    TRY(check_act(d));
     if (d->gemm_mode != 0) {
         const int gm = d->gemm_mode & ~(TFNAS_GEMM_EXPLICIT | TFNAS_GEMM_EVERYWHERE);
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
-    if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7)) return TFNAS_EINVAL;
+    if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS)) return TFNAS_EINVAL;
     if (!(d->flags & TFNAS_CELL_K7)) {            // kernel size 7 is opt-in: without the bit it is refused as it always was
         for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g)
             if (d->g[g].k == 7) return TFNAS_EINVAL;
@@ -185,7 +194,7 @@ extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
     if (d->N < 1 || d->H < 1 || d->W < 1 || d->oc < 4 || (d->oc & 3)) return TFNAS_EINVAL;
     if (d->oc > 1024) return TFNAS_EINVAL;
     if (d->stride != 1 && d->stride != 2) return TFNAS_EINVAL;
-    if (d->act != TFNAS_ACT_RELU && d->act != TFNAS_ACT_SWISH) return TFNAS_EINVAL;
+    TRY(check_act(d));                          // (ReLU6 / hard-swish: with TFNAS_CELL_ACTS only)
     if (d->has_res && (d->ic != d->oc || d->stride != 1)) return TFNAS_EINVAL;
     TRY(check_modes(d));
     // conv output size with pad = k/2 (same for k = 3, 5 and 7)
@@ -600,6 +609,7 @@ extern "C" int tfnas_head_affine_fwd(const TfnasCellDesc* dp, const TfnasBnAffin
                                      float* part, float* pooled, void* stream) {
     if (!dp || !bn || !x || !E || !stats || !part || !pooled) return TFNAS_ENULL;
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    TRY(check_act(dp));
     return head_fwd_impl(*dp, bn, x, E, stats, part, pooled, S(stream));
 }
 
@@ -608,6 +618,7 @@ extern "C" int tfnas_head_affine_bwd(const TfnasCellDesc* dp, const TfnasBnAffin
                                      float* part, float* dx, float* dxp, void* stream) {
     if (!dp || !bn || !x || !E || !stats || !dpooled || !dEh || !cb1 || !red || !part || !dx) return TFNAS_ENULL;
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    TRY(check_act(dp));
     if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
     return head_bwd_impl(*dp, bn, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
@@ -616,6 +627,7 @@ extern "C" int tfnas_head_fwd(const TfnasCellDesc* dp, const float* x, float* E,
                               float* pooled, void* stream) {
     if (!dp || !x || !E || !stats || !part || !pooled) return TFNAS_ENULL;
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    TRY(check_act(dp));
     return head_fwd_impl(*dp, nullptr, x, E, stats, part, pooled, S(stream));
 }
 
@@ -624,6 +636,7 @@ extern "C" int tfnas_head_bwd(const TfnasCellDesc* dp, const float* x, const flo
                               float* dxp, void* stream) {
     if (!dp || !x || !E || !stats || !dpooled || !dEh || !cb1 || !red || !part || !dx) return TFNAS_ENULL;
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    TRY(check_act(dp));
     if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
     return head_bwd_impl(*dp, nullptr, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
@@ -633,6 +646,7 @@ extern "C" int tfnas_head_wgrad(const TfnasCellDesc* dp, const float* x, const f
     if (!dp || !x || !E || !dEh || !cb1 || !part) return TFNAS_ENULL;
     const TfnasCellDesc& d = *dp;
     if (d.mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    TRY(check_act(dp));
     if (!d.g[0].g_expand) return TFNAS_ENULL;
     return launch_expand_wgrad(d, dEh, E, cb1, x, part, S(stream));
 }

@@ -640,7 +640,9 @@ static size_t dw_wout_size(const TfnasCellDesc& d) {
 // a group with a kernel size other than 3 / 5 (that is 7: tfnas_cell_plan).  The register-window and the ring kernels hold K x K
 // taps or accumulators in registers and are built for 3 and 5 only: such a cell takes the tile kernels in every pass, whatever
 // TFNAS_ROUTE_DW_* asks, never fuses the weight gradient into the backward-data pass, and always has E (efree_supported).
-static bool dw_has_k7(const TfnasCellDesc& d) {
+// The same holds for a cell with TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH: only the tile kernels are instantiated for them.
+static bool dw_tile_only(const TfnasCellDesc& d) {
+    if (act_tile_only(d.act)) return true;
     for (int g = 0; g < d.G; ++g)
         if (d.g[g].k != 3 && d.g[g].k != 5) return true;
     return false;
@@ -714,7 +716,8 @@ static void dw_tile_plan(const TfnasCellDesc& d, int Th, int Tw, bool fwd_like, 
 // ---------------------------------------------------------------------------------------------------- ring kernels
 // geometry of the ring kernels for d.H x d.W images (stride 1): false if unsupported
 static bool pick_slide(const TfnasCellDesc& d, int K, DwSlide& gm) {
-    if (K != 3 && K != 5) return false;   // (dw_has_k7)
+    if (K != 3 && K != 5) return false;   // (dw_tile_only)
+    if (act_tile_only(d.act)) return false;
     const int ws_min = 14;                // (7-wide images: only the weight gradient gained, and the register-window kernel has it)
     if (d.stride != 1 || d.W > 56 || d.W < ws_min) return false;
     if ((size_t)d.N * d.H * d.W * d.M >= ((size_t)1 << 30)) return false;     // 32-bit element offsets
@@ -739,7 +742,7 @@ static bool pick_slide(const TfnasCellDesc& d, int K, DwSlide& gm) {
 
 // the ring kernels for both kernel sizes, one image lane (= partial row) count: false if the route or a geometry rules them out
 static bool dws_plan(const TfnasCellDesc& d, size_t row_floats, DwPlan& p) {
-    if (route_dw(d) == 3 || dw_has_k7(d)) return false;
+    if (route_dw(d) == 3 || dw_tile_only(d)) return false;
     int gx = d.N;
     for (int i = 0; i < 2; ++i) {
         if (!pick_slide(d, 3 + 2 * i, p.ring[i])) return false;
@@ -798,7 +801,7 @@ static int dwd_jw(const TfnasCellDesc& d) {
 static bool dwd_plan(const TfnasCellDesc& d, size_t row_floats, int jw, int kind, DwPlan& p) {
     constexpr int lpp = 16;                                  // lanes per pixel of the k_dwd_* kernels (2 channels each)
     if (d.stride != 1 && d.stride != 2) return false;
-    if (dw_has_k7(d)) return false;
+    if (dw_tile_only(d)) return false;
     if ((size_t)d.N * d.H * d.W * d.M >= ((size_t)1 << 30)) return false;                 // 32-bit element offsets
     for (int g = 0; g < d.G; ++g)
         if (d.g[g].mc & 1) return false;
@@ -907,19 +910,24 @@ static DwPlan dw_plan_wgrad(const TfnasCellDesc& d) {
 }
 
 // ---------------------------------------------------------------------------------------------------- launchers
-// Template arguments of a launch from its runtime kernel size (3 | 5, and 7 where K7), stride (1 | 2), activation (ReLU -> 0,
-// swish -> 1) and variant (one of Vs): calls f(K, S, ACT, V) with std::integral_constant arguments.  False if the kernel size or
-// the variant is not among them.  (Every combination is instantiated: a kernel without a stride or variant parameter ignores that
-// argument.)  dw_dispatch: the register-window and ring launches (3 | 5); dw_tile_dispatch: the tile launches (3 | 5 | 7).
-template <bool K7, int... Vs, class F>
+// Template arguments of a launch from its runtime kernel size (3 | 5, and 7 where TILE), stride (1 | 2), activation (ReLU | Swish,
+// and ReLU6 | hard-swish where TILE) and variant (one of Vs): calls f(K, S, ACT, V) with std::integral_constant arguments.  False
+// if the kernel size, the activation or the variant is not among them -- the launchers return TFNAS_EINVAL.  (Every combination
+// is instantiated: a kernel without a stride or variant parameter ignores that argument.)  dw_dispatch: the register-window and
+// ring launches (3 | 5, two activations); dw_tile_dispatch: the tile launches (3 | 5 | 7, four activations).
+template <bool TILE, int... Vs, class F>
 static bool dw_dispatch_k(int k, int stride, int act, int v, F&& f) {
     bool hit = false;
     auto with_v = [&](auto K, auto S, auto A) {
         ((v == Vs ? (f(K, S, A, std::integral_constant<int, Vs>{}), hit = true) : false) || ...);
     };
     auto with_a = [&](auto K, auto S) {
-        if (act == TFNAS_ACT_RELU) with_v(K, S, std::integral_constant<int, 0>{});
-        else with_v(K, S, std::integral_constant<int, 1>{});
+        if (act == TFNAS_ACT_RELU) with_v(K, S, std::integral_constant<int, TFNAS_ACT_RELU>{});
+        else if (act == TFNAS_ACT_SWISH) with_v(K, S, std::integral_constant<int, TFNAS_ACT_SWISH>{});
+        else if constexpr (TILE) {
+            if (act == TFNAS_ACT_RELU6) with_v(K, S, std::integral_constant<int, TFNAS_ACT_RELU6>{});
+            else if (act == TFNAS_ACT_HSWISH) with_v(K, S, std::integral_constant<int, TFNAS_ACT_HSWISH>{});
+        }
     };
     auto with_s = [&](auto K) {
         if (stride == 1) with_a(K, std::integral_constant<int, 1>{});
@@ -927,7 +935,7 @@ static bool dw_dispatch_k(int k, int stride, int act, int v, F&& f) {
     };
     if (k == 3) with_s(std::integral_constant<int, 3>{});
     else if (k == 5) with_s(std::integral_constant<int, 5>{});
-    else if constexpr (K7) {
+    else if constexpr (TILE) {
         if (k == 7) with_s(std::integral_constant<int, 7>{});
     }
     return hit;
@@ -959,14 +967,14 @@ static int dw_reduce_wgrad(const TfnasCellDesc& d, const float* wpart, int rows,
 
 int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const double* stats1, float* D,
                   double* stats2, float* part, hipStream_t s) {
-    if (!E && (!efree_ic_ok(d.ic) || dw_has_k7(d))) return TFNAS_EINVAL;
+    if (!E && (!efree_ic_ok(d.ic) || dw_tile_only(d))) return TFNAS_EINVAL;
     const DwPlan p = dw_plan_fwd(d, E == nullptr, x != nullptr);
     for (int i = 0; i < DW_NK; ++i) {
         if (!p.chunks[i]) continue;
         const int kk = 3 + 2 * i;
         ProfScope _prof(TK_DW_FWD, s, d.G > 2);
         bool ok = false;
-        if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_has_k7)
+        if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_tile_only)
         if (p.fam == DW_DIRECT) {
             const DwDirect gm = p.direct[i];
             ok = dw_dispatch<2, 4>(kk, d.stride, d.act, p.jw, [&](auto K, auto S, auto A, auto JW) {
@@ -985,7 +993,7 @@ int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const 
             const size_t shm = (size_t)(tile + kk * kk * gm.CC + 2 * gm.CC) * sizeof(float);
             if (shm > 64 * 1024) return TFNAS_ERANGE;
             ok = dw_tile_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
-                if constexpr (K != 7 || KQ == 0)              // (no E-free 7 x 7 kernels: refused above)
+                if constexpr ((K != 7 && !act_tile_only(A)) || KQ == 0)     // (no E-free 7 x 7 / ReLU6 / hard-swish kernels: refused above)
                     hipLaunchKernelGGL((k_dw_fwd<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, E, x, stats1, D,
                                        part, gm);
             });
@@ -998,7 +1006,7 @@ int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const 
 int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
                        const float* D, const double* stats2, const double* red2, const float* E, const float* x,
                        const double* stats1, float* dEh, double* red1, float* part, hipStream_t s, float* cb1) {
-    if (!E && (!efree_ic_ok(d.ic) || dw_has_k7(d))) return TFNAS_EINVAL;
+    if (!E && (!efree_ic_ok(d.ic) || dw_tile_only(d))) return TFNAS_EINVAL;
     const size_t wout = dw_wout_size(d);
     float* wpart = part + (((size_t)p.rows * 2 * d.M + 63) & ~(size_t)63);    // (fuse_wgrad: behind the statistics partials)
     for (int i = 0; i < DW_NK; ++i) {
@@ -1006,7 +1014,7 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
         const int kk = 3 + 2 * i;
         ProfScope _prof(TK_DW_BWD_DATA, s, d.G > 2);
         bool ok = false;
-        if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_has_k7)
+        if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_tile_only)
         if (p.fam == DW_DIRECT) {
             const DwDirect gm = p.direct[i];
             ok = dw_dispatch<2, 4, DW_WG>(kk, d.stride, d.act, p.fuse_wgrad ? DW_WG : p.jw, [&](auto K, auto S, auto A, auto V) {
@@ -1040,7 +1048,7 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
                                sizeof(float);
             if (shm > 64 * 1024) return TFNAS_ERANGE;
             ok = dw_tile_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
-                if constexpr (K != 7 || KQ == 0)
+                if constexpr ((K != 7 && !act_tile_only(A)) || KQ == 0)
                     hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate,
                                        dpooled, D, stats2, red2, E, x, stats1, dEh, part, gm);
             });
@@ -1066,7 +1074,7 @@ int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, 
         if (!p.chunks[i]) continue;
         const int kk = 3 + 2 * i;
         ProfScope _prof(TK_DW_WGRAD, s);
-        if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_has_k7)
+        if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_tile_only)
         if (p.fam == DW_DIRECT) {
             const DwDirect gm = p.direct[i];
             dw_dispatch<2, 4>(kk, d.stride, d.act, p.jw, [&](auto K, auto S, auto A, auto JW) {

@@ -32,6 +32,7 @@ static int fx_ks(int ic) { return (ic + 31) / 32; }
 
 bool fx_plan(const TfnasCellDesc& d, FxPlan& pl, bool bwd) {
     if (d.mode != TFNAS_MODE_CELL || d.need_wgrad) return false;
+    if (d.act != TFNAS_ACT_RELU && d.act != TFNAS_ACT_SWISH) return false;     // (the kernels are instantiated for these two)
     if (stats_sync_on(d)) return false;                     // (BN1 statistics come from the Gram matrix of x: efree_kernels.hip)
     if (d.ic < 64 || d.ic > 192 || (d.ic & 15)) return false;
     if (d.stride != 1) return false;                       // (stride-2 cells keep the materialised route)
@@ -1415,7 +1416,9 @@ int launch_fx_fwd(const TfnasCellDesc& d, const float* x, const double* stats1, 
     }
 #define FX_FWD_A(KS_, RT_)                                                       \
     {                                                                            \
-        if (d.act == TFNAS_ACT_RELU) FX_FWD(0, KS_, RT_) else FX_FWD(1, KS_, RT_) \
+        if (d.act == TFNAS_ACT_RELU) FX_FWD(TFNAS_ACT_RELU, KS_, RT_)            \
+        else if (d.act == TFNAS_ACT_SWISH) FX_FWD(TFNAS_ACT_SWISH, KS_, RT_)     \
+        else return TFNAS_EINVAL;                                                \
     }
         const int key = pl.KS * 10 + pl.RTF;
         switch (key) {
@@ -1509,7 +1512,9 @@ int launch_fx_bwd(const TfnasCellDesc& d, const float* x, const float* Eh, const
     }
 #define FX_BWD_A(CT_, RT_)                                                       \
     {                                                                            \
-        if (d.act == TFNAS_ACT_RELU) FX_BWD(0, CT_, RT_) else FX_BWD(1, CT_, RT_) \
+        if (d.act == TFNAS_ACT_RELU) FX_BWD(TFNAS_ACT_RELU, CT_, RT_)            \
+        else if (d.act == TFNAS_ACT_SWISH) FX_BWD(TFNAS_ACT_SWISH, CT_, RT_)     \
+        else return TFNAS_EINVAL;                                                \
     }
         const int key = (d.ic / 16) * 10 + (Eh ? pl.RTF : pl.RT);
         switch (key) {

@@ -481,7 +481,7 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_project_dgrad(TfnasCel
                                [&](int i, const float* st) {        // the wave's slab i (16 rows x BN) is still in LDS
                                    if (d.act == TFNAS_ACT_RELU)
                                        fold_slab<NT, TFNAS_ACT_RELU>(st, LDC, Dcol, M, pw0 + 16 * i, Po, bnd, c2f, cokf, has_se, sum);
-                                   else
+                                   else      // Swish: launch_project_dgrad refuses every other activation for this variant
                                        fold_slab<NT, TFNAS_ACT_SWISH>(st, LDC, Dcol, M, pw0 + 16 * i, Po, bnd, c2f, cokf, has_se, sum);
                                });
             // waves -> image slots of the tile, in wave order (emit_tile_rows ended with a barrier: the GEMM LDS is free)
@@ -1147,9 +1147,7 @@ static constexpr int kGtLdsFloats[8] = {0, GT<1>::LDS_FLOATS, GT<2>::LDS_FLOATS,
         case 3: { constexpr int MM = 3; __VA_ARGS__; } break;  \
         default: { constexpr int MM = 6; __VA_ARGS__; } break; \
     }
-#define DISPATCH_ACT(act, ...)                                                        \
-    if ((act) == TFNAS_ACT_RELU) { constexpr int ACT = TFNAS_ACT_RELU; __VA_ARGS__; } \
-    else { constexpr int ACT = TFNAS_ACT_SWISH; __VA_ARGS__; }
+#define DISPATCH_ACT(act, ...) ACT_DISPATCH(act, __VA_ARGS__)       // (kernels.h: four-way, any other value TFNAS_EINVAL)
 
 // Arithmetic of the row-tiled 1x1-convolution GEMMs (gemm_x3.h): 6 = split-bf16 with six products per element pair (fp32-level
 // accuracy on the bf16 matrix pipe; the default), 0 = v_mfma_f32_16x16x4_f32, 3 = split-bf16 keeping the 2^-16 terms,
@@ -1354,6 +1352,7 @@ int launch_project_dgrad(const TfnasCellDesc& d, const float* dout, const float*
                          const double* stats2, float* rec) {
     ProfScope _prof(TK_PROJECT_DGRAD, s);
     if (rec && (!D || !stats2)) return TFNAS_ENULL;
+    if (rec && d.act != TFNAS_ACT_RELU && d.act != TFNAS_ACT_SWISH) return TFNAS_EINVAL;     // (FOLD epilogue: project_fold_ok)
     const GemmPlan p = gemm_plan_project_dgrad(d, rec != nullptr);
     DISPATCH_MM(p.mm, DISPATCH_NT_GROUPS(p.nt, {
         if (p.var == GEMM_FOLD)

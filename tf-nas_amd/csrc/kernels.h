@@ -31,10 +31,17 @@ static inline int route_se(const TfnasCellDesc& d) { return (d.route & TFNAS_ROU
 static inline bool route_side(const TfnasCellDesc& d) { return !(d.route & TFNAS_ROUTE_WGRAD_INLINE); }
 // TFNAS_CELL_ACCUM_WGRAD: every weight-gradient store of the launch adds to its destination (g <- g + v)
 static inline int wgrad_accum(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_ACCUM_WGRAD) ? 1 : 0; }
-// the ReLU / Swish fork of a launcher: the statements run with ACT = the launch's activation as a compile-time constant
-#define ACT_DISPATCH(act, ...)                                                          \
-    if ((act) == TFNAS_ACT_RELU) { constexpr int ACT = TFNAS_ACT_RELU; __VA_ARGS__; }   \
-    else { constexpr int ACT = TFNAS_ACT_SWISH; __VA_ARGS__; }
+// TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH: the kernel families built for ReLU and Swish only (ring, register-window, E-free, fused
+// per-image, the FOLD epilogue of the project dgrad) are never planned for such a cell and refuse it if asked
+static constexpr bool act_tile_only(int act) { return act == TFNAS_ACT_RELU6 || act == TFNAS_ACT_HSWISH; }
+// the activation fork of a launcher (inside a function returning int): the statements run with ACT = the launch's activation as a
+// compile-time constant; any other value is TFNAS_EINVAL
+#define ACT_DISPATCH(act, ...)                                                                        \
+    if ((act) == TFNAS_ACT_RELU) { constexpr int ACT = TFNAS_ACT_RELU; __VA_ARGS__; }                 \
+    else if ((act) == TFNAS_ACT_SWISH) { constexpr int ACT = TFNAS_ACT_SWISH; __VA_ARGS__; }          \
+    else if ((act) == TFNAS_ACT_RELU6) { constexpr int ACT = TFNAS_ACT_RELU6; __VA_ARGS__; }          \
+    else if ((act) == TFNAS_ACT_HSWISH) { constexpr int ACT = TFNAS_ACT_HSWISH; __VA_ARGS__; }        \
+    else return TFNAS_EINVAL;
 
 // gemm_kernels.hip
 int gemm_mode();            // arithmetic of the row-tiled GEMMs (tfnas_hip.h: TFNAS_GEMM_*): the process default ...
@@ -78,6 +85,7 @@ constexpr int FOLD_SLOTS = 4, FOLD_Q = 5;       // records of the FOLD epilogue:
 static inline bool project_fold_ok(const TfnasCellDesc& d, size_t scratch_floats) {
     const int HW = d.Ho * d.Wo;
     const size_t nrt = ((size_t)d.N * HW + 127) / 128;
+    if (act_tile_only(d.act)) return false;          // (the epilogue forks ReLU / Swish; such a cell runs k_bn2_pool)
     return HW >= 43 && nrt * FOLD_SLOTS * FOLD_Q * (size_t)d.M <= scratch_floats;
 }
 int launch_project_wgrad(const TfnasCellDesc& d, const float* dout, const float* Pr, const float* D,
@@ -95,7 +103,8 @@ int launch_expand_wgrad(const TfnasCellDesc& d, const float* dEh, const float* E
 
 // dwconv_kernels.hip: the depthwise k x k convolution in three kernel families, each with the geometry struct its kernels take by
 // value: k = 3 | 5 in all of them, k = 7 in the LDS tile kernels only (a cell with a 7 x 7 group is planned onto those in every
-// pass).  Register-window kernels (dw_direct.inc):
+// pass); ReLU | Swish in all of them, ReLU6 | hard-swish in the tile kernels only (act_tile_only: the same rule).
+// Register-window kernels (dw_direct.inc):
 struct DwDirect {
     int chunks;      // 32-channel chunks of the groups with this kernel size
     int ncg;         // column groups per image: ceil(Wo / (4 * JW))

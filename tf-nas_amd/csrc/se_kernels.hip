@@ -618,13 +618,15 @@ static SePlan se_plan(const TfnasCellDesc& d, size_t scratch_floats) {
 }
 
 template <int MODE>
-static void se_gemm(const TfnasCellDesc& d, const SeArgs& a, int rows, int cols, int ng, hipStream_t s) {
+static int se_gemm(const TfnasCellDesc& d, const SeArgs& a, int rows, int cols, int ng, hipStream_t s) {
     dim3 grid(cdiv(rows, 128) * ((MODE == 0 || MODE == 2) ? a.ksplit : 1), cdiv(cols, 64), ng);
     ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_gemm<MODE, ACT>), grid, dim3(256), 0, s, d, a); })
     if constexpr (MODE == 0 || MODE == 2) {      // (their K-split partials)
-        if (a.ksplit > 1)
+        if (a.ksplit > 1) {
             ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_finish<MODE, ACT>), dim3(cdiv(d.N * d.SE, 256)), dim3(256), 0, s, d, a); })
+        }
     }
+    return 0;
 }
 
 int launch_se_fc_fwd(const TfnasCellDesc& d, const float* pooled, float* hpre, float* gate, float* scratch,
@@ -641,9 +643,9 @@ int launch_se_fc_fwd(const TfnasCellDesc& d, const float* pooled, float* hpre, f
     } else if (p.var == SE_IMAGE) {
         ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_fused_fwd<ACT>), dim3(d.N, p.ng), dim3(256), p.shm, s, d, pooled, hpre, gate); })
     } else {
-        se_gemm<0>(d, a, d.N, p.se_max, p.ng, s);
+        if (se_gemm<0>(d, a, d.N, p.se_max, p.ng, s)) return TFNAS_EINVAL;
         a.out0 = gate;
-        se_gemm<1>(d, a, d.N, p.mcp_max, p.ng, s);
+        if (se_gemm<1>(d, a, d.N, p.mcp_max, p.ng, s)) return TFNAS_EINVAL;
     }
     return (int)hipGetLastError();
 }
@@ -664,9 +666,9 @@ int launch_se_fc_bwd(const TfnasCellDesc& d, const float* dgate, const float* ga
             hipLaunchKernelGGL((k_se_fused_bwd<ACT>), dim3(d.N, p.ng), dim3(256), p.shm, s, d, dgate, gate, hpre, dhpre, dpooled);
         })
     } else {
-        se_gemm<2>(d, a, d.N, p.se_max, p.ng, s);
+        if (se_gemm<2>(d, a, d.N, p.se_max, p.ng, s)) return TFNAS_EINVAL;
         a.out0 = dpooled;
-        se_gemm<3>(d, a, d.N, p.mcp_max, p.ng, s);
+        if (se_gemm<3>(d, a, d.N, p.mcp_max, p.ng, s)) return TFNAS_EINVAL;
     }
     return (int)hipGetLastError();
 }

@@ -18,22 +18,35 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline uint64_t cdiv64(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
 // ----------------------------------------------------------------------------- activations
-// reference: Swish = x * sigmoid(x) (models/layers.py:26-35), ReLU (layers.py:470-471)
+// reference: Swish = x * sigmoid(x) (models/layers.py:26-35), ReLU (layers.py:470-471), ReLU6 / HardSwish (layers.py:38-47)
 // 1/(1+e^-x) through v_exp_f32 + v_rcp_f32 (1 ulp each).  An IEEE `/` costs ~10 more VALU instructions per element
 // (v_div_scale x2, fma chain, v_div_fmas, v_div_fixup), and the operand loaders that apply the activation are VALU-issue
 // bound: 682 VALU instructions per 32 MFMAs in k_project_fwd<4, swish> before this.
 __device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
+// ReLU6 = min(max(x, 0), 6), hard-swish = x * min(max(x + 3, 0), 6) / 6 (layers.py:38-47): no transcendental.  The derivatives
+// are torch's: hardtanh backward is 1 strictly inside (0, 6); hardswish backward is (2x + 3) / 6 strictly inside (-3, 3), 1 from 3
+// up, 0 from -3 down.  ReLU6's lower kink decides exactly as ReLU's does (x > 0).
+// Every fork is exhaustive: a value the kernels were not written for does not compile.
 template <int ACT>
 __device__ __forceinline__ float act_f(float x) {
-    if (ACT == TFNAS_ACT_RELU) return fmaxf(x, 0.f);
-    return x * sigmoid_f(x);
+    static_assert(ACT == TFNAS_ACT_RELU || ACT == TFNAS_ACT_SWISH || ACT == TFNAS_ACT_RELU6 || ACT == TFNAS_ACT_HSWISH,
+                  "unknown activation");
+    if constexpr (ACT == TFNAS_ACT_RELU) return fmaxf(x, 0.f);
+    else if constexpr (ACT == TFNAS_ACT_SWISH) return x * sigmoid_f(x);
+    else if constexpr (ACT == TFNAS_ACT_RELU6) return fminf(fmaxf(x, 0.f), 6.f);
+    else return x * fminf(fmaxf(x + 3.f, 0.f), 6.f) * (1.f / 6.f);
 }
 // derivative w.r.t. the pre-activation x
 template <int ACT>
 __device__ __forceinline__ float act_d(float x) {
-    if (ACT == TFNAS_ACT_RELU) return x > 0.f ? 1.f : 0.f;
-    const float s = sigmoid_f(x);
-    return s * (1.f + x * (1.f - s));
+    static_assert(ACT == TFNAS_ACT_RELU || ACT == TFNAS_ACT_SWISH || ACT == TFNAS_ACT_RELU6 || ACT == TFNAS_ACT_HSWISH,
+                  "unknown activation");
+    if constexpr (ACT == TFNAS_ACT_RELU) return x > 0.f ? 1.f : 0.f;
+    else if constexpr (ACT == TFNAS_ACT_SWISH) {
+        const float s = sigmoid_f(x);
+        return s * (1.f + x * (1.f - s));
+    } else if constexpr (ACT == TFNAS_ACT_RELU6) return (x > 0.f && x < 6.f) ? 1.f : 0.f;
+    else return x >= 3.f ? 1.f : (x > -3.f ? (2.f * x + 3.f) * (1.f / 6.f) : 0.f);
 }
 template <int ACT>
 __device__ __forceinline__ f32x4 act_f4(f32x4 v) {

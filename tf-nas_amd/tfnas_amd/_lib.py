@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TFNAS_LIB') or os.path.join(_HERE, 'libtfnas_hip.so')     # (TFNAS_LIB: an experiment build of the same ABI)
 
 MAX_GROUPS, MAX_SINK, MAX_CELLS = 8, 4, 32
-ACT = {'relu': 0, 'swish': 1}
+ACT = {'relu': 0, 'swish': 1, 'relu6': 2, 'h-swish': 3}       # the reference's spellings (models/layers.py:38-47); TFNAS_ACT_*
 MODE_CELL, MODE_STEM, MODE_HEAD = 0, 1, 2
 
 _W_FIELDS = ('w_expand', 'w_dw', 'w_proj', 'w_se_r', 'b_se_r', 'w_se_e', 'b_se_e')
@@ -25,6 +25,7 @@ _G_FIELDS = ('g_expand', 'g_dw', 'g_proj', 'g_se_r', 'gb_se_r', 'g_se_e', 'gb_se
 GEMM_EXPLICIT, GEMM_EVERYWHERE, CELL_LAZY_JOIN = 0x1000, 0x100, 1
 CELL_ACCUM_WGRAD = 0x20      # TfnasCellDesc.flags: the backward adds its weight gradients to their destinations
 CELL_K7 = 0x80               # TfnasCellDesc.flags: groups may have depthwise kernel size 7 (refused without the bit)
+CELL_ACTS = 0x100            # TfnasCellDesc.flags: act may be 'relu6' / 'h-swish' (refused without the bit)
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
 ROUTE_FX_OFF, ROUTE_FOLD_OFF, ROUTE_DWWG_OFF, ROUTE_DWWG2_OFF, ROUTE_XG_OFF, ROUTE_XG_ALL = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 ROUTE_DW = {'auto': 0, 'direct': 1 << 6, 'lds': 2 << 6, 'tiled': 3 << 6}
@@ -32,6 +33,20 @@ ROUTE_SE = {'wave': 0, 'fused': 1 << 8, 'gemm': 2 << 8}
 ROUTE_WGRAD_INLINE, ROUTE_GRAM2 = 0x400, 0x800
 ROUTE_TAKEN_VALID, ROUTE_TAKEN_FX = 1, 2
 GEMM_MODES = {'f32': 0, 'bf16': 1, 'x2': 3, 'x3': 6}
+
+
+def act_id(name):
+    """TFNAS_ACT_* of an activation name; ValueError (naming the legal ones) for any other."""
+    try:
+        return ACT[name]
+    except (KeyError, TypeError):
+        raise ValueError('tfnas_amd: unknown activation %r (one of %s)' % (name, ', '.join(repr(a) for a in ACT))) from None
+
+
+def act_flags(act):
+    """TfnasCellDesc.flags bit a descriptor with activation id ``act`` needs (the library takes the two newer activations only
+    from callers that say they know them)."""
+    return CELL_ACTS if act in (ACT['relu6'], ACT['h-swish']) else 0
 
 
 class TfnasGroup(C.Structure):

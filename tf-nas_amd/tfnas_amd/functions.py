@@ -136,6 +136,7 @@ class HipModes:
         d.flags = _lib.CELL_LAZY_JOIN if self.lazy_join else 0
         if any(d.g[g].k == 7 for g in range(min(d.G, _lib.MAX_GROUPS))):
             d.flags |= _lib.CELL_K7                    # (the library takes 7 x 7 groups only from callers that say they know them)
+        d.flags |= _lib.act_flags(d.act)               # (... and 'relu6' / 'h-swish')
         d.route = ENV_ROUTE if self.route is None else int(self.route)
         if self.sync is None:
             d.sync_fn, d.sync_user, d.sync_world = None, None, 0
@@ -198,7 +199,7 @@ class CellPlan:
             d.mode = self.mode
             if self.mode == _lib.MODE_STEM:            # (H, W) given = image size; plan derives the conv output size
                 d.Hi, d.Wi = H, W
-            d.act, d.has_res, d.G, d.need_wgrad, d.eps = _lib.ACT[self.act], self.has_res, len(self.blocks), 0, BN_EPS
+            d.act, d.has_res, d.G, d.need_wgrad, d.eps = _lib.act_id(self.act), self.has_res, len(self.blocks), 0, BN_EPS
             for g, b in enumerate(self.blocks):
                 d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
             self.modes.apply(d)                        # (before the plan: it validates the modes; every launch re-checks them)

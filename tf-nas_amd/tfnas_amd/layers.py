@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ._lib import act_id
 from .functions import CellPlan, MixedOpFn, BN_EPS
 
 
@@ -87,6 +88,7 @@ class MBInvertedResBlock(nn.Module):
     def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size=3, stride=1,
                  affine=False, act_func='relu'):
         super().__init__()
+        act_id(act_func)                                   # (ValueError for a name the library has no kernels for)
         self.in_channels, self.mid_channels = in_channels, mid_channels
         self.se_channels, self.out_channels = se_channels, out_channels
         self.kernel_size, self.stride, self.act_func = kernel_size, stride, act_func

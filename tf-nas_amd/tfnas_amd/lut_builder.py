@@ -52,10 +52,10 @@ class _BlockTimer:
             raise ValueError(mode)
         d = _lib.TfnasCellDesc()
         d.N, d.H, d.W, d.ic, d.oc, d.stride = batch, size, size, ic, oc, stride
-        d.mode, d.act, d.G, d.need_wgrad, d.eps = _lib.MODE_CELL, _lib.ACT[act], 1, 0, BN_EPS
+        d.mode, d.act, d.G, d.need_wgrad, d.eps = _lib.MODE_CELL, _lib.act_id(act), 1, 0, BN_EPS
         d.has_res = int(ic == oc and stride == 1)
         d.g[0].mc, d.g[0].k, d.g[0].se = mc, k, se
-        d.flags = _lib.CELL_K7 if k == 7 else 0
+        d.flags = (_lib.CELL_K7 if k == 7 else 0) | _lib.act_flags(d.act)
         _lib.check(lib.tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
         ws = _lib.TfnasCellWs()
         _lib.check(lib.tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
@@ -112,7 +112,8 @@ class _BlockTimer:
         return float(np.median(times))
 
 
-Measurer = _BlockTimer          # public name: Measurer(device).measure(ic, mc, se, oc, k, stride, act, size, ...), k in {3, 5, 7}
+Measurer = _BlockTimer          # public name: Measurer(device).measure(ic, mc, se, oc, k, stride, act, size, ...), k in {3, 5, 7},
+                                # act in 'relu' | 'swish' | 'relu6' | 'h-swish'
 
 
 def lut_keys():

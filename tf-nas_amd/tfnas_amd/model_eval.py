@@ -46,8 +46,9 @@ class _HeadBlock:
 
 
 class _DerivedBase(nn.Module):
-    def _finish(self, num_classes):
-        self.feature_mix_layer = ConvLayer(320, 1280, kernel_size=1, stride=1, affine=True, act_func='swish')
+    def _finish(self, num_classes, head_act='swish'):
+        _lib.act_id(head_act)
+        self.feature_mix_layer = ConvLayer(320, 1280, kernel_size=1, stride=1, affine=True, act_func=head_act)
         self.global_avg_pooling = nn.AdaptiveAvgPool2d(1)
         self.classifier = LinearLayer(1280, num_classes)
         self._initialization()
@@ -121,7 +122,7 @@ class _DerivedBase(nn.Module):
         cfg = {'first_stem': _conv_layer_config(3, 32, 3, 2, 'relu'), 'second_stem': self._block_config(self.second_stem)}
         for i, stage in enumerate(self._stages(), start=1):
             cfg['stage%d' % i] = [self._block_config(b) for b in stage]
-        cfg['feature_mix_layer'] = _conv_layer_config(320, 1280, 1, 1, 'swish')
+        cfg['feature_mix_layer'] = _conv_layer_config(320, 1280, 1, 1, self.feature_mix_layer.act_func)
         cl = self.classifier
         cfg['classifier'] = {'name': 'LinearLayer', 'in_features': cl.in_features, 'out_features': cl.out_features,
                              'bias': True, 'use_bn': False, 'affine': False, 'act_func': None, 'ops_order': 'weight_bn_act'}
@@ -192,7 +193,8 @@ class NetworkCfg(_DerivedBase):
                 blk.drop_connect_rate = self.drop_connect_rate * self.block_idx / self.block_count
                 stage.append(blk)
             setattr(self, 'stage%d' % i, stage)
-        self._finish(num_classes)
+        # (the head's activation as the config names it: MobileNetV3-style configs end in 'h-swish')
+        self._finish(num_classes, model_config.get('feature_mix_layer', {}).get('act_func') or 'swish')
 
 
 class CrossEntropyLabelSmooth(nn.Module):

@@ -163,7 +163,7 @@ class PathRunner:
         d = TfnasCellDesc()
         d.N, d.H, d.W, d.ic, d.oc, d.stride = N, H, W, cell.in_channels, cell.out_channels, cell.stride
         d.mode = _lib.MODE_CELL
-        d.act, d.G, d.need_wgrad, d.eps = _lib.ACT[cell.act_func], len(blocks), 0, BN_EPS
+        d.act, d.G, d.need_wgrad, d.eps = _lib.act_id(cell.act_func), len(blocks), 0, BN_EPS
         d.has_res = int(cell.in_channels == cell.out_channels and cell.stride == 1)
         for g, b in enumerate(blocks):
             d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
