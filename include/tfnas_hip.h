@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-/* 4, additive: TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH in a descriptor whose flags carry TFNAS_CELL_ACTS (cells, affine blocks, head;
+/* 4, additive: TFNAS_CELL_NOEXPAND -- a block without expand convolution (mid <= in channels) through tfnas_mixedop_* / tfnas_mbconv_*.
+ * 4, additive: TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH in a descriptor whose flags carry TFNAS_CELL_ACTS (cells, affine blocks, head;
  * materialised route and LDS tile depthwise kernels only).
  * 4, additive: tfnas_cls_wgrad_ex (tfnas_cls_wgrad + the search epoch's running loss / top-1 / top-5 / invalid-target meter).
  * 4, additive: tfnas_cls_ce_ex / tfnas_cls_reduce (the derived network's retrain tail: label smoothing, rank, forward-only form,
@@ -132,7 +133,8 @@ typedef struct TfnasCellDesc {
                                  stream (see tfnas_set_lazy_join, which sets the default for descriptors without the bit);
                                  TFNAS_CELL_ACCUM_WGRAD: the backward adds its weight gradients to their destinations;
                                  TFNAS_CELL_K7: groups may have depthwise kernel size 7;
-                                 TFNAS_CELL_ACTS: act may be TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH                         [in]
+                                 TFNAS_CELL_ACTS: act may be TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH;
+                                 TFNAS_CELL_NOEXPAND: the one group has no expand convolution                           [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -184,6 +186,34 @@ typedef struct TfnasCellDesc {
  * 2 or 3 (any other value is TFNAS_EINVAL either way).  Checked by tfnas_cell_plan and again by every entry point.  The Python
  * mirror sets it for every descriptor with one of the two (functions.HipModes.apply). */
 #define TFNAS_CELL_ACTS 0x100
+/* TfnasCellDesc.flags: the caller knows cells WITHOUT an expand convolution -- the reference's MBInvertedResBlock with
+ * mid_channels <= in_channels (models/layers.py:463-482: no inverted_bottleneck), the "expand ratio 1" block of the MobileNet family
+ * and the reference's own second_stem:  out = BN3(project(SE(act(BN2(dw(x)))))) [+ x].  Additive like TFNAS_CELL_K7: without the
+ * bit every descriptor is accepted, refused, planned, routed and launched exactly as before it existed.  With it the descriptor
+ * describes ONE such block:
+ *   geometry   mode == TFNAS_MODE_CELL, G == 1, g[0].mc == ic, g[0].w_expand == NULL and g[0].g_expand == NULL; anything else --
+ *              G > 1, mc != ic, an expand pointer, stem or head mode -- is TFNAS_EINVAL, and so is tfnas_path_plan on a cell that
+ *              carries the bit.  A mixed cell in which only SOME candidates lack the expand convolution is deliberately out of scope.
+ *              k in {3, 5, 7 (TFNAS_CELL_K7)}, all four activations (two with TFNAS_CELL_ACTS), stride 1 | 2, se 0 or a multiple of
+ *              4, ic any multiple of 4 >= 4, has_res as for any cell.
+ *   arithmetic D = dw(x) on the raw cell input: no BatchNorm and no activation before the depthwise convolution; `act` applies after
+ *              BN2 and in the SE hidden layer only.  Everything after D is the ordinary cell.
+ *   workspace  tfnas_cell_ws reports E = 0 and dxp = 4 (the minimum).  The entry points accept E == NULL (dxp too) and never touch
+ *              E, stats1, red1 or cb1 (their slots in stats / red / bsmall keep their offsets).  dEh STAYS [N*H*W][M]: it is never a
+ *              gradient tensor here, but still the scratch of the project dgrad's BN2-backward records and of the SE backward's
+ *              K-split partials.  The backward writes dx [N*H*W][ic] straight from the depthwise backward-data pass, the residual
+ *              gradient added in the same store (in the affine form with drop-connect: the unscaled dout).
+ *   routes     tfnas_efree_supported and tfnas_fx_supported return 0, tfnas_cell_route returns TFNAS_ROUTE_TAKEN_VALID.  The cell
+ *              runs its depthwise passes on the LDS tile kernels (their raw-input form) whatever TFNAS_ROUTE_DW_* asks, the depthwise
+ *              weight gradient in its own launch (the 7 x 7 rule).  TFNAS_ROUTE_XG_* and TFNAS_ROUTE_GRAM2 mean nothing to it and are
+ *              ignored; the SE and TFNAS_ROUTE_WGRAD_INLINE bits are honoured; weight-gradient fork 2 (wgrad_stream[2]) is never used.
+ *   modes      tfnas_mixedop_fwd/bwd (sampled form, wmix == NULL) and tfnas_mbconv_fwd/bwd; TFNAS_CELL_ACCUM_WGRAD,
+ *              TFNAS_CELL_LAZY_JOIN, wgrad_stream[], the GEMM modes (the project GEMMs) and the sync-stats hook (two forward tables,
+ *              two backward tables) as for any cell.
+ *   affine     BatchNorm site 0 does not exist: every site-0 pointer of TfnasBnAffine must be NULL (else TFNAS_EINVAL).
+ * Checked by tfnas_cell_plan and again by every entry point.  The Python mirror sets it for a block whose inverted_bottleneck is
+ * None (functions.HipModes.apply). */
+#define TFNAS_CELL_NOEXPAND 0x200
 /* TfnasCellDesc.route (ABI 4; rounds 2-5 read these from TFNAS_* environment variables latched once per process) */
 #define TFNAS_ROUTE_FX_OFF 0x1        /* frozen-weight launches of the 14 x 14 / 7 x 7 cells through the materialised route instead
                                          of the fused per-image kernels (csrc/fx_kernels.hip)                                   */
@@ -195,8 +225,8 @@ typedef struct TfnasCellDesc {
 #define TFNAS_ROUTE_XG_OFF 0x10       /* expand weight gradient never in Gram form                                              */
 #define TFNAS_ROUTE_XG_ALL 0x20       /* ... in Gram form wherever the shape allows (default: where E >= 100 MB)                */
 #define TFNAS_ROUTE_DW_SHIFT 6        /* 2 bits: 0 per-launch policy, 1 register-window kernels wherever the geometry allows,   */
-#define TFNAS_ROUTE_DW_MASK 0xc0      /*         2 LDS ring / tile kernels only, 3 tile kernels only (7 x 7 cells and
-                                         TFNAS_ACT_RELU6 / _HSWISH cells: always 3)                                             */
+#define TFNAS_ROUTE_DW_MASK 0xc0      /*         2 LDS ring / tile kernels only, 3 tile kernels only (7 x 7 cells,
+                                         TFNAS_ACT_RELU6 / _HSWISH cells and TFNAS_CELL_NOEXPAND cells: always 3)                                             */
 #define TFNAS_ROUTE_SE_SHIFT 8        /* 2 bits: 0 wave-level MFMA kernels for the excite FCs, 1 one fused per-image kernel,    */
 #define TFNAS_ROUTE_SE_MASK 0x300     /*         2 LDS-tiled GEMMs                                                              */
 #define TFNAS_ROUTE_WGRAD_INLINE 0x400 /* weight-gradient kernels on the caller's stream (no side stream)                       */

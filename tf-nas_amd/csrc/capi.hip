@@ -157,6 +157,14 @@ static int check_act(const TfnasCellDesc* d) {
     return 0;
 }
 
+// TFNAS_CELL_NOEXPAND: one expand-free block -- cell mode, one group of mc == ic channels, no expand weight or gradient pointer
+static int check_noexpand(const TfnasCellDesc* d) {
+    if (!(d->flags & TFNAS_CELL_NOEXPAND)) return 0;
+    if (d->mode != TFNAS_MODE_CELL || d->G != 1) return TFNAS_EINVAL;
+    if (d->g[0].mc != d->ic || d->g[0].w_expand || d->g[0].g_expand) return TFNAS_EINVAL;
+    return 0;
+}
+
 // the per-launch modes of a descriptor (callers may change them between tfnas_cell_plan and a launch: every entry point re-checks)
 static int check_modes(const TfnasCellDesc* d) {
     TRY(check_act(d));
@@ -164,7 +172,9 @@ static int check_modes(const TfnasCellDesc* d) {
         const int gm = d->gemm_mode & ~(TFNAS_GEMM_EXPLICIT | TFNAS_GEMM_EVERYWHERE);
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
-    if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS)) return TFNAS_EINVAL;
+    if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS | TFNAS_CELL_NOEXPAND))
+        return TFNAS_EINVAL;
+    TRY(check_noexpand(d));
     if (!(d->flags & TFNAS_CELL_K7)) {            // kernel size 7 is opt-in: without the bit it is refused as it always was
         for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g)
             if (d->g[g].k == 7) return TFNAS_EINVAL;
@@ -234,7 +244,8 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     const uint64_t P = (uint64_t)d->N * d->H * d->W, Po = (uint64_t)d->N * d->Ho * d->Wo;
     const uint64_t M = d->M, N = d->N, SE = d->SE, G = d->G, oc = d->oc;
     // the four stream tensors: P*M / Po*M fp32 elements
-    ws->E = P * M;
+    const bool noexp = (d->flags & TFNAS_CELL_NOEXPAND) != 0;
+    ws->E = noexp ? 0 : P * M;                   // (no expand convolution: D = dw(x), nothing to save)
     ws->D = Po * M;
     ws->Pr = G * Po * oc;
     ws->off_pooled = 0;
@@ -247,7 +258,8 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     ws->stats = 4 * M + 2 * G * oc;
     ws->out = Po * oc;
     ws->dZ = Po * M;
-    ws->dEh = P * M;
+    ws->dEh = P * M;                             // (an expand-free cell keeps it: scratch of the project dgrad's epilogue records and
+                                                 //  of the SE backward's K-split partials, never a gradient tensor)
     ws->off_dgate = 0;
     ws->off_dpooled = N * M;
     ws->off_dgl = 2 * N * M;
@@ -262,7 +274,7 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     ws->part = (d->need_wgrad ? 2 : 1) * (uint64_t)TFNAS_PART_ALLOC;   // second half: weight-gradient side stream
     ws->dx = P * d->ic;
     {
-        const int ns = d->mode == TFNAS_MODE_STEM ? 1 : gemm_plan_expand_dgrad(*d, true).splits;
+        const int ns = (d->mode == TFNAS_MODE_STEM || noexp) ? 1 : gemm_plan_expand_dgrad(*d, true).splits;
         ws->dxp = ns > 1 ? (uint64_t)ns * P * d->ic : 4;   /* split-K partials of the expand dgrad */
     }
     return 0;
@@ -286,6 +298,13 @@ static void bn_site(const TfnasCellDesc& d, int site, int& nch, uint64_t& cnt) {
     const uint64_t P = (uint64_t)d.N * d.H * d.W, Po = (uint64_t)d.N * d.Ho * d.Wo;
     nch = site == 2 ? d.oc : d.g[0].mc;
     cnt = site == 0 ? P : Po;
+}
+// an expand-free block has no BatchNorm site 0: every site-0 pointer of its TfnasBnAffine must be NULL
+static int check_bn_sites(const TfnasCellDesc& d, const TfnasBnAffine* bn) {
+    if (!cell_noexpand(d)) return 0;
+    if (bn->weight[0] || bn->bias[0] || bn->g_weight[0] || bn->g_bias[0] || bn->running_mean[0] || bn->running_var[0])
+        return TFNAS_EINVAL;
+    return 0;
 }
 static int bn_fwd_fix(const TfnasCellDesc& d, const TfnasBnAffine* bn, int site, double* stats, hipStream_t s) {
     int nch;
@@ -314,14 +333,19 @@ int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdB
     const int taken = route_taken(d0, bn != nullptr);
     if (route) *route = taken;
     const bool fx = (taken & TFNAS_ROUTE_TAKEN_FX) != 0;
+    const bool sync = !(bn && bn->eval);          // (eval mode normalises with the running statistics: nothing to reduce)
+    if (cell_noexpand(d)) {
+        // no expand convolution, no BatchNorm site 0: the depthwise reads the raw cell input (E and stats1 are not touched)
+        TRY(launch_dw_fwd(d, nullptr, b.x, nullptr, b.D, stats2, b.part, s));
+    } else {
     if (fx) TRY(launch_fx_stats(d, b.x, stats1, b.part, s));                  // BN1 statistics from the Gram matrix of x
     else if (b.E) TRY(launch_expand_fwd(d, b.x, b.E, stats1, b.part, s));     // 1x1 expand (all groups) + BN1 statistics
     else TRY(launch_expand_stats_gram(d, b.x, stats1, b.part, s));            // E-free: BN1 statistics from the Gram matrix of x
-    const bool sync = !(bn && bn->eval);          // (eval mode normalises with the running statistics: nothing to reduce)
     if (sync) TRY(stats_sync(d, stats1, 2 * (size_t)d.M, s));                    // sync-stats: global-batch sums (no-op without a hook)
     if (bn) TRY(bn_fwd_fix(d0, bn, 0, stats1, s));
     if (fx) TRY(launch_fx_fwd(d, b.x, stats1, b.E, b.D, stats2, b.part, s));  // expand + BN1 + act + depthwise in one kernel
     else TRY(launch_dw_fwd(d, b.E, b.x, stats1, b.D, stats2, b.part, s));     // BN1+act fused load, depthwise, BN2 statistics
+    }
     if (sync) TRY(stats_sync(d, stats2, 2 * (size_t)d.M, s));
     if (bn) TRY(bn_fwd_fix(d0, bn, 1, stats2, s));
     TRY(launch_se_pool(d, b.D, stats2, pooled, s));                           // SE squeeze (SE groups only)
@@ -412,7 +436,7 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
     if (d.need_wgrad) {
         for (int g = 0; g < d.G; ++g) {
             const TfnasGroup& gr = d.g[g];
-            if (!gr.g_expand || !gr.g_dw || !gr.g_proj) return TFNAS_ENULL;
+            if ((!gr.g_expand && !cell_noexpand(d)) || !gr.g_dw || !gr.g_proj) return TFNAS_ENULL;
             if (gr.se > 0 && (!gr.g_se_r || !gr.gb_se_r || !gr.g_se_e || !gr.gb_se_e)) return TFNAS_ENULL;
         }
     }
@@ -447,6 +471,18 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
     else TRY(launch_bn2_bwd(d, b.dZ, b.D, stats2, gate, dpooled, red2, part, s));
     TRY(stats_sync(d, red2, 2 * (size_t)d.M, s));
     if (bn) TRY(bn_bwd_fix(d0, bn, 1, red2, s));
+    if (cell_noexpand(d)) {
+        // no expand convolution: the depthwise weight gradient reads the raw cell input, and the depthwise backward-data pass
+        // writes dx itself (+ the unscaled residual gradient); no BN1 backward, no Gram operator, no expand dgrad / wgrad
+        if (d.need_wgrad) {
+            hipStream_t sw = fork_to(so, 1, s);
+            if (d.SE > 0) TRY(launch_se_wgrad(d, dgate, gate, dhpre, hpre, pooled, sw));
+            TRY(launch_dw_wgrad(d, b.dZ, gate, dpooled, b.D, stats2, red2, b.x, nullptr, part_w1, sw));
+        }
+        if (b.dx)
+            TRY(launch_dw_bwd_dx(d, b.dZ, gate, dpooled, b.D, stats2, red2, d.has_res ? dout_res : nullptr, b.dx, s));
+        return 0;
+    }
     if (taken & TFNAS_ROUTE_TAKEN_FX) {
         // fused per-image route: depthwise dgrad + act' + the dE (rstd . W1) term of the expand dgrad in one kernel (dE never
         // materialised; partial sums per channel slice in the dEh buffer), then the BN1-backward correction -x G + b
@@ -489,8 +525,9 @@ extern "C" int tfnas_mixedop_fwd(const TfnasCellDesc* dp, const float* x, const 
     if (!dp || !x || !D || !Pr || !fsmall || !stats || !part || !out) return TFNAS_ENULL;
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    if (!E && !efree_supported(d)) return TFNAS_ENULL;       // E may be omitted only in E-free mode (tfnas_efree_supported)
     TRY(check_modes(dp));
+    // E may be omitted only in E-free mode (tfnas_efree_supported) and by an expand-free cell, which never touches it
+    if (!E && !efree_supported(d) && !cell_noexpand(d)) return TFNAS_ENULL;
     TfnasCellWs ws;
     TRY(tfnas_cell_ws(dp, &ws));
     CellFwdBufs b = {x, wmix, E, D, Pr, fsmall, stats, part, out};
@@ -537,8 +574,8 @@ extern "C" int tfnas_mixedop_bwd(const TfnasCellDesc* dp, const float* x, const 
         return TFNAS_ENULL;
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    if (!E && !efree_supported(d)) return TFNAS_ENULL;
     TRY(check_modes(dp));
+    if (!E && !efree_supported(d) && !cell_noexpand(d)) return TFNAS_ENULL;
     CellBwdBufs b = {x, wmix, E, D, Pr, fsmall, stats, dout, dZ, dEh, bsmall, red, part, part + TFNAS_PART_ALLOC,
                      dx, dxp, dwmix, nullptr, nullptr};
     return cell_bwd_entry(d, b, S(stream), d.wgrad_stream, false);
@@ -547,10 +584,12 @@ extern "C" int tfnas_mixedop_bwd(const TfnasCellDesc* dp, const float* x, const 
 extern "C" int tfnas_mbconv_fwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn, const float* drop_scale, const float* x,
                                 float* E, float* D, float* Pr, float* fsmall, double* stats, float* part, float* out,
                                 void* stream) {
-    if (!dp || !bn || !x || !E || !D || !Pr || !fsmall || !stats || !part || !out) return TFNAS_ENULL;
+    if (!dp || !bn || !x || !D || !Pr || !fsmall || !stats || !part || !out) return TFNAS_ENULL;
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD || d.G != 1) return TFNAS_EINVAL;
     TRY(check_modes(dp));
+    if (!E && !cell_noexpand(d)) return TFNAS_ENULL;
+    TRY(check_bn_sites(d, bn));
     TfnasCellWs ws;
     TRY(tfnas_cell_ws(dp, &ws));
     CellFwdBufs b = {x, nullptr, E, D, Pr, fsmall, stats, part, out};
@@ -563,12 +602,14 @@ extern "C" int tfnas_mbconv_bwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn
                                 const float* E, const float* D, const float* Pr, const float* fsmall, const double* stats,
                                 const float* dout, float* dout_s, float* dZ, float* dEh, float* bsmall, double* red,
                                 float* part, float* dx, float* dxp, void* stream) {
-    if (!dp || !bn || !x || !E || !D || !Pr || !fsmall || !stats || !dout || !dZ || !dEh || !bsmall || !red || !part)
+    if (!dp || !bn || !x || !D || !Pr || !fsmall || !stats || !dout || !dZ || !dEh || !bsmall || !red || !part)
         return TFNAS_ENULL;
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD || d.G != 1) return TFNAS_EINVAL;
     if (d.wgrad_stream[0] || d.wgrad_stream[1] || d.wgrad_stream[2]) return TFNAS_EINVAL;     // (tfnas_mixedop_bwd only)
     TRY(check_modes(dp));
+    if (!E && !cell_noexpand(d)) return TFNAS_ENULL;
+    TRY(check_bn_sites(d, bn));
     CellBwdBufs b = {x, nullptr, E, D, Pr, fsmall, stats, dout, dZ, dEh, bsmall, red, part, part + TFNAS_PART_ALLOC,
                      dx, dxp, nullptr, nullptr, nullptr};
     b.bn = bn;
@@ -610,6 +651,7 @@ extern "C" int tfnas_head_affine_fwd(const TfnasCellDesc* dp, const TfnasBnAffin
     if (!dp || !bn || !x || !E || !stats || !part || !pooled) return TFNAS_ENULL;
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
+    TRY(check_noexpand(dp));
     return head_fwd_impl(*dp, bn, x, E, stats, part, pooled, S(stream));
 }
 
@@ -619,6 +661,7 @@ extern "C" int tfnas_head_affine_bwd(const TfnasCellDesc* dp, const TfnasBnAffin
     if (!dp || !bn || !x || !E || !stats || !dpooled || !dEh || !cb1 || !red || !part || !dx) return TFNAS_ENULL;
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
+    TRY(check_noexpand(dp));
     if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
     return head_bwd_impl(*dp, bn, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
@@ -628,6 +671,7 @@ extern "C" int tfnas_head_fwd(const TfnasCellDesc* dp, const float* x, float* E,
     if (!dp || !x || !E || !stats || !part || !pooled) return TFNAS_ENULL;
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
+    TRY(check_noexpand(dp));
     return head_fwd_impl(*dp, nullptr, x, E, stats, part, pooled, S(stream));
 }
 
@@ -637,6 +681,7 @@ extern "C" int tfnas_head_bwd(const TfnasCellDesc* dp, const float* x, const flo
     if (!dp || !x || !E || !stats || !dpooled || !dEh || !cb1 || !red || !part || !dx) return TFNAS_ENULL;
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
+    TRY(check_noexpand(dp));
     if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
     return head_bwd_impl(*dp, nullptr, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
@@ -647,6 +692,7 @@ extern "C" int tfnas_head_wgrad(const TfnasCellDesc* dp, const float* x, const f
     const TfnasCellDesc& d = *dp;
     if (d.mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
+    TRY(check_noexpand(dp));
     if (!d.g[0].g_expand) return TFNAS_ENULL;
     return launch_expand_wgrad(d, dEh, E, cb1, x, part, S(stream));
 }

@@ -146,7 +146,9 @@ __device__ __forceinline__ void load_tile(float* tile, int L0, int L1, int CC, i
 
 // ============================================================================ forward
 // KQ = 0: the tile is loaded from E.  KQ = ic/4 > 0 (E-free, efree.h): the tile is recomputed from the cell input x.
-template <int K, int S, int ACT, int KQ>
+// RAW (TFNAS_CELL_NOEXPAND: a block without expand convolution, mc == ic): the tile is the cell input x itself, rows of ic floats,
+// neither normalised nor activated -- no BN1 table is built or read (stats1 and E are not touched), ACT is unused (instantiated 0).
+template <int K, int S, int ACT, int KQ, bool RAW = false>
 __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float* __restrict__ E,
                                                    const float* __restrict__ x,
                                                    const double* __restrict__ stats1, float* __restrict__ D,
@@ -166,9 +168,11 @@ __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float*
     float* wts = lds + tile_floats;
     float2* cst = reinterpret_cast<float2*>(wts + K * K * CC);
 
+    if constexpr (!RAW) {
     if (tid < CC)
         cst[tid] = (c0 + tid < mc) ? bn_consts(stats1 + 2 * (size_t)(off + c0 + tid), 1.0 / ((double)d.N * H * W), d.eps)
                                    : make_float2(0.f, 0.f);
+    }
     stage_weights(wts, d.g[g].w_dw, K * K, CC, c0, mc);
     ExpandB<(KQ > 0 ? KQ : 2)> xb;
     if (KQ > 0) {
@@ -192,6 +196,14 @@ __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float*
                 a = ((size_t)(n * H + hi) * W + wi) * d.ic;
                 return hi >= 0 && hi < H && wi >= 0 && wi < W;
             });
+        } else if constexpr (RAW) {
+            load_tile(in_tile, IH, IW, CC, gm.cq_shift, x,
+                      [&](int r, int c, int cq, size_t& a) {
+                          const int hi = hi0 + r, wi = wi0 + c;
+                          a = ((size_t)(n * H + hi) * W + wi) * d.ic + c0 + 4 * cq;
+                          return hi >= 0 && hi < H && wi >= 0 && wi < W && c0 + 4 * cq < mcp;
+                      },
+                      [&](f32x4 v, int) { return v; });
         } else
         load_tile(in_tile, IH, IW, CC, gm.cq_shift, E,
                   [&](int r, int c, int cq, size_t& a) {
@@ -286,7 +298,10 @@ __device__ __forceinline__ void fill_cst2(f32x4* cst2, const TfnasCellDesc& d, i
 // epilogue: deh = dA1 * act'(ehat) -> dEh, and the BN1-backward sums (T1 = sum deh, T2 = sum deh*ehat)
 // KQ > 0 (E-free, efree.h): ehat of the tile's input pixels is recomputed from x into a second LDS tile instead of
 // being read from E.
-template <int K, int S, int ACT, int KQ>
+// RAW (TFNAS_CELL_NOEXPAND, mc == ic): the depthwise input is the cell input, so dA1 IS the branch's dx.  The epilogue stores it to
+// `dEh` = dx [N*H*W][ic] (row stride ic), plus `x` = the residual gradient dout [N*H*W][ic] when non-NULL (has_res: oc == ic,
+// stride 1), in the same store.  No BN1-backward sums: E, stats1 and `part` are not touched.
+template <int K, int S, int ACT, int KQ, bool RAW = false>
 __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const float* __restrict__ dZ,
                                                         const float* __restrict__ gate, const float* __restrict__ dpooled,
                                                         const float* __restrict__ D, const double* __restrict__ stats2,
@@ -312,9 +327,11 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
     float2* cst1 = reinterpret_cast<float2*>(cst2 + CC);
 
     fill_cst2(cst2, d, CC, c0, mc, off, stats2, red2);
+    if constexpr (!RAW) {
     if (tid < CC)
         cst1[tid] = (c0 + tid < mc) ? bn_consts(stats1 + 2 * (size_t)(off + c0 + tid), 1.0 / ((double)d.N * H * W), d.eps)
                                     : make_float2(0.f, 0.f);
+    }
     stage_weights(wts, d.g[g].w_dw, K * K, CC, c0, mc);
     float* eh_tile = reinterpret_cast<float*>(cst1 + CC);     // [TIH*TIW][CC] (E-free only)
     ExpandB<(KQ > 0 ? KQ : 2)> xb;
@@ -373,7 +390,9 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
             for (int j = 0; j < 4; ++j) {
                 const int wi = wi0 + iw0 + j;
                 const bool okj = hi < H && wi < W && c0 + 4 * cq < mcp;
-                if (KQ > 0) ev[j] = ld4(eh_tile + (ih * TIW + iw0 + j) * CC + 4 * cq);
+                if constexpr (RAW)        // the residual gradient of the same dx element (x: dout of a residual block, else NULL)
+                    ev[j] = (okj && x) ? ld4_nt(x + (((size_t)(n * H + hi) * W + wi) * d.ic + c0 + 4 * cq)) : zero4();
+                else if (KQ > 0) ev[j] = ld4(eh_tile + (ih * TIW + iw0 + j) * CC + 4 * cq);
                 else ev[j] = okj ? ld4_nt(E + (((size_t)(n * H + hi) * W + wi) * M + off + c0 + 4 * cq)) : zero4();
             }
             if (S == 1) {
@@ -418,6 +437,9 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
                 for (int j = 0; j < 4; ++j) {
                     const int wi = wi0 + iw0 + j;
                     if (wi < W) {
+                        if constexpr (RAW) {
+                            st4_nt(dEh + (((size_t)(n * H + hi) * W + wi) * d.ic + c0 + 4 * cq), acc[j] + ev[j]);
+                        } else {
                         const size_t a = ((size_t)(n * H + hi) * W + wi) * M + off + c0 + 4 * cq;
                         const f32x4 e = ev[j];
                         f32x4 deh;
@@ -430,12 +452,13 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
                             t2[q] += deh[q] * eh;
                         }
                         st4_nt(dEh + a, deh);
+                        }
                     }
                 }
             }
         }
     }
-    dw_flush_stats(t1, t2, dd_tile, CC, c0, mcp, off, M, part, lane);
+    if constexpr (!RAW) dw_flush_stats(t1, t2, dd_tile, CC, c0, mcp, off, M, part, lane);
 }
 
 // ============================================================================ weight gradient
@@ -446,7 +469,8 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
 // (KR = 4: rows 0-3 and 4-6, 28 and 21 accumulators); each part stages the tile itself and writes its own K * KR-float slice of
 // every channel's K * K block of the partial row.
 // (KY0, KR as template arguments: tap rows [KY0, KY0 + KR) with every accumulator index a compile-time constant)
-template <int K, int S, int ACT, int KY0, int KR>
+// RAW (TFNAS_CELL_NOEXPAND): a1 is the cell input itself -- `E` = x [N*H*W][ic], row stride ic; stats1 is not touched.
+template <int K, int S, int ACT, int KY0, int KR, bool RAW>
 __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const float* __restrict__ dZ,
                                               const float* __restrict__ gate, const float* __restrict__ dpooled,
                                               const float* __restrict__ D, const double* __restrict__ stats2,
@@ -471,9 +495,11 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
     float2* cst1 = reinterpret_cast<float2*>(cst2 + CC);
 
     fill_cst2(cst2, d, CC, c0, mc, off, stats2, red2);
+    if constexpr (!RAW) {
     if (tid < CC)
         cst1[tid] = (c0 + tid < mc) ? bn_consts(stats1 + 2 * (size_t)(off + c0 + tid), 1.0 / ((double)d.N * H * W), d.eps)
                                     : make_float2(0.f, 0.f);
+    }
 
     constexpr int WIN = 3 * S + K;
     const int nsw = TW >> 2, nstrips = TH * nsw;
@@ -517,6 +543,15 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
             if (tid < nitems) item_ops(tid, pdd, pdv, pok);
         }
         __syncthreads();
+        if constexpr (RAW) {
+            load_tile(in_tile, IH, IW, CC, gm.cq_shift, E,
+                      [&](int r, int c, int cq, size_t& a) {
+                          const int hi = hi0 + r, wi = wi0 + c;
+                          a = ((size_t)(n * H + hi) * W + wi) * d.ic + c0 + 4 * cq;
+                          return hi >= 0 && hi < H && wi >= 0 && wi < W && c0 + 4 * cq < mcp;
+                      },
+                      [&](f32x4 v, int) { return v; });
+        } else
         load_tile(in_tile, IH, IW, CC, gm.cq_shift, E,
                   [&](int r, int c, int cq, size_t& a) {
                       const int hi = hi0 + r, wi = wi0 + c;
@@ -592,7 +627,7 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
         }
     }
 }
-template <int K, int S, int ACT, int KR = K>
+template <int K, int S, int ACT, int KR = K, bool RAW = false>
 __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const float* __restrict__ dZ,
                                                      const float* __restrict__ gate, const float* __restrict__ dpooled,
                                                      const float* __restrict__ D, const double* __restrict__ stats2,
@@ -601,11 +636,11 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
                                                      size_t out_size, DwGeom gm) {
     static_assert(KR == K || (KR < K && 2 * KR >= K), "one part, or two over blockIdx.z");
     if constexpr (KR == K) {
-        dw_wgrad_rows<K, S, ACT, 0, K>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
+        dw_wgrad_rows<K, S, ACT, 0, K, RAW>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
     } else if (blockIdx.z == 0) {
-        dw_wgrad_rows<K, S, ACT, 0, KR>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
+        dw_wgrad_rows<K, S, ACT, 0, KR, RAW>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
     } else {
-        dw_wgrad_rows<K, S, ACT, KR, K - KR>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
+        dw_wgrad_rows<K, S, ACT, KR, K - KR, RAW>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
     }
 }
 
@@ -640,9 +675,10 @@ static size_t dw_wout_size(const TfnasCellDesc& d) {
 // a group with a kernel size other than 3 / 5 (that is 7: tfnas_cell_plan).  The register-window and the ring kernels hold K x K
 // taps or accumulators in registers and are built for 3 and 5 only: such a cell takes the tile kernels in every pass, whatever
 // TFNAS_ROUTE_DW_* asks, never fuses the weight gradient into the backward-data pass, and always has E (efree_supported).
-// The same holds for a cell with TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH: only the tile kernels are instantiated for them.
+// The same holds for a cell with TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH: only the tile kernels are instantiated for them, and for a
+// cell without expand convolution (TFNAS_CELL_NOEXPAND): only the tile kernels have the raw-input form.
 static bool dw_tile_only(const TfnasCellDesc& d) {
-    if (act_tile_only(d.act)) return true;
+    if (act_tile_only(d.act) || cell_noexpand(d)) return true;
     for (int g = 0; g < d.G; ++g)
         if (d.g[g].k != 3 && d.g[g].k != 5) return true;
     return false;
@@ -967,8 +1003,9 @@ static int dw_reduce_wgrad(const TfnasCellDesc& d, const float* wpart, int rows,
 
 int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const double* stats1, float* D,
                   double* stats2, float* part, hipStream_t s) {
-    if (!E && (!efree_ic_ok(d.ic) || dw_tile_only(d))) return TFNAS_EINVAL;
-    const DwPlan p = dw_plan_fwd(d, E == nullptr, x != nullptr);
+    const bool raw = cell_noexpand(d);           // D = dw(x): the tile kernels' raw-input form (E and stats1 are not touched)
+    if (raw ? !x : (!E && (!efree_ic_ok(d.ic) || dw_tile_only(d)))) return TFNAS_EINVAL;
+    const DwPlan p = dw_plan_fwd(d, !raw && E == nullptr, x != nullptr);
     for (int i = 0; i < DW_NK; ++i) {
         if (!p.chunks[i]) continue;
         const int kk = 3 + 2 * i;
@@ -992,6 +1029,12 @@ int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const 
             const int tile = gm.L0 * gm.L1 * gm.CC > 2048 ? gm.L0 * gm.L1 * gm.CC : 2048;
             const size_t shm = (size_t)(tile + kk * kk * gm.CC + 2 * gm.CC) * sizeof(float);
             if (shm > 64 * 1024) return TFNAS_ERANGE;
+            if (raw)        // (no activation before the depthwise: one instantiation per K, S)
+                ok = dw_tile_dispatch<0>(kk, d.stride, TFNAS_ACT_RELU, 0, [&](auto K, auto S, auto, auto) {
+                    hipLaunchKernelGGL((k_dw_fwd<K, S, TFNAS_ACT_RELU, 0, true>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d,
+                                       nullptr, x, nullptr, D, part, gm);
+                });
+            else
             ok = dw_tile_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
                 if constexpr ((K != 7 && !act_tile_only(A)) || KQ == 0)     // (no E-free 7 x 7 / ReLU6 / hard-swish kernels: refused above)
                     hipLaunchKernelGGL((k_dw_fwd<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, E, x, stats1, D,
@@ -1006,6 +1049,7 @@ int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const 
 int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
                        const float* D, const double* stats2, const double* red2, const float* E, const float* x,
                        const double* stats1, float* dEh, double* red1, float* part, hipStream_t s, float* cb1) {
+    if (cell_noexpand(d)) return TFNAS_EINVAL;       // (launch_dw_bwd_dx)
     if (!E && (!efree_ic_ok(d.ic) || dw_tile_only(d))) return TFNAS_EINVAL;
     const size_t wout = dw_wout_size(d);
     float* wpart = part + (((size_t)p.rows * 2 * d.M + 63) & ~(size_t)63);    // (fuse_wgrad: behind the statistics partials)
@@ -1064,6 +1108,31 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
     return launch_reduce_rows(part, p.rows, 2 * d.M, 2 * (size_t)d.M, red1, nullptr, s);
 }
 
+// A cell without expand convolution (TFNAS_CELL_NOEXPAND): the depthwise backward-data pass writes the cell's dx [N*H*W][ic] itself,
+// dx = dw^T(dd) (+ dres: the residual gradient dout of a residual block, NULL otherwise).  Tile kernels only, no BN1-backward sums,
+// no partial rows, no reduction.
+int launch_dw_bwd_dx(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
+                     const double* stats2, const double* red2, const float* dres, float* dx, hipStream_t s) {
+    if (!cell_noexpand(d) || !dx) return TFNAS_EINVAL;
+    const DwPlan p = dw_plan_bwd_data(d, false, false);
+    if (p.fam != DW_TILE) return TFNAS_EINVAL;       // (never planned: dw_tile_only)
+    for (int i = 0; i < DW_NK; ++i) {
+        if (!p.chunks[i]) continue;
+        const int kk = 3 + 2 * i;
+        ProfScope _prof(TK_DW_BWD_DATA, s, false);
+        const DwGeom gm = p.tile[i];
+        const int tile = gm.L0 * gm.L1 * gm.CC > 2048 ? gm.L0 * gm.L1 * gm.CC : 2048;
+        const size_t shm = (size_t)(tile + kk * kk * gm.CC + 4 * gm.CC + 2 * gm.CC) * sizeof(float);
+        if (shm > 64 * 1024) return TFNAS_ERANGE;
+        const bool ok = dw_tile_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
+            hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, 0, true>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate, dpooled,
+                               D, stats2, red2, nullptr, dres, nullptr, dx, nullptr, gm);
+        });
+        if (!ok) return TFNAS_EINVAL;
+    }
+    return (int)hipGetLastError();
+}
+
 int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
                     const double* stats2, const double* red2, const float* E, const double* stats1, float* part,
                     hipStream_t s) {
@@ -1097,6 +1166,13 @@ int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, 
             if (tile < 4 * kr * kk * gm.CC) tile = 4 * kr * kk * gm.CC;
             const size_t shm = (size_t)(tile + 4 * gm.CC + 2 * gm.CC) * sizeof(float);
             if (shm > 64 * 1024) return TFNAS_ERANGE;
+            if (cell_noexpand(d))        // (E = the cell input x, raw)
+                dw_tile_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
+                    constexpr int KR = K == 7 ? 4 : (int)K;
+                    hipLaunchKernelGGL((k_dw_wgrad<K, S, A, KR, true>), dim3(p.rows, p.chunks[i], (K + KR - 1) / KR), dim3(256), shm,
+                                       s, d, dZ, gate, dpooled, D, stats2, red2, E, nullptr, part, wout, gm);
+                });
+            else
             dw_tile_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
                 constexpr int KR = K == 7 ? 4 : (int)K;
                 hipLaunchKernelGGL((k_dw_wgrad<K, S, A, KR>), dim3(p.rows, p.chunks[i], (K + KR - 1) / KR), dim3(256), shm, s, d,

@@ -34,6 +34,9 @@ static inline int wgrad_accum(const TfnasCellDesc& d) { return (d.flags & TFNAS_
 // TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH: the kernel families built for ReLU and Swish only (ring, register-window, E-free, fused
 // per-image, the FOLD epilogue of the project dgrad) are never planned for such a cell and refuse it if asked
 static constexpr bool act_tile_only(int act) { return act == TFNAS_ACT_RELU6 || act == TFNAS_ACT_HSWISH; }
+// TFNAS_CELL_NOEXPAND: a block without expand convolution (G = 1, mc == ic).  D = dw(x) on the raw cell input: no E, no BatchNorm
+// site 0, the depthwise passes on the raw-input form of the LDS tile kernels, dx from the depthwise backward-data pass itself
+static inline bool cell_noexpand(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_NOEXPAND) != 0; }
 // the activation fork of a launcher (inside a function returning int): the statements run with ACT = the launch's activation as a
 // compile-time constant; any other value is TFNAS_EINVAL
 #define ACT_DISPATCH(act, ...)                                                                        \
@@ -170,6 +173,9 @@ DwPlan dw_plan_bwd_data(const TfnasCellDesc& d, bool efree, bool has_x);
 int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
                        const float* D, const double* stats2, const double* red2, const float* E, const float* x,
                        const double* stats1, float* dEh, double* red1, float* part, hipStream_t s, float* cb1 = nullptr);
+// cell_noexpand(d): dx [N*H*W][ic] = dw^T(dd) (+ dres [N*H*W][ic], the residual gradient, or NULL) in one tile-kernel pass
+int launch_dw_bwd_dx(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
+                     const double* stats2, const double* red2, const float* dres, float* dx, hipStream_t s);
 int launch_reduce_bn1(const TfnasCellDesc& d, const float* part, int nb, const double* stats1, double* red1, float* cb1,
                       hipStream_t s);
 int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,

@@ -26,6 +26,7 @@ GEMM_EXPLICIT, GEMM_EVERYWHERE, CELL_LAZY_JOIN = 0x1000, 0x100, 1
 CELL_ACCUM_WGRAD = 0x20      # TfnasCellDesc.flags: the backward adds its weight gradients to their destinations
 CELL_K7 = 0x80               # TfnasCellDesc.flags: groups may have depthwise kernel size 7 (refused without the bit)
 CELL_ACTS = 0x100            # TfnasCellDesc.flags: act may be 'relu6' / 'h-swish' (refused without the bit)
+CELL_NOEXPAND = 0x200        # TfnasCellDesc.flags: the one group has no expand convolution (mid == in channels; refused without the bit)
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
 ROUTE_FX_OFF, ROUTE_FOLD_OFF, ROUTE_DWWG_OFF, ROUTE_DWWG2_OFF, ROUTE_XG_OFF, ROUTE_XG_ALL = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 ROUTE_DW = {'auto': 0, 'direct': 1 << 6, 'lds': 2 << 6, 'tiled': 3 << 6}

@@ -137,6 +137,11 @@ class HipModes:
         if any(d.g[g].k == 7 for g in range(min(d.G, _lib.MAX_GROUPS))):
             d.flags |= _lib.CELL_K7                    # (the library takes 7 x 7 groups only from callers that say they know them)
         d.flags |= _lib.act_flags(d.act)               # (... and 'relu6' / 'h-swish')
+        # ... and a block without expand convolution (D = dw(x)).  The modules build one exactly when mid > in and normalise
+        # mid to in otherwise (layers.MBInvertedResBlock: inverted_bottleneck is None), so a one-block cell descriptor of a plan
+        # with mc == ic is such a block
+        if d.mode == _lib.MODE_CELL and d.G == 1 and d.g[0].mc == d.ic:
+            d.flags |= _lib.CELL_NOEXPAND
         d.route = ENV_ROUTE if self.route is None else int(self.route)
         if self.sync is None:
             d.sync_fn, d.sync_user, d.sync_world = None, None, 0
@@ -216,12 +221,14 @@ class CellPlan:
         i = 0
         for g, b in enumerate(self.blocks):
             n = 1 if self.mode == _lib.MODE_HEAD else (7 if b.se_channels > 0 else 3)
-            for j, f in enumerate(_lib._W_FIELDS[:n]):
+            # (a block without expand convolution has no first field: TFNAS_CELL_NOEXPAND wants w_expand / g_expand NULL)
+            first = int(self.mode == _lib.MODE_CELL and getattr(b, 'inverted_bottleneck', False) is None)
+            for j, f in enumerate(_lib._W_FIELDS[first:n]):
                 setattr(d.g[g], f, params[i + j].data_ptr())
             if grads is not None:
-                for j, f in enumerate(_lib._G_FIELDS[:n]):
+                for j, f in enumerate(_lib._G_FIELDS[first:n]):
                     setattr(d.g[g], f, grads[i + j].data_ptr())
-            i += n
+            i += n - first
         d.need_wgrad = int(grads is not None)
 
 
@@ -247,7 +254,8 @@ def _cell_forward(ctx, plan, xh, N, H, W, wmix, params):
     #  TFNAS_EFREE=all drops it there too and the backward recomputes)
     efree = (EFREE and ((plan.stride == 2 and plan.ic <= 24) or EFREE_STRIDE1) and not any(ctx.needs_input_grad[3:])
              and bool(_lib.lib().tfnas_efree_supported(C.byref(d))))
-    E = None if efree else torch.empty(ws.E, device=dev, dtype=torch.float32)
+    # (ws.E == 0: a cell without expand convolution -- the library never touches E)
+    E = None if (efree or ws.E == 0) else torch.empty(ws.E, device=dev, dtype=torch.float32)
     D = torch.empty(ws.D, device=dev, dtype=torch.float32)
     Pr = torch.empty(ws.Pr, device=dev, dtype=torch.float32)
     fsmall = torch.empty(ws.fsmall, device=dev, dtype=torch.float32)
@@ -529,16 +537,19 @@ def _part(floats, dev):
 
 
 def _bn_struct(bns, training, grads=None):
-    """TfnasBnAffine for up to three nn.BatchNorm2d modules (None entries: site without affine)."""
+    """TfnasBnAffine for up to three nn.BatchNorm2d modules (None entries: site without affine, or a site that does not exist --
+    site 0 of a block without expand convolution); ``grads``: (d gamma, d beta) of the modules that are there, in order."""
     a = _lib.TfnasBnAffine()
     mom = 0.1
+    k = 0
     for i, bn in enumerate(bns):
         if bn is None:
             continue
         a.weight[i], a.bias[i] = bn.weight.data_ptr(), bn.bias.data_ptr()
         a.running_mean[i], a.running_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
         if grads is not None:
-            a.g_weight[i], a.g_bias[i] = grads[2 * i].data_ptr(), grads[2 * i + 1].data_ptr()
+            a.g_weight[i], a.g_bias[i] = grads[2 * k].data_ptr(), grads[2 * k + 1].data_ptr()
+        k += 1
         mom = 0.1 if bn.momentum is None else bn.momentum
     a.momentum = mom
     a.eval = int(not training)
@@ -595,8 +606,9 @@ def _direct_targets(params, modes):
 
 class MBConvAffineFn(torch.autograd.Function):
     """One MBInvertedResBlock of the derived network (or the stem cell: plan.mode == MODE_STEM) with affine BatchNorm.
-    inputs: plan, x, drop_scale [N] or None, bns (three nn.BatchNorm2d), training flag, n_conv, *params where
-    params = conv weights (hip_params order) followed by (gamma1, beta1, gamma2, beta2, gamma3, beta3)."""
+    inputs: plan, x, drop_scale [N] or None, bns (three nn.BatchNorm2d; a block without expand convolution: None, then two),
+    training flag, n_conv, *params where params = conv weights (hip_params order) followed by (gamma, beta) of every module of
+    bns that is there."""
 
     @staticmethod
     def forward(ctx, plan, x, drop_scale, bns, training, n_conv, *params):
@@ -612,7 +624,7 @@ class MBConvAffineFn(torch.autograd.Function):
         plan.bind(d, conv)
         dev = xh.device
         _same_device(dev, list(params) + [drop_scale], 'a block parameter')
-        E = torch.empty(ws.E, device=dev, dtype=torch.float32)
+        E = torch.empty(ws.E, device=dev, dtype=torch.float32) if ws.E else None     # (0: no expand convolution, never touched)
         D = torch.empty(ws.D, device=dev, dtype=torch.float32)
         Pr = torch.empty(ws.Pr, device=dev, dtype=torch.float32)
         fsmall = torch.empty(ws.fsmall, device=dev, dtype=torch.float32)

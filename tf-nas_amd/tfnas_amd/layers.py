@@ -82,8 +82,10 @@ def _seq(**mods):
 class MBInvertedResBlock(nn.Module):
     """MBConv block: 1x1 expand -> BN -> act -> depthwise kxk -> BN -> act -> [SE] -> 1x1 project -> BN [-> +x].
 
-    With an expand convolution (every search candidate) ``forward`` runs the fused HIP path (sampled mode of
-    ``tfnas_mixedop_fwd``); without one (only ``second_stem``: mid == in) it is a stem and uses torch ops."""
+    ``forward`` runs the fused HIP path (sampled mode of ``tfnas_mixedop_fwd``; ``affine=True``: ``tfnas_mbconv_fwd``).  With
+    ``mid_channels <= in_channels`` there is no expand convolution (``inverted_bottleneck is None``, mid normalised to in: the
+    reference's layers.py:463-482): depthwise -> BN -> act -> [SE] -> project -> BN [+ x], the library's TFNAS_CELL_NOEXPAND cell
+    with two BatchNorm sites.  (``Network._stem`` runs ``second_stem`` fused with ``first_stem`` instead.)"""
 
     def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size=3, stride=1,
                  affine=False, act_func='relu'):
@@ -120,21 +122,14 @@ class MBInvertedResBlock(nn.Module):
 
     def hip_params(self):
         """Weights in the order of TfnasGroup's pointer fields."""
-        ps = [self.inverted_bottleneck.conv.weight, self.depth_conv.conv.weight, self.point_linear.conv.weight]
+        ps = [] if self.inverted_bottleneck is None else [self.inverted_bottleneck.conv.weight]
+        ps += [self.depth_conv.conv.weight, self.point_linear.conv.weight]
         if self.squeeze_excite is not None:
             se = self.squeeze_excite
             ps += [se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias]
         return ps
 
-    def _stem_forward(self, x):
-        # second_stem (mid == in: no expand convolution) runs fused with first_stem as ONE stem cell of the HIP library
-        # (Network._stem); no stock-torch body on purpose (see ConvLayer.forward)
-        raise RuntimeError('tfnas_amd: an MBInvertedResBlock without expand convolution (second_stem) runs only as part of '
-                           'Network._stem; it has no standalone forward')
-
     def forward(self, x):
-        if self.inverted_bottleneck is None:
-            return self._stem_forward(x)
         if self._plan is None:
             self._plan = CellPlan(self.in_channels, self.out_channels, self.stride, self.act_func, [self])
         if self.affine:
@@ -142,7 +137,9 @@ class MBInvertedResBlock(nn.Module):
         return MixedOpFn.apply(self._plan, x, None, *self.hip_params())
 
     def bn_modules(self):
-        return [self.inverted_bottleneck.bn, self.depth_conv.bn, self.point_linear.bn]
+        """The block's BatchNorm modules in order: three, or two without an expand convolution."""
+        first = [] if self.inverted_bottleneck is None else [self.inverted_bottleneck.bn]
+        return first + [self.depth_conv.bn, self.point_linear.bn]
 
     def _affine_forward(self, x):
         """Derived-network block (layers.py:539-561 with affine BatchNorm; drop_connect of tools/utils.py:77-86 on the residual
@@ -157,4 +154,6 @@ class MBInvertedResBlock(nn.Module):
         bns = self.bn_modules()
         conv = self.hip_params()
         bnp = [t for m in bns for t in (m.weight, m.bias)]
+        if self.inverted_bottleneck is None:
+            bns = [None] + bns                                  # (BatchNorm site 0 does not exist)
         return MBConvAffineFn.apply(self._plan, x, ds, bns, self.training, len(conv), *conv, *bnp)

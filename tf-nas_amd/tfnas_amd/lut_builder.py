@@ -54,8 +54,11 @@ class _BlockTimer:
         d.N, d.H, d.W, d.ic, d.oc, d.stride = batch, size, size, ic, oc, stride
         d.mode, d.act, d.G, d.need_wgrad, d.eps = _lib.MODE_CELL, _lib.act_id(act), 1, 0, BN_EPS
         d.has_res = int(ic == oc and stride == 1)
+        noexp = mc <= ic             # (no expand convolution, mid normalised to in: layers.MBInvertedResBlock)
+        if noexp:
+            mc = ic
         d.g[0].mc, d.g[0].k, d.g[0].se = mc, k, se
-        d.flags = (_lib.CELL_K7 if k == 7 else 0) | _lib.act_flags(d.act)
+        d.flags = (_lib.CELL_K7 if k == 7 else 0) | _lib.act_flags(d.act) | (_lib.CELL_NOEXPAND if noexp else 0)
         _lib.check(lib.tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
         ws = _lib.TfnasCellWs()
         _lib.check(lib.tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
@@ -64,22 +67,24 @@ class _BlockTimer:
         o = 0
         for f, n in (('w_expand', mc * ic), ('w_dw', mc * k * k), ('w_proj', oc * mc), ('w_se_r', se * mc), ('b_se_r', se),
                      ('w_se_e', mc * se), ('b_se_e', mc)):
-            if n and (se or not f.endswith(('se_r', 'se_e'))):
+            if n and (se or not f.endswith(('se_r', 'se_e'))) and not (noexp and f == 'w_expand'):
                 setattr(d.g[0], f, w.data_ptr() + 4 * o)
                 o += (n + 3) // 4 * 4
         x = self._buf('x', batch * size * size * ic)
         x.normal_()
-        E, D, Pr = self._buf('E', ws.E), self._buf('D', ws.D), self._buf('Pr', ws.Pr)
+        D, Pr = self._buf('D', ws.D), self._buf('Pr', ws.Pr)
+        pE = _lib.ptr(self._buf('E', ws.E)) if ws.E else None       # (0: no expand convolution, the library never touches E)
         fs, st = self._buf('fsmall', ws.fsmall), self._buf('stats', ws.stats, torch.float64)
         part, out = self._buf('part', ws.part), self._buf('out', ws.out)
         stream = torch.cuda.current_stream(dev)
         sp = C.c_void_p(stream.cuda_stream)
         if mode == 'search':
             fn, what = lib.tfnas_mixedop_fwd, 'tfnas_mixedop_fwd'
-            args = (C.byref(d), _lib.ptr(x), None, _lib.ptr(E), _lib.ptr(D), _lib.ptr(Pr), _lib.ptr(fs), _lib.ptr(st),
+            args = (C.byref(d), _lib.ptr(x), None, pE, _lib.ptr(D), _lib.ptr(Pr), _lib.ptr(fs), _lib.ptr(st),
                     _lib.ptr(part), _lib.ptr(out), sp)
         else:
-            # eval-mode affine BatchNorm at the three sites (mc, mc, oc channels): gamma ~ 1, beta ~ 0, running mean 0 / var 1
+            # eval-mode affine BatchNorm at the three sites (mc, mc, oc channels; without expand convolution: the last two):
+            # gamma ~ 1, beta ~ 0, running mean 0 / var 1
             fn, what = lib.tfnas_mbconv_fwd, 'tfnas_mbconv_fwd'
             nb = 2 * mc + oc
             aff = self._buf('bn', 4 * nb + 64)
@@ -91,11 +96,11 @@ class _BlockTimer:
             o2 = 0
             for site, ch in enumerate((mc, mc, oc)):
                 for fi, f in enumerate(('weight', 'bias', 'running_mean', 'running_var')):
-                    getattr(bn, f)[site] = aff.data_ptr() + 4 * (fi * nb + o2)
+                    getattr(bn, f)[site] = None if (noexp and site == 0) else aff.data_ptr() + 4 * (fi * nb + o2)
                 o2 += ch
             bn.momentum, bn.eval = 0.1, 1
             self._bn = bn                                   # (keep the struct alive while its launches are enqueued)
-            args = (C.byref(d), C.byref(bn), None, _lib.ptr(x), _lib.ptr(E), _lib.ptr(D), _lib.ptr(Pr), _lib.ptr(fs),
+            args = (C.byref(d), C.byref(bn), None, _lib.ptr(x), pE, _lib.ptr(D), _lib.ptr(Pr), _lib.ptr(fs),
                     _lib.ptr(st), _lib.ptr(part), _lib.ptr(out), sp)
         for _ in range(warmup):
             _lib.check(fn(*args), what)
@@ -113,7 +118,7 @@ class _BlockTimer:
 
 
 Measurer = _BlockTimer          # public name: Measurer(device).measure(ic, mc, se, oc, k, stride, act, size, ...), k in {3, 5, 7},
-                                # act in 'relu' | 'swish' | 'relu6' | 'h-swish'
+                                # act in 'relu' | 'swish' | 'relu6' | 'h-swish'; mc <= ic: the block without expand convolution
 
 
 def lut_keys():
