@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-/* 4, additive: TFNAS_CELL_NOEXPAND -- a block without expand convolution (mid <= in channels) through tfnas_mixedop_* / tfnas_mbconv_*.
+/* 4, additive: TFNAS_CELL_FUSED -- a Fused-MBConv block (dense 3 x 3 convolution, no depthwise) through tfnas_mixedop_* / tfnas_mbconv_*.
+ * 4, additive: TFNAS_CELL_NOEXPAND -- a block without expand convolution (mid <= in channels) through tfnas_mixedop_* / tfnas_mbconv_*.
  * 4, additive: TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH in a descriptor whose flags carry TFNAS_CELL_ACTS (cells, affine blocks, head;
  * materialised route and LDS tile depthwise kernels only).
  * 4, additive: tfnas_cls_wgrad_ex (tfnas_cls_wgrad + the search epoch's running loss / top-1 / top-5 / invalid-target meter).
@@ -134,7 +135,8 @@ typedef struct TfnasCellDesc {
                                  TFNAS_CELL_ACCUM_WGRAD: the backward adds its weight gradients to their destinations;
                                  TFNAS_CELL_K7: groups may have depthwise kernel size 7;
                                  TFNAS_CELL_ACTS: act may be TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH;
-                                 TFNAS_CELL_NOEXPAND: the one group has no expand convolution                           [in]
+                                 TFNAS_CELL_NOEXPAND: the one group has no expand convolution;
+                                 TFNAS_CELL_FUSED: the one group is a Fused-MBConv block (dense 3 x 3 convolution)       [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -214,6 +216,39 @@ typedef struct TfnasCellDesc {
  * Checked by tfnas_cell_plan and again by every entry point.  The Python mirror sets it for a block whose inverted_bottleneck is
  * None (functions.HipModes.apply). */
 #define TFNAS_CELL_NOEXPAND 0x200
+/* TfnasCellDesc.flags: the caller knows Fused-MBConv blocks (EfficientNetV2, MobileNet-EdgeTPU, MnasNet-fused): ONE dense 3 x 3
+ * convolution in place of the 1 x 1 expand plus the depthwise convolution,
+ *   out = BN_b(project(SE(act(BN_a(conv3x3(x, W_f[mc][ic][3][3], stride, padding 1)))))) [+ x].
+ * Additive like TFNAS_CELL_NOEXPAND: without the bit every descriptor is accepted, refused, planned, routed and launched exactly
+ * as before it existed.  With it the descriptor describes ONE such block:
+ *   geometry   mode == TFNAS_MODE_CELL, G == 1, g[0].k == 3, stride 1 | 2, ic a multiple of 4, any g[0].mc >= 1 (ragged widths
+ *              included), se 0 or a multiple of 4, all four activations (two with TFNAS_CELL_ACTS), has_res as for any cell.
+ *              g[0].w_expand / g_expand hold the dense weight / its gradient in torch's OIHW order [mc][ic][3][3]; g[0].w_dw and
+ *              g[0].g_dw are NULL.  Two groups, k != 3, a depthwise pointer, the bit together with TFNAS_CELL_NOEXPAND, stem or
+ *              head mode are TFNAS_EINVAL, and so is tfnas_path_plan on a cell that carries the bit.  A width whose
+ *              weight-gradient partial row (9 ic mc floats) does not fit the partial-row scratch, or whose repacked weight
+ *              (9 ic mcp floats) does not fit it next to 128 statistics rows of 2 M floats, is TFNAS_ERANGE at plan time (the
+ *              widest block of the supernet, 192 -> 1536, fits); the depthwise-only limits do not apply.
+ *              No bias, no 5 x 5 / 7 x 7, always a project convolution.
+ *   arithmetic D = conv3x3(x) on the raw cell input in the launch's GEMM mode (gemm_mode: split-bf16 by default, fp32 or bf16 on
+ *              request, fp32 accumulation; the weight gradient always in fp32 MFMA like every weight gradient of the library).
+ *              Everything after D is the ordinary cell: BN_a / BN_b are BatchNorm sites 1 and 2.
+ *   workspace  tfnas_cell_ws reports E = 0 and dxp = 4.  The entry points accept E == NULL (dxp too) and never touch E, stats1,
+ *              red1 or cb1.  The convolution writes D at Ho x Wo.  dEh keeps its size [N*H*W][M]: after the SE backward has used
+ *              it as scratch it holds dd, the gradient w.r.t. D [N*Ho*Wo][M], which the weight-gradient and the data-gradient
+ *              GEMM both read.  The backward writes dx [N*H*W][ic] from the data-gradient GEMM, the residual gradient added in
+ *              the same store (in the affine form with drop-connect: the unscaled dout); dx == NULL skips that launch.
+ *   routes     tfnas_efree_supported and tfnas_fx_supported return 0, tfnas_cell_route returns TFNAS_ROUTE_TAKEN_VALID.
+ *              TFNAS_ROUTE_DW_*, TFNAS_ROUTE_XG_* and TFNAS_ROUTE_GRAM2 mean nothing to it and are ignored; the SE, FOLD and
+ *              TFNAS_ROUTE_WGRAD_INLINE bits are honoured; weight-gradient fork 2 (wgrad_stream[2]) is never used: the SE and
+ *              the convolution weight gradients share fork 1.
+ *   modes      tfnas_mixedop_fwd/bwd (sampled form, wmix == NULL) and tfnas_mbconv_fwd/bwd; TFNAS_CELL_ACCUM_WGRAD,
+ *              TFNAS_CELL_LAZY_JOIN, wgrad_stream[], the GEMM modes, the sync-stats hook (two forward tables, two backward
+ *              tables), need_wgrad = 0 and dx == NULL as for any cell.
+ *   affine     BatchNorm site 0 does not exist: every site-0 pointer of TfnasBnAffine must be NULL (else TFNAS_EINVAL).
+ * Checked by tfnas_cell_plan and again by every entry point.  The Python mirror sets it for a one-block plan whose block is a
+ * layers.FusedMBConvBlock (functions.HipModes.apply). */
+#define TFNAS_CELL_FUSED 0x400
 /* TfnasCellDesc.route (ABI 4; rounds 2-5 read these from TFNAS_* environment variables latched once per process) */
 #define TFNAS_ROUTE_FX_OFF 0x1        /* frozen-weight launches of the 14 x 14 / 7 x 7 cells through the materialised route instead
                                          of the fused per-image kernels (csrc/fx_kernels.hip)                                   */

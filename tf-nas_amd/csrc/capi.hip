@@ -165,6 +165,15 @@ static int check_noexpand(const TfnasCellDesc* d) {
     return 0;
 }
 
+// TFNAS_CELL_FUSED: one Fused-MBConv block -- cell mode, one group with a dense 3 x 3 weight (w_expand), no depthwise pointer
+static int check_fused(const TfnasCellDesc* d) {
+    if (!(d->flags & TFNAS_CELL_FUSED)) return 0;
+    if (d->flags & TFNAS_CELL_NOEXPAND) return TFNAS_EINVAL;
+    if (d->mode != TFNAS_MODE_CELL || d->G != 1) return TFNAS_EINVAL;
+    if (d->g[0].k != 3 || d->g[0].w_dw || d->g[0].g_dw) return TFNAS_EINVAL;
+    return 0;
+}
+
 // the per-launch modes of a descriptor (callers may change them between tfnas_cell_plan and a launch: every entry point re-checks)
 static int check_modes(const TfnasCellDesc* d) {
     TRY(check_act(d));
@@ -172,9 +181,11 @@ static int check_modes(const TfnasCellDesc* d) {
         const int gm = d->gemm_mode & ~(TFNAS_GEMM_EXPLICIT | TFNAS_GEMM_EVERYWHERE);
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
-    if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS | TFNAS_CELL_NOEXPAND))
+    if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS | TFNAS_CELL_NOEXPAND |
+                     TFNAS_CELL_FUSED))
         return TFNAS_EINVAL;
     TRY(check_noexpand(d));
+    TRY(check_fused(d));
     if (!(d->flags & TFNAS_CELL_K7)) {            // kernel size 7 is opt-in: without the bit it is refused as it always was
         for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g)
             if (d->g[g].k == 7) return TFNAS_EINVAL;
@@ -186,6 +197,8 @@ static int check_modes(const TfnasCellDesc* d) {
     if (d->sync_fn && d->sync_world < 1) return TFNAS_ERANGE;
     return 0;
 }
+
+static bool wgrad_row_fits(const TfnasCellDesc& d) { return cell_fused(d) ? conv_wgrad_row_fits(d) : dw_wgrad_row_fits(d); }
 
 extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
     if (!d) return TFNAS_ENULL;
@@ -233,19 +246,20 @@ extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
     d->M = off;
     d->SE = se_off;
     if ((double)d->N * d->H * d->W >= 2147483647.0) return TFNAS_ERANGE;   // row indices are int, offsets size_t
-    if (!dw_wgrad_row_fits(*d)) return TFNAS_ERANGE;     // one row of depthwise weight-gradient partials (sum of mc * k * k)
+    // one row of weight-gradient partials: depthwise (sum of mc * k * k); Fused-MBConv: the dense weight instead (9 ic mc)
+    if (!wgrad_row_fits(*d)) return TFNAS_ERANGE;
     return 0;
 }
 
 extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     if (!d || !ws) return TFNAS_ENULL;
     memset(ws, 0, sizeof(*ws));
-    if (!dw_wgrad_row_fits(*d)) return TFNAS_ERANGE;
+    if (!wgrad_row_fits(*d)) return TFNAS_ERANGE;
     const uint64_t P = (uint64_t)d->N * d->H * d->W, Po = (uint64_t)d->N * d->Ho * d->Wo;
     const uint64_t M = d->M, N = d->N, SE = d->SE, G = d->G, oc = d->oc;
     // the four stream tensors: P*M / Po*M fp32 elements
-    const bool noexp = (d->flags & TFNAS_CELL_NOEXPAND) != 0;
-    ws->E = noexp ? 0 : P * M;                   // (no expand convolution: D = dw(x), nothing to save)
+    const bool noexp = (d->flags & (TFNAS_CELL_NOEXPAND | TFNAS_CELL_FUSED)) != 0;
+    ws->E = noexp ? 0 : P * M;                   // (no expand convolution: D = dw(x) / D = conv3x3(x), nothing to save)
     ws->D = Po * M;
     ws->Pr = G * Po * oc;
     ws->off_pooled = 0;
@@ -259,7 +273,8 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     ws->out = Po * oc;
     ws->dZ = Po * M;
     ws->dEh = P * M;                             // (an expand-free cell keeps it: scratch of the project dgrad's epilogue records and
-                                                 //  of the SE backward's K-split partials, never a gradient tensor)
+                                                 //  of the SE backward's K-split partials, never a gradient tensor; a Fused-MBConv
+                                                 //  cell then keeps dd [N*Ho*Wo][M] there)
     ws->off_dgate = 0;
     ws->off_dpooled = N * M;
     ws->off_dgl = 2 * N * M;
@@ -299,9 +314,9 @@ static void bn_site(const TfnasCellDesc& d, int site, int& nch, uint64_t& cnt) {
     nch = site == 2 ? d.oc : d.g[0].mc;
     cnt = site == 0 ? P : Po;
 }
-// an expand-free block has no BatchNorm site 0: every site-0 pointer of its TfnasBnAffine must be NULL
+// an expand-free block and a Fused-MBConv block have no BatchNorm site 0: every site-0 pointer of their TfnasBnAffine must be NULL
 static int check_bn_sites(const TfnasCellDesc& d, const TfnasBnAffine* bn) {
-    if (!cell_noexpand(d)) return 0;
+    if (!cell_noexpand(d) && !cell_fused(d)) return 0;
     if (bn->weight[0] || bn->bias[0] || bn->g_weight[0] || bn->g_bias[0] || bn->running_mean[0] || bn->running_var[0])
         return TFNAS_EINVAL;
     return 0;
@@ -334,7 +349,10 @@ int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdB
     if (route) *route = taken;
     const bool fx = (taken & TFNAS_ROUTE_TAKEN_FX) != 0;
     const bool sync = !(bn && bn->eval);          // (eval mode normalises with the running statistics: nothing to reduce)
-    if (cell_noexpand(d)) {
+    if (cell_fused(d)) {
+        // Fused-MBConv: one dense 3 x 3 convolution of the raw cell input writes D and the BN_a statistics (no E, no stats1)
+        TRY(launch_conv_fwd(d, b.x, b.D, stats2, b.part, s));
+    } else if (cell_noexpand(d)) {
         // no expand convolution, no BatchNorm site 0: the depthwise reads the raw cell input (E and stats1 are not touched)
         TRY(launch_dw_fwd(d, nullptr, b.x, nullptr, b.D, stats2, b.part, s));
     } else {
@@ -436,7 +454,7 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
     if (d.need_wgrad) {
         for (int g = 0; g < d.G; ++g) {
             const TfnasGroup& gr = d.g[g];
-            if ((!gr.g_expand && !cell_noexpand(d)) || !gr.g_dw || !gr.g_proj) return TFNAS_ENULL;
+            if ((!gr.g_expand && !cell_noexpand(d)) || (!gr.g_dw && !cell_fused(d)) || !gr.g_proj) return TFNAS_ENULL;
             if (gr.se > 0 && (!gr.g_se_r || !gr.gb_se_r || !gr.g_se_e || !gr.gb_se_e)) return TFNAS_ENULL;
         }
     }
@@ -471,6 +489,18 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
     else TRY(launch_bn2_bwd(d, b.dZ, b.D, stats2, gate, dpooled, red2, part, s));
     TRY(stats_sync(d, red2, 2 * (size_t)d.M, s));
     if (bn) TRY(bn_bwd_fix(d0, bn, 1, red2, s));
+    if (cell_fused(d)) {
+        // Fused-MBConv: dd, the gradient w.r.t. D, goes to dEh once (free since the SE backward above); the convolution's weight
+        // gradient and its data gradient (which writes dx, + the unscaled residual gradient) both read it
+        TRY(launch_conv_dd(d, b.dZ, b.D, gate, dpooled, stats2, red2, b.dEh, s));
+        if (d.need_wgrad) {
+            hipStream_t sw = fork_to(so, 1, s);
+            if (d.SE > 0) TRY(launch_se_wgrad(d, dgate, gate, dhpre, hpre, pooled, sw));
+            TRY(launch_conv_wgrad(d, b.dEh, b.x, part_w1, sw));
+        }
+        if (b.dx) TRY(launch_conv_dgrad(d, b.dEh, d.has_res ? dout_res : nullptr, b.dx, part, s));
+        return 0;
+    }
     if (cell_noexpand(d)) {
         // no expand convolution: the depthwise weight gradient reads the raw cell input, and the depthwise backward-data pass
         // writes dx itself (+ the unscaled residual gradient); no BN1 backward, no Gram operator, no expand dgrad / wgrad
@@ -527,7 +557,7 @@ extern "C" int tfnas_mixedop_fwd(const TfnasCellDesc* dp, const float* x, const 
     if (d.mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_modes(dp));
     // E may be omitted only in E-free mode (tfnas_efree_supported) and by an expand-free cell, which never touches it
-    if (!E && !efree_supported(d) && !cell_noexpand(d)) return TFNAS_ENULL;
+    if (!E && !efree_supported(d) && !cell_noexpand(d) && !cell_fused(d)) return TFNAS_ENULL;
     TfnasCellWs ws;
     TRY(tfnas_cell_ws(dp, &ws));
     CellFwdBufs b = {x, wmix, E, D, Pr, fsmall, stats, part, out};
@@ -575,7 +605,7 @@ extern "C" int tfnas_mixedop_bwd(const TfnasCellDesc* dp, const float* x, const 
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_modes(dp));
-    if (!E && !efree_supported(d) && !cell_noexpand(d)) return TFNAS_ENULL;
+    if (!E && !efree_supported(d) && !cell_noexpand(d) && !cell_fused(d)) return TFNAS_ENULL;
     CellBwdBufs b = {x, wmix, E, D, Pr, fsmall, stats, dout, dZ, dEh, bsmall, red, part, part + TFNAS_PART_ALLOC,
                      dx, dxp, dwmix, nullptr, nullptr};
     return cell_bwd_entry(d, b, S(stream), d.wgrad_stream, false);
@@ -588,7 +618,7 @@ extern "C" int tfnas_mbconv_fwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD || d.G != 1) return TFNAS_EINVAL;
     TRY(check_modes(dp));
-    if (!E && !cell_noexpand(d)) return TFNAS_ENULL;
+    if (!E && !cell_noexpand(d) && !cell_fused(d)) return TFNAS_ENULL;
     TRY(check_bn_sites(d, bn));
     TfnasCellWs ws;
     TRY(tfnas_cell_ws(dp, &ws));
@@ -608,7 +638,7 @@ extern "C" int tfnas_mbconv_bwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn
     if (d.mode == TFNAS_MODE_HEAD || d.G != 1) return TFNAS_EINVAL;
     if (d.wgrad_stream[0] || d.wgrad_stream[1] || d.wgrad_stream[2]) return TFNAS_EINVAL;     // (tfnas_mixedop_bwd only)
     TRY(check_modes(dp));
-    if (!E && !cell_noexpand(d)) return TFNAS_ENULL;
+    if (!E && !cell_noexpand(d) && !cell_fused(d)) return TFNAS_ENULL;
     TRY(check_bn_sites(d, bn));
     CellBwdBufs b = {x, nullptr, E, D, Pr, fsmall, stats, dout, dZ, dEh, bsmall, red, part, part + TFNAS_PART_ALLOC,
                      dx, dxp, nullptr, nullptr, nullptr};
@@ -652,6 +682,7 @@ extern "C" int tfnas_head_affine_fwd(const TfnasCellDesc* dp, const TfnasBnAffin
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
     TRY(check_noexpand(dp));
+    TRY(check_fused(dp));
     return head_fwd_impl(*dp, bn, x, E, stats, part, pooled, S(stream));
 }
 
@@ -662,6 +693,7 @@ extern "C" int tfnas_head_affine_bwd(const TfnasCellDesc* dp, const TfnasBnAffin
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
     TRY(check_noexpand(dp));
+    TRY(check_fused(dp));
     if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
     return head_bwd_impl(*dp, bn, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
@@ -672,6 +704,7 @@ extern "C" int tfnas_head_fwd(const TfnasCellDesc* dp, const float* x, float* E,
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
     TRY(check_noexpand(dp));
+    TRY(check_fused(dp));
     return head_fwd_impl(*dp, nullptr, x, E, stats, part, pooled, S(stream));
 }
 
@@ -682,6 +715,7 @@ extern "C" int tfnas_head_bwd(const TfnasCellDesc* dp, const float* x, const flo
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
     TRY(check_noexpand(dp));
+    TRY(check_fused(dp));
     if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
     return head_bwd_impl(*dp, nullptr, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
@@ -693,6 +727,7 @@ extern "C" int tfnas_head_wgrad(const TfnasCellDesc* dp, const float* x, const f
     if (d.mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_act(dp));
     TRY(check_noexpand(dp));
+    TRY(check_fused(dp));
     if (!d.g[0].g_expand) return TFNAS_ENULL;
     return launch_expand_wgrad(d, dEh, E, cb1, x, part, S(stream));
 }

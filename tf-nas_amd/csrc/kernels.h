@@ -37,6 +37,9 @@ static constexpr bool act_tile_only(int act) { return act == TFNAS_ACT_RELU6 || 
 // TFNAS_CELL_NOEXPAND: a block without expand convolution (G = 1, mc == ic).  D = dw(x) on the raw cell input: no E, no BatchNorm
 // site 0, the depthwise passes on the raw-input form of the LDS tile kernels, dx from the depthwise backward-data pass itself
 static inline bool cell_noexpand(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_NOEXPAND) != 0; }
+// TFNAS_CELL_FUSED: a Fused-MBConv block (G = 1, k = 3): D = conv3x3(x) with the dense OIHW weight in w_expand, no depthwise
+// weight, no E, no BatchNorm site 0; the three implicit GEMMs of conv_kernels.hip stand where the depthwise passes stand
+static inline bool cell_fused(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_FUSED) != 0; }
 // the activation fork of a launcher (inside a function returning int): the statements run with ACT = the launch's activation as a
 // compile-time constant; any other value is TFNAS_EINVAL
 #define ACT_DISPATCH(act, ...)                                                                        \
@@ -181,6 +184,20 @@ int launch_reduce_bn1(const TfnasCellDesc& d, const float* part, int nb, const d
 int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
                     const double* stats2,
                     const double* red2, const float* E, const double* stats1, float* part, hipStream_t s);
+
+// conv_kernels.hip: the dense 3x3 convolution of a cell_fused(d) block, x [N*H*W][ic] NHWC, weight OIHW in g[0].w_expand
+// forward: D [N*Ho*Wo][M] and the BatchNorm statistics of D (partial rows in `part`, reduced into stats2; the repacked weight at
+// the top of `part`)
+int launch_conv_fwd(const TfnasCellDesc& d, const float* x, float* D, double* stats2, float* part, hipStream_t s);
+// dd [N*Ho*Wo][M] = the gradient w.r.t. D (BatchNorm + activation + SE gate backward of dZ), pad columns zero
+int launch_conv_dd(const TfnasCellDesc& d, const float* dZ, const float* D, const float* gate, const float* dpooled,
+                   const double* stats2, const double* red2, float* dd, hipStream_t s);
+// g[0].g_expand (OIHW) = or += the weight gradient, K-split over pixels through `part`
+int launch_conv_wgrad(const TfnasCellDesc& d, const float* dd, const float* x, float* part, hipStream_t s);
+bool conv_wgrad_row_fits(const TfnasCellDesc& d);     // the partial weight gradient of one split (9 ic mc floats) fits the partials
+                                                       // region, the repacked weight next to 128 statistics rows (tfnas_cell_plan: else TFNAS_ERANGE)
+// dx [N*H*W][ic] = conv^T(dd) (+ dres [N*H*W][ic], the residual gradient, or NULL); `part`: scratch of the repacked weight
+int launch_conv_dgrad(const TfnasCellDesc& d, const float* dd, const float* dres, float* dx, float* part, hipStream_t s);
 
 // pointwise_kernels.hip (SE squeeze, BN2 backward statistics, mixing epilogue, BN constant tables)
 // se_kernels.hip (SE excite FCs as small GEMMs: launch_se_fc_fwd / launch_se_fc_bwd / launch_se_wgrad)

@@ -77,6 +77,7 @@ int plan_path(PathCtx& c, const TfnasPathDesc& in, TfnasPathWs* out) {
         TfnasCellDesc& d = pd.cell[i];
         if (d.mode != TFNAS_MODE_CELL) return TFNAS_EINVAL;
         if (d.flags & TFNAS_CELL_NOEXPAND) return TFNAS_EINVAL;   // (expand-free blocks run through the per-cell entry points only)
+        if (d.flags & TFNAS_CELL_FUSED) return TFNAS_EINVAL;      // (Fused-MBConv blocks too)
         if (!pd.soft && d.G != 1) return TFNAS_EINVAL;            // a sampled path evaluates one candidate per cell
         if (i > 0) {
             const TfnasCellDesc& p = pd.cell[i - 1];

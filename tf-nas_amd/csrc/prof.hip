@@ -14,7 +14,7 @@ static const char* kNames[TK_COUNT] = {
     "k_expand_fwd", "k_dw_fwd", "k_se_pool<fwd>", "k_se_fc_fwd", "k_project_fwd", "k_mix_fwd",
     "k_mix_bwd_stats", "k_project_dgrad", "k_project_wgrad", "k_se_pool<bwd>", "k_se_fc_bwd", "k_se_wgrad",
     "k_bn2_bwd", "k_dw_bwd_data", "k_dw_wgrad", "k_expand_dgrad", "k_expand_wgrad", "small(arch/sink/consts)",
-    "k_reduce_rows"};
+    "k_reduce_rows", "k_conv_fwd", "k_conv_dgrad", "k_conv_wgrad", "k_conv_dd"};
 
 ProfScope::ProfScope(int id_, hipStream_t s_, bool soft_) : id(id_), s(s_), e0(nullptr), on(false), soft(soft_) {
     if (g_mask & (1u << id)) {

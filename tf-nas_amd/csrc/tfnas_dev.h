@@ -101,6 +101,44 @@ __device__ __forceinline__ f32x4 ld4_guard(const float* base, int idx, int lim, 
     return r;
 }
 
+// ---------------------------------------------------------------------------- BN2-backward operand
+// From dZ (gradient w.r.t. the gated activation that feeds the project conv) to dd (gradient w.r.t. the raw depthwise
+// output D), i.e. the backward of  D -> BN2 -> act -> (* gate, SE pool path):
+//   dhat = (D - mean2) * rstd2 ; da = dZ*gate + dpooled/HW  (SE groups; else dZ) ; ddh = da * act'(dhat)
+//   dd   = rstd2 * (ddh - R1/Po - dhat * R2/Po)            R1 = sum ddh, R2 = sum ddh*dhat  (k_bn2_bwd)
+// cst2[c] = (mean2, rstd2, R1/Po, R2/Po).  ddh is recomputed here instead of being written back by k_bn2_bwd
+// (saves one write + nothing extra to read: dZ replaces ddh).
+template <int ACT>
+__device__ __forceinline__ f32x4 bn2_dd(const f32x4* cst2, int cl, f32x4 dz, f32x4 dv, bool has_se, f32x4 gate4,
+                                        f32x4 dpool4) {
+    f32x4 r;
+    if (has_se) dz = dz * gate4 + dpool4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const f32x4 t = cst2[cl + j];
+        const float dh = (dv[j] - t.x) * t.y;
+        const float ddh = dz[j] * act_d<ACT>(dh);
+        r[j] = t.y * (ddh - t.z - dh * t.w);
+    }
+    return r;
+}
+__device__ __forceinline__ void fill_cst2(f32x4* cst2, const TfnasCellDesc& d, int CC, int c0, int mc, int off,
+                                          const double* stats2, const double* red2) {
+    const int tid = threadIdx.x;
+    if (tid < CC) {
+        f32x4 t = zero4();
+        if (c0 + tid < mc) {
+            const double inv = 1.0 / ((double)d.N * d.Ho * d.Wo);
+            const float2 c = bn_consts(stats2 + 2 * (size_t)(off + c0 + tid), inv, d.eps);
+            t.x = c.x;
+            t.y = c.y;
+            t.z = (float)(red2[2 * (size_t)(off + c0 + tid) + 0] * inv);
+            t.w = (float)(red2[2 * (size_t)(off + c0 + tid) + 1] * inv);
+        }
+        cst2[tid] = t;
+    }
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -27,6 +27,7 @@ CELL_ACCUM_WGRAD = 0x20      # TfnasCellDesc.flags: the backward adds its weight
 CELL_K7 = 0x80               # TfnasCellDesc.flags: groups may have depthwise kernel size 7 (refused without the bit)
 CELL_ACTS = 0x100            # TfnasCellDesc.flags: act may be 'relu6' / 'h-swish' (refused without the bit)
 CELL_NOEXPAND = 0x200        # TfnasCellDesc.flags: the one group has no expand convolution (mid == in channels; refused without the bit)
+CELL_FUSED = 0x400           # TfnasCellDesc.flags: the one group is a Fused-MBConv block (dense 3 x 3 weight in w_expand, no depthwise)
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
 ROUTE_FX_OFF, ROUTE_FOLD_OFF, ROUTE_DWWG_OFF, ROUTE_DWWG2_OFF, ROUTE_XG_OFF, ROUTE_XG_ALL = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 ROUTE_DW = {'auto': 0, 'direct': 1 << 6, 'lds': 2 << 6, 'tiled': 3 << 6}

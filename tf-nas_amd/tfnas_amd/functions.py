@@ -140,7 +140,11 @@ class HipModes:
         # ... and a block without expand convolution (D = dw(x)).  The modules build one exactly when mid > in and normalise
         # mid to in otherwise (layers.MBInvertedResBlock: inverted_bottleneck is None), so a one-block cell descriptor of a plan
         # with mc == ic is such a block
-        if d.mode == _lib.MODE_CELL and d.G == 1 and d.g[0].mc == d.ic:
+        # ``d.fused_block`` (set by CellPlan.desc on the descriptors of a plan whose one block is a layers.FusedMBConvBlock): a
+        # dense 3 x 3 convolution, whatever its width
+        if getattr(d, 'fused_block', False) and d.mode == _lib.MODE_CELL and d.G == 1:
+            d.flags |= _lib.CELL_FUSED
+        elif d.mode == _lib.MODE_CELL and d.G == 1 and d.g[0].mc == d.ic:
             d.flags |= _lib.CELL_NOEXPAND
         d.route = ENV_ROUTE if self.route is None else int(self.route)
         if self.sync is None:
@@ -175,6 +179,11 @@ class CellPlan:
     def __init__(self, ic, oc, stride, act, blocks, mode=_lib.MODE_CELL, modes=None):
         self.ic, self.oc, self.stride, self.act = ic, oc, stride, act
         self.blocks = list(blocks)                     # MBInvertedResBlock modules (parameter containers)
+        # a plan of ONE layers.FusedMBConvBlock (TFNAS_CELL_FUSED); among several candidates the library has no such launch
+        self.fused = any(getattr(b, 'fused', False) for b in self.blocks)
+        if self.fused and (len(self.blocks) != 1 or mode != _lib.MODE_CELL):
+            raise NotImplementedError('tfnas_amd: a FusedMBConvBlock runs as a one-block cell only (not as a candidate of a '
+                                      'multi-candidate MixedOP launch, a stem or a head)')
         self._modes = modes
         self.mode = mode
         self.has_res = int(mode == _lib.MODE_CELL and ic == oc and stride == 1)
@@ -207,6 +216,7 @@ class CellPlan:
             d.act, d.has_res, d.G, d.need_wgrad, d.eps = _lib.act_id(self.act), self.has_res, len(self.blocks), 0, BN_EPS
             for g, b in enumerate(self.blocks):
                 d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
+            d.fused_block = self.fused                 # (a Python-side mark, not a field of the C struct: HipModes.apply)
             self.modes.apply(d)                        # (before the plan: it validates the modes; every launch re-checks them)
             check(_lib.lib().tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
             ws = TfnasCellWs()
@@ -222,13 +232,16 @@ class CellPlan:
         for g, b in enumerate(self.blocks):
             n = 1 if self.mode == _lib.MODE_HEAD else (7 if b.se_channels > 0 else 3)
             # (a block without expand convolution has no first field: TFNAS_CELL_NOEXPAND wants w_expand / g_expand NULL)
-            first = int(self.mode == _lib.MODE_CELL and getattr(b, 'inverted_bottleneck', False) is None)
-            for j, f in enumerate(_lib._W_FIELDS[first:n]):
-                setattr(d.g[g], f, params[i + j].data_ptr())
+            first = int(self.mode == _lib.MODE_CELL and not getattr(b, 'fused', False)
+                        and getattr(b, 'inverted_bottleneck', False) is None)
+            # (a Fused-MBConv block: the dense weight in the expand field, no depthwise field -- TFNAS_CELL_FUSED wants it NULL)
+            keep = [j for j in range(first, n) if not (self.fused and j == 1)]
+            for j, k in enumerate(keep):
+                setattr(d.g[g], _lib._W_FIELDS[k], params[i + j].data_ptr())
             if grads is not None:
-                for j, f in enumerate(_lib._G_FIELDS[first:n]):
-                    setattr(d.g[g], f, grads[i + j].data_ptr())
-            i += n - first
+                for j, k in enumerate(keep):
+                    setattr(d.g[g], _lib._G_FIELDS[k], grads[i + j].data_ptr())
+            i += len(keep)
         d.need_wgrad = int(grads is not None)
 
 

@@ -5,6 +5,9 @@ Only what the search hot path touches is provided:
                       (``inverted_bottleneck.conv``, ``depth_conv.conv``, ``squeeze_excite.conv_reduce/conv_expand``,
                       ``point_linear.conv``) so that train_search.py:164-193's ``exec`` weight slicing and the
                       state_dict keys (:244-258) keep working.  Its arithmetic runs in the HIP library.
+  FusedMBConvBlock    (no counterpart in the reference) -- the Fused-MBConv block of EfficientNetV2 / MobileNet-EdgeTPU / MnasNet:
+                      one dense 3x3 convolution in place of the 1x1 expand plus the depthwise; sub-modules ``fused_conv.conv``,
+                      ``squeeze_excite.conv_reduce/conv_expand``, ``point_linear.conv``.
   ConvLayer / LinearLayer (models/layers.py:190-271, :322-428) -- parameter containers of the stems and the head; inside
                       Network they run as HIP cells (TFNAS_MODE_STEM / _HEAD), the classifier is an nn.Linear.
   Swish               (models/layers.py:26-35)
@@ -79,7 +82,43 @@ def _seq(**mods):
     return nn.Sequential(OrderedDict(mods))
 
 
-class MBInvertedResBlock(nn.Module):
+class _HipBlock(nn.Module):
+    """What the blocks that run as ONE cell of the HIP library share: the launch (search form through ``tfnas_mixedop_fwd``,
+    ``affine=True`` through ``tfnas_mbconv_fwd``) and drop-connect.  A subclass provides ``hip_params()``, ``bn_modules()`` and
+    ``bn_sites()``; ``fused`` tells ``CellPlan`` which kind of cell the block is."""
+
+    fused = False                    # (True: TFNAS_CELL_FUSED -- the dense weight in the expand field, no depthwise field)
+
+    def forward(self, x):
+        if self._plan is None:
+            self._plan = CellPlan(self.in_channels, self.out_channels, self.stride, self.act_func, [self])
+        if self.affine:
+            return self._affine_forward(x)
+        return MixedOpFn.apply(self._plan, x, None, *self.hip_params())
+
+    def bn_sites(self):
+        """The three BatchNorm sites of the cell: the block's modules, None where a site does not exist."""
+        raise NotImplementedError
+
+    def _drop_scale(self, x):
+        """Per-image drop-connect scale of the residual block in training (tools/utils.py:77-86), else None."""
+        if not (self.training and self.has_residual and self.drop_connect_rate > 0.0):
+            return None
+        keep = 1.0 - self.drop_connect_rate
+        u = getattr(self, 'drop_u', None)                   # (tests inject the uniform draws)
+        u = torch.rand(x.size(0), dtype=x.dtype, device=x.device) if u is None else u.to(x.device)
+        return torch.floor(keep + u) / keep
+
+    def _affine_forward(self, x):
+        """Derived-network block (layers.py:539-561 with affine BatchNorm; drop_connect of tools/utils.py:77-86 on the residual
+        branch in training) -- tfnas_mbconv_fwd/bwd."""
+        from .functions import MBConvAffineFn
+        conv = self.hip_params()
+        bnp = [t for m in self.bn_modules() for t in (m.weight, m.bias)]
+        return MBConvAffineFn.apply(self._plan, x, self._drop_scale(x), self.bn_sites(), self.training, len(conv), *conv, *bnp)
+
+
+class MBInvertedResBlock(_HipBlock):
     """MBConv block: 1x1 expand -> BN -> act -> depthwise kxk -> BN -> act -> [SE] -> 1x1 project -> BN [-> +x].
 
     ``forward`` runs the fused HIP path (sampled mode of ``tfnas_mixedop_fwd``; ``affine=True``: ``tfnas_mbconv_fwd``).  With
@@ -129,31 +168,67 @@ class MBInvertedResBlock(nn.Module):
             ps += [se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias]
         return ps
 
-    def forward(self, x):
-        if self._plan is None:
-            self._plan = CellPlan(self.in_channels, self.out_channels, self.stride, self.act_func, [self])
-        if self.affine:
-            return self._affine_forward(x)
-        return MixedOpFn.apply(self._plan, x, None, *self.hip_params())
-
     def bn_modules(self):
         """The block's BatchNorm modules in order: three, or two without an expand convolution."""
         first = [] if self.inverted_bottleneck is None else [self.inverted_bottleneck.bn]
         return first + [self.depth_conv.bn, self.point_linear.bn]
 
-    def _affine_forward(self, x):
-        """Derived-network block (layers.py:539-561 with affine BatchNorm; drop_connect of tools/utils.py:77-86 on the residual
-        branch in training) -- tfnas_mbconv_fwd/bwd."""
-        from .functions import MBConvAffineFn
-        ds = None
-        if self.training and self.has_residual and self.drop_connect_rate > 0.0:
-            keep = 1.0 - self.drop_connect_rate
-            u = getattr(self, 'drop_u', None)                   # (tests inject the uniform draws)
-            u = torch.rand(x.size(0), dtype=x.dtype, device=x.device) if u is None else u.to(x.device)
-            ds = torch.floor(keep + u) / keep
+    def bn_sites(self):
         bns = self.bn_modules()
-        conv = self.hip_params()
-        bnp = [t for m in bns for t in (m.weight, m.bias)]
-        if self.inverted_bottleneck is None:
-            bns = [None] + bns                                  # (BatchNorm site 0 does not exist)
-        return MBConvAffineFn.apply(self._plan, x, ds, bns, self.training, len(conv), *conv, *bnp)
+        return bns if self.inverted_bottleneck is not None else [None] + bns     # (no expand: BatchNorm site 0 does not exist)
+
+
+class FusedMBConvBlock(_HipBlock):
+    """Fused-MBConv block: dense 3x3 conv (stride, padding 1, no bias) -> BN -> act -> [SE] -> 1x1 project -> BN [-> +x].
+
+    ``forward`` runs the HIP path as an MBInvertedResBlock does -- the library's TFNAS_CELL_FUSED cell (three implicit GEMMs of
+    csrc/conv_kernels.hip where the depthwise passes stand), two BatchNorm sites; the search form through ``tfnas_mixedop_fwd``,
+    ``affine=True`` (derived form, drop-connect on the residual branch in training) through ``tfnas_mbconv_fwd``.  Only as a
+    block of its own: not a candidate of a multi-candidate MixedOP, kernel size 3 only, always with a project convolution."""
+
+    fused = True                     # (CellPlan: TFNAS_CELL_FUSED, the dense weight in the expand field)
+
+    def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size=3, stride=1,
+                 affine=False, act_func='relu'):
+        super().__init__()
+        act_id(act_func)                                   # (ValueError for a name the library has no kernels for)
+        if kernel_size != 3:
+            raise NotImplementedError('tfnas_amd: FusedMBConvBlock has kernel size 3 only (got %r)' % (kernel_size,))
+        if in_channels % 4 or mid_channels < 1:
+            raise ValueError('tfnas_amd: FusedMBConvBlock wants in_channels a multiple of 4 and mid_channels >= 1')
+        self.in_channels, self.mid_channels = in_channels, mid_channels
+        self.se_channels, self.out_channels = se_channels, out_channels
+        self.kernel_size, self.stride, self.act_func = kernel_size, stride, act_func
+        self.affine = affine
+        self.drop_connect_rate = 0.0
+        def bn(ch):
+            return dict(bn=nn.BatchNorm2d(ch, affine=True, track_running_stats=True)) if affine else {}
+        self.fused_conv = _seq(conv=nn.Conv2d(in_channels, mid_channels, 3, stride, 1, bias=False), **bn(mid_channels))
+        if se_channels > 0:
+            self.squeeze_excite = _seq(conv_reduce=nn.Conv2d(mid_channels, se_channels, 1, 1, 0, bias=True),
+                                       conv_expand=nn.Conv2d(se_channels, mid_channels, 1, 1, 0, bias=True))
+        else:
+            self.squeeze_excite = None
+            self.se_channels = 0
+        self.point_linear = _seq(conv=nn.Conv2d(mid_channels, out_channels, 1, 1, 0, bias=False), **bn(out_channels))
+        self.has_residual = (in_channels == out_channels) and (stride == 1)
+        self._plan = None
+
+    @property
+    def name(self):
+        return 'FusedMBConvBlock'
+
+    def hip_params(self):
+        """Weights in the order of TfnasGroup's pointer fields (the dense weight in the expand field, no depthwise field)."""
+        ps = [self.fused_conv.conv.weight, self.point_linear.conv.weight]
+        if self.squeeze_excite is not None:
+            se = self.squeeze_excite
+            ps += [se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias]
+        return ps
+
+    def bn_modules(self):
+        """The block's two BatchNorm modules in order (affine form)."""
+        return [self.fused_conv.bn, self.point_linear.bn]
+
+    def bn_sites(self):
+        return [None] + self.bn_modules()                   # (BatchNorm site 0 does not exist)

@@ -46,28 +46,36 @@ class _BlockTimer:
             t = self.bufs[name] = torch.zeros(int(n * 1.25) + 64, device=self.dev, dtype=dtype)   # zero: `part` ticket counters
         return t
 
-    def measure(self, ic, mc, se, oc, k, stride, act, size, batch=32, warmup=3, iters=10, reps=3, mode='inference'):
+    def measure(self, ic, mc, se, oc, k, stride, act, size, batch=32, warmup=3, iters=10, reps=3, mode='inference',
+                block='MBInvertedResBlock'):
         lib, dev = self.lib, self.dev
         if mode not in ('inference', 'search'):
             raise ValueError(mode)
+        if block not in BLOCK_KINDS:
+            raise ValueError(block)
+        fused = block == 'FusedMBConvBlock'          # (a dense 3 x 3 convolution: its weight in the expand field, no depthwise)
+        if fused and k != 3:
+            raise NotImplementedError('tfnas_amd: FusedMBConvBlock has kernel size 3 only (got %r)' % (k,))
         d = _lib.TfnasCellDesc()
         d.N, d.H, d.W, d.ic, d.oc, d.stride = batch, size, size, ic, oc, stride
         d.mode, d.act, d.G, d.need_wgrad, d.eps = _lib.MODE_CELL, _lib.act_id(act), 1, 0, BN_EPS
         d.has_res = int(ic == oc and stride == 1)
-        noexp = mc <= ic             # (no expand convolution, mid normalised to in: layers.MBInvertedResBlock)
+        noexp = mc <= ic and not fused   # (no expand convolution, mid normalised to in: layers.MBInvertedResBlock)
         if noexp:
             mc = ic
         d.g[0].mc, d.g[0].k, d.g[0].se = mc, k, se
-        d.flags = (_lib.CELL_K7 if k == 7 else 0) | _lib.act_flags(d.act) | (_lib.CELL_NOEXPAND if noexp else 0)
+        d.flags = ((_lib.CELL_K7 if k == 7 else 0) | _lib.act_flags(d.act) | (_lib.CELL_NOEXPAND if noexp else 0)
+                   | (_lib.CELL_FUSED if fused else 0))
         _lib.check(lib.tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
         ws = _lib.TfnasCellWs()
         _lib.check(lib.tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
-        w = self._buf('w', mc * ic + mc * k * k + oc * mc + 2 * se * mc + se + mc + 64)
+        nx = mc * ic * (9 if fused else 1)
+        w = self._buf('w', nx + mc * k * k + oc * mc + 2 * se * mc + se + mc + 64)
         w.normal_(0, 0.1)
         o = 0
-        for f, n in (('w_expand', mc * ic), ('w_dw', mc * k * k), ('w_proj', oc * mc), ('w_se_r', se * mc), ('b_se_r', se),
+        for f, n in (('w_expand', nx), ('w_dw', mc * k * k), ('w_proj', oc * mc), ('w_se_r', se * mc), ('b_se_r', se),
                      ('w_se_e', mc * se), ('b_se_e', mc)):
-            if n and (se or not f.endswith(('se_r', 'se_e'))) and not (noexp and f == 'w_expand'):
+            if n and (se or not f.endswith(('se_r', 'se_e'))) and not (noexp and f == 'w_expand') and not (fused and f == 'w_dw'):
                 setattr(d.g[0], f, w.data_ptr() + 4 * o)
                 o += (n + 3) // 4 * 4
         x = self._buf('x', batch * size * size * ic)
@@ -83,7 +91,8 @@ class _BlockTimer:
             args = (C.byref(d), _lib.ptr(x), None, pE, _lib.ptr(D), _lib.ptr(Pr), _lib.ptr(fs), _lib.ptr(st),
                     _lib.ptr(part), _lib.ptr(out), sp)
         else:
-            # eval-mode affine BatchNorm at the three sites (mc, mc, oc channels; without expand convolution: the last two):
+            # eval-mode affine BatchNorm at the three sites (mc, mc, oc channels; without expand convolution and in a fused
+            # block: the last two):
             # gamma ~ 1, beta ~ 0, running mean 0 / var 1
             fn, what = lib.tfnas_mbconv_fwd, 'tfnas_mbconv_fwd'
             nb = 2 * mc + oc
@@ -96,7 +105,7 @@ class _BlockTimer:
             o2 = 0
             for site, ch in enumerate((mc, mc, oc)):
                 for fi, f in enumerate(('weight', 'bias', 'running_mean', 'running_var')):
-                    getattr(bn, f)[site] = None if (noexp and site == 0) else aff.data_ptr() + 4 * (fi * nb + o2)
+                    getattr(bn, f)[site] = None if ((noexp or fused) and site == 0) else aff.data_ptr() + 4 * (fi * nb + o2)
                 o2 += ch
             bn.momentum, bn.eval = 0.1, 1
             self._bn = bn                                   # (keep the struct alive while its launches are enqueued)
@@ -117,8 +126,12 @@ class _BlockTimer:
         return float(np.median(times))
 
 
+BLOCK_KINDS = ('MBInvertedResBlock', 'FusedMBConvBlock')      # ``block`` of measure / build_latency_lookup: the key's first word
+
+
 Measurer = _BlockTimer          # public name: Measurer(device).measure(ic, mc, se, oc, k, stride, act, size, ...), k in {3, 5, 7},
-                                # act in 'relu' | 'swish' | 'relu6' | 'h-swish'; mc <= ic: the block without expand convolution
+                                # act in 'relu' | 'swish' | 'relu6' | 'h-swish'; mc <= ic: the block without expand convolution;
+                                # block='FusedMBConvBlock' (k = 3): the dense 3 x 3 block of the same (ic, mc, se, oc)
 
 
 def lut_keys():
@@ -165,18 +178,28 @@ def measure_base(device, batch=32, iters=10, mode='inference'):
     return e0.elapsed_time(e1) / iters
 
 
-def build_latency_lookup(device='cuda', step=8, batch=32, iters=10, progress=None, keys=None, mode='inference'):
+def build_latency_lookup(device='cuda', step=8, batch=32, iters=10, progress=None, keys=None, mode='inference',
+                         block='MBInvertedResBlock'):
     """Measure the table on the current GPU.  ``step``: measure every step-th width (1 = every width, ~40 k measurements);
-    ``mode``: 'inference' (the reference's meaning) or 'search' (see the module docstring)."""
+    ``mode``: 'inference' (the reference's meaning) or 'search' (see the module docstring); ``block``: the block kind that is
+    timed -- 'FusedMBConvBlock' times the fused block of every k = 3 geometry (every width from 1 up: it has no expand-free
+    form) and writes keys that begin with that name, the ones model_eval.NetworkCfg.get_lookup_latency looks up."""
+    if block not in BLOCK_KINDS:
+        raise ValueError(block)
+    fused = block == 'FusedMBConvBlock'
     dev = torch.device(device)
     timer = _BlockTimer(dev)
     lut = OrderedDict()
     lut['base'] = measure_base(dev, batch, iters, mode)
     for key, gm in (keys or lut_keys()):
-        lo, hi = gm['ic'] + 1, gm['max_mc']
+        if fused:
+            if gm['k'] != 3:
+                continue
+            key = block + key[key.index('_'):]
+        lo, hi = (1 if fused else gm['ic'] + 1), gm['max_mc']
         widths = sorted(set(list(range(lo, hi + 1, step)) + [hi]))
         ms = [timer.measure(gm['ic'], w, gm['se'], gm['oc'], gm['k'], gm['stride'], gm['act'], gm['size'], batch,
-                            iters=iters, mode=mode) for w in widths]
+                            iters=iters, mode=mode, block=block) for w in widths]
         dense = np.interp(np.arange(1, hi + 1), widths, ms)          # (clamps to the end values outside [lo, hi])
         lut[key] = OrderedDict((w + 1, float(dense[w])) for w in range(hi))
         if progress:

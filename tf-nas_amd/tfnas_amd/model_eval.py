@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from . import _lib, geometry
 from .functions import CellPlan, HeadAffineFn, MBConvAffineFn
-from .layers import ConvLayer, LinearLayer, MBInvertedResBlock
+from .layers import ConvLayer, FusedMBConvBlock, LinearLayer, MBInvertedResBlock
 from .parsing import derived_config
 
 
@@ -112,7 +112,7 @@ class _DerivedBase(nn.Module):
 
     @staticmethod
     def _block_config(b):
-        return {'name': 'MBInvertedResBlock', 'in_channels': b.in_channels, 'mid_channels': b.mid_channels,
+        return {'name': b.name, 'in_channels': b.in_channels, 'mid_channels': b.mid_channels,
                 'se_channels': b.se_channels, 'out_channels': b.out_channels, 'kernel_size': b.kernel_size, 'stride': b.stride,
                 'groups': 1, 'has_shuffle': False, 'bias': False, 'use_bn': True, 'affine': True, 'act_func': b.act_func}
 
@@ -174,15 +174,18 @@ class NetworkCfg(_DerivedBase):
         self.block_count = 1 + sum(len(v) for k, v in model_config.items() if k.startswith('stage'))
         self.block_idx = 0
 
-        def mb(c):
-            if c['name'] != 'MBInvertedResBlock' or c.get('groups', 1) != 1 or c.get('has_shuffle') or c.get('bias'):
-                raise NotImplementedError('only plain MBInvertedResBlock configs are supported: %r' % (c,))
-            return MBInvertedResBlock(c['in_channels'], c['mid_channels'], c['se_channels'], c['out_channels'],
+        def mb(c, fused_ok=True):
+            kinds = {'MBInvertedResBlock': MBInvertedResBlock}
+            if fused_ok:                                   # (stage entries only: second_stem stays an MBConv, fused with first_stem)
+                kinds['FusedMBConvBlock'] = FusedMBConvBlock
+            if c['name'] not in kinds or c.get('groups', 1) != 1 or c.get('has_shuffle') or c.get('bias'):
+                raise NotImplementedError('only plain MBInvertedResBlock / FusedMBConvBlock configs are supported: %r' % (c,))
+            return kinds[c['name']](c['in_channels'], c['mid_channels'], c['se_channels'], c['out_channels'],
                                       c['kernel_size'], c['stride'], affine=c.get('affine', True), act_func=c['act_func'])
         fs = model_config['first_stem']
         self.first_stem = ConvLayer(fs['in_channels'], fs['out_channels'], fs['kernel_size'], fs['stride'], affine=True,
                                     act_func=fs['act_func'])
-        self.second_stem = mb(model_config['second_stem'])
+        self.second_stem = mb(model_config['second_stem'], fused_ok=False)
         self.block_idx += 1
         self.second_stem.drop_connect_rate = self.drop_connect_rate * self.block_idx / self.block_count
         for i in range(1, 7):

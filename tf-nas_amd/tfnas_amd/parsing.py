@@ -72,6 +72,13 @@ def count_macs_in_M(config, input_size=224):
         else:
             ic, mc, se, oc, k, s = (c[n] for n in ('in_channels', 'mid_channels', 'se_channels', 'out_channels',
                                                     'kernel_size', 'stride'))
+            if c['name'] == 'FusedMBConvBlock':                # dense k x k convolution at the output size, SE, project
+                size = (size - 1) // s + 1
+                total += k * k * ic * mc * size * size
+                if se > 0:
+                    total += (mc * se + se) + (se * mc + mc)
+                total += mc * oc * size * size
+                continue
             if mc > ic:                                        # expand conv only when mid > in (layers.py:462)
                 total += ic * mc * size * size
             else:
@@ -96,6 +103,11 @@ def count_params_in_MB(config):
             n += c['kernel_size'] ** 2 * c['in_channels'] * c['out_channels'] + 2 * c['out_channels']
         else:
             ic, mc, se, oc, k = (c[x] for x in ('in_channels', 'mid_channels', 'se_channels', 'out_channels', 'kernel_size'))
+            if c['name'] == 'FusedMBConvBlock':
+                n += k * k * ic * mc + 2 * mc + mc * oc + 2 * oc
+                if se > 0:
+                    n += mc * se + se + se * mc + mc
+                continue
             if mc > ic:
                 n += ic * mc + 2 * mc
             else:
