@@ -4,7 +4,6 @@ no such block; the fixture pins the restatement to a composition of the referenc
 identical weights, seeds whose float64 pre-activations stay clear of every activation kink, a raw-ABI launcher for what the
 Python modules do not expose (accumulation, dx == NULL, need_wgrad = 0), and a ``model.config`` whose stage 1 holds a fused block."""
 import copy
-import ctypes as C
 import itertools
 from collections import OrderedDict
 
@@ -13,6 +12,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import _k7
+import _rawcell
+from _rawcell import KINKS, KINK_TAU, ws_of  # noqa: F401
 
 BN_EPS = 1e-5
 
@@ -109,10 +110,6 @@ def hip_block_like(o):
 
 
 # ------------------------------------------------------------------------------------------------ kinks and seeds
-KINKS = {'relu': (0.0,), 'swish': (), 'relu6': (0.0, 6.0), 'h-swish': (-3.0, 3.0)}
-KINK_TAU = 1e-4
-
-
 def kink_distance(o, x):
     """Smallest distance, in a float64 copy of ``o`` (same mode), of a BN_a output or an SE hidden pre-activation from a kink of
     the block's activation (inf for swish).  The copy's buffers move, not ``o``'s."""
@@ -250,112 +247,15 @@ def compare(o, m, x, r):
 
 # ------------------------------------------------------------------------------------------------ raw ABI
 def cell_desc(N, H, W, ic, oc, mc, stride=1, act=0, se=0, flags=None, k=3, G=1, mode=0, need_wgrad=0):
-    """A descriptor of one block; flags = None: TFNAS_CELL_FUSED plus whatever the activation needs."""
+    """_rawcell.cell_desc of a Fused-MBConv block"""
     from tfnas_amd import _lib
-    d = _lib.TfnasCellDesc()
-    d.N, d.H, d.W, d.ic, d.oc, d.stride, d.act, d.G, d.mode = N, H, W, ic, oc, stride, act, G, mode
-    d.has_res = int(mode == 0 and ic == oc and stride == 1)
-    d.eps, d.need_wgrad = BN_EPS, need_wgrad
-    for g in range(G):
-        d.g[g].mc, d.g[g].k, d.g[g].se = mc, k, se
-    d.flags = (_lib.CELL_FUSED | _lib.act_flags(act)) if flags is None else flags
-    return d
+    return _rawcell.cell_desc(_lib.FUSED, N, H, W, ic, oc, mc, k, stride, act, se, flags, G, mode, need_wgrad)
 
 
-def ws_of(lib, d):
+def raw_cell(o, x, gemm=None):
+    """_rawcell.RawCell of a search-form FusedRef"""
     from tfnas_amd import _lib
-    ws = _lib.TfnasCellWs()
-    assert lib.tfnas_cell_ws(C.byref(d), C.byref(ws)) == 0
-    return ws
-
-
-W_FIELDS = ('w_expand', 'w_proj', 'w_se_r', 'b_se_r', 'w_se_e', 'b_se_e')
-G_FIELDS = ('g_expand', 'g_proj', 'g_se_r', 'gb_se_r', 'g_se_e', 'gb_se_e')
-
-
-class RawCell:
-    """One search-form fused block through tfnas_mixedop_fwd / _bwd with caller-made buffers: ``guard`` sentinel floats follow D
-    and dx; TFNAS_CELL_ACCUM_WGRAD, need_wgrad and dx == NULL are the caller's choice.  Weights come from a FusedRef."""
-    SENTINEL = -777.25
-
-    def __init__(self, o, x, guard=64, gemm=None):
-        from tfnas_amd import _lib
-        self.lib, self._lib = _lib.lib(), _lib
-        self.o, self.guard = o, guard
-        self.dev = torch.device('cuda')
-        N, _, H, W = x.shape
-        self.xh = x.permute(0, 2, 3, 1).contiguous().cuda()
-        self.d = cell_desc(N, H, W, o.in_channels, o.out_channels, o.mid_channels, o.stride, _lib.act_id(o.act_func),
-                           o.se_channels)
-        if gemm is not None:
-            self.d.gemm_mode = _lib.GEMM_EXPLICIT | _lib.GEMM_MODES[gemm]
-        _lib.check(self.lib.tfnas_cell_plan(C.byref(self.d)), 'tfnas_cell_plan')
-        self.ws = ws_of(self.lib, self.d)
-        self.names = ['fused_conv.conv.weight', 'point_linear.conv.weight']
-        if o.se_channels:
-            self.names += ['squeeze_excite.conv_reduce.weight', 'squeeze_excite.conv_reduce.bias',
-                           'squeeze_excite.conv_expand.weight', 'squeeze_excite.conv_expand.bias']
-        sd = dict(o.named_parameters())
-        self.w = [sd[n].detach().float().contiguous().cuda() for n in self.names]
-        for f, t in zip(W_FIELDS, self.w):
-            setattr(self.d.g[0], f, t.data_ptr())
-
-    def _buf(self, n, guard=0, dtype=torch.float32):
-        t = torch.empty(int(n) + guard, device=self.dev, dtype=dtype)
-        if guard:
-            t[int(n):] = self.SENTINEL
-        return t
-
-    def forward(self):
-        from tfnas_amd.functions import _part, _stream
-        d, ws, ptr = self.d, self.ws, self._lib.ptr
-        d.need_wgrad = 0
-        self.D = self._buf(ws.D, self.guard)
-        self.Pr, self.fsmall = self._buf(ws.Pr), self._buf(ws.fsmall)
-        self.stats = self._buf(ws.stats, dtype=torch.float64)
-        self.out = self._buf(ws.out)
-        part = _part(ws.part, self.dev)
-        self._lib.check(self.lib.tfnas_mixedop_fwd(C.byref(d), ptr(self.xh), None, None, ptr(self.D), ptr(self.Pr),
-                                                   ptr(self.fsmall), ptr(self.stats), ptr(part), ptr(self.out),
-                                                   _stream(self.dev)), 'tfnas_mixedop_fwd')
-        torch.cuda.synchronize()
-        return self.out.view(d.N, d.Ho, d.Wo, d.oc).permute(0, 3, 1, 2)
-
-    def backward(self, r, need_wgrad=True, want_dx=True, accum_into=None):
-        """returns (rc, dx [N, ic, H, W] or None, {parameter name: gradient} or None); accum_into: the gradients are ADDED to
-        copies of these tensors (same order as ``names``)"""
-        from tfnas_amd.functions import _part, _stream
-        d, ws, ptr = self.d, self.ws, self._lib.ptr
-        d.need_wgrad = int(need_wgrad)
-        base = d.flags
-        grads = None
-        if need_wgrad:
-            grads = [g.clone() for g in accum_into] if accum_into is not None else [torch.full_like(w, 3.5) for w in self.w]
-            for f, t in zip(G_FIELDS, grads):
-                setattr(d.g[0], f, t.data_ptr())
-            if accum_into is not None:
-                d.flags = base | self._lib.CELL_ACCUM_WGRAD
-        rh = r.permute(0, 2, 3, 1).contiguous().cuda()
-        P = d.N * d.H * d.W
-        dx = self._buf(P * d.ic, self.guard) if want_dx else None
-        dZ, dEh, bsmall = self._buf(ws.dZ), self._buf(ws.dEh), self._buf(ws.bsmall)
-        red = self._buf(ws.red, dtype=torch.float64)
-        part = _part(ws.part * 2, self.dev)
-        try:
-            rc = self.lib.tfnas_mixedop_bwd(C.byref(d), ptr(self.xh), None, None, ptr(self.D), ptr(self.Pr), ptr(self.fsmall),
-                                            ptr(self.stats), ptr(rh), ptr(dZ), ptr(dEh), ptr(bsmall), ptr(red), ptr(part),
-                                            ptr(dx), None, None, _stream(self.dev))
-            torch.cuda.synchronize()
-        finally:
-            d.flags, d.need_wgrad = base, 0
-            for f in self._lib._G_FIELDS:
-                setattr(d.g[0], f, None)
-        self.dx_raw = dx
-        dxo = None if dx is None else dx[:P * d.ic].view(d.N, d.H, d.W, d.ic).permute(0, 3, 1, 2)
-        return rc, dxo, (None if grads is None else OrderedDict(zip(self.names, grads)))
-
-    def guard_ok(self, t, n):
-        return bool((t[int(n):] == self.SENTINEL).all())
+    return _rawcell.RawCell(o, x, _lib.FUSED, _rawcell.param_names(_lib.FUSED, o.se_channels), gemm=gemm)
 
 
 def ref_grads(o, x, r):
@@ -370,12 +270,9 @@ def ref_grads(o, x, r):
 
 # ------------------------------------------------------------------------------------------------ derived network
 def fused_network_config(num_classes=20):
-    """A ``model.config`` (parsing.derived_config: two blocks per stage) whose stage1 holds Fused-MBConv blocks: 16 -> 48 -> 24 at
-    stride 2 with SE 16, then 24 -> 50 -> 24 (ragged width, residual) without."""
-    from tfnas_amd import geometry as g, parsing
-    arch = OrderedDict((st, OrderedDict((b, (i * 3 + j) % 8) for j, b in enumerate(bl) if j < 2))
-                       for i, (st, bl) in enumerate(g.initial_mc_num_dddict().items()))
-    cfg = parsing.derived_config(arch, g.initial_mc_num_dddict(), num_classes)
+    """_k7.base_network_config whose stage1 holds Fused-MBConv blocks: 16 -> 48 -> 24 at stride 2 with SE 16, then 24 -> 50 -> 24
+    (ragged width, residual) without."""
+    cfg = _k7.base_network_config(num_classes)
     a, b = cfg['stage1']
     a.update(name='FusedMBConvBlock', kernel_size=3, mid_channels=48, se_channels=16)
     b.update(name='FusedMBConvBlock', kernel_size=3, mid_channels=50, se_channels=0)
@@ -383,29 +280,5 @@ def fused_network_config(num_classes=20):
 
 
 def hand_counts(cfg, size):
-    """(MACs in millions at ``size`` x ``size``, parameters in millions) written out layer by layer, fused blocks as
-    9 ic mc So^2 + SE + mc oc So^2 MACs and 9 ic mc + 2 mc + SE + mc oc + 2 oc parameters."""
-    hw = (size - 1) // 2 + 1
-    macs = 3 * 3 * 3 * 32 * hw * hw
-    macs += 3 * 3 * 32 * hw * hw + (32 * 8 + 8) + (8 * 32 + 32) + 32 * 16 * hw * hw
-    n = 3 * 3 * 3 * 32 + 2 * 32
-    n += 3 * 3 * 32 + 2 * 32 + (32 * 8 + 8) + (8 * 32 + 32) + 32 * 16 + 2 * 16
-    for st in ('stage1', 'stage2', 'stage3', 'stage4', 'stage5', 'stage6'):
-        for c in cfg[st]:
-            ic, mc, se, oc, k, s = (c[x] for x in ('in_channels', 'mid_channels', 'se_channels', 'out_channels', 'kernel_size',
-                                                    'stride'))
-            sep = 2 * mc * se + se + mc if se else 0
-            if c['name'] == 'FusedMBConvBlock':
-                hw = (hw - 1) // s + 1
-                macs += 9 * ic * mc * hw * hw + sep + mc * oc * hw * hw
-                n += 9 * ic * mc + 2 * mc + sep + mc * oc + 2 * oc
-                continue
-            assert mc > ic
-            macs += ic * mc * hw * hw
-            hw = (hw - 1) // s + 1
-            macs += k * k * mc * hw * hw + sep + mc * oc * hw * hw
-            n += ic * mc + 2 * mc + k * k * mc + 2 * mc + sep + mc * oc + 2 * oc
-    macs += 320 * 1280 * hw * hw + 1280 * hw * hw
-    n += 320 * 1280 + 2 * 1280
-    ncls = cfg['classifier']['out_features']
-    return (macs + 1280 * ncls + ncls) / 1e6, (n + 1280 * ncls + ncls) / 1e6
+    """(MACs in millions at ``size`` x ``size``, parameters in millions): the hand counters of every block kind"""
+    return _k7.hand_macs_in_M(cfg, size), _k7.hand_params_in_MB(cfg)

@@ -163,52 +163,62 @@ def oracle_cell_from(fx):
 
 
 # ------------------------------------------------------------------------------------------------ derived network
-def k7_network_config(num_classes=50):
-    """A ``model.config`` (parsing.derived_config: two blocks per stage, SE and plain candidates) whose stage-3 and stage-5
-    blocks have depthwise kernel size 7."""
+def base_network_config(num_classes):
+    """A ``model.config`` of parsing.derived_config: two blocks per stage, SE and plain candidates (what the k7 / expand-free /
+    fused configurations start from)."""
     from tfnas_amd import geometry as g, parsing
     arch = OrderedDict((st, OrderedDict((b, (i * 3 + j) % 8) for j, b in enumerate(bl) if j < 2))
                        for i, (st, bl) in enumerate(g.initial_mc_num_dddict().items()))
-    cfg = parsing.derived_config(arch, g.initial_mc_num_dddict(), num_classes)
+    return parsing.derived_config(arch, g.initial_mc_num_dddict(), num_classes)
+
+
+def k7_network_config(num_classes=50):
+    """base_network_config whose stage-3 and stage-5 blocks have depthwise kernel size 7."""
+    cfg = base_network_config(num_classes)
     for st in ('stage3', 'stage5'):
         for blk in cfg[st]:
             blk['kernel_size'] = 7
     return cfg
 
 
-def hand_macs_in_M(cfg, size):
-    """Multiply-accumulates per image, in millions, of the network of ``cfg`` at ``size`` x ``size`` inputs, written out layer
-    by layer (the conventions of the reference's flops counter: bias adds and the global average pool count, SE pooling does
-    not)."""
+def _hand_count(cfg, size, block_term, stem, head):
+    """The stem, stage-loop and head arithmetic of both hand counters; ``block_term(kind, ic, mc, se, oc, k, hw_in, hw_out)`` is
+    what one block adds, kind = 'fused' | 'noexp' | 'plain'.  Independent of parsing.py, whose counters it checks."""
     hw = (size - 1) // 2 + 1
-    total = 3 * 3 * 3 * 32 * hw * hw                               # first stem: 3 x 3 / 2, 3 -> 32
-    total += 3 * 3 * 32 * hw * hw + (32 * 8 + 8) + (8 * 32 + 32) + 32 * 16 * hw * hw       # second stem: no expand, SE 8
+    total = stem(hw)
     for st in ('stage1', 'stage2', 'stage3', 'stage4', 'stage5', 'stage6'):
         for c in cfg[st]:
             ic, mc, se, oc, k, s = (c[n] for n in ('in_channels', 'mid_channels', 'se_channels', 'out_channels', 'kernel_size',
                                                     'stride'))
-            assert mc > ic
-            total += ic * mc * hw * hw                             # expand 1 x 1 at the input resolution
-            hw = (hw - 1) // s + 1
-            total += k * k * mc * hw * hw                          # depthwise k x k at the output resolution
-            if se:
-                total += 2 * mc * se + se + mc                     # the two SE convolutions on the pooled vector, with bias
-            total += mc * oc * hw * hw                             # project 1 x 1
-    total += 320 * 1280 * hw * hw + 1280 * hw * hw                 # feature mix 1 x 1, global average pool
+            kind = 'fused' if c['name'] == 'FusedMBConvBlock' else ('plain' if mc > ic else 'noexp')
+            hw_in, hw = hw, (hw - 1) // s + 1
+            total += block_term(kind, ic, ic if kind == 'noexp' else mc, se, oc, k, hw_in, hw)
     ncls = cfg['classifier']['out_features']
-    total += 1280 * ncls + ncls
-    return total / 1e6
+    return (total + head(hw) + 1280 * ncls + ncls) / 1e6
+
+
+def hand_macs_in_M(cfg, size):
+    """Multiply-accumulates per image, in millions, of the network of ``cfg`` at ``size`` x ``size`` inputs, written out layer
+    by layer (the conventions of the reference's flops counter: bias adds and the global average pool count, SE pooling does
+    not)."""
+    def block(kind, ic, mc, se, oc, k, hw_in, hw):
+        lead = {'plain': ic * mc * hw_in * hw_in + k * k * mc * hw * hw,    # expand 1 x 1 at the input resolution + depthwise k x k
+                'noexp': k * k * mc * hw * hw,                              # the depthwise alone, at the output resolution
+                'fused': 9 * ic * mc * hw * hw}[kind]                       # one dense 3 x 3
+        se_macs = 2 * mc * se + se + mc if se else 0                        # the two SE convolutions on the pooled vector, with bias
+        return lead + se_macs + mc * oc * hw * hw                           # project 1 x 1
+
+    def stem(hw):                                                           # 3 x 3 / 2, 3 -> 32; second stem: no expand, SE 8
+        return 3 * 3 * 3 * 32 * hw * hw + 3 * 3 * 32 * hw * hw + (32 * 8 + 8) + (8 * 32 + 32) + 32 * 16 * hw * hw
+    return _hand_count(cfg, size, block, stem, lambda hw: 320 * 1280 * hw * hw + 1280 * hw * hw)    # feature mix, average pool
 
 
 def hand_params_in_MB(cfg):
-    n = 3 * 3 * 3 * 32 + 2 * 32                                    # first stem + its BatchNorm
-    n += 3 * 3 * 32 + 2 * 32 + (32 * 8 + 8) + (8 * 32 + 32) + 32 * 16 + 2 * 16
-    for st in ('stage1', 'stage2', 'stage3', 'stage4', 'stage5', 'stage6'):
-        for c in cfg[st]:
-            ic, mc, se, oc, k = (c[x] for x in ('in_channels', 'mid_channels', 'se_channels', 'out_channels', 'kernel_size'))
-            n += ic * mc + 2 * mc + k * k * mc + 2 * mc + mc * oc + 2 * oc
-            if se:
-                n += 2 * mc * se + se + mc
-    n += 320 * 1280 + 2 * 1280
-    ncls = cfg['classifier']['out_features']
-    return (n + 1280 * ncls + ncls) / 1e6
+    """Parameters of the network of ``cfg`` in millions, BatchNorm gamma / beta included, layer by layer."""
+    def block(kind, ic, mc, se, oc, k, hw_in, hw):
+        lead = {'plain': ic * mc + 2 * mc + k * k * mc + 2 * mc, 'noexp': k * k * mc + 2 * mc, 'fused': 9 * ic * mc + 2 * mc}[kind]
+        return lead + (2 * mc * se + se + mc if se else 0) + mc * oc + 2 * oc
+
+    def stem(hw):                                                           # first stem + its BatchNorm, second stem
+        return 3 * 3 * 3 * 32 + 2 * 32 + 3 * 3 * 32 + 2 * 32 + (32 * 8 + 8) + (8 * 32 + 32) + 32 * 16 + 2 * 16
+    return _hand_count(cfg, 224, block, stem, lambda hw: 320 * 1280 + 2 * 1280)

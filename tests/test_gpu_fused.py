@@ -34,7 +34,7 @@ def test_search_form_block_matches_the_restatement(geom):
 
 def _raw_case(gemm=None, geom=_fused.RAW_GEOM):
     o, x, r, seed = _fused.case_data(*geom, base=300)
-    cell = _fused.RawCell(o, x, gemm=gemm)
+    cell = _fused.raw_cell(o, x, gemm=gemm)
     return o, x, r, cell
 
 

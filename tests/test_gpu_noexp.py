@@ -97,7 +97,7 @@ def _raw(name):
     with _acts.wrapped_oracle():
         o, x, r = _case(name)
         out_o, det, dx_o = _oracle_run(o, x, r)
-    return o, x, r, out_o, dx_o, _noexp.RawCell(o, x)
+    return o, x, r, out_o, dx_o, _noexp.raw_cell(o, x)
 
 
 @pytest.mark.parametrize('name', ['two_col_tiles_res_se', 's2_odd_ic20_relu6_se'])
@@ -114,29 +114,28 @@ def test_raw_abi_route_word_accumulation_and_guard_bands(name):
     D0 = written_D()
     assert cell.guard_ok(cell.D, ws.D)
     rc, dx0, g0 = cell.backward(r)
-    assert rc == 0 and cell.guard_ok(dx0, P * d.ic)
-    res = {'out': hc.err(out0.view(d.N, d.Ho, d.Wo, d.oc), hc.nhwc(out_o)), 'dx': hc.err(dx0[:P * d.ic].view(d.N, d.H, d.W, d.ic),
-                                                                                           hc.nhwc(dx_o))}
-    op = o.params()
-    for nme, g in zip(cell.names, g0):
+    assert rc == 0 and cell.guard_ok(cell.dx_raw, P * d.ic)
+    res = {'out': hc.err(out0, out_o), 'dx': hc.err(dx0, dx_o)}
+    op = dict(o.named_parameters())
+    for nme, g in g0.items():
         res['grad_' + nme] = hc.err(g, op[nme].grad)
     assert not hc.worst(res), hc.worst(res)
     # the route word cannot move the cell: register-window, ring and tile requests (and the expand-side bits) are one launch plan
     for route in (1 << 6, 2 << 6, 3 << 6, (1 << 6) | _lib.ROUTE_XG_ALL | _lib.ROUTE_GRAM2 | _lib.ROUTE_DWWG_OFF | _lib.ROUTE_DWWG2_OFF):
         assert torch.equal(cell.forward(route), out0) and torch.equal(written_D(), D0) and cell.guard_ok(cell.D, ws.D)
         rc, dx1, g1 = cell.backward(r, route)
-        assert rc == 0 and torch.equal(dx1, dx0) and all(torch.equal(a, b) for a, b in zip(g1, g0))
+        assert rc == 0 and torch.equal(dx1, dx0) and all(torch.equal(a, b) for a, b in zip(g1.values(), g0.values()))
     cell.forward()
     # TFNAS_CELL_ACCUM_WGRAD: g + v bit for bit; dx unchanged
     gen = torch.Generator().manual_seed(5)
-    have = [torch.randn(g.shape, generator=gen).cuda() for g in g0]
+    have = [torch.randn(g.shape, generator=gen).cuda() for g in g0.values()]
     rc, dx2, g2 = cell.backward(r, accum_into=have)
     assert rc == 0 and torch.equal(dx2, dx0)
-    for h, v, got in zip(have, g0, g2):
+    for h, v, got in zip(have, g0.values(), g2.values()):
         assert torch.equal(got, h + v)
     # weight gradients on the caller's stream: the same numbers
     rc, dx3, g3 = cell.backward(r, _lib.ROUTE_WGRAD_INLINE)
-    assert rc == 0 and torch.equal(dx3, dx0) and all(torch.equal(a, b) for a, b in zip(g3, g0))
+    assert rc == 0 and torch.equal(dx3, dx0) and all(torch.equal(a, b) for a, b in zip(g3.values(), g0.values()))
     # frozen weights: dx alone, and nothing at all when dx is not wanted either
     rc, dx4, _ = cell.backward(r, need_wgrad=False)
     assert rc == 0 and torch.equal(dx4, dx0)
@@ -144,7 +143,7 @@ def test_raw_abi_route_word_accumulation_and_guard_bands(name):
     assert rc == 0 and dx5 is None
     # weight gradients without dx: the depthwise backward-data pass is skipped, the gradients are the same
     rc, dx6, g6 = cell.backward(r, want_dx=False)
-    assert rc == 0 and dx6 is None and all(torch.equal(a, b) for a, b in zip(g6, g0))
+    assert rc == 0 and dx6 is None and all(torch.equal(a, b) for a, b in zip(g6.values(), g0.values()))
 
 
 def test_entry_points_refuse_a_changed_descriptor_before_launching():

@@ -157,20 +157,16 @@ static int check_act(const TfnasCellDesc* d) {
     return 0;
 }
 
-// TFNAS_CELL_NOEXPAND: one expand-free block -- cell mode, one group of mc == ic channels, no expand weight or gradient pointer
-static int check_noexpand(const TfnasCellDesc* d) {
-    if (!(d->flags & TFNAS_CELL_NOEXPAND)) return 0;
+// the kind bits of a descriptor.  Both newer kinds are ONE block in cell mode; TFNAS_CELL_NOEXPAND: mc == ic channels, no expand
+// weight or gradient pointer; TFNAS_CELL_FUSED: a dense 3 x 3 weight (w_expand), no depthwise pointer; never both bits
+static int check_kind(const TfnasCellDesc* d) {
+    const CellKind kind = cell_kind(*d);
+    if (kind == TFNAS_KIND_MBCONV) return 0;
+    if (cell_noexpand(*d) && cell_fused(*d)) return TFNAS_EINVAL;
     if (d->mode != TFNAS_MODE_CELL || d->G != 1) return TFNAS_EINVAL;
-    if (d->g[0].mc != d->ic || d->g[0].w_expand || d->g[0].g_expand) return TFNAS_EINVAL;
-    return 0;
-}
-
-// TFNAS_CELL_FUSED: one Fused-MBConv block -- cell mode, one group with a dense 3 x 3 weight (w_expand), no depthwise pointer
-static int check_fused(const TfnasCellDesc* d) {
-    if (!(d->flags & TFNAS_CELL_FUSED)) return 0;
-    if (d->flags & TFNAS_CELL_NOEXPAND) return TFNAS_EINVAL;
-    if (d->mode != TFNAS_MODE_CELL || d->G != 1) return TFNAS_EINVAL;
-    if (d->g[0].k != 3 || d->g[0].w_dw || d->g[0].g_dw) return TFNAS_EINVAL;
+    const TfnasGroup& g = d->g[0];
+    if (kind == TFNAS_KIND_NOEXPAND && (g.mc != d->ic || g.w_expand || g.g_expand)) return TFNAS_EINVAL;
+    if (kind == TFNAS_KIND_FUSED && (g.k != 3 || g.w_dw || g.g_dw)) return TFNAS_EINVAL;
     return 0;
 }
 
@@ -184,8 +180,7 @@ static int check_modes(const TfnasCellDesc* d) {
     if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS | TFNAS_CELL_NOEXPAND |
                      TFNAS_CELL_FUSED))
         return TFNAS_EINVAL;
-    TRY(check_noexpand(d));
-    TRY(check_fused(d));
+    TRY(check_kind(d));
     if (!(d->flags & TFNAS_CELL_K7)) {            // kernel size 7 is opt-in: without the bit it is refused as it always was
         for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g)
             if (d->g[g].k == 7) return TFNAS_EINVAL;
@@ -258,8 +253,7 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     const uint64_t P = (uint64_t)d->N * d->H * d->W, Po = (uint64_t)d->N * d->Ho * d->Wo;
     const uint64_t M = d->M, N = d->N, SE = d->SE, G = d->G, oc = d->oc;
     // the four stream tensors: P*M / Po*M fp32 elements
-    const bool noexp = (d->flags & (TFNAS_CELL_NOEXPAND | TFNAS_CELL_FUSED)) != 0;
-    ws->E = noexp ? 0 : P * M;                   // (no expand convolution: D = dw(x) / D = conv3x3(x), nothing to save)
+    ws->E = cell_has_E(*d) ? P * M : 0;                  // (no expand convolution: D = dw(x) / D = conv3x3(x), nothing to save)
     ws->D = Po * M;
     ws->Pr = G * Po * oc;
     ws->off_pooled = 0;
@@ -289,7 +283,7 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     ws->part = (d->need_wgrad ? 2 : 1) * (uint64_t)TFNAS_PART_ALLOC;   // second half: weight-gradient side stream
     ws->dx = P * d->ic;
     {
-        const int ns = (d->mode == TFNAS_MODE_STEM || noexp) ? 1 : gemm_plan_expand_dgrad(*d, true).splits;
+        const int ns = (d->mode == TFNAS_MODE_STEM || !cell_has_E(*d)) ? 1 : gemm_plan_expand_dgrad(*d, true).splits;
         ws->dxp = ns > 1 ? (uint64_t)ns * P * d->ic : 4;   /* split-K partials of the expand dgrad */
     }
     return 0;
@@ -316,7 +310,7 @@ static void bn_site(const TfnasCellDesc& d, int site, int& nch, uint64_t& cnt) {
 }
 // an expand-free block and a Fused-MBConv block have no BatchNorm site 0: every site-0 pointer of their TfnasBnAffine must be NULL
 static int check_bn_sites(const TfnasCellDesc& d, const TfnasBnAffine* bn) {
-    if (!cell_noexpand(d) && !cell_fused(d)) return 0;
+    if (cell_has_bn0(d)) return 0;
     if (bn->weight[0] || bn->bias[0] || bn->g_weight[0] || bn->g_bias[0] || bn->running_mean[0] || bn->running_var[0])
         return TFNAS_EINVAL;
     return 0;
@@ -327,6 +321,21 @@ static int bn_fwd_fix(const TfnasCellDesc& d, const TfnasBnAffine* bn, int site,
     bn_site(d, site, nch, cnt);
     return launch_bn_fwd_fix(stats, nch, cnt, d.eps, bn->weight[site], bn->bias[site], bn->running_mean[site],
                              bn->running_var[site], bn->momentum, bn->eval, s, stats_world(d));   // (sync-stats: global batch)
+}
+
+// the front of a plain MBConv cell's forward: expand + BN1 + act + depthwise, by one of three routes; writes D and stats2
+// (d: the launch's descriptor, eps = -1 with affine BatchNorm; d0: the caller's)
+static int fwd_front_mbconv(const TfnasCellDesc& d, const TfnasCellDesc& d0, const CellFwdBufs& b, bool fx, bool sync,
+                            double* stats1, double* stats2, hipStream_t s) {
+    const TfnasBnAffine* bn = b.bn;
+    if (fx) TRY(launch_fx_stats(d, b.x, stats1, b.part, s));                  // BN1 statistics from the Gram matrix of x
+    else if (b.E) TRY(launch_expand_fwd(d, b.x, b.E, stats1, b.part, s));     // 1x1 expand (all groups) + BN1 statistics
+    else TRY(launch_expand_stats_gram(d, b.x, stats1, b.part, s));            // E-free: BN1 statistics from the Gram matrix of x
+    if (sync) TRY(stats_sync(d, stats1, 2 * (size_t)d.M, s));                    // sync-stats: global-batch sums (no-op without a hook)
+    if (bn) TRY(bn_fwd_fix(d0, bn, 0, stats1, s));
+    if (fx) TRY(launch_fx_fwd(d, b.x, stats1, b.E, b.D, stats2, b.part, s));  // expand + BN1 + act + depthwise in one kernel
+    else TRY(launch_dw_fwd(d, b.E, b.x, stats1, b.D, stats2, b.part, s));     // BN1+act fused load, depthwise, BN2 statistics
+    return 0;
 }
 
 int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdBufs& b, hipStream_t s, int* route) {
@@ -349,20 +358,18 @@ int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdB
     if (route) *route = taken;
     const bool fx = (taken & TFNAS_ROUTE_TAKEN_FX) != 0;
     const bool sync = !(bn && bn->eval);          // (eval mode normalises with the running statistics: nothing to reduce)
-    if (cell_fused(d)) {
+    switch (cell_kind(d)) {                       // ... D and stats2 are written:
+    case TFNAS_KIND_FUSED:
         // Fused-MBConv: one dense 3 x 3 convolution of the raw cell input writes D and the BN_a statistics (no E, no stats1)
         TRY(launch_conv_fwd(d, b.x, b.D, stats2, b.part, s));
-    } else if (cell_noexpand(d)) {
+        break;
+    case TFNAS_KIND_NOEXPAND:
         // no expand convolution, no BatchNorm site 0: the depthwise reads the raw cell input (E and stats1 are not touched)
         TRY(launch_dw_fwd(d, nullptr, b.x, nullptr, b.D, stats2, b.part, s));
-    } else {
-    if (fx) TRY(launch_fx_stats(d, b.x, stats1, b.part, s));                  // BN1 statistics from the Gram matrix of x
-    else if (b.E) TRY(launch_expand_fwd(d, b.x, b.E, stats1, b.part, s));     // 1x1 expand (all groups) + BN1 statistics
-    else TRY(launch_expand_stats_gram(d, b.x, stats1, b.part, s));            // E-free: BN1 statistics from the Gram matrix of x
-    if (sync) TRY(stats_sync(d, stats1, 2 * (size_t)d.M, s));                    // sync-stats: global-batch sums (no-op without a hook)
-    if (bn) TRY(bn_fwd_fix(d0, bn, 0, stats1, s));
-    if (fx) TRY(launch_fx_fwd(d, b.x, stats1, b.E, b.D, stats2, b.part, s));  // expand + BN1 + act + depthwise in one kernel
-    else TRY(launch_dw_fwd(d, b.E, b.x, stats1, b.D, stats2, b.part, s));     // BN1+act fused load, depthwise, BN2 statistics
+        break;
+    case TFNAS_KIND_MBCONV:
+        TRY(fwd_front_mbconv(d, d0, b, fx, sync, stats1, stats2, s));
+        break;
     }
     if (sync) TRY(stats_sync(d, stats2, 2 * (size_t)d.M, s));
     if (bn) TRY(bn_fwd_fix(d0, bn, 1, stats2, s));
@@ -415,46 +422,38 @@ static int expand_dx(const TfnasCellDesc& d, const float* dEh, const float* x, c
 // TFNAS_ROUTE_FOLD_OFF: BN2-backward tables in their own pass (k_bn2_pool) instead of the epilogue of k_project_dgrad; both
 // are compared with the oracle (tests/test_gpu_cell.py::test_variant_against_oracle)
 
-int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdBufs& b0, hipStream_t s, const CellSide* so,
-                  int fwd_route) {
-    const TfnasBnAffine* bn = b0.bn;
-    TfnasCellDesc dc = d0;
-    if (bn) dc.eps = -1.f;
-    const TfnasCellDesc& d = dc;
-    CellBwdBufs b = b0;
-    // The launch's ONE route decision, against the forward's when the caller recorded it (per cell: tfnas_cell_route ->
-    // TfnasCellDesc.fwd_route; path level: PathCtx): a backward that would read the E buffer differently from how the forward
-    // wrote it (need_wgrad, the sync hook or the process-default GEMM mode changed in between) refuses before it launches anything
-    const int taken = route_taken(d0, bn != nullptr);
-    if ((fwd_route & TFNAS_ROUTE_TAKEN_VALID) && taken != fwd_route) return TFNAS_EINVAL;
-    const float* dout_res = b0.dout;                       // the residual branch sees the unscaled gradient
-    if (b0.drop_scale && d.has_res) {
-        if (!b0.dout_s) return TFNAS_ENULL;
-        TRY(launch_rowscale(b0.dout_s, b0.dout, nullptr, b0.drop_scale, d.N, (uint64_t)d.Ho * d.Wo * d.oc, s));
-        b.dout = b0.dout_s;
-    }
-    const double* stats1 = b.stats + ws.off_stats1;
-    const double* stats2 = b.stats + ws.off_stats2;
-    const double* stats3 = b.stats + ws.off_stats3;
-    const float* pooled = b.fsmall + ws.off_pooled;
-    const float* gate = b.fsmall + ws.off_gate;
-    const float* hpre = b.fsmall + ws.off_hpre;
-    float* dgate = b.bsmall + ws.off_dgate;
-    float* dpooled = b.bsmall + ws.off_dpooled;
-    float* dhpre = b.bsmall + ws.off_dhpre;
-    float* cb1 = b.bsmall + ws.off_cb1;
-    double* red3 = b.red + ws.off_red3;
-    double* red2 = b.red + ws.off_red2;
-    double* red1 = b.red + ws.off_red1;
-    float* part = b.part;
-    float* part_w = b.part_w;
-    float* part_w1 = b.part_w1 ? b.part_w1 : b.part_w;      // (forks on streams of their own must not share split-K scratch)
-    float* part_w2 = b.part_w2 ? b.part_w2 : b.part_w;
+// One cell backward in flight: the launch's descriptor and buffers and the views into them.  The common prefix and the three
+// kind-specific tails are member functions, so every launch line reads as it would inside one function.
+namespace {
+struct CellBwd {
+    const TfnasCellDesc& d0;         // the caller's descriptor
+    TfnasCellDesc d;                 // the launch's: eps = -1 with affine BatchNorm
+    const TfnasCellWs& ws;
+    CellBwdBufs b;
+    hipStream_t s;
+    const CellSide* so;
+    const TfnasBnAffine* bn;
+    int taken;                       // the launch's ONE route decision (route_taken)
+    const float* dout_res;           // the residual branch sees the unscaled gradient
+    const double *stats1, *stats2, *stats3;
+    const float *pooled, *gate, *hpre;
+    float *dgate, *dpooled, *dhpre, *cb1;
+    double *red3, *red2, *red1;
+    float *part, *part_w, *part_w1, *part_w2;
 
+    int run();
+    int tail_fused();
+    int tail_noexpand();
+    int tail_mbconv();
+};
+
+// everything up to and including the BN2 backward sums, then the tail of the cell's kind
+int CellBwd::run() {
     if (d.need_wgrad) {
+        const CellKind kind = cell_kind(d);
         for (int g = 0; g < d.G; ++g) {
             const TfnasGroup& gr = d.g[g];
-            if ((!gr.g_expand && !cell_noexpand(d)) || (!gr.g_dw && !cell_fused(d)) || !gr.g_proj) return TFNAS_ENULL;
+            if ((!gr.g_expand && kind != TFNAS_KIND_NOEXPAND) || (!gr.g_dw && kind != TFNAS_KIND_FUSED) || !gr.g_proj) return TFNAS_ENULL;
             if (gr.se > 0 && (!gr.g_se_r || !gr.gb_se_r || !gr.g_se_e || !gr.gb_se_e)) return TFNAS_ENULL;
         }
     }
@@ -489,30 +488,41 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
     else TRY(launch_bn2_bwd(d, b.dZ, b.D, stats2, gate, dpooled, red2, part, s));
     TRY(stats_sync(d, red2, 2 * (size_t)d.M, s));
     if (bn) TRY(bn_bwd_fix(d0, bn, 1, red2, s));
-    if (cell_fused(d)) {
-        // Fused-MBConv: dd, the gradient w.r.t. D, goes to dEh once (free since the SE backward above); the convolution's weight
-        // gradient and its data gradient (which writes dx, + the unscaled residual gradient) both read it
-        TRY(launch_conv_dd(d, b.dZ, b.D, gate, dpooled, stats2, red2, b.dEh, s));
-        if (d.need_wgrad) {
-            hipStream_t sw = fork_to(so, 1, s);
-            if (d.SE > 0) TRY(launch_se_wgrad(d, dgate, gate, dhpre, hpre, pooled, sw));
-            TRY(launch_conv_wgrad(d, b.dEh, b.x, part_w1, sw));
-        }
-        if (b.dx) TRY(launch_conv_dgrad(d, b.dEh, d.has_res ? dout_res : nullptr, b.dx, part, s));
-        return 0;
+    switch (cell_kind(d)) {
+    case TFNAS_KIND_FUSED: return tail_fused();
+    case TFNAS_KIND_NOEXPAND: return tail_noexpand();
+    case TFNAS_KIND_MBCONV: break;
     }
-    if (cell_noexpand(d)) {
-        // no expand convolution: the depthwise weight gradient reads the raw cell input, and the depthwise backward-data pass
-        // writes dx itself (+ the unscaled residual gradient); no BN1 backward, no Gram operator, no expand dgrad / wgrad
-        if (d.need_wgrad) {
-            hipStream_t sw = fork_to(so, 1, s);
-            if (d.SE > 0) TRY(launch_se_wgrad(d, dgate, gate, dhpre, hpre, pooled, sw));
-            TRY(launch_dw_wgrad(d, b.dZ, gate, dpooled, b.D, stats2, red2, b.x, nullptr, part_w1, sw));
-        }
-        if (b.dx)
-            TRY(launch_dw_bwd_dx(d, b.dZ, gate, dpooled, b.D, stats2, red2, d.has_res ? dout_res : nullptr, b.dx, s));
-        return 0;
+    return tail_mbconv();
+}
+
+int CellBwd::tail_fused() {
+    // Fused-MBConv: dd, the gradient w.r.t. D, goes to dEh once (free since the SE backward above); the convolution's weight
+    // gradient and its data gradient (which writes dx, + the unscaled residual gradient) both read it
+    TRY(launch_conv_dd(d, b.dZ, b.D, gate, dpooled, stats2, red2, b.dEh, s));
+    if (d.need_wgrad) {
+        hipStream_t sw = fork_to(so, 1, s);
+        if (d.SE > 0) TRY(launch_se_wgrad(d, dgate, gate, dhpre, hpre, pooled, sw));
+        TRY(launch_conv_wgrad(d, b.dEh, b.x, part_w1, sw));
     }
+    if (b.dx) TRY(launch_conv_dgrad(d, b.dEh, d.has_res ? dout_res : nullptr, b.dx, part, s));
+    return 0;
+}
+
+int CellBwd::tail_noexpand() {
+    // no expand convolution: the depthwise weight gradient reads the raw cell input, and the depthwise backward-data pass
+    // writes dx itself (+ the unscaled residual gradient); no BN1 backward, no Gram operator, no expand dgrad / wgrad
+    if (d.need_wgrad) {
+        hipStream_t sw = fork_to(so, 1, s);
+        if (d.SE > 0) TRY(launch_se_wgrad(d, dgate, gate, dhpre, hpre, pooled, sw));
+        TRY(launch_dw_wgrad(d, b.dZ, gate, dpooled, b.D, stats2, red2, b.x, nullptr, part_w1, sw));
+    }
+    if (b.dx)
+        TRY(launch_dw_bwd_dx(d, b.dZ, gate, dpooled, b.D, stats2, red2, d.has_res ? dout_res : nullptr, b.dx, s));
+    return 0;
+}
+
+int CellBwd::tail_mbconv() {
     if (taken & TFNAS_ROUTE_TAKEN_FX) {
         // fused per-image route: depthwise dgrad + act' + the dE (rstd . W1) term of the expand dgrad in one kernel (dE never
         // materialised; partial sums per channel slice in the dEh buffer), then the BN1-backward correction -x G + b
@@ -549,6 +559,40 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
         TRY(expand_dx(d, b.dEh, b.x, cb1, part, dout_res, b.wmix, b.dx, b.dxp, s, b.add_src, b.add_scale));
     return 0;
 }
+}  // namespace
+
+int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdBufs& b0, hipStream_t s, const CellSide* so,
+                  int fwd_route) {
+    const TfnasBnAffine* bn = b0.bn;
+    // The launch's ONE route decision, against the forward's when the caller recorded it (per cell: tfnas_cell_route ->
+    // TfnasCellDesc.fwd_route; path level: PathCtx): a backward that would read the E buffer differently from how the forward
+    // wrote it (need_wgrad, the sync hook or the process-default GEMM mode changed in between) refuses before it launches anything
+    const int taken = route_taken(d0, bn != nullptr);
+    if ((fwd_route & TFNAS_ROUTE_TAKEN_VALID) && taken != fwd_route) return TFNAS_EINVAL;
+    const CellBwdBufs& b = b0;
+    CellBwd c = {d0, d0, ws, b0, s, so, bn, taken, b0.dout,
+                 b.stats + ws.off_stats1, b.stats + ws.off_stats2, b.stats + ws.off_stats3,
+                 b.fsmall + ws.off_pooled, b.fsmall + ws.off_gate, b.fsmall + ws.off_hpre,
+                 b.bsmall + ws.off_dgate, b.bsmall + ws.off_dpooled, b.bsmall + ws.off_dhpre, b.bsmall + ws.off_cb1,
+                 b.red + ws.off_red3, b.red + ws.off_red2, b.red + ws.off_red1,
+                 b.part, b.part_w,
+                 b.part_w1 ? b.part_w1 : b.part_w,       // (forks on streams of their own must not share split-K scratch)
+                 b.part_w2 ? b.part_w2 : b.part_w};
+    if (bn) c.d.eps = -1.f;
+    if (b0.drop_scale && d0.has_res) {
+        if (!b0.dout_s) return TFNAS_ENULL;
+        TRY(launch_rowscale(b0.dout_s, b0.dout, nullptr, b0.drop_scale, d0.N, (uint64_t)d0.Ho * d0.Wo * d0.oc, s));
+        c.b.dout = b0.dout_s;
+    }
+    return c.run();
+}
+
+// E may be omitted only by a kind that has no E buffer (it is never touched) and -- where the entry point offers it -- in E-free
+// mode (tfnas_efree_supported)
+static int check_E(const TfnasCellDesc& d, const float* E, bool efree_counts) {
+    if (E || !cell_has_E(d) || (efree_counts && efree_supported(d))) return 0;
+    return TFNAS_ENULL;
+}
 
 extern "C" int tfnas_mixedop_fwd(const TfnasCellDesc* dp, const float* x, const float* wmix, float* E, float* D,
                                  float* Pr, float* fsmall, double* stats, float* part, float* out, void* stream) {
@@ -556,8 +600,7 @@ extern "C" int tfnas_mixedop_fwd(const TfnasCellDesc* dp, const float* x, const 
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_modes(dp));
-    // E may be omitted only in E-free mode (tfnas_efree_supported) and by an expand-free cell, which never touches it
-    if (!E && !efree_supported(d) && !cell_noexpand(d) && !cell_fused(d)) return TFNAS_ENULL;
+    TRY(check_E(d, E, true));
     TfnasCellWs ws;
     TRY(tfnas_cell_ws(dp, &ws));
     CellFwdBufs b = {x, wmix, E, D, Pr, fsmall, stats, part, out};
@@ -605,7 +648,7 @@ extern "C" int tfnas_mixedop_bwd(const TfnasCellDesc* dp, const float* x, const 
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_modes(dp));
-    if (!E && !efree_supported(d) && !cell_noexpand(d) && !cell_fused(d)) return TFNAS_ENULL;
+    TRY(check_E(d, E, true));
     CellBwdBufs b = {x, wmix, E, D, Pr, fsmall, stats, dout, dZ, dEh, bsmall, red, part, part + TFNAS_PART_ALLOC,
                      dx, dxp, dwmix, nullptr, nullptr};
     return cell_bwd_entry(d, b, S(stream), d.wgrad_stream, false);
@@ -618,7 +661,7 @@ extern "C" int tfnas_mbconv_fwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD || d.G != 1) return TFNAS_EINVAL;
     TRY(check_modes(dp));
-    if (!E && !cell_noexpand(d) && !cell_fused(d)) return TFNAS_ENULL;
+    TRY(check_E(d, E, false));
     TRY(check_bn_sites(d, bn));
     TfnasCellWs ws;
     TRY(tfnas_cell_ws(dp, &ws));
@@ -638,7 +681,7 @@ extern "C" int tfnas_mbconv_bwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn
     if (d.mode == TFNAS_MODE_HEAD || d.G != 1) return TFNAS_EINVAL;
     if (d.wgrad_stream[0] || d.wgrad_stream[1] || d.wgrad_stream[2]) return TFNAS_EINVAL;     // (tfnas_mixedop_bwd only)
     TRY(check_modes(dp));
-    if (!E && !cell_noexpand(d) && !cell_fused(d)) return TFNAS_ENULL;
+    TRY(check_E(d, E, false));
     TRY(check_bn_sites(d, bn));
     CellBwdBufs b = {x, nullptr, E, D, Pr, fsmall, stats, dout, dZ, dEh, bsmall, red, part, part + TFNAS_PART_ALLOC,
                      dx, dxp, nullptr, nullptr, nullptr};
@@ -676,13 +719,17 @@ static int head_bwd_impl(const TfnasCellDesc& d0, const TfnasBnAffine* bn, const
     return 0;
 }
 
+// what every head entry point asks of its descriptor
+static int check_head(const TfnasCellDesc* dp) {
+    if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    TRY(check_act(dp));
+    return check_kind(dp);
+}
+
 extern "C" int tfnas_head_affine_fwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn, const float* x, float* E, double* stats,
                                      float* part, float* pooled, void* stream) {
     if (!dp || !bn || !x || !E || !stats || !part || !pooled) return TFNAS_ENULL;
-    if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    TRY(check_act(dp));
-    TRY(check_noexpand(dp));
-    TRY(check_fused(dp));
+    TRY(check_head(dp));
     return head_fwd_impl(*dp, bn, x, E, stats, part, pooled, S(stream));
 }
 
@@ -690,10 +737,7 @@ extern "C" int tfnas_head_affine_bwd(const TfnasCellDesc* dp, const TfnasBnAffin
                                      const double* stats, const float* dpooled, float* dEh, float* cb1, double* red,
                                      float* part, float* dx, float* dxp, void* stream) {
     if (!dp || !bn || !x || !E || !stats || !dpooled || !dEh || !cb1 || !red || !part || !dx) return TFNAS_ENULL;
-    if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    TRY(check_act(dp));
-    TRY(check_noexpand(dp));
-    TRY(check_fused(dp));
+    TRY(check_head(dp));
     if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
     return head_bwd_impl(*dp, bn, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
@@ -701,10 +745,7 @@ extern "C" int tfnas_head_affine_bwd(const TfnasCellDesc* dp, const TfnasBnAffin
 extern "C" int tfnas_head_fwd(const TfnasCellDesc* dp, const float* x, float* E, double* stats, float* part,
                               float* pooled, void* stream) {
     if (!dp || !x || !E || !stats || !part || !pooled) return TFNAS_ENULL;
-    if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    TRY(check_act(dp));
-    TRY(check_noexpand(dp));
-    TRY(check_fused(dp));
+    TRY(check_head(dp));
     return head_fwd_impl(*dp, nullptr, x, E, stats, part, pooled, S(stream));
 }
 
@@ -712,10 +753,7 @@ extern "C" int tfnas_head_bwd(const TfnasCellDesc* dp, const float* x, const flo
                               const float* dpooled, float* dEh, float* cb1, double* red, float* part, float* dx,
                               float* dxp, void* stream) {
     if (!dp || !x || !E || !stats || !dpooled || !dEh || !cb1 || !red || !part || !dx) return TFNAS_ENULL;
-    if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    TRY(check_act(dp));
-    TRY(check_noexpand(dp));
-    TRY(check_fused(dp));
+    TRY(check_head(dp));
     if (dp->need_wgrad && !dp->g[0].g_expand) return TFNAS_ENULL;
     return head_bwd_impl(*dp, nullptr, x, E, stats, dpooled, dEh, cb1, red, part, dx, dxp, S(stream));
 }
@@ -723,11 +761,8 @@ extern "C" int tfnas_head_bwd(const TfnasCellDesc* dp, const float* x, const flo
 extern "C" int tfnas_head_wgrad(const TfnasCellDesc* dp, const float* x, const float* E, const float* dEh, const float* cb1,
                                 float* part, void* stream) {
     if (!dp || !x || !E || !dEh || !cb1 || !part) return TFNAS_ENULL;
+    TRY(check_head(dp));
     const TfnasCellDesc& d = *dp;
-    if (d.mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
-    TRY(check_act(dp));
-    TRY(check_noexpand(dp));
-    TRY(check_fused(dp));
     if (!d.g[0].g_expand) return TFNAS_ENULL;
     return launch_expand_wgrad(d, dEh, E, cb1, x, part, S(stream));
 }

@@ -40,6 +40,15 @@ static inline bool cell_noexpand(const TfnasCellDesc& d) { return (d.flags & TFN
 // TFNAS_CELL_FUSED: a Fused-MBConv block (G = 1, k = 3): D = conv3x3(x) with the dense OIHW weight in w_expand, no depthwise
 // weight, no E, no BatchNorm site 0; the three implicit GEMMs of conv_kernels.hip stand where the depthwise passes stand
 static inline bool cell_fused(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_FUSED) != 0; }
+// The kind of a cell, decided once per function that forks on it (the table's Python twin: tfnas_amd/_lib.py, BlockKind).  A
+// descriptor with both bits is refused by every entry point (capi.hip: check_kind) before anything asks.
+enum CellKind { TFNAS_KIND_MBCONV, TFNAS_KIND_NOEXPAND, TFNAS_KIND_FUSED };
+static inline CellKind cell_kind(const TfnasCellDesc& d) {
+    return cell_fused(d) ? TFNAS_KIND_FUSED : cell_noexpand(d) ? TFNAS_KIND_NOEXPAND : TFNAS_KIND_MBCONV;
+}
+// the two facts of a kind the host code asks for repeatedly: an E buffer, a BatchNorm site 0 (today: the plain MBConv cell has both)
+static inline bool cell_has_E(const TfnasCellDesc& d) { return cell_kind(d) == TFNAS_KIND_MBCONV; }
+static inline bool cell_has_bn0(const TfnasCellDesc& d) { return cell_kind(d) == TFNAS_KIND_MBCONV; }
 // the activation fork of a launcher (inside a function returning int): the statements run with ACT = the launch's activation as a
 // compile-time constant; any other value is TFNAS_EINVAL
 #define ACT_DISPATCH(act, ...)                                                                        \

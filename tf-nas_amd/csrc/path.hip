@@ -76,8 +76,7 @@ int plan_path(PathCtx& c, const TfnasPathDesc& in, TfnasPathWs* out) {
     for (int i = 0; i < pd.ncell; ++i) {
         TfnasCellDesc& d = pd.cell[i];
         if (d.mode != TFNAS_MODE_CELL) return TFNAS_EINVAL;
-        if (d.flags & TFNAS_CELL_NOEXPAND) return TFNAS_EINVAL;   // (expand-free blocks run through the per-cell entry points only)
-        if (d.flags & TFNAS_CELL_FUSED) return TFNAS_EINVAL;      // (Fused-MBConv blocks too)
+        if (cell_kind(d) != TFNAS_KIND_MBCONV) return TFNAS_EINVAL;   // (the other kinds run through the per-cell entry points only)
         if (!pd.soft && d.G != 1) return TFNAS_EINVAL;            // a sampled path evaluates one candidate per cell
         if (i > 0) {
             const TfnasCellDesc& p = pd.cell[i - 1];

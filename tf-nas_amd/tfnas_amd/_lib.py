@@ -3,6 +3,7 @@
 The shared library is built in-tree by ``tf-nas_amd/csrc/Makefile`` (``__graft_entry__.build()``).  There is
 NO fallback: if the library is missing or an entry point returns non-zero, a RuntimeError is raised.
 """
+import collections
 import ctypes as C
 import os
 
@@ -17,6 +18,7 @@ LIB_PATH = os.environ.get('TFNAS_LIB') or os.path.join(_HERE, 'libtfnas_hip.so')
 MAX_GROUPS, MAX_SINK, MAX_CELLS = 8, 4, 32
 ACT = {'relu': 0, 'swish': 1, 'relu6': 2, 'h-swish': 3}       # the reference's spellings (models/layers.py:38-47); TFNAS_ACT_*
 MODE_CELL, MODE_STEM, MODE_HEAD = 0, 1, 2
+BN_EPS = 1e-5                # TfnasCellDesc.eps of every descriptor (the reference's BatchNorm eps)
 
 _W_FIELDS = ('w_expand', 'w_dw', 'w_proj', 'w_se_r', 'b_se_r', 'w_se_e', 'b_se_e')
 _G_FIELDS = ('g_expand', 'g_dw', 'g_proj', 'g_se_r', 'gb_se_r', 'g_se_e', 'gb_se_e')
@@ -49,6 +51,34 @@ def act_flags(act):
     """TfnasCellDesc.flags bit a descriptor with activation id ``act`` needs (the library takes the two newer activations only
     from callers that say they know them)."""
     return CELL_ACTS if act in (ACT['relu6'], ACT['h-swish']) else 0
+
+
+class BlockKind(collections.namedtuple('BlockKind', 'name flag fields bn_sites has_E')):
+    """One kind of one-block cell -- THE table of what a kind is (its C twin: cell_kind() and the two predicates next to it in
+    csrc/kernels.h).  ``flag``: its TfnasCellDesc.flags bit; ``fields``: the indices into _W_FIELDS / _G_FIELDS it binds, with SE
+    (without: those below 3); ``bn_sites``: which of the three BatchNorm sites exist; ``has_E``: whether it has an E buffer."""
+    __slots__ = ()
+
+    def bound(self, se):
+        """The TfnasGroup field indices a block of this kind binds, in hip_params() order (``se``: it has squeeze-excite)."""
+        return self.fields if se else tuple(k for k in self.fields if k < 3)
+
+
+MBCONV = BlockKind('MBCONV', 0, (0, 1, 2, 3, 4, 5, 6), (0, 1, 2), True)                    # expand, depthwise, project
+NOEXPAND = BlockKind('NOEXPAND', CELL_NOEXPAND, (1, 2, 3, 4, 5, 6), (1, 2), False)         # no expand convolution: D = dw(x)
+FUSED = BlockKind('FUSED', CELL_FUSED, (0, 2, 3, 4, 5, 6), (1, 2), False)                  # dense 3 x 3 weight in w_expand, no depthwise
+KINDS = (MBCONV, NOEXPAND, FUSED)
+
+
+def describe_block(kind, N, H, W, ic, mc, se, oc, k, stride, act):
+    """A one-block TFNAS_MODE_CELL descriptor of ``kind``, before tfnas_cell_plan: the geometry words, has_res, eps and the flags
+    the geometry itself asks for (CELL_K7, the activation's bit, the kind's bit).  ``act``: a TFNAS_ACT_* id.  Pure host code."""
+    d = TfnasCellDesc()
+    d.N, d.H, d.W, d.ic, d.oc, d.stride, d.act, d.G, d.mode = N, H, W, ic, oc, stride, act, 1, MODE_CELL
+    d.has_res, d.eps = int(ic == oc and stride == 1), BN_EPS
+    d.g[0].mc, d.g[0].k, d.g[0].se = mc, k, se
+    d.flags = (CELL_K7 if k == 7 else 0) | act_flags(act) | kind.flag
+    return d
 
 
 class TfnasGroup(C.Structure):

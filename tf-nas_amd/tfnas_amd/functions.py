@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import TfnasCellDesc, TfnasCellWs, ptr, ptr_array, check
 
-BN_EPS = 1e-5
+BN_EPS = _lib.BN_EPS
 # TFNAS_EFREE = 1 (default policy: stride-2 cells with ic <= 24 -- cells 0 and 2 of the supernet, -25 % / -16 % of their alpha-step
 # time) | 0 (the expanded tensor E is kept in every cell: A/B timing, equivalence tests) | all (E-free wherever the library
 # supports it -- stride 1 and ic = 40 too, where the row-streaming kernels on a materialised E are still faster: tests)
@@ -130,22 +130,19 @@ class HipModes:
         st['sync'] = None
         return st
 
-    def apply(self, d):
+    def apply(self, d, kind=None):
+        """Write this model's modes and the flags the descriptor's own content asks for; ``kind``: the _lib.BlockKind of the plan
+        that owns ``d`` (CellPlan.desc).  A bare descriptor (None) is taken for what its words say: a one-block cell with
+        mc == ic is an expand-free block, anything else a plain one."""
         d.gemm_mode = 0 if self.gemm is None else (_lib.GEMM_EXPLICIT | _lib.GEMM_MODES[self.gemm]
                                                    | (_lib.GEMM_EVERYWHERE if self.everywhere else 0))
         d.flags = _lib.CELL_LAZY_JOIN if self.lazy_join else 0
         if any(d.g[g].k == 7 for g in range(min(d.G, _lib.MAX_GROUPS))):
             d.flags |= _lib.CELL_K7                    # (the library takes 7 x 7 groups only from callers that say they know them)
         d.flags |= _lib.act_flags(d.act)               # (... and 'relu6' / 'h-swish')
-        # ... and a block without expand convolution (D = dw(x)).  The modules build one exactly when mid > in and normalise
-        # mid to in otherwise (layers.MBInvertedResBlock: inverted_bottleneck is None), so a one-block cell descriptor of a plan
-        # with mc == ic is such a block
-        # ``d.fused_block`` (set by CellPlan.desc on the descriptors of a plan whose one block is a layers.FusedMBConvBlock): a
-        # dense 3 x 3 convolution, whatever its width
-        if getattr(d, 'fused_block', False) and d.mode == _lib.MODE_CELL and d.G == 1:
-            d.flags |= _lib.CELL_FUSED
-        elif d.mode == _lib.MODE_CELL and d.G == 1 and d.g[0].mc == d.ic:
-            d.flags |= _lib.CELL_NOEXPAND
+        if kind is None:
+            kind = _lib.NOEXPAND if (d.mode == _lib.MODE_CELL and d.G == 1 and d.g[0].mc == d.ic) else _lib.MBCONV
+        d.flags |= kind.flag                           # (... and the two newer block kinds)
         d.route = ENV_ROUTE if self.route is None else int(self.route)
         if self.sync is None:
             d.sync_fn, d.sync_user, d.sync_world = None, None, 0
@@ -179,11 +176,23 @@ class CellPlan:
     def __init__(self, ic, oc, stride, act, blocks, mode=_lib.MODE_CELL, modes=None):
         self.ic, self.oc, self.stride, self.act = ic, oc, stride, act
         self.blocks = list(blocks)                     # MBInvertedResBlock modules (parameter containers)
-        # a plan of ONE layers.FusedMBConvBlock (TFNAS_CELL_FUSED); among several candidates the library has no such launch
-        self.fused = any(getattr(b, 'fused', False) for b in self.blocks)
-        if self.fused and (len(self.blocks) != 1 or mode != _lib.MODE_CELL):
+        # the kind is decided HERE, once: a one-block cell is what its block is (_lib.BlockKind), every other plan is plain
+        kinds = [getattr(b, 'kind', _lib.MBCONV) for b in self.blocks]
+        if _lib.FUSED in kinds and (len(self.blocks) != 1 or mode != _lib.MODE_CELL):
             raise NotImplementedError('tfnas_amd: a FusedMBConvBlock runs as a one-block cell only (not as a candidate of a '
                                       'multi-candidate MixedOP launch, a stem or a head)')
+        self.kind = kinds[0] if (mode == _lib.MODE_CELL and len(self.blocks) == 1) else _lib.MBCONV
+        # (what desc() hands HipModes.apply after the descriptor: a plain plan names no kind, so that a subclass which overrides
+        # apply(d) alone keeps working -- for such a plan apply's own inference says MBCONV too)
+        self._kind_arg = () if self.kind is _lib.MBCONV else (self.kind,)
+        # (group, field index) of every parameter bind() is handed, in params() order: a head binds its one weight, the stem all
+        # seven fields, a cell's block the fields of its kind
+        slots = []
+        for g, (b, kind) in enumerate(zip(self.blocks, kinds)):
+            fields = (0,) if mode == _lib.MODE_HEAD else (kind if mode == _lib.MODE_CELL else _lib.MBCONV).bound(b.se_channels > 0)
+            slots += [(g, k) for k in fields]
+        self._w_slots = [(g, _lib._W_FIELDS[k]) for g, k in slots]
+        self._g_slots = [(g, _lib._G_FIELDS[k]) for g, k in slots]
         self._modes = modes
         self.mode = mode
         self.has_res = int(mode == _lib.MODE_CELL and ic == oc and stride == 1)
@@ -216,32 +225,22 @@ class CellPlan:
             d.act, d.has_res, d.G, d.need_wgrad, d.eps = _lib.act_id(self.act), self.has_res, len(self.blocks), 0, BN_EPS
             for g, b in enumerate(self.blocks):
                 d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
-            d.fused_block = self.fused                 # (a Python-side mark, not a field of the C struct: HipModes.apply)
-            self.modes.apply(d)                        # (before the plan: it validates the modes; every launch re-checks them)
+            self.modes.apply(d, *self._kind_arg)       # (before the plan: it validates the modes; every launch re-checks them)
             check(_lib.lib().tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
             ws = TfnasCellWs()
             check(_lib.lib().tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
             hit = (d, ws)
             self._desc_cache[key] = hit
-        self.modes.apply(hit[0])                       # (every launch: the descriptor is cached, the model's modes may change)
+        self.modes.apply(hit[0], *self._kind_arg)      # (every launch: the descriptor is cached, the model's modes may change)
         return hit
 
     def bind(self, d, params, grads=None):
         """Write current weight (and gradient) pointers into the descriptor."""
-        i = 0
-        for g, b in enumerate(self.blocks):
-            n = 1 if self.mode == _lib.MODE_HEAD else (7 if b.se_channels > 0 else 3)
-            # (a block without expand convolution has no first field: TFNAS_CELL_NOEXPAND wants w_expand / g_expand NULL)
-            first = int(self.mode == _lib.MODE_CELL and not getattr(b, 'fused', False)
-                        and getattr(b, 'inverted_bottleneck', False) is None)
-            # (a Fused-MBConv block: the dense weight in the expand field, no depthwise field -- TFNAS_CELL_FUSED wants it NULL)
-            keep = [j for j in range(first, n) if not (self.fused and j == 1)]
-            for j, k in enumerate(keep):
-                setattr(d.g[g], _lib._W_FIELDS[k], params[i + j].data_ptr())
-            if grads is not None:
-                for j, k in enumerate(keep):
-                    setattr(d.g[g], _lib._G_FIELDS[k], grads[i + j].data_ptr())
-            i += len(keep)
+        for (g, f), p in zip(self._w_slots, params):
+            setattr(d.g[g], f, p.data_ptr())
+        if grads is not None:
+            for (g, f), t in zip(self._g_slots, grads):
+                setattr(d.g[g], f, t.data_ptr())
         d.need_wgrad = int(grads is not None)
 
 

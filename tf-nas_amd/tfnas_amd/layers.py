@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._lib import act_id
+from ._lib import act_id, MBCONV, NOEXPAND, FUSED
 from .functions import CellPlan, MixedOpFn, BN_EPS
 
 
@@ -83,11 +83,39 @@ def _seq(**mods):
 
 
 class _HipBlock(nn.Module):
-    """What the blocks that run as ONE cell of the HIP library share: the launch (search form through ``tfnas_mixedop_fwd``,
-    ``affine=True`` through ``tfnas_mbconv_fwd``) and drop-connect.  A subclass provides ``hip_params()``, ``bn_modules()`` and
-    ``bn_sites()``; ``fused`` tells ``CellPlan`` which kind of cell the block is."""
+    """What the blocks that run as ONE cell of the HIP library share: everything after the leading convolutions (squeeze-excite,
+    the project convolution, the residual), the parameter / BatchNorm lists in the order of the library's fields, the launch
+    (search form through ``tfnas_mixedop_fwd``, ``affine=True`` through ``tfnas_mbconv_fwd``) and drop-connect.  A subclass
+    validates its arguments, registers its leading convolution modules through ``lead(mid_channels)`` (an ordered
+    {name: module or None}) and names its ``kind`` (_lib.BlockKind: which fields and BatchNorm sites such a cell has)."""
 
-    fused = False                    # (True: TFNAS_CELL_FUSED -- the dense weight in the expand field, no depthwise field)
+    kind = MBCONV
+
+    def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead):
+        super().__init__()
+        act_id(act_func)                                   # (ValueError for a name the library has no kernels for)
+        self.in_channels, self.mid_channels = in_channels, mid_channels
+        self.se_channels, self.out_channels = max(se_channels, 0), out_channels
+        self.kernel_size, self.stride, self.act_func = kernel_size, stride, act_func
+        self.affine = affine
+        self.drop_connect_rate = 0.0
+        leading = lead(mid_channels)
+        for name, mod in leading.items():
+            setattr(self, name, mod)
+        if se_channels > 0:
+            self.squeeze_excite = _seq(conv_reduce=nn.Conv2d(mid_channels, se_channels, 1, 1, 0, bias=True),
+                                       conv_expand=nn.Conv2d(se_channels, mid_channels, 1, 1, 0, bias=True))
+        else:
+            self.squeeze_excite = None
+        self.point_linear = _seq(conv=nn.Conv2d(mid_channels, out_channels, 1, 1, 0, bias=False), **self.bn(out_channels))
+        self.has_residual = (in_channels == out_channels) and (stride == 1)
+        # the conv (+ bn) modules in the order of the library's fields: the leading ones that are there, then the project
+        self._convs = [m for m in leading.values() if m is not None] + [self.point_linear]
+        self._plan = None
+
+    def bn(self, ch):
+        """affine=True: the derived network's BatchNorm2d(affine, running statistics), layers.py:468,497,533"""
+        return dict(bn=nn.BatchNorm2d(ch, affine=True, track_running_stats=True)) if self.affine else {}
 
     def forward(self, x):
         if self._plan is None:
@@ -96,9 +124,24 @@ class _HipBlock(nn.Module):
             return self._affine_forward(x)
         return MixedOpFn.apply(self._plan, x, None, *self.hip_params())
 
+    def hip_params(self):
+        """Weights in the order of the TfnasGroup pointer fields this kind binds."""
+        ps = [m.conv.weight for m in self._convs]
+        se = self.squeeze_excite
+        if se is not None:
+            ps += [se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias]
+        return ps
+
+    def bn_modules(self):
+        """The block's BatchNorm modules in order (affine form): one per BatchNorm site of its kind."""
+        return [m.bn for m in self._convs]
+
     def bn_sites(self):
         """The three BatchNorm sites of the cell: the block's modules, None where a site does not exist."""
-        raise NotImplementedError
+        sites = [None, None, None]
+        for i, m in zip(self.kind.bn_sites, self._convs):
+            sites[i] = m.bn
+        return sites
 
     def _drop_scale(self, x):
         """Per-image drop-connect scale of the residual block in training (tools/utils.py:77-86), else None."""
@@ -128,54 +171,21 @@ class MBInvertedResBlock(_HipBlock):
 
     def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size=3, stride=1,
                  affine=False, act_func='relu'):
-        super().__init__()
-        act_id(act_func)                                   # (ValueError for a name the library has no kernels for)
-        self.in_channels, self.mid_channels = in_channels, mid_channels
-        self.se_channels, self.out_channels = se_channels, out_channels
-        self.kernel_size, self.stride, self.act_func = kernel_size, stride, act_func
-        self.affine = affine
-        self.drop_connect_rate = 0.0
-        def bn(ch):          # affine=True: the derived network's BatchNorm2d(affine, running statistics), layers.py:468,497,533
-            return dict(bn=nn.BatchNorm2d(ch, affine=True, track_running_stats=True)) if affine else {}
-        if mid_channels > in_channels:
-            self.inverted_bottleneck = _seq(conv=nn.Conv2d(in_channels, mid_channels, 1, 1, 0, bias=False), **bn(mid_channels))
-        else:
-            self.inverted_bottleneck = None
-            self.mid_channels = mid_channels = in_channels
-        self.depth_conv = _seq(conv=nn.Conv2d(mid_channels, mid_channels, kernel_size, stride,
-                                              get_same_padding(kernel_size), groups=mid_channels, bias=False),
-                               **bn(mid_channels))
-        if se_channels > 0:
-            self.squeeze_excite = _seq(conv_reduce=nn.Conv2d(mid_channels, se_channels, 1, 1, 0, bias=True),
-                                       conv_expand=nn.Conv2d(se_channels, mid_channels, 1, 1, 0, bias=True))
-        else:
-            self.squeeze_excite = None
-            self.se_channels = 0
-        self.point_linear = _seq(conv=nn.Conv2d(mid_channels, out_channels, 1, 1, 0, bias=False), **bn(out_channels))
-        self.has_residual = (in_channels == out_channels) and (stride == 1)
-        self._plan = None
+        expand = mid_channels > in_channels
+        if not expand:
+            mid_channels = in_channels
+            self.kind = NOEXPAND
+
+        def lead(mc):
+            return OrderedDict(
+                inverted_bottleneck=_seq(conv=nn.Conv2d(in_channels, mc, 1, 1, 0, bias=False), **self.bn(mc)) if expand else None,
+                depth_conv=_seq(conv=nn.Conv2d(mc, mc, kernel_size, stride, get_same_padding(kernel_size), groups=mc,
+                                               bias=False), **self.bn(mc)))
+        super().__init__(in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead)
 
     @property
     def name(self):
         return 'MBInvertedResBlock'
-
-    def hip_params(self):
-        """Weights in the order of TfnasGroup's pointer fields."""
-        ps = [] if self.inverted_bottleneck is None else [self.inverted_bottleneck.conv.weight]
-        ps += [self.depth_conv.conv.weight, self.point_linear.conv.weight]
-        if self.squeeze_excite is not None:
-            se = self.squeeze_excite
-            ps += [se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias]
-        return ps
-
-    def bn_modules(self):
-        """The block's BatchNorm modules in order: three, or two without an expand convolution."""
-        first = [] if self.inverted_bottleneck is None else [self.inverted_bottleneck.bn]
-        return first + [self.depth_conv.bn, self.point_linear.bn]
-
-    def bn_sites(self):
-        bns = self.bn_modules()
-        return bns if self.inverted_bottleneck is not None else [None] + bns     # (no expand: BatchNorm site 0 does not exist)
 
 
 class FusedMBConvBlock(_HipBlock):
@@ -186,49 +196,20 @@ class FusedMBConvBlock(_HipBlock):
     ``affine=True`` (derived form, drop-connect on the residual branch in training) through ``tfnas_mbconv_fwd``.  Only as a
     block of its own: not a candidate of a multi-candidate MixedOP, kernel size 3 only, always with a project convolution."""
 
-    fused = True                     # (CellPlan: TFNAS_CELL_FUSED, the dense weight in the expand field)
+    kind = FUSED
 
     def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size=3, stride=1,
                  affine=False, act_func='relu'):
-        super().__init__()
-        act_id(act_func)                                   # (ValueError for a name the library has no kernels for)
+        act_id(act_func)                                   # (first, as ever: ValueError for a name the library has no kernels for)
         if kernel_size != 3:
             raise NotImplementedError('tfnas_amd: FusedMBConvBlock has kernel size 3 only (got %r)' % (kernel_size,))
         if in_channels % 4 or mid_channels < 1:
             raise ValueError('tfnas_amd: FusedMBConvBlock wants in_channels a multiple of 4 and mid_channels >= 1')
-        self.in_channels, self.mid_channels = in_channels, mid_channels
-        self.se_channels, self.out_channels = se_channels, out_channels
-        self.kernel_size, self.stride, self.act_func = kernel_size, stride, act_func
-        self.affine = affine
-        self.drop_connect_rate = 0.0
-        def bn(ch):
-            return dict(bn=nn.BatchNorm2d(ch, affine=True, track_running_stats=True)) if affine else {}
-        self.fused_conv = _seq(conv=nn.Conv2d(in_channels, mid_channels, 3, stride, 1, bias=False), **bn(mid_channels))
-        if se_channels > 0:
-            self.squeeze_excite = _seq(conv_reduce=nn.Conv2d(mid_channels, se_channels, 1, 1, 0, bias=True),
-                                       conv_expand=nn.Conv2d(se_channels, mid_channels, 1, 1, 0, bias=True))
-        else:
-            self.squeeze_excite = None
-            self.se_channels = 0
-        self.point_linear = _seq(conv=nn.Conv2d(mid_channels, out_channels, 1, 1, 0, bias=False), **bn(out_channels))
-        self.has_residual = (in_channels == out_channels) and (stride == 1)
-        self._plan = None
+
+        def lead(mc):
+            return OrderedDict(fused_conv=_seq(conv=nn.Conv2d(in_channels, mc, 3, stride, 1, bias=False), **self.bn(mc)))
+        super().__init__(in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead)
 
     @property
     def name(self):
         return 'FusedMBConvBlock'
-
-    def hip_params(self):
-        """Weights in the order of TfnasGroup's pointer fields (the dense weight in the expand field, no depthwise field)."""
-        ps = [self.fused_conv.conv.weight, self.point_linear.conv.weight]
-        if self.squeeze_excite is not None:
-            se = self.squeeze_excite
-            ps += [se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias]
-        return ps
-
-    def bn_modules(self):
-        """The block's two BatchNorm modules in order (affine form)."""
-        return [self.fused_conv.bn, self.point_linear.bn]
-
-    def bn_sites(self):
-        return [None] + self.bn_modules()                   # (BatchNorm site 0 does not exist)

@@ -29,7 +29,6 @@ import numpy as np
 import torch
 
 from . import _lib, geometry
-from .functions import BN_EPS
 
 
 class _BlockTimer:
@@ -46,38 +45,45 @@ class _BlockTimer:
             t = self.bufs[name] = torch.zeros(int(n * 1.25) + 64, device=self.dev, dtype=dtype)   # zero: `part` ticket counters
         return t
 
+    @staticmethod
+    def _describe(ic, mc, se, oc, k, stride, act, H, W, batch, block):
+        """Pure host: the planned descriptor of one block (no pointers yet), its workspace, its _lib.BlockKind, the width after
+        normalisation, {weight field: float offset} into one weight buffer of ``nw`` floats (4-float rounding) and
+        {BatchNorm site: channel offset} into the 2 mc + oc channels of the affine tables."""
+        if block not in BLOCK_KINDS:
+            raise ValueError(block)
+        if block == 'FusedMBConvBlock':              # (a dense 3 x 3 convolution: its weight in the expand field, no depthwise)
+            if k != 3:
+                raise NotImplementedError('tfnas_amd: FusedMBConvBlock has kernel size 3 only (got %r)' % (k,))
+            kind = _lib.FUSED
+        elif mc <= ic:                               # (no expand convolution, mid normalised to in: layers.MBInvertedResBlock)
+            kind, mc = _lib.NOEXPAND, ic
+        else:
+            kind = _lib.MBCONV
+        d = _lib.describe_block(kind, batch, H, W, ic, mc, se, oc, k, stride, _lib.act_id(act))
+        lib = _lib.lib()
+        _lib.check(lib.tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
+        ws = _lib.TfnasCellWs()
+        _lib.check(lib.tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
+        nx = mc * ic * (9 if kind is _lib.FUSED else 1)
+        sizes = (nx, mc * k * k, oc * mc, se * mc, se, mc * se, mc)
+        woff, o = {}, 0
+        for j in kind.bound(se > 0):
+            woff[_lib._W_FIELDS[j]] = o
+            o += (sizes[j] + 3) // 4 * 4
+        site_off = (0, mc, 2 * mc)
+        return d, ws, kind, mc, woff, sum(sizes) + 64, {site: site_off[site] for site in kind.bn_sites}
+
     def measure(self, ic, mc, se, oc, k, stride, act, size, batch=32, warmup=3, iters=10, reps=3, mode='inference',
                 block='MBInvertedResBlock'):
         lib, dev = self.lib, self.dev
         if mode not in ('inference', 'search'):
             raise ValueError(mode)
-        if block not in BLOCK_KINDS:
-            raise ValueError(block)
-        fused = block == 'FusedMBConvBlock'          # (a dense 3 x 3 convolution: its weight in the expand field, no depthwise)
-        if fused and k != 3:
-            raise NotImplementedError('tfnas_amd: FusedMBConvBlock has kernel size 3 only (got %r)' % (k,))
-        d = _lib.TfnasCellDesc()
-        d.N, d.H, d.W, d.ic, d.oc, d.stride = batch, size, size, ic, oc, stride
-        d.mode, d.act, d.G, d.need_wgrad, d.eps = _lib.MODE_CELL, _lib.act_id(act), 1, 0, BN_EPS
-        d.has_res = int(ic == oc and stride == 1)
-        noexp = mc <= ic and not fused   # (no expand convolution, mid normalised to in: layers.MBInvertedResBlock)
-        if noexp:
-            mc = ic
-        d.g[0].mc, d.g[0].k, d.g[0].se = mc, k, se
-        d.flags = ((_lib.CELL_K7 if k == 7 else 0) | _lib.act_flags(d.act) | (_lib.CELL_NOEXPAND if noexp else 0)
-                   | (_lib.CELL_FUSED if fused else 0))
-        _lib.check(lib.tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
-        ws = _lib.TfnasCellWs()
-        _lib.check(lib.tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
-        nx = mc * ic * (9 if fused else 1)
-        w = self._buf('w', nx + mc * k * k + oc * mc + 2 * se * mc + se + mc + 64)
+        d, ws, kind, mc, woff, nw, boff = self._describe(ic, mc, se, oc, k, stride, act, size, size, batch, block)
+        w = self._buf('w', nw)
         w.normal_(0, 0.1)
-        o = 0
-        for f, n in (('w_expand', nx), ('w_dw', mc * k * k), ('w_proj', oc * mc), ('w_se_r', se * mc), ('b_se_r', se),
-                     ('w_se_e', mc * se), ('b_se_e', mc)):
-            if n and (se or not f.endswith(('se_r', 'se_e'))) and not (noexp and f == 'w_expand') and not (fused and f == 'w_dw'):
-                setattr(d.g[0], f, w.data_ptr() + 4 * o)
-                o += (n + 3) // 4 * 4
+        for f, o in woff.items():
+            setattr(d.g[0], f, w.data_ptr() + 4 * o)
         x = self._buf('x', batch * size * size * ic)
         x.normal_()
         D, Pr = self._buf('D', ws.D), self._buf('Pr', ws.Pr)
@@ -102,11 +108,9 @@ class _BlockTimer:
             aff[2 * nb:3 * nb].zero_()
             aff[3 * nb:4 * nb].fill_(1.0)
             bn = _lib.TfnasBnAffine()
-            o2 = 0
-            for site, ch in enumerate((mc, mc, oc)):
+            for site, o2 in boff.items():
                 for fi, f in enumerate(('weight', 'bias', 'running_mean', 'running_var')):
-                    getattr(bn, f)[site] = None if ((noexp or fused) and site == 0) else aff.data_ptr() + 4 * (fi * nb + o2)
-                o2 += ch
+                    getattr(bn, f)[site] = aff.data_ptr() + 4 * (fi * nb + o2)
             bn.momentum, bn.eval = 0.1, 1
             self._bn = bn                                   # (keep the struct alive while its launches are enqueued)
             args = (C.byref(d), C.byref(bn), None, _lib.ptr(x), pE, _lib.ptr(D), _lib.ptr(Pr), _lib.ptr(fs),
