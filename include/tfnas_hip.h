@@ -621,14 +621,17 @@ int tfnas_paths_bwd(int npath, void *const *ctx, const float *const *x0, const f
  * g <- g * grad_scale * min(1, max_norm / (total + 1e-6));  m <- momentum*m + (g + wd*w);  w <- w - lr*m.
  * max_norm <= 0 disables clipping.  scratch: device doubles, >= sum ceil(len/8192).  norm_out: device float or NULL.
  * goff: NULL (gradients at the same offsets as the weights) or the offsets of the ranges inside `g` when `g` is the packed
- * all-reduce message built by tfnas_pack_ranges.  Two launches, no atomics, deterministic. */
+ * all-reduce message built by tfnas_pack_ranges.  Two launches, no atomics, deterministic.
+ * The ranges must be disjoint -- (off[i], len[i]) among themselves and, with goff, (goff[i], len[i]) among themselves:
+ * overlapping ranges return TFNAS_EINVAL before anything is launched. */
 int tfnas_sgd_clip_step(float *w, float *g, float *m, int nranges, const uint64_t *off, const uint64_t *goff, const uint64_t *len,
                         float max_norm, float lr, float momentum, float wd, float grad_scale, double *scratch,
                         uint64_t scratch_doubles, float *norm_out, void *stream);
 
 /* dst[doff[i] .. +len[i]) = src[off[i] .. +len[i]) for nranges <= 64 ranges (one launch): gathers the sampled candidates'
  * gradient ranges into ONE contiguous buffer = one RCCL all-reduce message (no torch.cat, no copy back: the SGD step reads
- * the reduced message through `goff`). */
+ * the reduced message through `goff`).  The ranges must be disjoint, in src and in dst: overlapping (off[i], len[i]) or
+ * (doff[i], len[i]) return TFNAS_EINVAL before anything is launched. */
 int tfnas_pack_ranges(const float *src, float *dst, int nranges, const uint64_t *off, const uint64_t *doff,
                       const uint64_t *len, void *stream);
 

@@ -299,7 +299,7 @@ int launch_sink_bwd(int K, const float* bw, const float* const* res, const float
         pk.res[k] = res[k];
         pk.dres[k] = dres[k];
     }
-    hipError_t e = hipMemsetAsync(dots, 0, sizeof(double) * TFNAS_MAX_SINK, s);
+    hipError_t e = hipMemsetAsync(dots, 0, sizeof(double) * K, s);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_sink_bwd, dim3(stream_blocks(count / 4)), dim3(256), 0, s, K, bw, pk, dout, count / 4, dots);
     hipLaunchKernelGGL(k_sink_bwd_fin, dim3(1), dim3(64), 0, s, K, bw, cell_lat, dlat, dots, dbetas, dcell_lat);

@@ -110,6 +110,13 @@ static int fill_ranges(OptRanges& R, int nranges, const uint64_t* off, const uin
     }
     R.first_block[nranges] = nb;
     R.nblocks = nb;
+    // ranges must be disjoint, in the arenas and in the gradient buffer: two workgroups would otherwise update the same floats
+    // (and the norm would count them twice).  <= 64 ranges: a plain O(n^2) loop
+    for (int i = 0; i < nranges; ++i)
+        for (int j = i + 1; j < nranges; ++j) {
+            if (R.off[i] < R.off[j] + R.len[j] && R.off[j] < R.off[i] + R.len[i]) return TFNAS_EINVAL;
+            if (goff && R.goff[i] < R.goff[j] + R.len[j] && R.goff[j] < R.goff[i] + R.len[i]) return TFNAS_EINVAL;
+        }
     return 0;
 }
 
