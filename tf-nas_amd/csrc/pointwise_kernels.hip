@@ -131,61 +131,103 @@ __global__ __launch_bounds__(256) void k_mix_fwd(TfnasCellDesc d, const float* _
 
 // ============================================================================ mixing epilogue (backward sums)
 // red3[g][o] = ( S1 = sum_p dout[p][o] ,  S2 = sum_p dout[p][o] * phat_g[p][o] )
+// threads = (column quad oq) x (row lane pr): the active threads of a row step read RP consecutive rows as one contiguous
+// stream.  UN row steps are in flight per thread -- UN * (1 + has_res + G) independent 16-byte loads, all issued before the
+// first use; rows past the workgroup's share are clamped in the address and masked in the arithmetic.  GMAX >= G bounds the
+// unrolled group loops.  Epilogue: every accumulator goes to LDS once, then ONE thread per output column sums its row lanes
+// in registers -- in the order of the block-wide tree the kernel used to run once per accumulator (level s = 32, 16, .. 1:
+// lane r += lane r + s), so the partial rows keep their bits -- three barriers per workgroup, whatever G and RP are.
+constexpr int MIX_RP_MAX = 64;           // row lanes per column (the epilogue holds one column's lanes in registers)
+// acc = [2 + G][1024] floats (accumulator q, row lane r, column c at q * 1024 + r * oc + c), RP <= RPC row lanes: one thread per
+// (accumulator, column) sums the lanes as the tree does -- level s = RPC/2 .. 1: lane r += lane r + s where that lane exists --
+// and writes the workgroup's partial row: [G*oc][2] (S1,S2) followed by [oc] partial <dout,x> sums
+template <int RPC>
+__device__ __forceinline__ void mix_sum_lanes(const float* acc, float* prow, int G, int oc, int RP, int tid) {
+    for (int i = tid; i < (2 + G) * oc; i += 256) {
+        const int q = i / oc, c = i - q * oc;              // accumulator (S1, <dout,x>, S2 of group q - 2) and column
+        const float* b = acc + q * 1024 + c;
+        float v[RPC];
+#pragma unroll
+        for (int r = 0; r < RPC; ++r) v[r] = b[min(r, RP - 1) * oc];
+#pragma unroll
+        for (int s = RPC / 2; s > 0; s >>= 1) {
+#pragma unroll
+            for (int r = 0; r < s; ++r) v[r] = (s < RP && r + s < RP) ? v[r] + v[r + s] : v[r];
+        }
+        if (q == 0) {
+            for (int g = 0; g < G; ++g) prow[2 * (g * oc + c)] = v[0];
+        } else if (q == 1) {
+            prow[2 * G * oc + c] = v[0];
+        } else {
+            prow[2 * ((q - 2) * oc + c) + 1] = v[0];
+        }
+    }
+}
+template <int GMAX, int UN>
 __global__ __launch_bounds__(256) void k_mix_bwd_stats(TfnasCellDesc d, const float* __restrict__ dout,
                                                        const float* __restrict__ Pr,
                                                        const double* __restrict__ stats3,
                                                        const float* __restrict__ x, float* __restrict__ part,
                                                        int rows_per_block) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int oc = d.oc, TQ = oc >> 2, RP = 256 / TQ;
+    const int oc = d.oc, TQ = oc >> 2, RP = min(256 / TQ, MIX_RP_MAX);
     const int Po = d.N * d.Ho * d.Wo;
-    const int G = d.G, Gall = d.G;
+    const int G = d.G;
     float2* tab = reinterpret_cast<float2*>(lds);                    // [G*oc] (mean3, rstd3)
-    f32x4* buf = reinterpret_cast<f32x4*>(lds + 2 * Gall * oc);      // [256]
+    f32x4* buf = reinterpret_cast<f32x4*>(lds);                      // [2 + G][256] accumulators, over tab once the rows are read
     for (int i = threadIdx.x; i < G * oc; i += 256) tab[i] = bn_consts(stats3 + 2 * (size_t)i, 1.0 / (double)Po, d.eps);
     __syncthreads();
     const int tid = threadIdx.x, oq = tid % TQ, pr = tid / TQ, o = 4 * oq;
     const bool active = pr < RP;
     const int p0 = blockIdx.x * rows_per_block, p1 = min(Po, p0 + rows_per_block);
-    f32x4 s1 = zero4(), sx = zero4(), s2[TFNAS_MAX_GROUPS];
+    f32x4 s1 = zero4(), sx = zero4(), s2[GMAX];
 #pragma unroll
-    for (int g = 0; g < TFNAS_MAX_GROUPS; ++g) s2[g] = zero4();
+    for (int g = 0; g < GMAX; ++g) s2[g] = zero4();
     if (active) {
-        for (int p = p0 + pr; p < p1; p += RP) {
-            const f32x4 dv = ld4(dout + (size_t)p * oc + o);
-            s1 += dv;
-            if (d.has_res) sx += dv * ld4(x + (size_t)p * d.ic + o);   // residual cells: ic == oc
+        for (int p = p0 + pr; p < p1; p += UN * RP) {
+            f32x4 dv[UN], xv[UN], pv[GMAX][UN];
 #pragma unroll
-            for (int g = 0; g < TFNAS_MAX_GROUPS; ++g) {
-                if (g < G) {
-                    const f32x4 pv = ld4(Pr + ((size_t)g * Po + p) * oc + o);
+            for (int u = 0; u < UN; ++u) {
+                const int q = min(p + u * RP, p1 - 1);
+                dv[u] = ld4(dout + (size_t)q * oc + o);
+                xv[u] = d.has_res ? ld4(x + (size_t)q * d.ic + o) : zero4();   // residual cells: ic == oc
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float2 t = tab[g * oc + o + j];
-                        s2[g][j] += dv[j] * ((pv[j] - t.x) * t.y);
+                for (int g = 0; g < GMAX; ++g) pv[g][u] = g < G ? ld4(Pr + ((size_t)g * Po + q) * oc + o) : zero4();
+            }
+#pragma unroll
+            for (int u = 0; u < UN; ++u) {
+                if (p + u * RP < p1) {
+                    s1 += dv[u];
+                    if (d.has_res) sx += dv[u] * xv[u];
+#pragma unroll
+                    for (int g = 0; g < GMAX; ++g) {
+                        if (g < G) {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                const float2 t = tab[g * oc + o + j];
+                                s2[g][j] += dv[u][j] * ((pv[g][u][j] - t.x) * t.y);
+                            }
+                        }
                     }
                 }
             }
         }
     }
-    // this workgroup's row of the partials matrix: [G*oc][2] (S1,S2) followed by [oc] partial <dout,x> sums
-    float* prow = part + (size_t)blockIdx.x * (2 * Gall * oc + oc);
-    s1 = reduce_rows(s1, buf, pr, oq, RP, TQ, active);
-    sx = reduce_rows(sx, buf, pr, oq, RP, TQ, active);
-    if (active && pr == 0) st4(prow + 2 * Gall * oc + o, sx);
+    __syncthreads();                                                 // tab is dead: buf takes its place
+    if (active) {                                                    // (tid < RP * TQ: float index q * 1024 + pr * oc + column)
+        buf[tid] = s1;
+        buf[256 + tid] = sx;
 #pragma unroll
-    for (int g = 0; g < TFNAS_MAX_GROUPS; ++g) {
-        if (g < G) {
-            const f32x4 r = reduce_rows(s2[g], buf, pr, oq, RP, TQ, active);
-            if (active && pr == 0) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    prow[2 * ((size_t)g * oc + o + j) + 0] = s1[j];
-                    prow[2 * ((size_t)g * oc + o + j) + 1] = r[j];
-                }
-            }
-        }
+        for (int g = 0; g < GMAX; ++g)
+            if (g < G) buf[(2 + g) * 256 + tid] = s2[g];
     }
+    __syncthreads();
+    float* prow = part + (size_t)blockIdx.x * (2 * G * oc + oc);
+    if (RP <= 4) mix_sum_lanes<4>(lds, prow, G, oc, RP, tid);
+    else if (RP <= 8) mix_sum_lanes<8>(lds, prow, G, oc, RP, tid);
+    else if (RP <= 16) mix_sum_lanes<16>(lds, prow, G, oc, RP, tid);
+    else if (RP <= 32) mix_sum_lanes<32>(lds, prow, G, oc, RP, tid);
+    else mix_sum_lanes<MIX_RP_MAX>(lds, prow, G, oc, RP, tid);
 }
 
 // dwmix[g] = d loss / d wmix[g] = <dout, phat_g [+ x]> = sum_o S2[g][o] [+ <dout,x>]
@@ -281,6 +323,8 @@ __global__ __launch_bounds__(256) void k_bn2_pool(TfnasCellDesc d, const float* 
 // Per-image tables from the records the FOLD epilogue of k_project_dgrad wrote (gemm_kernels.hip): image n covers the row tiles
 // n*HW/128 .. ((n+1)*HW-1)/128, its slot in tile t is n - (first image of t); summed in tile order, in double.  Writes exactly what
 // k_bn2_pool writes: pp = A1 | B1 | A2 | B2 [N][M] and dgate [N][M] (the last three for SE groups only).
+// k_bn2_gather: images of many row tiles (HW > 384: the stem's 99, 25 on 56 x 56, 7 on 28 x 28) -- the tiles of an image are
+// spread over the four waves of a workgroup, 8 per wave in flight.  k_bn2_gather_few below takes the smaller images.
 __global__ __launch_bounds__(256) void k_bn2_gather(TfnasCellDesc d, const float* __restrict__ rec, float* __restrict__ dgate,
                                                     float* __restrict__ pp) {
     __shared__ double sh[4][FOLD_Q][64];
@@ -331,6 +375,57 @@ __global__ __launch_bounds__(256) void k_bn2_gather(TfnasCellDesc d, const float
             dgate[o] = (float)v[2];
             pp[2 * NM + o] = (float)v[3];
             pp[3 * NM + o] = (float)v[4];
+        }
+    }
+}
+
+// Images of at most 4 row tiles (HW <= 384: every 14 x 14 and 7 x 7 cell): one thread per (image, channel quad) loads the
+// image's real records of every quantity with 16-byte loads -- no masked duplicates, no LDS, no barrier -- and sums them as
+// k_bn2_gather does with at most one tile per part: ((p0 + p1) + p2) + p3 in double, p_k = 0.0 + record of tile t0 + k
+// (bit-identical tables).
+__global__ __launch_bounds__(256) void k_bn2_gather_few(TfnasCellDesc d, const float* __restrict__ rec,
+                                                        float* __restrict__ dgate, float* __restrict__ pp) {
+    const int M = d.M, MQ = M >> 2, HW = d.Ho * d.Wo;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= d.N * MQ) return;
+    const int n = i / MQ, ch = 4 * (i - n * MQ);
+    bool in_group = false, has_se = false;            // (pad columns between the groups belong to nobody)
+#pragma unroll
+    for (int g = 0; g < TFNAS_MAX_GROUPS; ++g) {
+        if (g < d.G) {
+            const bool h = ch >= d.g[g].off && ch < d.g[g].off + d.g[g].mcp;
+            in_group |= h;
+            has_se |= h && d.g[g].se > 0;
+        }
+    }
+    if (!in_group) return;
+    const int t0 = (n * HW) >> 7, nt = (((n + 1) * HW - 1) >> 7) - t0 + 1;      // 1..4 tiles
+    const int nq = has_se ? FOLD_Q : 2;
+    f32x4 v[FOLD_Q][4];
+#pragma unroll
+    for (int q = 0; q < FOLD_Q; ++q) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[q][k] = zero4();
+            if (q < nq && k < nt) {
+                const int tt = t0 + k, slot = n - (tt * 128) / HW;
+                v[q][k] = ld4(rec + (((size_t)tt * FOLD_SLOTS + slot) * FOLD_Q + q) * M + ch);
+            }
+        }
+    }
+    const size_t NM = (size_t)d.N * M, o = (size_t)n * M + ch;
+    float* const dst[FOLD_Q] = {pp + o, pp + NM + o, dgate + o, pp + 2 * NM + o, pp + 3 * NM + o};
+#pragma unroll
+    for (int q = 0; q < FOLD_Q; ++q) {
+        if (q < nq) {
+            f32x4 r;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double q0 = 0.0 + (double)v[q][0][j], q1 = 0.0 + (double)v[q][1][j];
+                const double q2 = 0.0 + (double)v[q][2][j], q3 = 0.0 + (double)v[q][3][j];
+                r[j] = (float)(((q0 + q1) + q2) + q3);
+            }
+            st4(dst[q], r);
         }
     }
 }
@@ -782,16 +877,30 @@ int launch_mix_fwd(const TfnasCellDesc& d, const float* Pr, const double* stats3
 int launch_mix_bwd_stats(const TfnasCellDesc& d, const float* dout, const float* Pr, const double* stats3,
                          const float* x, double* red3, float* part, hipStream_t s) {
     ProfScope _prof(TK_MIX_BWD_STATS, s);
-    const int Po = d.N * d.Ho * d.Wo;
-    const int ncols = 2 * d.G * d.oc + d.oc;       // (S1,S2) pairs + per-channel <dout,x>; reduced into red3|resdot
+    const int Po = d.N * d.Ho * d.Wo, G = d.G;
+    const int ncols = 2 * G * d.oc + d.oc;         // (S1,S2) pairs + per-channel <dout,x>; reduced into red3|resdot
     size_t nblk = 1024;
     if (nblk > TFNAS_PART_FLOATS / (size_t)ncols) nblk = TFNAS_PART_FLOATS / (size_t)ncols;
+    // row steps in flight per thread: at least 8 sixteen-byte loads of (1 + has_res + G) per row
+    const int UN = G == 1 ? 4 : (G == 2 ? 3 : (G <= 6 ? 2 : 1));
+    int RP = 256 / (d.oc / 4);
+    if (RP > MIX_RP_MAX) RP = MIX_RP_MAX;
+    // a workgroup's share of the rows decides which rows a partial sum holds, hence the last bits of red3: unchanged (twice the
+    // workgroups on the 14 x 14 / 7 x 7 cells measured 8 % faster on this kernel in the alpha-step)
     int rpb = cdiv(Po, (int)nblk);
-    const int RP = 256 / (d.oc / 4);
     if (rpb < 8 * RP) rpb = 8 * RP;
-    const size_t shm = (size_t)(2 * d.G * d.oc + 4 * 256) * sizeof(float);
+    size_t shf = (size_t)2 * G * d.oc;             // the table, then the accumulators in its place
+    if (shf < (size_t)(2 + G) * 1024) shf = (size_t)(2 + G) * 1024;
+    const size_t shm = shf * sizeof(float);
     const int gx = cdiv(Po, rpb);
-    hipLaunchKernelGGL(k_mix_bwd_stats, dim3(gx), dim3(256), shm, s, d, dout, Pr, stats3, x, part, rpb);
+#define MIX_BWD_STATS(GMAX, UNR) \
+    hipLaunchKernelGGL((k_mix_bwd_stats<GMAX, UNR>), dim3(gx), dim3(256), shm, s, d, dout, Pr, stats3, x, part, rpb)
+    if (G == 1) MIX_BWD_STATS(1, 4);
+    else if (G == 2) MIX_BWD_STATS(2, 3);
+    else if (G <= 4) MIX_BWD_STATS(4, 2);
+    else if (G <= 6) MIX_BWD_STATS(8, 2);
+    else MIX_BWD_STATS(8, 1);
+#undef MIX_BWD_STATS
     _prof.stop();
     return launch_reduce_rows(part, gx, ncols, (size_t)ncols, red3, nullptr, s);
 }
@@ -837,7 +946,10 @@ int launch_bn2_pool(const TfnasCellDesc& d, const float* dZ, const float* D, con
 
 int launch_bn2_gather(const TfnasCellDesc& d, const float* rec, float* dgate, float* pp, hipStream_t s) {
     ProfScope _prof(TK_SE_BWD_REDUCE, s);
-    hipLaunchKernelGGL(k_bn2_gather, dim3(d.N, chunk_count(d, 64, false)), dim3(256), 0, s, d, rec, dgate, pp);
+    if (d.Ho * d.Wo <= 384)                        // at most 4 row tiles per image
+        hipLaunchKernelGGL(k_bn2_gather_few, dim3(cdiv(d.N * (d.M / 4), 256)), dim3(256), 0, s, d, rec, dgate, pp);
+    else
+        hipLaunchKernelGGL(k_bn2_gather, dim3(d.N, chunk_count(d, 64, false)), dim3(256), 0, s, d, rec, dgate, pp);
     return (int)hipGetLastError();
 }
 

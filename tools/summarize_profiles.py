@@ -28,7 +28,7 @@ def family(name):
            'k_dwd_fwd': 'k_dw_fwd', 'k_dwd_bwd': 'k_dw_bwd_data', 'k_dwd_wgrad': 'k_dw_wgrad',
            'k_fx_fwd': 'k_dw_fwd', 'k_fx_bwde': 'k_dw_bwd_data', 'k_fx_bwd': 'k_dw_bwd_data',
            'k_bn2_finish': 'k_bn2_bwd'}.get(fam, fam)
-    if fam in ('k_bn2_pool', 'k_bn2_gather'):
+    if fam in ('k_bn2_pool', 'k_bn2_gather', 'k_bn2_gather_few'):
         return 'k_se_pool<bwd>'
     if fam == 'k_se_pool':
         fam += '<bwd>' if m.group(2) and m.group(2).replace(' ', '').endswith(',1>') else '<fwd>'
