@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-/* 4, additive: TFNAS_CELL_FUSED -- a Fused-MBConv block (dense 3 x 3 convolution, no depthwise) through tfnas_mixedop_* / tfnas_mbconv_*.
+/* 4, additive: TFNAS_CELL_KINDS -- a per-group kind (TfnasGroup.kind): plain, expand-free and Fused-MBConv candidates in ONE cell.
+ * 4, additive: TFNAS_CELL_FUSED -- a Fused-MBConv block (dense 3 x 3 convolution, no depthwise) through tfnas_mixedop_* / tfnas_mbconv_*.
  * 4, additive: TFNAS_CELL_NOEXPAND -- a block without expand convolution (mid <= in channels) through tfnas_mixedop_* / tfnas_mbconv_*.
  * 4, additive: TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH in a descriptor whose flags carry TFNAS_CELL_ACTS (cells, affine blocks, head;
  * materialised route and LDS tile depthwise kernels only).
@@ -105,7 +106,8 @@ typedef struct TfnasGroup {
     int32_t mcp;      /* mc rounded up to a multiple of 4                   [plan] */
     int32_t off;      /* first column of this group in the [.][M] tensors (multiple of 32) [plan] */
     int32_t se_off;   /* first column in the [N][SE] hidden tensors         [plan] */
-    int32_t pad0, pad1;
+    int32_t kind;     /* TFNAS_GROUP_*: read only from a descriptor whose flags carry TFNAS_CELL_KINDS [in]  */
+    int32_t pad1;
     const float *w_expand, *w_dw, *w_proj, *w_se_r, *b_se_r, *w_se_e, *b_se_e;
     float *g_expand, *g_dw, *g_proj, *g_se_r, *gb_se_r, *g_se_e, *gb_se_e;
 } TfnasGroup;
@@ -136,7 +138,8 @@ typedef struct TfnasCellDesc {
                                  TFNAS_CELL_K7: groups may have depthwise kernel size 7;
                                  TFNAS_CELL_ACTS: act may be TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH;
                                  TFNAS_CELL_NOEXPAND: the one group has no expand convolution;
-                                 TFNAS_CELL_FUSED: the one group is a Fused-MBConv block (dense 3 x 3 convolution)       [in]
+                                 TFNAS_CELL_FUSED: the one group is a Fused-MBConv block (dense 3 x 3 convolution);
+                                 TFNAS_CELL_KINDS: every group has a kind of its own (TfnasGroup.kind)                   [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -249,6 +252,37 @@ typedef struct TfnasCellDesc {
  * Checked by tfnas_cell_plan and again by every entry point.  The Python mirror sets it for a one-block plan whose block is a
  * layers.FusedMBConvBlock (functions.HipModes.apply). */
 #define TFNAS_CELL_FUSED 0x400
+/* TfnasCellDesc.flags: the caller knows cells whose candidates differ in kind.  Additive like the two bits above: without the bit
+ * TfnasGroup.kind is not read and every descriptor means what it meant before (TFNAS_CELL_NOEXPAND / TFNAS_CELL_FUSED with G > 1
+ * stay TFNAS_EINVAL).  With it every group g says what it is in g.kind:
+ *   TFNAS_GROUP_MBCONV    expand 1 x 1 + BN + act + depthwise k x k (the ordinary candidate)
+ *   TFNAS_GROUP_NOEXPAND  depthwise k x k of the raw cell input: mc == ic, w_expand == NULL and g_expand == NULL
+ *   TFNAS_GROUP_FUSED     dense 3 x 3 convolution of the raw cell input: k == 3, the OIHW weight [mc][ic][3][3] in w_expand /
+ *                         g_expand, w_dw == NULL and g_dw == NULL
+ * and the cell computes  out = sum_g wmix[g] BN3_g(project_g(SE_g(act(BN2_g(front_g(x)))))) [+ x]  in the caller's group order
+ * (dwmix[g] belongs to group g).  Rules, checked by tfnas_cell_plan and again by every entry point:
+ *   - mode == TFNAS_MODE_CELL only; TFNAS_CELL_NOEXPAND and TFNAS_CELL_FUSED must both be clear; a kind outside 0..2, a NOEXPAND
+ *     group with mc != ic or an expand pointer, a FUSED group with k != 3 or a depthwise pointer are TFNAS_EINVAL;
+ *   - TFNAS_CELL_K7 / TFNAS_CELL_ACTS apply as before; the size limits of the one-block kinds hold per group (the dense weight's
+ *     partial row and repacked copy of every FUSED group; the depthwise weight-gradient row of the MBCONV groups and of the
+ *     NOEXPAND groups): TFNAS_ERANGE;
+ *   - tfnas_mbconv_fwd/bwd and tfnas_path_plan refuse the bit (TFNAS_EINVAL); tfnas_efree_supported and tfnas_fx_supported return
+ *     0 when any group is not plain: the plain groups of such a cell always materialise E (E == NULL is TFNAS_ENULL);
+ *   - tfnas_cell_ws reports E = 0 when no group is plain (E, stats1, red1, cb1 are then never touched);
+ *   - a descriptor whose groups are ALL TFNAS_GROUP_MBCONV, and a ONE-group descriptor of any kind, plan, size, route and run
+ *     exactly like the same descriptor without the bit (the one group under its own TFNAS_CELL_NOEXPAND / _FUSED bit).
+ * Launch sequence of a cell with groups of more than one kind: the fronts run per kind on their own groups' columns
+ * of the [pixels][M] tensors -- the MBCONV groups' expand + depthwise, the NOEXPAND groups' raw-input depthwise, one dense
+ * convolution per FUSED group -- then everything from the SE squeeze to the mix runs once over all groups.  The backward runs
+ * the shared prefix once, then the MBCONV groups' tail, the NOEXPAND groups', the FUSED groups'.  dx is written by the first
+ * branch in that order (with the residual gradient, once) and read-added-stored by every later one on the caller's stream: a
+ * fixed summation order, no atomics, bit-reproducible.  Weight gradients go to the forks as for the one-block kinds (fork 1
+ * carries the SE, depthwise and dense-convolution weight gradients in stream order).  TFNAS_CELL_ACCUM_WGRAD, dx == NULL,
+ * need_wgrad == 0, the dwmix-only early return, wgrad_stream[] and the sync-stats hook keep their meaning. */
+#define TFNAS_CELL_KINDS 0x800
+#define TFNAS_GROUP_MBCONV 0
+#define TFNAS_GROUP_NOEXPAND 1
+#define TFNAS_GROUP_FUSED 2
 /* TfnasCellDesc.route (ABI 4; rounds 2-5 read these from TFNAS_* environment variables latched once per process) */
 #define TFNAS_ROUTE_FX_OFF 0x1        /* frozen-weight launches of the 14 x 14 / 7 x 7 cells through the materialised route instead
                                          of the fused per-image kernels (csrc/fx_kernels.hip)                                   */

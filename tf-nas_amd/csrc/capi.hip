@@ -159,7 +159,18 @@ static int check_act(const TfnasCellDesc* d) {
 
 // the kind bits of a descriptor.  Both newer kinds are ONE block in cell mode; TFNAS_CELL_NOEXPAND: mc == ic channels, no expand
 // weight or gradient pointer; TFNAS_CELL_FUSED: a dense 3 x 3 weight (w_expand), no depthwise pointer; never both bits
+// TFNAS_CELL_KINDS: the same rules per group (TfnasGroup.kind), any G; the two one-block bits must then be clear
 static int check_kind(const TfnasCellDesc* d) {
+    if (cell_mixed(*d)) {
+        if (d->mode != TFNAS_MODE_CELL || cell_noexpand(*d) || cell_fused(*d)) return TFNAS_EINVAL;
+        for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g) {
+            const TfnasGroup& gr = d->g[g];
+            if (gr.kind < TFNAS_GROUP_MBCONV || gr.kind > TFNAS_GROUP_FUSED) return TFNAS_EINVAL;
+            if (gr.kind == TFNAS_GROUP_NOEXPAND && (gr.mc != d->ic || gr.w_expand || gr.g_expand)) return TFNAS_EINVAL;
+            if (gr.kind == TFNAS_GROUP_FUSED && (gr.k != 3 || gr.w_dw || gr.g_dw)) return TFNAS_EINVAL;
+        }
+        return 0;
+    }
     const CellKind kind = cell_kind(*d);
     if (kind == TFNAS_KIND_MBCONV) return 0;
     if (cell_noexpand(*d) && cell_fused(*d)) return TFNAS_EINVAL;
@@ -178,7 +189,7 @@ static int check_modes(const TfnasCellDesc* d) {
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
     if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS | TFNAS_CELL_NOEXPAND |
-                     TFNAS_CELL_FUSED))
+                     TFNAS_CELL_FUSED | TFNAS_CELL_KINDS))
         return TFNAS_EINVAL;
     TRY(check_kind(d));
     if (!(d->flags & TFNAS_CELL_K7)) {            // kernel size 7 is opt-in: without the bit it is refused as it always was
@@ -193,7 +204,50 @@ static int check_modes(const TfnasCellDesc* d) {
     return 0;
 }
 
-static bool wgrad_row_fits(const TfnasCellDesc& d) { return cell_fused(d) ? conv_wgrad_row_fits(d) : dw_wgrad_row_fits(d); }
+// The canonical form of a (checked) descriptor, which everything past the checks works on: without TFNAS_CELL_KINDS the
+// descriptor itself.  With it: all groups plain -- the bit dropped; one group -- its one-block bit instead (both then plan,
+// size, route and run exactly like the descriptor a caller without the bit would have written); anything else keeps the bit: a
+// mixed cell (kernels.h: cell_mixed).
+static TfnasCellDesc kinds_canon(const TfnasCellDesc& d) {
+    TfnasCellDesc c = d;
+    if (!cell_mixed(d)) return c;
+    bool plain = true;
+    for (int g = 0; g < d.G && g < TFNAS_MAX_GROUPS; ++g) plain = plain && d.g[g].kind == TFNAS_GROUP_MBCONV;
+    if (plain || d.G == 1) {
+        c.flags &= ~TFNAS_CELL_KINDS;
+        if (!plain) c.flags |= d.g[0].kind == TFNAS_GROUP_FUSED ? TFNAS_CELL_FUSED : TFNAS_CELL_NOEXPAND;
+    }
+    return c;
+}
+// the groups of one kind of a mixed cell as a sub-descriptor (kernels.h: cell_mixed): same geometry, M and offsets, the kind's
+// one-block bit; returns how many there are.  group_alone: group g of a (sub-)descriptor as a one-group descriptor.
+static int kind_subset(const TfnasCellDesc& d, CellKind kind, TfnasCellDesc& sub) {
+    sub = d;
+    int n = 0;
+    for (int g = 0; g < d.G; ++g)
+        if ((CellKind)d.g[g].kind == kind) sub.g[n++] = d.g[g];
+    sub.G = n;
+    sub.flags |= kind == TFNAS_KIND_FUSED ? TFNAS_CELL_FUSED : kind == TFNAS_KIND_NOEXPAND ? TFNAS_CELL_NOEXPAND : 0;
+    return n;
+}
+static TfnasCellDesc group_alone(const TfnasCellDesc& sub, int g) {
+    TfnasCellDesc one = sub;
+    one.g[0] = sub.g[g];
+    one.G = 1;
+    return one;
+}
+
+// (a canonical descriptor; a mixed cell: the limits of the one-block kinds hold per kind / per FUSED group)
+static bool wgrad_row_fits(const TfnasCellDesc& d) {
+    if (!cell_mixed(d)) return cell_fused(d) ? conv_wgrad_row_fits(d) : dw_wgrad_row_fits(d);
+    TfnasCellDesc sub;
+    if (kind_subset(d, TFNAS_KIND_MBCONV, sub) && !dw_wgrad_row_fits(sub)) return false;
+    if (kind_subset(d, TFNAS_KIND_NOEXPAND, sub) && !dw_wgrad_row_fits(sub)) return false;
+    const int nf = kind_subset(d, TFNAS_KIND_FUSED, sub);
+    for (int g = 0; g < nf; ++g)
+        if (!conv_wgrad_row_fits(group_alone(sub, g))) return false;
+    return true;
+}
 
 extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
     if (!d) return TFNAS_ENULL;
@@ -242,18 +296,25 @@ extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
     d->SE = se_off;
     if ((double)d->N * d->H * d->W >= 2147483647.0) return TFNAS_ERANGE;   // row indices are int, offsets size_t
     // one row of weight-gradient partials: depthwise (sum of mc * k * k); Fused-MBConv: the dense weight instead (9 ic mc)
-    if (!wgrad_row_fits(*d)) return TFNAS_ERANGE;
+    if (!wgrad_row_fits(kinds_canon(*d))) return TFNAS_ERANGE;
     return 0;
 }
 
+static int cell_ws_canon(const TfnasCellDesc* d, TfnasCellWs* ws);
 extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     if (!d || !ws) return TFNAS_ENULL;
     memset(ws, 0, sizeof(*ws));
+    if (cell_mixed(*d) && check_kind(d) != 0) return TFNAS_EINVAL;      // (TfnasGroup.kind is about to be read)
+    const TfnasCellDesc c = kinds_canon(*d);
+    return cell_ws_canon(&c, ws);
+}
+static int cell_ws_canon(const TfnasCellDesc* d, TfnasCellWs* ws) {
     if (!wgrad_row_fits(*d)) return TFNAS_ERANGE;
     const uint64_t P = (uint64_t)d->N * d->H * d->W, Po = (uint64_t)d->N * d->Ho * d->Wo;
     const uint64_t M = d->M, N = d->N, SE = d->SE, G = d->G, oc = d->oc;
     // the four stream tensors: P*M / Po*M fp32 elements
-    ws->E = cell_has_E(*d) ? P * M : 0;                  // (no expand convolution: D = dw(x) / D = conv3x3(x), nothing to save)
+    ws->E = any_group_has_E(*d) ? P * M : 0;             // (no expand convolution: D = dw(x) / D = conv3x3(x), nothing to save;
+                                                         //  a mixed cell: the whole [pixels][M] tensor if any group is plain)
     ws->D = Po * M;
     ws->Pr = G * Po * oc;
     ws->off_pooled = 0;
@@ -283,21 +344,25 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     ws->part = (d->need_wgrad ? 2 : 1) * (uint64_t)TFNAS_PART_ALLOC;   // second half: weight-gradient side stream
     ws->dx = P * d->ic;
     {
-        const int ns = (d->mode == TFNAS_MODE_STEM || !cell_has_E(*d)) ? 1 : gemm_plan_expand_dgrad(*d, true).splits;
+        // (a mixed cell: the expand dgrad runs over its plain groups, kind_subset)
+        TfnasCellDesc sub = *d;
+        const bool has_E = cell_mixed(*d) ? kind_subset(*d, TFNAS_KIND_MBCONV, sub) > 0 : cell_has_E(*d);
+        const int ns = (d->mode == TFNAS_MODE_STEM || !has_E) ? 1 : gemm_plan_expand_dgrad(sub, true).splits;
         ws->dxp = ns > 1 ? (uint64_t)ns * P * d->ic : 4;   /* split-K partials of the expand dgrad */
     }
     return 0;
 }
 
-extern "C" int tfnas_efree_supported(const TfnasCellDesc* dp) { return (dp && efree_supported(*dp)) ? 1 : 0; }
+// (the three queries below: of the canonical descriptor, so an all-plain TFNAS_CELL_KINDS cell answers like the unflagged one)
+extern "C" int tfnas_efree_supported(const TfnasCellDesc* dp) { return (dp && efree_supported(kinds_canon(*dp))) ? 1 : 0; }
 // (fx_plan refuses every mode but TFNAS_MODE_CELL, need_wgrad and ic < 64 -- the E-free widths 16 / 24 / 40 -- by itself)
-extern "C" int tfnas_fx_supported(const TfnasCellDesc* dp) { return (dp && fx_supported(*dp)) ? 1 : 0; }
+extern "C" int tfnas_fx_supported(const TfnasCellDesc* dp) { return (dp && fx_supported(kinds_canon(*dp))) ? 1 : 0; }
 // what a forward of this descriptor leaves in the saved buffers (tfnas_hip.h): the one decision of cell_fwd_impl that changes
 // their MEANING is the fused per-image route (ehat instead of E); affine / eval BatchNorm launches (tfnas_mbconv_*) never take it
 static int route_taken(const TfnasCellDesc& d, bool affine) {
     return TFNAS_ROUTE_TAKEN_VALID | ((!affine && fx_supported(d)) ? TFNAS_ROUTE_TAKEN_FX : 0);
 }
-extern "C" int tfnas_cell_route(const TfnasCellDesc* dp) { return dp ? route_taken(*dp, false) : 0; }
+extern "C" int tfnas_cell_route(const TfnasCellDesc* dp) { return dp ? route_taken(kinds_canon(*dp), false) : 0; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // One cell, forward / backward: the launch sequences shared by the per-cell entry points below and by the path level
@@ -338,6 +403,21 @@ static int fwd_front_mbconv(const TfnasCellDesc& d, const TfnasCellDesc& d0, con
     return 0;
 }
 
+// the fronts of a mixed cell, kind by kind on that kind's groups (sub-descriptors: kind_subset): the plain groups' materialised
+// route, the expand-free groups' raw-input depthwise in one launch, one dense convolution per Fused-MBConv group.  Each writes
+// its groups' columns of D and of stats2 and nothing else of either (reduce_pair_rows).
+static int fwd_front_mixed(const TfnasCellDesc& d, const CellFwdBufs& b, bool sync, double* stats1, double* stats2, hipStream_t s) {
+    TfnasCellDesc sub;
+    if (kind_subset(d, TFNAS_KIND_MBCONV, sub)) {
+        if (!b.E) return TFNAS_ENULL;
+        TRY(fwd_front_mbconv(sub, sub, b, false, sync, stats1, stats2, s));
+    }
+    if (kind_subset(d, TFNAS_KIND_NOEXPAND, sub)) TRY(launch_dw_fwd(sub, nullptr, b.x, nullptr, b.D, stats2, b.part, s));
+    const int nf = kind_subset(d, TFNAS_KIND_FUSED, sub);
+    for (int g = 0; g < nf; ++g) TRY(launch_conv_fwd(group_alone(sub, g), b.x, b.D, stats2, b.part, s));
+    return 0;
+}
+
 int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdBufs& b, hipStream_t s, int* route) {
     double* stats1 = b.stats + ws.off_stats1;
     double* stats2 = b.stats + ws.off_stats2;
@@ -358,6 +438,10 @@ int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdB
     if (route) *route = taken;
     const bool fx = (taken & TFNAS_ROUTE_TAKEN_FX) != 0;
     const bool sync = !(bn && bn->eval);          // (eval mode normalises with the running statistics: nothing to reduce)
+    if (cell_mixed(d)) {                          // (no affine form: tfnas_mbconv_* refuse the bit)
+        if (bn) return TFNAS_EINVAL;
+        TRY(fwd_front_mixed(d, b, sync, stats1, stats2, s));
+    } else
     switch (cell_kind(d)) {                       // ... D and stats2 are written:
     case TFNAS_KIND_FUSED:
         // Fused-MBConv: one dense 3 x 3 convolution of the raw cell input writes D and the BN_a statistics (no E, no stats1)
@@ -442,6 +526,8 @@ struct CellBwd {
     float *part, *part_w, *part_w1, *part_w2;
 
     int run();
+    int chain_mbconv(const TfnasCellDesc& d, bool se_wgrad);
+    int tail_mixed();
     int tail_fused();
     int tail_noexpand();
     int tail_mbconv();
@@ -450,9 +536,9 @@ struct CellBwd {
 // everything up to and including the BN2 backward sums, then the tail of the cell's kind
 int CellBwd::run() {
     if (d.need_wgrad) {
-        const CellKind kind = cell_kind(d);
         for (int g = 0; g < d.G; ++g) {
             const TfnasGroup& gr = d.g[g];
+            const CellKind kind = group_kind(d, g);
             if ((!gr.g_expand && kind != TFNAS_KIND_NOEXPAND) || (!gr.g_dw && kind != TFNAS_KIND_FUSED) || !gr.g_proj) return TFNAS_ENULL;
             if (gr.se > 0 && (!gr.g_se_r || !gr.gb_se_r || !gr.g_se_e || !gr.gb_se_e)) return TFNAS_ENULL;
         }
@@ -488,6 +574,7 @@ int CellBwd::run() {
     else TRY(launch_bn2_bwd(d, b.dZ, b.D, stats2, gate, dpooled, red2, part, s));
     TRY(stats_sync(d, red2, 2 * (size_t)d.M, s));
     if (bn) TRY(bn_bwd_fix(d0, bn, 1, red2, s));
+    if (cell_mixed(d)) return tail_mixed();
     switch (cell_kind(d)) {
     case TFNAS_KIND_FUSED: return tail_fused();
     case TFNAS_KIND_NOEXPAND: return tail_noexpand();
@@ -531,6 +618,13 @@ int CellBwd::tail_mbconv() {
         if (b.dx) TRY(expand_dx(d, nullptr, b.x, cb1, part, dout_res, b.wmix, b.dx, b.dEh, s, b.add_src, b.add_scale, nsl));
         return 0;
     }
+    return chain_mbconv(d, true);
+}
+
+// the materialised route of plain groups from the depthwise backward on: the cell's own descriptor, or the plain groups of a mixed
+// cell (se_wgrad = false: tail_mixed launched the SE weight gradients of ALL groups itself)
+int CellBwd::chain_mbconv(const TfnasCellDesc& d, bool se_wgrad) {
+    const bool se = se_wgrad && d.SE > 0;
     // the depthwise backward-data pass below, planned once; on the stride-1 ring cells and the stride-2 register-window cells
     // it also produces the depthwise weight gradient (same dd window, same E elements: no second read of E, dZ and D)
     const DwPlan dw_bwd = dw_plan_bwd_data(d, b.E == nullptr, b.x != nullptr);
@@ -538,9 +632,9 @@ int CellBwd::tail_mbconv() {
     if (d.need_wgrad) {
         // ONE fork for the SE and the depthwise weight gradients (every fork is an event record + a stream wait on the
         // host-bound w-step; cells without SE launch nothing for it)
-        if (d.SE > 0 || !dw_fused) {
+        if (se || !dw_fused) {
             hipStream_t sw = fork_to(so, 1, s);
-            if (d.SE > 0) TRY(launch_se_wgrad(d, dgate, gate, dhpre, hpre, pooled, sw));
+            if (se) TRY(launch_se_wgrad(d, dgate, gate, dhpre, hpre, pooled, sw));
             if (!dw_fused) TRY(launch_dw_wgrad(d, b.dZ, gate, dpooled, b.D, stats2, red2, b.E, stats1, part_w1, sw));
         }
     }
@@ -557,6 +651,46 @@ int CellBwd::tail_mbconv() {
     if (d.need_wgrad) TRY(launch_expand_wgrad(d, b.dEh, b.E, cb1, b.x, part_w2, fork_to(so, 2, s)));
     if (b.dx && d.mode != TFNAS_MODE_STEM)
         TRY(expand_dx(d, b.dEh, b.x, cb1, part, dout_res, b.wmix, b.dx, b.dxp, s, b.add_src, b.add_scale));
+    return 0;
+}
+
+// A cell whose groups differ in kind, after the shared prefix: the tail of each kind on that kind's groups (sub-descriptors,
+// kind_subset), always in the order plain -> expand-free -> Fused-MBConv, groups in the caller's order inside a kind.
+// dx: the FIRST branch that runs stores it, every later one read-adds-stores it, all on the chain stream `s` -- one fixed
+// summation order, no atomics.  The branches run with has_res = 0 (their group indices do not index wmix); the residual gradient
+// (sum of ALL mix weights) x dout is added once at the end.  dEh: the plain groups' dE and every Fused-MBConv group's dd live in
+// their own groups' columns of the same rows, so the kinds never overwrite each other and the weight-gradient forks may lag.
+// Fork 1 carries, in stream order, the SE weight gradients of all groups, then each kind's depthwise / dense weight gradients
+// (they share that fork's scratch); fork 2 the plain groups' expand weight gradient.
+int CellBwd::tail_mixed() {
+    if (bn || b.add_src) return TFNAS_EINVAL;         // (no affine form; the path level, which adds the sink gradient, refuses the bit)
+    TfnasCellDesc full = d, sub;
+    full.has_res = 0;
+    bool stored = false;                              // dx holds the sum of the branches so far
+    if (d.need_wgrad && d.SE > 0) TRY(launch_se_wgrad(d, dgate, gate, dhpre, hpre, pooled, fork_to(so, 1, s)));
+    if (kind_subset(full, TFNAS_KIND_MBCONV, sub)) {
+        TRY(chain_mbconv(sub, false));
+        stored = b.dx != nullptr;
+    }
+    if (kind_subset(full, TFNAS_KIND_NOEXPAND, sub)) {
+        if (d.need_wgrad)
+            TRY(launch_dw_wgrad(sub, b.dZ, gate, dpooled, b.D, stats2, red2, b.x, nullptr, part_w1, fork_to(so, 1, s)));
+        for (int g = 0; b.dx && g < sub.G; ++g) {     // (one launch per group: each owns every element of dx)
+            TRY(launch_dw_bwd_dx(group_alone(sub, g), b.dZ, gate, dpooled, b.D, stats2, red2, nullptr, b.dx, s, stored));
+            stored = true;
+        }
+    }
+    const int nf = kind_subset(full, TFNAS_KIND_FUSED, sub);
+    for (int g = 0; g < nf; ++g) {
+        const TfnasCellDesc one = group_alone(sub, g);
+        TRY(launch_conv_dd(one, b.dZ, b.D, gate, dpooled, stats2, red2, b.dEh, s));
+        if (d.need_wgrad) TRY(launch_conv_wgrad(one, b.dEh, b.x, part_w1, fork_to(so, 1, s)));
+        if (b.dx) {
+            TRY(launch_conv_dgrad(one, b.dEh, nullptr, b.dx, part, s, stored));
+            stored = true;
+        }
+    }
+    if (b.dx && d.has_res) TRY(launch_dx_add_res(d, dout_res, b.wmix, b.dx, s));
     return 0;
 }
 }  // namespace
@@ -590,19 +724,19 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
 // E may be omitted only by a kind that has no E buffer (it is never touched) and -- where the entry point offers it -- in E-free
 // mode (tfnas_efree_supported)
 static int check_E(const TfnasCellDesc& d, const float* E, bool efree_counts) {
-    if (E || !cell_has_E(d) || (efree_counts && efree_supported(d))) return 0;
+    if (E || !any_group_has_E(d) || (efree_counts && efree_supported(d))) return 0;
     return TFNAS_ENULL;
 }
 
 extern "C" int tfnas_mixedop_fwd(const TfnasCellDesc* dp, const float* x, const float* wmix, float* E, float* D,
                                  float* Pr, float* fsmall, double* stats, float* part, float* out, void* stream) {
     if (!dp || !x || !D || !Pr || !fsmall || !stats || !part || !out) return TFNAS_ENULL;
-    const TfnasCellDesc& d = *dp;
-    if (d.mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    if (dp->mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_modes(dp));
+    const TfnasCellDesc d = kinds_canon(*dp);      // (TFNAS_CELL_KINDS: all groups plain / one group -> the unflagged descriptor)
     TRY(check_E(d, E, true));
     TfnasCellWs ws;
-    TRY(tfnas_cell_ws(dp, &ws));
+    TRY(tfnas_cell_ws(&d, &ws));
     CellFwdBufs b = {x, wmix, E, D, Pr, fsmall, stats, part, out};
     return cell_fwd_impl(d, ws, b, S(stream));
 }
@@ -645,9 +779,9 @@ extern "C" int tfnas_mixedop_bwd(const TfnasCellDesc* dp, const float* x, const 
                                  float* dx, float* dxp, float* dwmix, void* stream) {
     if (!dp || !x || !D || !Pr || !fsmall || !stats || !dout || !dZ || !dEh || !bsmall || !red || !part)
         return TFNAS_ENULL;
-    const TfnasCellDesc& d = *dp;
-    if (d.mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    if (dp->mode == TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     TRY(check_modes(dp));
+    const TfnasCellDesc d = kinds_canon(*dp);
     TRY(check_E(d, E, true));
     CellBwdBufs b = {x, wmix, E, D, Pr, fsmall, stats, dout, dZ, dEh, bsmall, red, part, part + TFNAS_PART_ALLOC,
                      dx, dxp, dwmix, nullptr, nullptr};
@@ -660,6 +794,7 @@ extern "C" int tfnas_mbconv_fwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn
     if (!dp || !bn || !x || !D || !Pr || !fsmall || !stats || !part || !out) return TFNAS_ENULL;
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD || d.G != 1) return TFNAS_EINVAL;
+    if (cell_mixed(d)) return TFNAS_EINVAL;        // (derived blocks are one-block cells: their kind is a one-block bit)
     TRY(check_modes(dp));
     TRY(check_E(d, E, false));
     TRY(check_bn_sites(d, bn));
@@ -680,6 +815,7 @@ extern "C" int tfnas_mbconv_bwd(const TfnasCellDesc* dp, const TfnasBnAffine* bn
     const TfnasCellDesc& d = *dp;
     if (d.mode == TFNAS_MODE_HEAD || d.G != 1) return TFNAS_EINVAL;
     if (d.wgrad_stream[0] || d.wgrad_stream[1] || d.wgrad_stream[2]) return TFNAS_EINVAL;     // (tfnas_mixedop_bwd only)
+    if (cell_mixed(d)) return TFNAS_EINVAL;
     TRY(check_modes(dp));
     TRY(check_E(d, E, false));
     TRY(check_bn_sites(d, bn));

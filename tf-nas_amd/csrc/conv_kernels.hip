@@ -202,10 +202,12 @@ __global__ __launch_bounds__(256, conv_wgrad_lb(NT)) void k_conv_wgrad(TfnasCell
 // rows: input pixels; K = 9 mcp ordered (tap, m) (dd's pad columns are zeros); columns: input channels.  At stride 2 a tap
 // contributes only where both divisions are exact (row / column parity); every other element is a masked zero.
 // dres: the residual-branch gradient [N*H*W][ic] of a residual block (NULL otherwise), added in the same store.
+// accum: dx already holds the data gradient of the cell's earlier branches (a mixed cell, kernels.h: cell_mixed): the same
+// store adds it, each element read and written by the one thread that owns it -- no atomics, a fixed order on the stream.
 template <int NT, int MM>
 __global__ __launch_bounds__(256, conv_lb(MM)) void k_conv_dgrad(TfnasCellDesc d, const float* __restrict__ dd,
                                                                  const float* __restrict__ dres, float* __restrict__ dx,
-                                                                 const float* __restrict__ wd) {
+                                                                 const float* __restrict__ wd, int accum) {
     using T = GT<NT>;
     static_assert(T::B_ITERS == 1, "one B item per thread: its K position is the same in every chunk");
     __shared__ __attribute__((aligned(16))) float lds[T::LDS_FLOATS];
@@ -270,6 +272,7 @@ __global__ __launch_bounds__(256, conv_lb(MM)) void k_conv_dgrad(TfnasCellDesc d
             if (q < P && n0 + lc < ic) {
                 const size_t a = (size_t)q * ic + n0 + lc;
                 if (dres) v += ld4_nt(dres + a);
+                if (accum) v += ld4_nt(dx + a);
                 st4_nt(dx + a, v);
             }
         });
@@ -352,7 +355,7 @@ int launch_conv_fwd(const TfnasCellDesc& d, const float* x, float* D, double* st
         else hipLaunchKernelGGL((k_conv_fwd<2, MM>), grid, dim3(256), 0, s, d, x, D, part, wrp);
     })
     _prof.stop();
-    return launch_reduce_rows(part, grid.x, 2 * d.M, 2 * (size_t)d.M, stats2, nullptr, s);
+    return reduce_pair_rows(d, part, grid.x, stats2, s);       // (a FUSED group of a mixed cell: its own columns of stats2 only)
 }
 
 int launch_conv_dd(const TfnasCellDesc& d, const float* dZ, const float* D, const float* gate, const float* dpooled,
@@ -394,7 +397,8 @@ int launch_conv_wgrad(const TfnasCellDesc& d, const float* dd, const float* x, f
     return launch_reduce_rows(part, splits, (int)out, out, nullptr, d.g[0].g_expand, s, wgrad_accum(d));
 }
 
-int launch_conv_dgrad(const TfnasCellDesc& d, const float* dd, const float* dres, float* dx, float* part, hipStream_t s) {
+int launch_conv_dgrad(const TfnasCellDesc& d, const float* dd, const float* dres, float* dx, float* part, hipStream_t s,
+                      bool accum) {
     if (!cell_fused(d) || !dx || !d.g[0].w_expand) return TFNAS_EINVAL;
     ProfScope _prof(TK_CONV_DGRAD, s);
     const size_t rpf = conv_repack_floats(d);
@@ -405,8 +409,8 @@ int launch_conv_dgrad(const TfnasCellDesc& d, const float* dd, const float* dres
     const int tiles = cdiv(d.ic, wide ? 64 : 32);
     const dim3 grid(conv_row_blocks(d.N * d.H * d.W, tiles, 1024, 256 * conv_lb(mm)), tiles);
     CONV_MM(mm, {
-        if (wide) hipLaunchKernelGGL((k_conv_dgrad<4, MM>), grid, dim3(256), 0, s, d, dd, dres, dx, wrp);
-        else hipLaunchKernelGGL((k_conv_dgrad<2, MM>), grid, dim3(256), 0, s, d, dd, dres, dx, wrp);
+        if (wide) hipLaunchKernelGGL((k_conv_dgrad<4, MM>), grid, dim3(256), 0, s, d, dd, dres, dx, wrp, (int)accum);
+        else hipLaunchKernelGGL((k_conv_dgrad<2, MM>), grid, dim3(256), 0, s, d, dd, dres, dx, wrp, (int)accum);
     })
     return (int)hipGetLastError();
 }

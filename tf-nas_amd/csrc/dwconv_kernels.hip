@@ -265,7 +265,9 @@ __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float*
 // being read from E.
 // RAW (TFNAS_CELL_NOEXPAND, mc == ic): the depthwise input is the cell input, so dA1 IS the branch's dx.  The epilogue stores it to
 // `dEh` = dx [N*H*W][ic] (row stride ic), plus `x` = the residual gradient dout [N*H*W][ic] when non-NULL (has_res: oc == ic,
-// stride 1), in the same store.  No BN1-backward sums: E, stats1 and `part` are not touched.
+// stride 1), in the same store.  No BN1-backward sums: E, stats1 and `part` are not touched.  dx_accum: dx already holds the data
+// gradient of the cell's earlier branches (a mixed cell) and the same store adds it -- read and written by the one thread that
+// owns the element, its load issued with the residual's before the tap loop.
 template <int K, int S, int ACT, int KQ, bool RAW = false>
 __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const float* __restrict__ dZ,
                                                         const float* __restrict__ gate, const float* __restrict__ dpooled,
@@ -273,7 +275,7 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
                                                         const double* __restrict__ red2, const float* __restrict__ E,
                                                         const float* __restrict__ x,
                                                         const double* __restrict__ stats1, float* __restrict__ dEh,
-                                                        float* __restrict__ part, DwGeom gm) {
+                                                        float* __restrict__ part, DwGeom gm, int dx_accum) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int g, c0, lane = blockIdx.x, cy = blockIdx.y;
     if (KQ > 0) efree_lane_chunk(lane, cy);
@@ -355,8 +357,11 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
             for (int j = 0; j < 4; ++j) {
                 const int wi = wi0 + iw0 + j;
                 const bool okj = hi < H && wi < W && c0 + 4 * cq < mcp;
-                if constexpr (RAW)        // the residual gradient of the same dx element (x: dout of a residual block, else NULL)
-                    ev[j] = (okj && x) ? ld4_nt(x + (((size_t)(n * H + hi) * W + wi) * d.ic + c0 + 4 * cq)) : zero4();
+                if constexpr (RAW) {      // the residual gradient of the same dx element (x: dout of a residual block, else NULL)
+                    const size_t a = ((size_t)(n * H + hi) * W + wi) * d.ic + c0 + 4 * cq;
+                    ev[j] = (okj && x) ? ld4_nt(x + a) : zero4();
+                    if (okj && dx_accum) ev[j] += ld4_nt(dEh + a);
+                }
                 else if (KQ > 0) ev[j] = ld4(eh_tile + (ih * TIW + iw0 + j) * CC + 4 * cq);
                 else ev[j] = okj ? ld4_nt(E + (((size_t)(n * H + hi) * W + wi) * M + off + c0 + 4 * cq)) : zero4();
             }
@@ -1008,7 +1013,7 @@ int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const 
         }
         if (!ok) return TFNAS_EINVAL;
     }
-    return launch_reduce_rows(part, p.rows, 2 * d.M, 2 * (size_t)d.M, stats2, nullptr, s);
+    return reduce_pair_rows(d, part, p.rows, stats2, s);       // (some groups of a mixed cell: their own columns of stats2 only)
 }
 
 int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled,
@@ -1059,7 +1064,7 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
             ok = dw_tile_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
                 if constexpr ((K != 7 && !act_tile_only(A)) || KQ == 0)
                     hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate,
-                                       dpooled, D, stats2, red2, E, x, stats1, dEh, part, gm);
+                                       dpooled, D, stats2, red2, E, x, stats1, dEh, part, gm, 0);
             });
         }
         if (!ok) return TFNAS_EINVAL;
@@ -1077,8 +1082,9 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
 // dx = dw^T(dd) (+ dres: the residual gradient dout of a residual block, NULL otherwise).  Tile kernels only, no BN1-backward sums,
 // no partial rows, no reduction.
 int launch_dw_bwd_dx(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
-                     const double* stats2, const double* red2, const float* dres, float* dx, hipStream_t s) {
+                     const double* stats2, const double* red2, const float* dres, float* dx, hipStream_t s, bool accum) {
     if (!cell_noexpand(d) || !dx) return TFNAS_EINVAL;
+    if (accum && d.G != 1) return TFNAS_EINVAL;      // (two groups' workgroups would read-add-store the same dx elements)
     const DwPlan p = dw_plan_bwd_data(d, false, false);
     if (p.fam != DW_TILE) return TFNAS_EINVAL;       // (never planned: dw_tile_only)
     for (int i = 0; i < DW_NK; ++i) {
@@ -1091,7 +1097,7 @@ int launch_dw_bwd_dx(const TfnasCellDesc& d, const float* dZ, const float* gate,
         if (shm > 64 * 1024) return TFNAS_ERANGE;
         const bool ok = dw_tile_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
             hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, 0, true>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate, dpooled,
-                               D, stats2, red2, nullptr, dres, nullptr, dx, nullptr, gm);
+                               D, stats2, red2, nullptr, dres, nullptr, dx, nullptr, gm, (int)accum);
         });
         if (!ok) return TFNAS_EINVAL;
     }

@@ -1465,7 +1465,8 @@ static bool fx_bwd_layout(const TfnasCellDesc& d, const FxPlan& pl, size_t scrat
 
 bool fx_supported(const TfnasCellDesc& d) {
     FxPlan pl;
-    if (cell_noexpand(d) || cell_fused(d)) return false; // (the fused kernels start with the expand convolution)
+    if (cell_noexpand(d) || cell_fused(d) || cell_mixed(d)) return false; // (the fused kernels start with the expand convolution;
+                                                                            //  the plain groups of a mixed cell materialise E)
     if (!fx_enabled(d) || !fx_plan(d, pl, false)) return false;
     // the fused kernels' expand / dgrad products exist in the split-bf16 x3 arithmetic only: a launch in another mode (the
     // descriptor's own, else the process default) takes the materialised route, so that one model runs ONE arithmetic in both

@@ -812,6 +812,29 @@ __global__ __launch_bounds__(256) void k_dx_reduce(TfnasCellDesc d, const float*
     }
 }
 
+// dx += (sum_g wmix[g]) * dout: the residual gradient of a cell whose groups differ in kind (kernels.h: cell_mixed), added ONCE
+// after the last branch's data gradient (every branch runs with has_res = 0: the branches see sub-descriptors, whose group
+// indices do not index wmix).  One more pass over dx [N*H*W][ic], the narrowest tensor of the backward; each element read and
+// written by one thread.  wmix == NULL: weight 1.
+__global__ __launch_bounds__(256) void k_dx_add_res(const float* __restrict__ dout, const float* __restrict__ wmix, int G,
+                                                    float* __restrict__ dx, size_t n4) {
+    float sumw = 1.f;
+    if (wmix) {
+        sumw = 0.f;
+        for (int g = 0; g < G; ++g) sumw += wmix[g];
+    }
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
+        st4(dx + 4 * i, ld4(dx + 4 * i) + splat4(sumw) * ld4(dout + 4 * i));
+}
+int launch_dx_add_res(const TfnasCellDesc& d, const float* dout, const float* wmix, float* dx, hipStream_t s) {
+    if (!d.has_res || !dout || !dx) return TFNAS_EINVAL;
+    const size_t n4 = (size_t)d.N * d.H * d.W * d.ic / 4;
+    size_t gx = (n4 + 255) / 256;
+    if (gx > 2048) gx = 2048;
+    hipLaunchKernelGGL(k_dx_add_res, dim3((unsigned)gx), dim3(256), 0, s, dout, wmix, d.G, dx, n4);
+    return (int)hipGetLastError();
+}
+
 // ============================================================================ BN1-backward correction operator
 // part[split][(ic+4)*ic]:  rows c' < ic: G[c'][c] = sum_m W[m][c'] s_m W[m][c];  row ic: b[c] = sum_m coef_m W[m][c];
 // s_m = rstd_m^2 t2_m, coef_m = s_m mu_m - rstd_m t1_m   (see k_expand_dgrad).  GEMM rows = input channels (+ the b row),
@@ -1280,7 +1303,7 @@ int launch_expand_fwd(const TfnasCellDesc& d, const float* x, float* E, double* 
             DISPATCH_NT_GROUPS(p.nt, { hipLaunchKernelGGL((k_expand_fwd<NT, false, MM>), p.grid, dim3(256), 0, s, d, x, E, part); })
     })
     _prof.stop();
-    return launch_reduce_rows(part, p.grid.x, 2 * d.M, 2 * (size_t)d.M, stats1, nullptr, s);
+    return reduce_pair_rows(d, part, p.grid.x, stats1, s);
 }
 
 // caps of the K-splits of the w-step's one-candidate launches (see gemm_plan_expand_dgrad); build flags, tools/README.md

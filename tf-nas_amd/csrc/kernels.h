@@ -49,6 +49,24 @@ static inline CellKind cell_kind(const TfnasCellDesc& d) {
 // the two facts of a kind the host code asks for repeatedly: an E buffer, a BatchNorm site 0 (today: the plain MBConv cell has both)
 static inline bool cell_has_E(const TfnasCellDesc& d) { return cell_kind(d) == TFNAS_KIND_MBCONV; }
 static inline bool cell_has_bn0(const TfnasCellDesc& d) { return cell_kind(d) == TFNAS_KIND_MBCONV; }
+// TFNAS_CELL_KINDS: a cell whose groups each have a kind of their own (TfnasGroup.kind).  "Mixed" is not a fourth kind: the entry
+// points canonicalise the descriptor first (capi.hip: kinds_canon -- all groups plain: the bit is dropped; one group: its one-block
+// bit instead), so past them the bit means a cell with several groups of which at least one is not plain.  Its launch sequences
+// run every kind's front / tail on a SUB-descriptor: the groups of that kind only (same M, same off / se_off: the same columns
+// of the [pixels][M] tensors), the kind's one-block bit set next to TFNAS_CELL_KINDS -- cell_kind() of a sub-descriptor is its
+// groups' kind.  A launcher handed one must leave the other groups' columns of every shared table alone (reduce_pair_rows).
+// (Shared: stats2 -- every kind's front writes its own columns.  stats1, red1 and cb1 belong to the plain groups alone: their other
+// columns are never read, and whole-row reductions into them may leave anything there.)
+static inline bool cell_mixed(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_KINDS) != 0; }
+static inline CellKind group_kind(const TfnasCellDesc& d, int g) {
+    return cell_mixed(d) && !cell_fused(d) && !cell_noexpand(d) ? (CellKind)d.g[g].kind : cell_kind(d);
+}
+// group-aware forms of the two facts: some group has an E buffer / a BatchNorm site 0
+static inline bool any_group_has_E(const TfnasCellDesc& d) {
+    for (int g = 0; g < d.G; ++g)
+        if (group_kind(d, g) == TFNAS_KIND_MBCONV) return true;
+    return false;
+}
 // the activation fork of a launcher (inside a function returning int): the statements run with ACT = the launch's activation as a
 // compile-time constant; any other value is TFNAS_EINVAL
 #define ACT_DISPATCH(act, ...)                                                                        \
@@ -115,6 +133,8 @@ int launch_expand_dgrad(const TfnasCellDesc& d, const float* dEh, const float* x
                         const float* add_src = nullptr, const float* add_scale = nullptr, int nsl = -1);
 int launch_expand_wgrad(const TfnasCellDesc& d, const float* dEh, const float* E, const float* cb1,
                         const float* x, float* part, hipStream_t s);
+// dx += (sum of the d.G mix weights) * dout: the residual gradient of a mixed residual cell, after its last branch
+int launch_dx_add_res(const TfnasCellDesc& d, const float* dout, const float* wmix, float* dx, hipStream_t s);
 
 // dwconv_kernels.hip: the depthwise k x k convolution in three kernel families, each with the geometry struct its kernels take by
 // value: k = 3 | 5 in all of them, k = 7 in the LDS tile kernels only (a cell with a 7 x 7 group is planned onto those in every
@@ -186,8 +206,9 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
                        const float* D, const double* stats2, const double* red2, const float* E, const float* x,
                        const double* stats1, float* dEh, double* red1, float* part, hipStream_t s, float* cb1 = nullptr);
 // cell_noexpand(d): dx [N*H*W][ic] = dw^T(dd) (+ dres [N*H*W][ic], the residual gradient, or NULL) in one tile-kernel pass
+// accum: dx += instead (a later branch of a mixed cell; ONE group per launch then: every NOEXPAND group owns all of dx)
 int launch_dw_bwd_dx(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
-                     const double* stats2, const double* red2, const float* dres, float* dx, hipStream_t s);
+                     const double* stats2, const double* red2, const float* dres, float* dx, hipStream_t s, bool accum = false);
 int launch_reduce_bn1(const TfnasCellDesc& d, const float* part, int nb, const double* stats1, double* red1, float* cb1,
                       hipStream_t s);
 int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
@@ -206,7 +227,9 @@ int launch_conv_wgrad(const TfnasCellDesc& d, const float* dd, const float* x, f
 bool conv_wgrad_row_fits(const TfnasCellDesc& d);     // the partial weight gradient of one split (9 ic mc floats) fits the partials
                                                        // region, the repacked weight next to 128 statistics rows (tfnas_cell_plan: else TFNAS_ERANGE)
 // dx [N*H*W][ic] = conv^T(dd) (+ dres [N*H*W][ic], the residual gradient, or NULL); `part`: scratch of the repacked weight
-int launch_conv_dgrad(const TfnasCellDesc& d, const float* dd, const float* dres, float* dx, float* part, hipStream_t s);
+// accum: dx += instead (a later branch of a mixed cell)
+int launch_conv_dgrad(const TfnasCellDesc& d, const float* dd, const float* dres, float* dx, float* part, hipStream_t s,
+                      bool accum = false);
 
 // pointwise_kernels.hip (SE squeeze, BN2 backward statistics, mixing epilogue, BN constant tables)
 // se_kernels.hip (SE excite FCs as small GEMMs: launch_se_fc_fwd / launch_se_fc_bwd / launch_se_wgrad)
@@ -240,6 +263,18 @@ int launch_head_bwd(const TfnasCellDesc& d, const float* E, const double* stats1
 // weight-gradient outputs of a TFNAS_CELL_ACCUM_WGRAD launch; the double output is always overwritten)
 int launch_reduce_rows(const float* part, int nb, int ncols, size_t stride, double* out_d, float* out_f,
                        hipStream_t s, int accum = 0);
+// `rows` partial rows of 2 * M (sum, sumsq) pairs -> a [M][2] table of doubles.  One launch over the whole row; for a
+// sub-descriptor of a mixed cell one launch per group over its own columns: the table is shared with the other kinds' groups,
+// whose columns of these partial rows were never written.
+static inline int reduce_pair_rows(const TfnasCellDesc& d, const float* part, int rows, double* table, hipStream_t s) {
+    if (!cell_mixed(d)) return launch_reduce_rows(part, rows, 2 * d.M, 2 * (size_t)d.M, table, nullptr, s);
+    for (int g = 0; g < d.G; ++g) {
+        const size_t o = 2 * (size_t)d.g[g].off;
+        const int rc = launch_reduce_rows(part + o, rows, 2 * d.g[g].mcp, 2 * (size_t)d.M, table + o, nullptr, s);
+        if (rc) return rc;
+    }
+    return 0;
+}
 /* One `part` scratch region = TFNAS_PART_ALLOC floats (16 MiB): TFNAS_PART_FLOATS for per-workgroup partial rows / split-K
    tiles; the last TFNAS_TAIL_SLOTS words are reserved (they held the ticket counters of the removed "last workgroup reduces"
    epilogues; the size of the region is part of the workspace ABI and stays). */

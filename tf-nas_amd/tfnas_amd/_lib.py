@@ -30,6 +30,7 @@ CELL_K7 = 0x80               # TfnasCellDesc.flags: groups may have depthwise ke
 CELL_ACTS = 0x100            # TfnasCellDesc.flags: act may be 'relu6' / 'h-swish' (refused without the bit)
 CELL_NOEXPAND = 0x200        # TfnasCellDesc.flags: the one group has no expand convolution (mid == in channels; refused without the bit)
 CELL_FUSED = 0x400           # TfnasCellDesc.flags: the one group is a Fused-MBConv block (dense 3 x 3 weight in w_expand, no depthwise)
+CELL_KINDS = 0x800           # TfnasCellDesc.flags: every group names its own kind in TfnasGroup.kind (group_kind_id; refused without the bit)
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
 ROUTE_FX_OFF, ROUTE_FOLD_OFF, ROUTE_DWWG_OFF, ROUTE_DWWG2_OFF, ROUTE_XG_OFF, ROUTE_XG_ALL = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 ROUTE_DW = {'auto': 0, 'direct': 1 << 6, 'lds': 2 << 6, 'tiled': 3 << 6}
@@ -70,6 +71,12 @@ FUSED = BlockKind('FUSED', CELL_FUSED, (0, 2, 3, 4, 5, 6), (1, 2), False)       
 KINDS = (MBCONV, NOEXPAND, FUSED)
 
 
+def group_kind_id(kind):
+    """TFNAS_GROUP_* of a BlockKind: what TfnasGroup.kind holds in a descriptor with CELL_KINDS (a cell whose candidates differ
+    in kind -- not a fourth kind: every group of it has one of the three)."""
+    return KINDS.index(kind)
+
+
 def describe_block(kind, N, H, W, ic, mc, se, oc, k, stride, act):
     """A one-block TFNAS_MODE_CELL descriptor of ``kind``, before tfnas_cell_plan: the geometry words, has_res, eps and the flags
     the geometry itself asks for (CELL_K7, the activation's bit, the kind's bit).  ``act``: a TFNAS_ACT_* id.  Pure host code."""
@@ -82,7 +89,7 @@ def describe_block(kind, N, H, W, ic, mc, se, oc, k, stride, act):
 
 
 class TfnasGroup(C.Structure):
-    _fields_ = ([(n, C.c_int32) for n in ('mc', 'k', 'se', 'mcp', 'off', 'se_off', 'pad0', 'pad1')]
+    _fields_ = ([(n, C.c_int32) for n in ('mc', 'k', 'se', 'mcp', 'off', 'se_off', 'kind', 'pad1')]
                 + [(n, C.c_void_p) for n in _W_FIELDS] + [(n, C.c_void_p) for n in _G_FIELDS])
 
 

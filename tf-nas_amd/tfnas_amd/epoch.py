@@ -64,10 +64,34 @@ def _resolve(module, dotted):
     return obj
 
 
+def require_default_primitives(what, primitives=None, model=None):
+    """The epoch boundary slices, scatters and re-ranks a candidate's mid channels by the tensors of a plain MBConv block (the L1
+    norm of its depthwise filters picks the channels); a Fused-MBConv or expand-free candidate has no such tensors.  Raises
+    NotImplementedError naming the first primitive outside geometry.PRIMITIVES -- of a ``primitives`` argument (one list, or a
+    {stage: {block: list}} mapping) or of the cells of ``model``.  A fixed-width search through search.w_step / a_step works."""
+    found = []
+    if isinstance(primitives, dict):
+        found += [(st, b, list(p)) for st, blocks in primitives.items() for b, p in (blocks or {}).items() if p is not None]
+    elif primitives is not None:
+        found.append(('every stage', 'every block', list(primitives)))
+    net = getattr(model, 'module', model)
+    if net is not None and hasattr(net, 'stages'):
+        for st, stage in zip(getattr(net, '_stage_names', []), net.stages()):
+            for b, cell in enumerate(stage.blocks(), start=1):
+                found.append((st, 'block%d' % b, list(getattr(cell, 'primitives', geometry.PRIMITIVES))))
+    for st, b, names in found:
+        for i, n in enumerate(names):
+            if i >= len(geometry.PRIMITIVES) or n != geometry.PRIMITIVES[i]:
+                raise NotImplementedError('tfnas_amd: %s works on the default primitives only; %s.%s holds %r as candidate %d (the '
+                                          'epoch boundary ranks mid channels by the depthwise weight of a plain MBConv block)'
+                                          % (what, st, b, n, i))
+
+
 def slice_weights_from_max(model, state_dict, mc_mask_dddict, prefix='module.'):
     """Load a current-width ``model`` (built from ``get_mc_num_dddict(mc_mask_dddict)``) from the max-width store:
     tensors outside ``m_ops`` are taken as they are, candidate weights are ``index_select``-ed with the channel masks.
     ``model`` is the bare Network (what the reference reaches as ``model.module``)."""
+    require_default_primitives('slice_weights_from_max', model=model)
     net = getattr(model, 'module', model)
     dev = next(net.parameters()).device
     for key, val in state_dict.items():
@@ -88,6 +112,7 @@ def slice_weights_from_max(model, state_dict, mc_mask_dddict, prefix='module.'):
 
 def scatter_weights_to_max(state_dict, model, mc_mask_dddict, prefix='module.'):
     """Write the trained current-width weights back into the rows / columns of the max-width store they came from."""
+    require_default_primitives('scatter_weights_to_max', model=model)
     net = getattr(model, 'module', model)
     cur = {prefix + k: v for k, v in net.state_dict().items()}
     for key in state_dict:
@@ -164,9 +189,11 @@ def shrink_or_expand(parsed_arch, mc_mask_dddict, mc_maxnum_dddict, lat_lookup_k
     return mc_num, before, after
 
 
-def remask_by_l1(parsed_arch, mc_num_dddict, mc_mask_dddict, state_dict, prefix='module.'):
+def remask_by_l1(parsed_arch, mc_num_dddict, mc_mask_dddict, state_dict, prefix='module.', primitives=None):
     """Where elasticity scaling changed a chosen candidate's width, re-select its active channels: the ``mc_num`` output
-    channels of the max-width depthwise filter bank with the largest L1 norm (train_search.py:293-305).  In place."""
+    channels of the max-width depthwise filter bank with the largest L1 norm (train_search.py:293-305).  In place.
+    ``primitives``: what the network was built with; anything but the defaults is refused (require_default_primitives)."""
+    require_default_primitives('remask_by_l1', primitives)
     changed = []
     for stage, blocks in parsed_arch.items():
         for block, op_idx in blocks.items():
@@ -216,7 +243,7 @@ def train_stats(stats, m, epoch, arch_epoch, num_classes):
 def search_epoch(epoch, state_dict, mc_mask_dddict, lat_lookup, train_queue, val_queue, *, num_classes=100, epochs=100,
                  lr=0.025, T=5.0, w_mom=0.9, w_wd=1e-5, a_lr=0.01, a_wd=5e-4, a_betas=(0.5, 0.999), grad_clip=5.0,
                  target_lat=15.0, lambda_lat=0.1, warmup_epochs=10, noise=None, device='cuda', group=None, log=None,
-                 print_freq=100):
+                 print_freq=100, primitives=None):
     """One epoch of the reference's main loop (train_search.py:155-307) on the HIP model.  ``state_dict`` / ``mc_mask_dddict``
     are updated in place and returned together with the epoch's statistics.  ``train_queue`` / ``val_queue``: iterables of
     (x, target) batches (the weight-sharing / arch-step queues of train_w_arch).
@@ -225,7 +252,9 @@ def search_epoch(epoch, state_dict, mc_mask_dddict, lat_lookup, train_queue, val
     (tail.SearchMeter) and read once after the loop -- summed over the ranks of ``group`` first -- into ``stats['train_top1']``,
     ``['train_top5']``, ``['train_objs_w']`` and, in architecture epochs, ``['train_objs_a']``, ``['train_objs_l']``.  With a ``log``
     the reference's TRAIN lines are logged every ``print_freq`` steps from this rank's running sums: one more read, i.e. one host
-    synchronisation, per ``print_freq`` steps, and none without a ``log``."""
+    synchronisation, per ``print_freq`` steps, and none without a ``log``.
+    ``primitives``: refused unless None / the defaults (require_default_primitives)."""
+    require_default_primitives('search_epoch', primitives)
     from . import search
     from .tail import SearchMeter
     from .model_search import Network
@@ -302,6 +331,7 @@ def run_search(save_dir, lat_lookup, make_train_queue, make_val_queue, *, num_cl
                T_decay=0.96, warmup_epochs=10, seed=2, start_epoch=0, device='cuda', log=print, **kw):
     """The whole schedule of train_search.py:84-315: initial max-width checkpoint, per-epoch model at the current widths,
     cosine learning-rate list, temperature decay after every arch epoch, per-epoch checkpoints ``searched_model_XX.pth.tar``."""
+    require_default_primitives('run_search', kw.get('primitives'))     # (before anything is written)
     from .model_search import Network
     from .search import TfnasDataParallel
     os.makedirs(save_dir, exist_ok=True)

@@ -173,15 +173,20 @@ class CellPlan:
     def __deepcopy__(self, memo):
         return None
 
-    def __init__(self, ic, oc, stride, act, blocks, mode=_lib.MODE_CELL, modes=None):
+    def __init__(self, ic, oc, stride, act, blocks, mode=_lib.MODE_CELL, modes=None, mixed_kinds=False):
         self.ic, self.oc, self.stride, self.act = ic, oc, stride, act
         self.blocks = list(blocks)                     # MBInvertedResBlock modules (parameter containers)
-        # the kind is decided HERE, once: a one-block cell is what its block is (_lib.BlockKind), every other plan is plain
+        # the kind is decided HERE, once: a one-block cell is what its block is (_lib.BlockKind), every other plan is plain --
+        # unless the caller allows blocks of different kinds in one plan (``mixed_kinds``: MixedOP._plan), where every group keeps
+        # its block's kind (TfnasGroup.kind under CELL_KINDS) as soon as one of them is not plain
         kinds = [getattr(b, 'kind', _lib.MBCONV) for b in self.blocks]
-        if _lib.FUSED in kinds and (len(self.blocks) != 1 or mode != _lib.MODE_CELL):
+        many = len(self.blocks) != 1 or mode != _lib.MODE_CELL
+        mixed = bool(mixed_kinds) and mode == _lib.MODE_CELL and len(self.blocks) > 1 and any(k is not _lib.MBCONV for k in kinds)
+        if _lib.FUSED in kinds and many and not mixed:
             raise NotImplementedError('tfnas_amd: a FusedMBConvBlock runs as a one-block cell only (not as a candidate of a '
                                       'multi-candidate MixedOP launch, a stem or a head)')
         self.kind = kinds[0] if (mode == _lib.MODE_CELL and len(self.blocks) == 1) else _lib.MBCONV
+        self.group_kinds = tuple(kinds) if mixed else None
         # (what desc() hands HipModes.apply after the descriptor: a plain plan names no kind, so that a subclass which overrides
         # apply(d) alone keeps working -- for such a plan apply's own inference says MBCONV too)
         self._kind_arg = () if self.kind is _lib.MBCONV else (self.kind,)
@@ -226,13 +231,22 @@ class CellPlan:
             for g, b in enumerate(self.blocks):
                 d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
             self.modes.apply(d, *self._kind_arg)       # (before the plan: it validates the modes; every launch re-checks them)
+            self._mark_kinds(d)
             check(_lib.lib().tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
             ws = TfnasCellWs()
             check(_lib.lib().tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
             hit = (d, ws)
             self._desc_cache[key] = hit
         self.modes.apply(hit[0], *self._kind_arg)      # (every launch: the descriptor is cached, the model's modes may change)
+        self._mark_kinds(hit[0])
         return hit
+
+    def _mark_kinds(self, d):
+        """A plan of blocks of different kinds: CELL_KINDS and every group's own kind (after HipModes.apply, which rewrites flags)."""
+        if self.group_kinds is not None:
+            d.flags |= _lib.CELL_KINDS
+            for g, kind in enumerate(self.group_kinds):
+                d.g[g].kind = _lib.group_kind_id(kind)
 
     def bind(self, d, params, grads=None):
         """Write current weight (and gradient) pointers into the descriptor."""

@@ -23,6 +23,33 @@ OP_KERNEL = (3, 3, 5, 5, 3, 3, 5, 5)
 OP_EXPAND = (3, 6, 3, 6, 3, 6, 3, 6)
 OP_SE_MULT = (0, 0, 0, 0, 1, 2, 1, 2)
 
+# Every named primitive a cell may hold (model_search.OPS builds the modules; ``primitives=`` of MixedOP / MixedStage / Network
+# chooses 8 per cell, PRIMITIVES by default): name -> (layer class, kernel size, SE width as a multiple of ic, own width).
+# own width False: the block is as wide as mc_num_dict[i] says; True ('DS_*', expand-free): mid = ic whatever it says.
+PRIMITIVE_SPECS = OrderedDict(
+    [(n, ('MBInvertedResBlock', OP_KERNEL[i], OP_SE_MULT[i], False)) for i, n in enumerate(PRIMITIVES)]
+    + [('MBI_k7_%s%s' % (e, '_se' if se else ''), ('MBInvertedResBlock', 7, se, False)) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))]
+    + [('FMB_k3_%s%s' % (e, '_se' if se else ''), ('FusedMBConvBlock', 3, se, False)) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))]
+    + [('DS_k%d%s' % (k, '_se' if se else ''), ('MBInvertedResBlock', k, se, True)) for k in (3, 5) for se in (0, 1)])
+
+
+def cell_primitives(primitives, stage, block):
+    """The 8 candidate names of cell (stage, block) under a ``primitives`` argument: None -> PRIMITIVES; one list -> that list for
+    every cell; a {stage: {block: list}} mapping -> its entry, PRIMITIVES where it has none."""
+    if isinstance(primitives, dict):
+        primitives = (primitives.get(stage) or {}).get(block)
+    return list(PRIMITIVES) if primitives is None else list(primitives)
+
+
+def primitive_block(name, ic, mc):
+    """(layer class name, mid_channels, se_channels, kernel_size) of primitive ``name`` in a cell of ``ic`` input channels whose
+    width table says ``mc``; ValueError (naming the legal ones) for an unknown name."""
+    if name not in PRIMITIVE_SPECS:
+        raise ValueError('tfnas_amd: unknown primitive %r (one of %s)' % (name, ', '.join(sorted(PRIMITIVE_SPECS))))
+    layer, k, se_mult, own = PRIMITIVE_SPECS[name]
+    return layer, (ic if own else mc), ic * se_mult, k
+
+
 # stage -> (in_channels[], out_channels[], strides[], act, stage_type)   (model_search.py:221-275)
 STAGES = OrderedDict([
     ('stage1', dict(ics=[16, 24], ocs=[24, 24], ss=[2, 1], act='relu', stage_type=1)),

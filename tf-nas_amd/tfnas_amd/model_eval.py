@@ -140,7 +140,8 @@ class _DerivedBase(nn.Module):
 
 
 class Network(_DerivedBase):
-    def __init__(self, num_classes, parsed_arch, mc_num_dddict, lat_lookup=None, dropout_rate=0.0, drop_connect_rate=0.0):
+    def __init__(self, num_classes, parsed_arch, mc_num_dddict, lat_lookup=None, dropout_rate=0.0, drop_connect_rate=0.0,
+                 primitives=None):
         super().__init__()
         self.lat_lookup, self.mc_num_dddict, self.parsed_arch = lat_lookup, mc_num_dddict, parsed_arch
         self.dropout_rate, self.drop_connect_rate = dropout_rate, drop_connect_rate
@@ -156,8 +157,11 @@ class Network(_DerivedBase):
                 self.block_idx += 1
                 op = parsed_arch[name][block_name]
                 ic, oc, s = cfg['ics'][i], cfg['ocs'][i], cfg['ss'][i]
-                blk = MBInvertedResBlock(ic, mc_num_dddict[name][block_name][op], geometry.se_channels(ic, op), oc,
-                                         geometry.OP_KERNEL[op], s, affine=True, act_func=cfg['act'])
+                # (``primitives``: what the searched network was built with, model_search.Network(primitives=...))
+                prim = geometry.cell_primitives(primitives, name, block_name)[op]
+                layer, mc, se, k = geometry.primitive_block(prim, ic, mc_num_dddict[name][block_name][op])
+                cls = FusedMBConvBlock if layer == 'FusedMBConvBlock' else MBInvertedResBlock
+                blk = cls(ic, mc, se, oc, k, s, affine=True, act_func=cfg['act'])
                 blk.drop_connect_rate = self.drop_connect_rate * self.block_idx / self.block_count
                 stage.append(blk)
             setattr(self, name, stage)

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .functions import ArchFn, CellPlan, HeadFn, MixedOpFn, SinkFn, StemFn, arch_sample
-from .layers import ConvLayer, LinearLayer, MBInvertedResBlock
+from .layers import ConvLayer, FusedMBConvBlock, LinearLayer, MBInvertedResBlock
 
 PRIMITIVES = [
     'MBI_k3_e3', 'MBI_k3_e6', 'MBI_k5_e3', 'MBI_k5_e6',
@@ -41,19 +41,62 @@ OPS = {
     for name, (k, se) in _OP_SPEC.items()
 }
 
+# Named primitives beside the eight defaults (PRIMITIVES itself stays the reference's): chosen per cell with ``primitives=``.
+#   MBI_k7_*  the 7 x 7 twins of the defaults
+#   FMB_k3_*  Fused-MBConv (dense 3 x 3 convolution), width from mc_num_dict[i] and SE = ic x {1, 2} like their MBI twins
+#   DS_k*     expand-free (depthwise-separable) blocks: mid = ic whatever mc_num_dict[i] says, SE = ic
+OPS.update({
+    'MBI_k7_%s%s' % (e, '_se' if se else ''): (lambda ic, mc, oc, s, aff, act, _se=se:
+                                               MBInvertedResBlock(ic, mc, ic * _se, oc, 7, s, affine=aff, act_func=act))
+    for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))})
+OPS.update({
+    'FMB_k3_%s%s' % (e, '_se' if se else ''): (lambda ic, mc, oc, s, aff, act, _se=se:
+                                               FusedMBConvBlock(ic, mc, ic * _se, oc, 3, s, affine=aff, act_func=act))
+    for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))})
+OPS.update({
+    'DS_k%d%s' % (k, '_se' if se else ''): (lambda ic, mc, oc, s, aff, act, _k=k, _se=se:
+                                            MBInvertedResBlock(ic, ic, ic * _se, oc, _k, s, affine=aff, act_func=act))
+    for k in (3, 5) for se in (0, 1)})
+
+
+def check_primitives(primitives):
+    """The candidate names of one MixedOP: None -> the defaults; else a list of exactly len(PRIMITIVES) registered names
+    (the architecture kernels and noise tensors are 8 wide).  ValueError names the legal ones."""
+    if primitives is None:
+        return list(PRIMITIVES)
+    names = list(primitives)
+    if len(names) != len(PRIMITIVES):
+        raise ValueError('tfnas_amd: a MixedOP takes exactly %d primitives, got %d' % (len(PRIMITIVES), len(names)))
+    for n in names:
+        if n not in OPS:
+            raise ValueError('tfnas_amd: unknown primitive %r (one of %s)' % (n, ', '.join(sorted(OPS))))
+    return names
+
+
+def _cell_primitives(primitives, stage, block):
+    """``primitives`` of a MixedStage / Network for one cell ('stage3', 'block2'): one list for every cell, or a
+    {stage: {block: list}} mapping whose missing entries mean the defaults (a MixedStage built on its own, without a stage
+    name, takes its {block: list} part)."""
+    if not isinstance(primitives, dict):
+        return primitives
+    per_stage = primitives if stage is None else (primitives.get(stage) or {})
+    return per_stage.get(block)
+
+
 _SAMPLE_MODES = {'gumbel': 0, 'gumbel_2': 0, 'min_alphas': 1, 'max_alphas': 2}
 
 
 class MixedOP(nn.Module):
-    def __init__(self, in_channels, out_channels, stride, affine, act_func, num_ops, mc_num_dict, lat_lookup):
+    def __init__(self, in_channels, out_channels, stride, affine, act_func, num_ops, mc_num_dict, lat_lookup, primitives=None):
         super().__init__()
+        self.primitives = check_primitives(primitives)
         self.num_ops = num_ops
         self.lat_lookup = lat_lookup
         self.mc_num_dict = mc_num_dict
         self.in_channels, self.out_channels, self.stride, self.act_func = in_channels, out_channels, stride, act_func
         self.m_ops = nn.ModuleList()
         for i in range(num_ops):
-            self.m_ops.append(OPS[PRIMITIVES[i]](in_channels, self.mc_num_dict[i], out_channels, stride, affine,
+            self.m_ops.append(OPS[self.primitives[i]](in_channels, self.mc_num_dict[i], out_channels, stride, affine,
                                                  act_func))
         self._initialize_log_alphas()
         self.reset_switches()
@@ -99,7 +142,7 @@ class MixedOP(nn.Module):
             self._plans, p = {}, None
         if p is None:
             p = CellPlan(self.in_channels, self.out_channels, self.stride, self.act_func,
-                         [self.m_ops[i] for i in idxs])
+                         [self.m_ops[i] for i in idxs], mixed_kinds=True)
             self._plans[key] = p
         return p
 
@@ -163,7 +206,7 @@ class MixedOP(nn.Module):
 
 
 class MixedStage(nn.Module):
-    def __init__(self, ics, ocs, ss, affs, acts, mc_num_ddict, lat_lookup, stage_type):
+    def __init__(self, ics, ocs, ss, affs, acts, mc_num_ddict, lat_lookup, stage_type, primitives=None, stage_name=None):
         super().__init__()
         self.lat_lookup = lat_lookup
         self.mc_num_ddict = mc_num_ddict
@@ -177,7 +220,7 @@ class MixedStage(nn.Module):
         for b in range(nblocks):
             setattr(self, 'block%d' % (b + 1),
                     MixedOP(ics[b], ocs[b], ss[b], affs[b], acts[b], len(PRIMITIVES), mc_num_ddict['block%d' % (b + 1)],
-                            lat_lookup))
+                            lat_lookup, primitives=_cell_primitives(primitives, stage_name, 'block%d' % (b + 1))))
         self._initialize_betas()
 
     def blocks(self):
@@ -214,7 +257,7 @@ SECOND_PATH_ON_SIDE_STREAM = True       # the 'random' forward of a bi-sampling 
 
 
 class Network(nn.Module):
-    def __init__(self, num_classes, mc_num_dddict, lat_lookup):
+    def __init__(self, num_classes, mc_num_dddict, lat_lookup, primitives=None):
         super().__init__()
         self.lat_lookup = lat_lookup
         self.mc_num_dddict = mc_num_dddict
@@ -232,7 +275,8 @@ class Network(nn.Module):
         self._stage_names = [c[0] for c in cfg]
         for name, ics, ocs, ss, act, st in cfg:
             setattr(self, name, MixedStage(ics=ics, ocs=ocs, ss=ss, affs=[False] * len(ics), acts=[act] * len(ics),
-                                           mc_num_ddict=mc_num_dddict[name], lat_lookup=lat_lookup, stage_type=st))
+                                           mc_num_ddict=mc_num_dddict[name], lat_lookup=lat_lookup, stage_type=st,
+                                           primitives=primitives, stage_name=name))
         self.feature_mix_layer = ConvLayer(320, 1280, kernel_size=1, stride=1, affine=False, act_func='swish')
         self.global_avg_pooling = nn.AdaptiveAvgPool2d(1)
         self.classifier = LinearLayer(1280, num_classes)
@@ -437,6 +481,8 @@ class Network(nn.Module):
         from . import search
         if not (MODULE_PATHS and search.USE_PATHS and x.is_cuda):
             return False
+        if not self.plain_candidates():               # (the path level runs plain candidates only)
+            return False
         p = self.first_stem.conv.weight
         return p.is_cuda and p.is_leaf and p.device == x.device
 
@@ -574,6 +620,13 @@ class Network(nn.Module):
         x = self._head(x)                      # feature_mix_layer + global_avg_pooling (HIP), [N, 1280]
         x = self.classifier(x)
         return x, out_lat
+
+    def plain_candidates(self):
+        """Every candidate of every cell is a plain MBConv block (what the path level and the epoch boundary are built for)."""
+        hit = self.__dict__.get('_plain')
+        if hit is None:
+            hit = self.__dict__['_plain'] = all(op.kind is _lib.MBCONV for c in self.cells() for op in c.m_ops)
+        return hit
 
     def set_temperature(self, T):
         for m in self.modules():

@@ -79,8 +79,10 @@ class SearchState:
         self._op_params = {}
         self._shared = None
         self._graded = []                  # parameters whose .grad was pointed into the arena by the last w-step
+        # (the path level, its weight arena and the fused optimizer tails are built for plain candidates: a network with an
+        #  expand-free or Fused-MBConv candidate -- model_search.Network(primitives=...) -- takes the per-cell route in every step)
         if USE_PATHS and hasattr(model, 'cells') and self.weights and self.weights[0].is_cuda \
-                and hasattr(model, 'arch_weights'):
+                and hasattr(model, 'arch_weights') and getattr(model, 'plain_candidates', lambda: True)():
             self.build_paths()
 
     def build_paths(self):

@@ -1,6 +1,6 @@
 // Host-side check of the library's block-kind handling, made to run under a sanitizer on a machine WITHOUT a GPU: it plans and
-// sizes a descriptor of each kind (plain MBConv, TFNAS_CELL_NOEXPAND, TFNAS_CELL_FUSED) and walks the refusal paths of the four
-// cell entry points and the five head entry points -- NULL arguments and descriptors changed after their plan -- every one of
+// sizes a descriptor of each kind (plain MBConv, TFNAS_CELL_NOEXPAND, TFNAS_CELL_FUSED) and a cell whose groups differ in kind
+// (TFNAS_CELL_KINDS), and walks the refusal paths of the four cell entry points and the five head entry points -- NULL arguments and descriptors changed after their plan -- every one of
 // which returns before anything is launched.  The buffers handed in are never touched (a few host floats stand for them).
 //
 // Build the library's objects with the sanitizer on the host side, this file with it, and link them into one program, e.g.
@@ -151,9 +151,83 @@ static void heads() {
     EXPECT(tfnas_head_wgrad(&h, F, F, nullptr, F, F, nullptr), TFNAS_ENULL);
 }
 
+// TFNAS_CELL_KINDS: a kind per group.  A three-group cell (plain 40, expand-free, Fused-MBConv 22) plans and sizes; every rule of
+// the bit is refused by the plan and again by the entry points, before anything is launched.
+static void mixed() {
+    TfnasBnAffine bn;
+    memset(&bn, 0, sizeof(bn));
+    TfnasCellDesc d = cell(TFNAS_CELL_KINDS, 40);
+    d.G = 3;
+    d.g[1].mc = 16, d.g[1].k = 5, d.g[1].se = 0, d.g[1].kind = TFNAS_GROUP_NOEXPAND;
+    d.g[2].mc = 22, d.g[2].k = 3, d.g[2].se = 8, d.g[2].kind = TFNAS_GROUP_FUSED;
+    TfnasCellWs ws, ws0;
+    EXPECT(tfnas_cell_plan(&d), 0);
+    EXPECT(tfnas_cell_ws(&d, &ws), 0);
+    EXPECT((int)(ws.E == (uint64_t)2 * 9 * 13 * d.M), 1);
+    EXPECT(tfnas_efree_supported(&d), 0);
+    EXPECT(tfnas_fx_supported(&d), 0);
+    EXPECT(tfnas_cell_route(&d), TFNAS_ROUTE_TAKEN_VALID);
+    // a plain group needs E; weight gradients wanted, no gradient pointer bound
+    EXPECT(fwd(&d, nullptr), TFNAS_ENULL);
+    EXPECT(bwd(&d, nullptr), TFNAS_ENULL);
+    d.need_wgrad = 1;
+    EXPECT(bwd(&d, F), TFNAS_ENULL);
+    d.need_wgrad = 0;
+    // the affine entry points refuse the bit (and more than one group)
+    EXPECT(afwd(&d, &bn, F), TFNAS_EINVAL);
+    EXPECT(abwd(&d, &bn, F), TFNAS_EINVAL);
+    TfnasCellDesc c = cell(TFNAS_CELL_KINDS, 40);       // (one plain group: plans like the unflagged cell, still not for them)
+    EXPECT(tfnas_cell_plan(&c), 0);
+    EXPECT(afwd(&c, &bn, F), TFNAS_EINVAL);
+    EXPECT(abwd(&c, &bn, F), TFNAS_EINVAL);
+    // no plain group: no E buffer, E may be NULL (the call is then refused for its next fault: a missing gradient pointer)
+    c = d;
+    c.g[0].mc = 16, c.g[0].kind = TFNAS_GROUP_NOEXPAND;
+    EXPECT(tfnas_cell_plan(&c), 0);
+    EXPECT(tfnas_cell_ws(&c, &ws0), 0);
+    EXPECT((int)(ws0.E == 0 && ws0.dxp == 4), 1);
+    c.need_wgrad = 1;
+    EXPECT(bwd(&c, nullptr), TFNAS_ENULL);
+    // the rules, at the plan and at the entry points
+    for (int variant = 0; variant < 9; ++variant) {
+        c = d;
+        switch (variant) {
+        case 0: c.flags |= TFNAS_CELL_NOEXPAND; break;                        // a one-block bit beside it
+        case 1: c.flags |= TFNAS_CELL_FUSED; break;
+        case 2: c.g[1].kind = 3; break;                                       // a kind outside 0..2
+        case 3: c.g[2].kind = -1; break;
+        case 4: c.g[1].mc = 24; break;                                        // NOEXPAND: mc != ic
+        case 5: c.g[1].w_expand = F; break;                                   // ... an expand pointer
+        case 6: c.g[2].k = 5; break;                                          // FUSED: k != 3
+        case 7: c.g[2].g_dw = F; break;                                       // ... a depthwise pointer
+        case 8: c.g[0].k = 7; break;                                          // 7 x 7 without TFNAS_CELL_K7, as ever
+        }
+        EXPECT(tfnas_cell_plan(&c), TFNAS_EINVAL);
+        EXPECT(fwd(&c, F), TFNAS_EINVAL);
+        EXPECT(bwd(&c, F), TFNAS_EINVAL);
+    }
+    c = d;
+    c.mode = TFNAS_MODE_STEM;
+    EXPECT(fwd(&c, F), TFNAS_EINVAL);
+    // without the bit the kind word is not read: the same words plan as three plain groups, and the one-block bits stay refused
+    c = d;
+    c.flags = 0;
+    EXPECT(tfnas_cell_plan(&c), 0);
+    c.flags = TFNAS_CELL_FUSED;
+    EXPECT(tfnas_cell_plan(&c), TFNAS_EINVAL);
+    c.flags = TFNAS_CELL_NOEXPAND;
+    EXPECT(fwd(&c, F), TFNAS_EINVAL);
+    // a head never carries the bit
+    TfnasCellDesc h = cell(TFNAS_CELL_KINDS, 1280, 3, 0);
+    h.H = h.W = 7, h.ic = 320, h.oc = 4, h.has_res = 0, h.act = TFNAS_ACT_SWISH, h.mode = TFNAS_MODE_HEAD;
+    EXPECT(tfnas_cell_plan(&h), TFNAS_EINVAL);
+    EXPECT(tfnas_head_fwd(&h, F, F, D, F, F, nullptr), TFNAS_EINVAL);
+}
+
 int main() {
     cells();
     heads();
+    mixed();
     if (g_bad) {
         fprintf(stderr, "kind_refusals: %d of %d checks FAILED\n", g_bad, g_checks);
         return 1;
