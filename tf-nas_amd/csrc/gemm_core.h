@@ -316,12 +316,15 @@ struct SlabNone {
 };
 // `slab(i, st)`: optional hook called by every wave after the stores of its slab i, while the slab (16 rows x BN, leading
 // dimension BN + 4) is still in LDS at `st`
+// `tid`: the thread index all staging indices derive from.  A kernel whose K loop has no register to spare hands in a copy it takes
+// afresh per tile (k_project_dgrad), so that these indices are recomputed per tile instead of living across the K loop
 template <int NT, class FEmit, class FSlab = SlabNone>
-__device__ __forceinline__ void emit_tile_rows(const f32x4 (&acc)[2][NT], float* lds, FEmit emit, FSlab slab = FSlab()) {
+__device__ __forceinline__ void emit_tile_rows(const f32x4 (&acc)[2][NT], float* lds, FEmit emit, FSlab slab = FSlab(),
+                                               int tid = threadIdx.x) {
     using T = GT<NT>;
     constexpr int LDC = T::BN + 4, Q = T::BN / 4;
     static_assert(4 * 16 * LDC <= T::LDS_FLOATS, "C staging does not fit the GEMM LDS buffer");
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+    const int lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
     float* st = lds + w * 16 * LDC;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {

@@ -326,43 +326,75 @@ __device__ __forceinline__ f32x4 bn3_fold_dp(const f32x4* tab, int o, f32x4 dout
 // A wave's 32 rows touch at most two images (HW >= 43), a 128-row tile at most four: one record per (row tile, image slot)
 //   rec[((rt * 4 + slot) * 5 + q) * M + channel],  slot = image - image_of(rt * 128),  q = A1 | B1 | dgate | A2 | B2
 // each written by exactly one workgroup (no atomics, fixed summation order); k_bn2_gather sums an image's records.
-template <int NT, int ACT>
-__device__ __forceinline__ void fold_slab(const float* st, int LDC, const float* __restrict__ Dcol, int M, int p0, int Po, int bnd,
-                                          const float2 (&c2)[(16 * NT + 63) / 64], const bool (&cok)[(16 * NT + 63) / 64],
-                                          bool has_se, float (&sum)[2][FOLD_Q][(16 * NT + 63) / 64]) {
-    constexpr int NC = (16 * NT + 63) / 64;
-    const int lane = threadIdx.x & 63;
+//
+// Everything about the rows is wave-uniform and kept in scalar registers: a wave's 32 rows are numbered R = 0..31, rows [0, S) belong
+// to its first image, rows [S, E) to its second, rows from E on lie past the end of the tensor (S = 32: no boundary, E = 32: all
+// valid).  Rows ascend, so every addend of the first image comes before every addend of the second: ONE running set of sums per
+// lane is enough -- at row S it is parked in `done` and restarts from zero (fold_split).  The rows are evaluated four at a time in
+// straight-line code (the exp/rcp latency of one row overlaps the arithmetic of its neighbours); a group of four rows that holds
+// neither row S nor the end E -- all but at most two of a wave's eight -- is added without any per-row test.
+//
+// The sums are summed in exactly this order and from exactly these roundings (the records feed BatchNorm backward of the whole
+// chain: a last-bit change here is visible after 25 training pairs): every addend is a ROUNDED product -- fold_rn keeps the
+// compiler, which contracts a * b + c wherever it sees one, from fusing it into the accumulation.
+__device__ __forceinline__ float fold_rn(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+constexpr int fold_nc(int nt) { return (16 * nt + 63) / 64; }          // columns of the tile per lane
+template <int NC>
+__device__ __forceinline__ void fold_split(float (&cur)[FOLD_Q][NC], float (&done)[FOLD_Q][NC], int c) {
+#pragma unroll
+    for (int q = 0; q < FOLD_Q; ++q) {
+        done[q][c] = cur[q][c];
+        cur[q][c] = 0.f;
+    }
+}
+// slab of 16 rows x BN at `st` (leading dimension LDC) = wave rows [R0, R0 + 16), tensor rows from p0 (all wave-uniform)
+template <int NT, int ACT, bool SE>
+__device__ __forceinline__ void fold_slab(const float* st, int LDC, const float* __restrict__ Dcol, int M, int lane, int p0, int Po,
+                                          int R0, int S, int E, const float2 (&c2)[fold_nc(NT)], const bool (&cok)[fold_nc(NT)],
+                                          float (&cur)[FOLD_Q][fold_nc(NT)], float (&done)[FOLD_Q][fold_nc(NT)]) {
+    constexpr int NC = fold_nc(NT);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         if (!cok[c]) continue;
         const int col = lane + 64 * c;
-        float dv[16];
+        float dv[16], zv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) dv[r] = __builtin_nontemporal_load(Dcol + (size_t)min(p0 + r, Po - 1) * M + col);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int p = p0 + r;
-            if (p >= Po) break;                                     // (wave-uniform)
-            const float z = st[r * LDC + col];
-            const float dh = (dv[r] - c2[c].x) * c2[c].y;
-            const float ad = act_d<ACT>(dh), zd = z * ad;
-            const float v2 = has_se ? z * act_f<ACT>(dh) : 0.f;
-            if (p >= bnd) {                                         // (wave-uniform: the row belongs to the wave's second image)
-                sum[1][0][c] += zd;
-                sum[1][1][c] += zd * dh;
-                if (has_se) {
-                    sum[1][2][c] += v2;
-                    sum[1][3][c] += ad;
-                    sum[1][4][c] += ad * dh;
+        for (int r = 0; r < 16; ++r) zv[r] = st[r * LDC + col];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float a[4][FOLD_Q];                                     // the addends of rows 4k .. 4k+3 (rows from E on: never added)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float z = zv[4 * k + j];
+                const float dh = (dv[4 * k + j] - c2[c].x) * c2[c].y;
+                const float ad = fold_rn(act_d<ACT>(dh)), zd = fold_rn(z * ad);
+                a[j][0] = zd;
+                a[j][1] = fold_rn(zd * dh);
+                if (SE) {
+                    a[j][2] = fold_rn(z * act_f<ACT>(dh));
+                    a[j][3] = ad;
+                    a[j][4] = fold_rn(ad * dh);
+                }
+            }
+            auto add = [&](int j) {
+#pragma unroll
+                for (int q = 0; q < (SE ? FOLD_Q : 2); ++q) cur[q][c] += a[j][q];
+            };
+            const int lo = R0 + 4 * k;
+            if (__builtin_expect((S >= lo && S < lo + 4) || E < lo + 4, 0)) {      // the image boundary or the tensor's end is here
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (lo + j == S) fold_split<NC>(cur, done, c);
+                    if (lo + j < E) add(j);
                 }
             } else {
-                sum[0][0][c] += zd;
-                sum[0][1][c] += zd * dh;
-                if (has_se) {
-                    sum[0][2][c] += v2;
-                    sum[0][3][c] += ad;
-                    sum[0][4][c] += ad * dh;
-                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) add(j);
             }
         }
     }
@@ -455,60 +487,81 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_project_dgrad(TfnasCel
         };
         PreNone pre;
         gemm_adirect<NT, false, MM>(pre, la, xa, lb, xb, nchunks, acc, lds);
+        // The thread index is taken afresh for the epilogue of every tile: what is derived from it would otherwise be hoisted out of
+        // the row-tile loop and stay live across the K loop, which has no register to spare
+        int te = tid;
+        asm volatile("" : "+v"(te));
         if (!FOLD) {
             emit_tile_rows<NT>(acc, lds, [&](int lrow, int lc, f32x4 v) {
                 const int p = rt * 128 + lrow;
                 if (p < Po && n0 + lc < mcp) st4_nt(dZ + ((size_t)p * M + off + n0 + lc), v);
-            });
+            }, SlabNone(), te);
         } else {
             constexpr int LDC = T::BN + 4;
-            const int w = tid >> 6, lane = tid & 63;
+            // the wave's rows, image boundary and valid end as scalars (see fold_slab)
+            const int w = __builtin_amdgcn_readfirstlane(te >> 6), lane = te & 63;
             const int pw0 = rt * 128 + w * 32;
-            const int imgA = min(pw0, Po - 1) / HW, bnd = (imgA + 1) * HW;
-            float sum[2][FOLD_Q][NC];
+            const int imgA = min(pw0, Po - 1) / HW;
+            const int S = min(max((imgA + 1) * HW - pw0, 0), 32), E = min(max(Po - pw0, 0), 32);
+            float cur[FOLD_Q][NC], done[FOLD_Q][NC];
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
+            for (int q = 0; q < FOLD_Q; ++q)
 #pragma unroll
-                for (int q = 0; q < FOLD_Q; ++q)
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) sum[a][q][c] = 0.f;
+                for (int c = 0; c < NC; ++c) cur[q][c] = done[q][c] = 0.f;
             const float* Dcol = D + off + n0;
+            // activation (Swish or ReLU: launch_project_dgrad refuses every other one for this variant) and SE form: one scalar
+            // choice per slab
+            const int form = (d.act == TFNAS_ACT_RELU ? 2 : 0) + (has_se ? 1 : 0);
             emit_tile_rows<NT>(acc, lds,
                                [&](int lrow, int lc, f32x4 v) {
                                    const int p = rt * 128 + lrow;
                                    if (p < Po && n0 + lc < mcp) st4_nt(dZ + ((size_t)p * M + off + n0 + lc), v);
                                },
                                [&](int i, const float* st) {        // the wave's slab i (16 rows x BN) is still in LDS
-                                   if (d.act == TFNAS_ACT_RELU)
-                                       fold_slab<NT, TFNAS_ACT_RELU>(st, LDC, Dcol, M, pw0 + 16 * i, Po, bnd, c2f, cokf, has_se, sum);
-                                   else      // Swish: launch_project_dgrad refuses every other activation for this variant
-                                       fold_slab<NT, TFNAS_ACT_SWISH>(st, LDC, Dcol, M, pw0 + 16 * i, Po, bnd, c2f, cokf, has_se, sum);
-                               });
+                                   const int p0 = pw0 + 16 * i;
+                                   if (form == 0) fold_slab<NT, TFNAS_ACT_SWISH, false>(st, LDC, Dcol, M, lane, p0, Po, 16 * i, S, E, c2f, cokf, cur, done);
+                                   else if (form == 1) fold_slab<NT, TFNAS_ACT_SWISH, true>(st, LDC, Dcol, M, lane, p0, Po, 16 * i, S, E, c2f, cokf, cur, done);
+                                   else if (form == 2) fold_slab<NT, TFNAS_ACT_RELU, false>(st, LDC, Dcol, M, lane, p0, Po, 16 * i, S, E, c2f, cokf, cur, done);
+                                   else fold_slab<NT, TFNAS_ACT_RELU, true>(st, LDC, Dcol, M, lane, p0, Po, 16 * i, S, E, c2f, cokf, cur, done);
+                               }, te);
             // waves -> image slots of the tile, in wave order (emit_tile_rows ended with a barrier: the GEMM LDS is free)
             static_assert(4 * 2 * FOLD_Q * T::BN + 4 <= T::LDS_FLOATS, "fold staging does not fit the GEMM LDS buffer");
             float* comb = lds;                                      // [4 waves][2 segments][5][BN]
             int* meta = reinterpret_cast<int*>(lds + 4 * 2 * FOLD_Q * T::BN);
+            const bool split = S < 32;                              // the running sums are the second image's: the first's are parked
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
+            for (int q = 0; q < FOLD_Q; ++q)
 #pragma unroll
-                for (int q = 0; q < FOLD_Q; ++q)
-#pragma unroll
-                    for (int c = 0; c < NC; ++c)
-                        if (lane + 64 * c < T::BN) comb[((w * 2 + a) * FOLD_Q + q) * T::BN + lane + 64 * c] = sum[a][q][c];
+                for (int c = 0; c < NC; ++c)
+                    if (lane + 64 * c < T::BN) {
+                        comb[((w * 2 + 0) * FOLD_Q + q) * T::BN + lane + 64 * c] = split ? done[q][c] : cur[q][c];
+                        comb[((w * 2 + 1) * FOLD_Q + q) * T::BN + lane + 64 * c] = split ? cur[q][c] : 0.f;
+                    }
             if (lane == 0) meta[w] = imgA;
             __syncthreads();
+            // one thread per (q, column): it walks the eight (wave, segment) entries once, in the order wave 0..3, segment 0, 1, and
+            // adds each to the slot of its image (a scalar per entry) -- the records' summation order
             const int img0 = min(rt * 128, Po - 1) / HW, imgL = min(rt * 128 + 127, Po - 1) / HW;
+            int slot[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) slot[e] = __builtin_amdgcn_readfirstlane(meta[e >> 1]) + (e & 1) - img0;
             const int nq = has_se ? FOLD_Q : 2;
-            for (int o = tid; o < FOLD_SLOTS * FOLD_Q * T::BN; o += 256) {
-                const int sl = o / (FOLD_Q * T::BN), q = (o / T::BN) % FOLD_Q, col = o % T::BN;
-                if (img0 + sl > imgL || q >= nq || n0 + col >= mcp) continue;
-                float t = 0.f;
+            for (int o = te; o < nq * T::BN; o += 256) {
+                const int q = o / T::BN, col = o - q * T::BN;
+                if (n0 + col >= mcp) continue;
+                float t[FOLD_SLOTS];
 #pragma unroll
-                for (int ww = 0; ww < 4; ++ww)
+                for (int sl = 0; sl < FOLD_SLOTS; ++sl) t[sl] = 0.f;
 #pragma unroll
-                    for (int a = 0; a < 2; ++a)
-                        if (meta[ww] + a - img0 == sl) t += comb[((ww * 2 + a) * FOLD_Q + q) * T::BN + col];
-                rec[(((size_t)rt * FOLD_SLOTS + sl) * FOLD_Q + q) * M + off + n0 + col] = t;
+                for (int e = 0; e < 8; ++e) {
+                    const float v = comb[(e * FOLD_Q + q) * T::BN + col];
+#pragma unroll
+                    for (int sl = 0; sl < FOLD_SLOTS; ++sl)
+                        if (slot[e] == sl) t[sl] += v;
+                }
+#pragma unroll
+                for (int sl = 0; sl < FOLD_SLOTS; ++sl)
+                    if (img0 + sl <= imgL) rec[(((size_t)rt * FOLD_SLOTS + sl) * FOLD_Q + q) * M + off + n0 + col] = t[sl];
             }
             __syncthreads();
         }
