@@ -66,7 +66,9 @@ extern "C" {
                                3x3 stride-2 pad-1 convolution of the 3-channel NCHW image (x = image, ic = 27 =
                                im2col depth, w_expand = first_stem.conv.weight [32][3*3*3]); G = 1, no dx           */
 #define TFNAS_MODE_HEAD 2   /* feature_mix_layer + global average pool (model_search.py:299-300): E = x W^T,
-                               pooled = mean_hw act(BN(E)); only tfnas_head_fwd/bwd accept it                      */
+                               pooled = mean_hw act(BN(E)); only tfnas_head_fwd/bwd accept it.  g[0].mc must be a
+                               multiple of 4 (else TFNAS_EINVAL from tfnas_cell_plan and every head entry point): the
+                               [N][mc] rows of pooled / dpooled move in quads                                       */
 
 #define TFNAS_ACT_RELU 0
 #define TFNAS_ACT_SWISH 1
@@ -407,7 +409,12 @@ int tfnas_mixedop_bwd(const TfnasCellDesc *d, const float *x, const float *wmix,
  * tools/utils.py:77-86 (drop_connect), trained by train_eval.py.  Same kernels as the search cells (G must be 1); the affine
  * transform is folded into the per-channel statistics tables (csrc/bn_affine.hip).
  * BatchNorm site i: 0 = after the 1x1 expand (stem mode: after the 3x3 image conv; head: after the 1x1 feature-mix conv),
- * 1 = after the depthwise conv, 2 = after the 1x1 project.  Channels: mc, mc, oc. */
+ * 1 = after the depthwise conv, 2 = after the 1x1 project.  Channels: mc, mc, oc.
+ * gamma == 0 cannot be represented by the fold (|gamma| is clamped to 1e-12, csrc/bn_affine.hip), and the fold is CONDITIONED by
+ * |beta / gamma|: consumers subtract m_eff = mu - beta / r_eff in fp32, and the backward forms gamma * sum(d * xhat) as
+ * S2y - beta * S1, so results lose about log2 |beta / gamma| bits of fp32 precision by construction.  The tests hold the path to
+ * 2e-5 + 1e-4 * max|ref| against float64 for |beta / gamma| <= 10 (tests/test_gpu_affine_f64.py); beyond that the error grows
+ * in proportion. */
 typedef struct TfnasBnAffine {
     const float *weight[3], *bias[3];          /* gamma / beta (device); NULL = that site has no affine part          */
     float *g_weight[3], *g_bias[3];            /* their gradients, written by the backward when non-NULL               */
@@ -440,7 +447,9 @@ int tfnas_head_affine_bwd(const TfnasCellDesc *d, const TfnasBnAffine *bn, const
 
 /* Network head (mode TFNAS_MODE_HEAD): pooled[N][mc] = mean over pixels of act(BN(x W_expand^T)).
  * Replaces feature_mix_layer (ConvLayer 1x1 + BN + swish) + AdaptiveAvgPool2d(1), models/model_search.py:299-300.
- * Buffers: E [N*H*W][M], stats doubles [M][2], part = scratch (ws.part floats). */
+ * Buffers: E [N*H*W][M], stats doubles [M][2], part = scratch (ws.part floats).
+ * g[0].mc must be a multiple of 4 (TFNAS_EINVAL otherwise, here and in every other head entry point): the kernels load and store
+ * the [N][mc] rows of pooled / dpooled 16 bytes at a time, and tfnas_cls_ce asks the same of its C. */
 int tfnas_head_fwd(const TfnasCellDesc *d, const float *x, float *E, double *stats, float *part, float *pooled,
                    void *stream);
 /* Backward of tfnas_head_fwd: dx [N*H*W][ic] and (need_wgrad) g_expand.  dEh [N*H*W][M], cb1 [M][4] floats and
@@ -451,7 +460,8 @@ int tfnas_head_bwd(const TfnasCellDesc *d, const float *x, const float *E, const
 /* The head's weight gradient alone (what tfnas_head_bwd does last when need_wgrad is set): g_expand of the group from dEh / E / cb1
  * as tfnas_head_bwd left them.  A leaf of the backward: the weight step calls tfnas_head_bwd with need_wgrad = 0 on a path's stream
  * and this on that path's weight-gradient stream, so that the cells' backward does not queue up behind it.  part: scratch of its
- * own (tfnas_cell_ws().part floats). */
+ * own (tfnas_cell_ws().part floats).  The two forms are bit-identical: dx of tfnas_head_bwd does not depend on need_wgrad, and
+ * g_expand of this call is what the one-call form stores. */
 int tfnas_head_wgrad(const TfnasCellDesc *d, const float *x, const float *E, const float *dEh, const float *cb1, float *part,
                      void *stream);
 

@@ -243,3 +243,35 @@ def test_modules_accept_the_reference_spellings(lib):
     assert net.config == cfg
     acts = [b.act_func for st in net._stages() for b in st]
     assert acts == [_acts.NEW_ACTS[i % 2] for i in range(len(acts))] and net.feature_mix_layer.act_func == 'h-swish'
+
+
+def test_ragged_head_widths_are_refused(lib):
+    """TFNAS_MODE_HEAD moves the [N][mc] rows of pooled / dpooled in quads (k_head_pool, k_head_bwd): a width that is no multiple
+    of 4 would store over the next image's row and past the buffer, so the plan and every head entry point refuse it (the entry
+    points before any pointer is looked at -- nothing is launched here).  Cell and stem descriptors plan exactly as before."""
+    from tfnas_amd import _lib
+    head = lambda mc: _desc(SWISH, False, N=2, H=7, W=7, ic=320, oc=4, mids=(mc,), ks=(3,), ses=(0,), mode=_lib.MODE_HEAD)  # noqa: E731
+    one = C.c_void_p(16)
+    bn = _lib.TfnasBnAffine()
+    for mc in (1281, 1282, 1283):
+        assert lib.tfnas_cell_plan(C.byref(head(mc))) == EINVAL, mc
+        h = head(1280)
+        assert lib.tfnas_cell_plan(C.byref(h)) == 0
+        h.g[0].mc = mc                                # (changed after the plan: the entry points refuse)
+        assert lib.tfnas_head_fwd(C.byref(h), one, one, one, one, one, None) == EINVAL
+        assert lib.tfnas_head_bwd(C.byref(h), one, one, one, one, one, one, one, one, one, one, None) == EINVAL
+        assert lib.tfnas_head_wgrad(C.byref(h), one, one, one, one, one, None) == EINVAL
+        assert lib.tfnas_head_affine_fwd(C.byref(h), C.byref(bn), one, one, one, one, one, None) == EINVAL
+        assert lib.tfnas_head_affine_bwd(C.byref(h), C.byref(bn), one, one, one, one, one, one, one, one, one, one, None) == EINVAL
+    for mc in (1280, 1284, 192, 4):
+        h = head(mc)
+        assert lib.tfnas_cell_plan(C.byref(h)) == 0, mc
+        assert h.g[0].mcp == mc and h.M >= mc
+    # ragged mid widths stay legal everywhere else: a cell (one group, several groups) and the stem plan as they always did
+    for mids, ks, ses in (((1281,), (3,), (0,)), ((53, 131), (3, 5), (0, 24))):
+        d = _desc(SWISH, False, mids=mids, ks=ks, ses=ses)
+        assert lib.tfnas_cell_plan(C.byref(d)) == 0
+        assert [d.g[g].mcp for g in range(len(mids))] == [(m + 3) & ~3 for m in mids]
+    stem = _desc(RELU, False, N=2, H=0, W=0, ic=27, oc=16, mids=(32,), ks=(3,), ses=(8,), mode=_lib.MODE_STEM)
+    stem.Hi = stem.Wi = 32
+    assert lib.tfnas_cell_plan(C.byref(stem)) == 0 and (stem.H, stem.W, stem.g[0].mcp) == (16, 16, 32)

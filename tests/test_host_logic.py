@@ -190,3 +190,50 @@ def test_bench_byte_model_splits_into_step_kinds():
         assert samp[2] > 0
         assert (soft[2] == 0) == (fam == 'k_dw_wgrad')
     assert bench.family_algorithmic('no_such_family', 128) is None
+
+
+def _bns(*moms, track=True):
+    return [None if m == 'absent' else torch.nn.BatchNorm2d(8, momentum=m, track_running_stats=track) for m in moms]
+
+
+def test_bn_struct_carries_the_modules_settings_or_refuses():
+    """functions._bn_struct (TfnasBnAffine of a block's BatchNorms; only data_ptr is needed): ONE momentum -- that of the modules,
+    not torch's default; modules that differ in it, and momentum=None (cumulative average), are refused instead of silently run with
+    another value; track_running_stats=False gives the NULL running pointers the ABI documents ("no update")."""
+    from tfnas_amd.functions import _bn_struct
+    bns = _bns(0.01, 0.01, 0.01)
+    a = _bn_struct(bns, True)
+    assert abs(a.momentum - 0.01) < 1e-9 and a.eval == 0
+    for i, bn in enumerate(bns):
+        assert a.weight[i] == bn.weight.data_ptr() and a.bias[i] == bn.bias.data_ptr()
+        assert a.running_mean[i] == bn.running_mean.data_ptr() and a.running_var[i] == bn.running_var.data_ptr()
+        assert not a.g_weight[i] and not a.g_bias[i]
+    assert _bn_struct(bns, False).eval == 1
+    # a site that does not exist stays NULL and does not take part; gradients go to the modules that are there, in order
+    bns = _bns('absent', 0.2, 0.2)
+    grads = [torch.zeros(8) for _ in range(4)]
+    a = _bn_struct(bns, True, grads)
+    assert abs(a.momentum - 0.2) < 1e-7
+    assert not a.weight[0] and not a.running_mean[0] and not a.g_weight[0]
+    assert (a.g_weight[1], a.g_bias[1], a.g_weight[2], a.g_bias[2]) == tuple(g.data_ptr() for g in grads)
+    with pytest.raises(ValueError, match='momentum'):
+        _bn_struct(_bns(0.1, 0.1, 0.01), True)
+    with pytest.raises(ValueError, match='momentum'):
+        _bn_struct(_bns(0.1, None, 0.1), True)
+    with pytest.raises(ValueError, match='momentum'):
+        _bn_struct(_bns(None), True)
+
+
+def test_bn_struct_without_running_statistics():
+    from tfnas_amd.functions import _bn_struct
+    bns = _bns(0.1, 0.1, 0.1, track=False)
+    assert all(bn.running_mean is None and bn.num_batches_tracked is None for bn in bns)
+    a = _bn_struct(bns, True)
+    for i, bn in enumerate(bns):
+        assert a.weight[i] == bn.weight.data_ptr() and not a.running_mean[i] and not a.running_var[i]
+    # torch normalises such a module with the batch statistics in eval mode too: never the "mean 0 / var 1" of NULL pointers
+    assert _bn_struct(bns, False).eval == 0
+    mixed = _bns(0.1, 0.1) + _bns(0.1, track=False)
+    assert _bn_struct(mixed, True).eval == 0
+    with pytest.raises(ValueError, match='running'):
+        _bn_struct(mixed, False)

@@ -13,6 +13,8 @@
 //             -> k_bn_bwd_fix rewrites the reduced (S1, S2y) table as P*(t1 - beta*c, c) and emits
 //                d gamma = (S2y - beta*S1)/gamma,  d beta = S1.
 // gamma == 0 cannot be represented (y would be the constant beta); the fix kernels clamp |gamma| to 1e-12.
+// Conditioning: m_eff = mu - beta/r_eff is subtracted in fp32 by the consumers and gamma * sum d*xhat is formed as S2y - beta*S1,
+// so about log2|beta/gamma| bits are lost by construction; the suite holds |beta/gamma| <= 10 to the cell gate (tfnas_hip.h).
 #include "tfnas_dev.h"
 #include "kernels.h"
 #include "prof.h"

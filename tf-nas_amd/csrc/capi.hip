@@ -262,6 +262,9 @@ extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
         return TFNAS_EINVAL;
     }
     if (d->mode == TFNAS_MODE_HEAD && d->G != 1) return TFNAS_EINVAL;
+    // the head's pooled / dpooled rows are [N][mc], moved in quads (k_head_pool, k_head_bwd): a ragged width would store over the
+    // next image's row and past the buffer; every consumer of pooled needs a multiple of 4 anyway (tfnas_cls_ce)
+    if (d->mode == TFNAS_MODE_HEAD && (d->g[0].mc & 3)) return TFNAS_EINVAL;
     if (d->stor != 0) return TFNAS_EINVAL;     // fp32 storage only (the bf16-storage build of rounds 1-3 was removed: tfnas_hip.h)
     if (d->N < 1 || d->H < 1 || d->W < 1 || d->oc < 4 || (d->oc & 3)) return TFNAS_EINVAL;
     if (d->oc > 1024) return TFNAS_EINVAL;
@@ -858,6 +861,7 @@ static int head_bwd_impl(const TfnasCellDesc& d0, const TfnasBnAffine* bn, const
 // what every head entry point asks of its descriptor
 static int check_head(const TfnasCellDesc* dp) {
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
+    if (dp->g[0].mc & 3) return TFNAS_EINVAL;      // (pooled / dpooled rows move in quads: tfnas_cell_plan refuses it too)
     TRY(check_act(dp));
     return check_kind(dp);
 }

@@ -1551,7 +1551,9 @@ GemmPlan gemm_plan_expand_dgrad(const TfnasCellDesc& d, bool split, int nsl) {
         // one-candidate launches of the weight step run beside three other queues: the chip is full anyway, and every extra split is
         // one more [P][ic] partial written, read back and summed (k_dx_reduce).  Capped at 2 (round 6, four alternating bench pairs on
         // one box: w-step 16.55 -> 16.37 ms; a cap of 1 loses: the 196-tile launches of the 14 x 14 cells then walk 40+ K-chunks each)
-        if (d.need_wgrad && d.G == 1 && ns > TFNAS_WSPLIT_DGRAD) ns = TFNAS_WSPLIT_DGRAD;
+        // (cells only: the head's weight gradient is a leaf that may run in a call of its own -- tfnas_head_wgrad after
+        //  tfnas_head_bwd with need_wgrad = 0, as the weight step does -- and dx must not depend on which form the caller chose)
+        if (d.need_wgrad && d.G == 1 && d.mode != TFNAS_MODE_HEAD && ns > TFNAS_WSPLIT_DGRAD) ns = TFNAS_WSPLIT_DGRAD;
         p.splits = ns < 1 ? 1 : ns;
     }
     p.grid = dim3(row_blocks(P, p.tiles * p.splits, 1u << 30, gemm_slots(p.nt, p.mm), 4096), p.tiles, p.splits);

@@ -564,21 +564,33 @@ def _part(floats, dev):
 
 def _bn_struct(bns, training, grads=None):
     """TfnasBnAffine for up to three nn.BatchNorm2d modules (None entries: site without affine, or a site that does not exist --
-    site 0 of a block without expand convolution); ``grads``: (d gamma, d beta) of the modules that are there, in order."""
+    site 0 of a block without expand convolution); ``grads``: (d gamma, d beta) of the modules that are there, in order.
+    The struct has ONE momentum: modules that differ in it, and ``momentum=None`` (torch's cumulative average, which the kernels
+    do not compute), are a ValueError.  ``track_running_stats=False``: NULL running pointers (batch statistics, no update)."""
     a = _lib.TfnasBnAffine()
-    mom = 0.1
+    moms = set()
     k = 0
     for i, bn in enumerate(bns):
         if bn is None:
             continue
         a.weight[i], a.bias[i] = bn.weight.data_ptr(), bn.bias.data_ptr()
-        a.running_mean[i], a.running_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+        if bn.running_mean is not None and bn.running_var is not None:
+            a.running_mean[i], a.running_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
         if grads is not None:
             a.g_weight[i], a.g_bias[i] = grads[2 * k].data_ptr(), grads[2 * k + 1].data_ptr()
         k += 1
-        mom = 0.1 if bn.momentum is None else bn.momentum
-    a.momentum = mom
-    a.eval = int(not training)
+        if bn.momentum is None:
+            raise ValueError('tfnas_amd: BatchNorm momentum=None (cumulative moving average) is not supported by the HIP path')
+        moms.add(float(bn.momentum))
+    if len(moms) > 1:
+        raise ValueError('tfnas_amd: the BatchNorms of one block must share one momentum (got %s)' % sorted(moms))
+    a.momentum = moms.pop() if moms else 0.1
+    # eval mode reads the running statistics; modules without them normalise with the batch statistics in eval mode too (torch:
+    # bn_training = training or no running statistics) -- the struct has one `eval` for all sites
+    tracked = [bn.running_mean is not None and bn.running_var is not None for bn in bns if bn is not None]
+    if not training and any(tracked) and not all(tracked):
+        raise ValueError('tfnas_amd: in eval mode the BatchNorms of one block must all track running statistics, or none')
+    a.eval = int(not training and all(tracked))
     return a
 
 
