@@ -318,7 +318,29 @@ struct SlabNone {
 // dimension BN + 4) is still in LDS at `st`
 // `tid`: the thread index all staging indices derive from.  A kernel whose K loop has no register to spare hands in a copy it takes
 // afresh per tile (k_project_dgrad), so that these indices are recomputed per tile instead of living across the K loop
-template <int NT, class FEmit, class FSlab = SlabNone>
+//
+// Ordering (BLOCK_SYNC = false).  The staging area of wave w (st = lds + w * 16 * LDC) is written and read by wave w alone, so between
+// a slab's stores, its reads (the slab hook's included) and the next slab's stores only the order WITHIN the wave matters:
+// wave_lds_order().  What the whole workgroup has to agree on is the aliasing of the staging area with the K loop's operand buffers:
+//   entry: no wave may stage before every wave has read its last B fragment -- every K loop of gemm_core.h / gemm_x3.h ends with a
+//          __syncthreads() (nchunks == 0: the one behind the prologue), and emit_tile_rows must be called straight after the loop,
+//          with no LDS access of the caller's in between;
+//   exit:  the __syncthreads() below -- the next tile's first operand stores, flush_colstats and the record combine of the FOLD
+//          epilogue all write `lds` again.
+// BLOCK_SYNC = true (the default) keeps a workgroup barrier in front of and behind every slab's stores, five per tile: the kernels
+// that measured no faster with wave-level ordering and the ones the benchmark does not launch keep it.
+//
+// A wave's LDS instructions execute in the order they were issued (one in-order queue per wave) and all lanes of a wave issue an
+// instruction together, so a ds_read issued after a ds_write sees what ANY lane of the wave wrote: no wait and no hardware barrier
+// is needed.  What is needed is that the compiler keeps that order -- it reasons about one lane and may move a load above a store to
+// an address it proves different for that lane.  The release / acquire fence pair at wavefront scope forbids exactly that (and
+// emits no instruction); wave_barrier keeps the scheduler from moving anything across the point.
+__device__ __forceinline__ void wave_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <int NT, bool BLOCK_SYNC = true, class FEmit, class FSlab = SlabNone>
 __device__ __forceinline__ void emit_tile_rows(const f32x4 (&acc)[2][NT], float* lds, FEmit emit, FSlab slab = FSlab(),
                                                int tid = threadIdx.x) {
     using T = GT<NT>;
@@ -328,12 +350,14 @@ __device__ __forceinline__ void emit_tile_rows(const f32x4 (&acc)[2][NT], float*
     float* st = lds + w * 16 * LDC;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        __syncthreads();
+        if (BLOCK_SYNC) __syncthreads();
+        else if (i > 0) wave_lds_order();          // slab 0's reads before slab 1's stores
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) st[(4 * lq + r) * LDC + 16 * j + lr] = acc[i][j][r];
-        __syncthreads();
+        if (BLOCK_SYNC) __syncthreads();
+        else wave_lds_order();
 #pragma unroll
         for (int it = 0; it < (16 * Q + 63) / 64; ++it) {
             const int idx = it * 64 + lane;

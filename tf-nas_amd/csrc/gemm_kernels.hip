@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_expand_fwd(TfnasCellDe
     const int n0 = ty * T::BN;
     const int P = d.N * d.H * d.W, ic = d.ic, M = d.M;
     const int nrt = (P + 127) >> 7, nchunks = (ic + 15) >> 4;
-    const int tid = threadIdx.x, lr = tid & 15, wrow = (tid >> 6) * 32;
+    const int tid = threadIdx.x;
 
     float cs[NT], cq[NT];
 #pragma unroll
@@ -75,7 +75,14 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_expand_fwd(TfnasCellDe
     for (int rt = BX; rt < nrt; rt += gridDim.x) {
         f32x4 acc[2][NT];
         acc_zero<NT>(acc);
-        // the lane's two A rows stay the same for the whole K loop: row pointers and validity live in registers
+        // the lane's two A rows stay the same for the whole K loop: row pointers and validity live in registers.  Stem: derived per
+        // tile from a fresh copy of the thread index, as the staging indices below -- the gathering loader has no register to spare
+        // and <4, true, 0> spilled 19 of them.  The plain variants keep the hoisted indices: with the copies they need 12-38
+        // registers less, fit one more workgroup per CU and ran SLOWER (B = 128, alpha-step: <5, false, 6> 342 -> 437 us,
+        // <4, false, 6> 144 -> 150 us)
+        int tr = tid;
+        if (STEM) asm volatile("" : "+v"(tr));
+        const int lr = tr & 15, wrow = (tr >> 6) * 32;
         int prow[2];
         const float* arow[2];
 #pragma unroll
@@ -103,10 +110,12 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_expand_fwd(TfnasCellDe
         };
         PreNone pre;
         gemm_adirect<NT, true, MM>(pre, la, xa, lb, xb, nchunks, acc, lds);
-        emit_tile_rows<NT>(acc, lds, [&](int lrow, int lc, f32x4 v) {
+        int te = tid;
+        if (STEM) asm volatile("" : "+v"(te));
+        emit_tile_rows<NT, false>(acc, lds, [&](int lrow, int lc, f32x4 v) {
             const int p = rt * 128 + lrow;
             if (p < P && n0 + lc < mcp) st4_nt(E + ((size_t)p * M + off + n0 + lc), v);
-        });
+        }, SlabNone(), te);
         acc_colstats<NT>(acc, cs, cq);
     }
     flush_colstats<NT>(cs, cq, lds, part + (size_t)BX * 2 * M + 2 * (size_t)off, n0, mcp);
@@ -202,10 +211,13 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_project_fwd(TfnasCellD
         };
         PreNone pre;
         gemm_adirect<NT, true, MM>(pre, la, xa, lb, xb, nchunks, acc, lds);
-        emit_tile_rows<NT>(acc, lds, [&](int lrow, int lc, f32x4 v) {
+        // (the staging indices derive from a copy of the thread index taken afresh per tile: see k_project_dgrad)
+        int te = tid;
+        asm volatile("" : "+v"(te));
+        emit_tile_rows<NT, false>(acc, lds, [&](int lrow, int lc, f32x4 v) {
             const int p = rt * 128 + lrow;
             if (p < Po && n0 + lc < oc) st4(dst + ((size_t)g * Po + p) * oc + n0 + lc, v);
-        });
+        }, SlabNone(), te);
         acc_colstats<NT>(acc, cs, cq);
     }
     if (nsplit == 1)
@@ -829,6 +841,9 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_expand_dgrad(TfnasCell
             return (n0 + n < ic && k0 + kl < klim_b) ? v : zero4();
         };
         gemm_adirect<NT, false, MM>(pre, la, xa, lb, xb, nchunks, acc, lds);
+        // (the staging indices derive from a copy of the thread index taken afresh per tile: see k_project_dgrad)
+        int te = tid;
+        asm volatile("" : "+v"(te));
         emit_tile_rows<NT>(acc, lds, [&](int lrow, int lc, f32x4 v) {
             const int p = rt * 128 + lrow, c = n0 + lc;
             if (p < P && c < ic) {
@@ -837,7 +852,7 @@ __global__ __launch_bounds__(256, gemm_lb(NT, MM)) void k_expand_dgrad(TfnasCell
                 if (add_sink) v = sink_add(v, sink_w, ld4(add_src + (size_t)p * ic + c));
                 st4(dst + (size_t)p * ic + c, v);
             }
-        });
+        }, SlabNone(), te);
     }
 }
 
