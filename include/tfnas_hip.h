@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-/* 4, additive: TFNAS_CELL_KINDS -- a per-group kind (TfnasGroup.kind): plain, expand-free and Fused-MBConv candidates in ONE cell.
+/* 4, additive: TFNAS_CELL_SE_STYLE -- TfnasCellDesc.se_style: the squeeze-excite hidden activation and gate function of a cell.
+ * 4, additive: TFNAS_CELL_KINDS -- a per-group kind (TfnasGroup.kind): plain, expand-free and Fused-MBConv candidates in ONE cell.
  * 4, additive: TFNAS_CELL_FUSED -- a Fused-MBConv block (dense 3 x 3 convolution, no depthwise) through tfnas_mixedop_* / tfnas_mbconv_*.
  * 4, additive: TFNAS_CELL_NOEXPAND -- a block without expand convolution (mid <= in channels) through tfnas_mixedop_* / tfnas_mbconv_*.
  * 4, additive: TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH in a descriptor whose flags carry TFNAS_CELL_ACTS (cells, affine blocks, head;
@@ -141,7 +142,8 @@ typedef struct TfnasCellDesc {
                                  TFNAS_CELL_ACTS: act may be TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH;
                                  TFNAS_CELL_NOEXPAND: the one group has no expand convolution;
                                  TFNAS_CELL_FUSED: the one group is a Fused-MBConv block (dense 3 x 3 convolution);
-                                 TFNAS_CELL_KINDS: every group has a kind of its own (TfnasGroup.kind)                   [in]
+                                 TFNAS_CELL_KINDS: every group has a kind of its own (TfnasGroup.kind);
+                                 TFNAS_CELL_SE_STYLE: se_style may be non-zero                                           [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -158,7 +160,10 @@ typedef struct TfnasCellDesc {
                                  route differs in a way that changes what the saved buffers mean (the fused per-image route
                                  leaves ehat = BN1(E), not E, in the E buffer) returns TFNAS_EINVAL instead of silently
                                  normalising twice                                                                          [in] */
-    int32_t pad_route;
+    int32_t se_style;         /* TFNAS_SE_*: hidden activation and gate function of the cell's squeeze-excite branches; non-zero
+                                 only in a descriptor whose flags carry TFNAS_CELL_SE_STYLE (0 = the cell's act, logistic gate).
+                                 This word was padding (pad_route) before: no struct changed size.  It is not part of the route:
+                                 tfnas_cell_route() ignores it, forward and backward each read it from their descriptor      [in] */
     void *wgrad_stream[3];    /* optional caller-owned streams for the weight-gradient kernels of this launch: fork 0 = project,
                                  1 = squeeze-excite + depthwise, 2 = expand weight gradient.  NULL entries: the library-owned
                                  side stream of the caller's stream.  Every stream used is joined before tfnas_mixedop_bwd
@@ -282,6 +287,30 @@ typedef struct TfnasCellDesc {
  * carries the SE, depthwise and dense-convolution weight gradients in stream order).  TFNAS_CELL_ACCUM_WGRAD, dx == NULL,
  * need_wgrad == 0, the dwmix-only early return, wgrad_stream[] and the sync-stats hook keep their meaning. */
 #define TFNAS_CELL_KINDS 0x800
+/* TfnasCellDesc.flags: the caller knows squeeze-excite styles (TfnasCellDesc.se_style).  Every SE branch of the library computes
+ *   gate = G(W_e . A(W_r . pool(D) + b_r) + b_e)
+ * and without the bit A is the cell's `act` and G the logistic function, as in the reference (models/layers.py:510-523, :550).
+ * MobileNetV3's SE has a ReLU hidden layer and a hard-sigmoid gate whatever the block's activation is.  Additive like TFNAS_CELL_K7:
+ * without the bit se_style must be 0 (anything else is TFNAS_EINVAL) and every descriptor plans, routes and launches as before.
+ * With it:
+ *   bits 0-3   hidden activation A: 0 = the cell's act | 1 + TFNAS_ACT_* = that activation (TFNAS_SE_HIDDEN(act)); ReLU6 and
+ *              hard-swish need TFNAS_CELL_ACTS as they do in `act`
+ *   bits 4-7   gate G: 0 logistic | 1 hard-sigmoid min(max(v + 3, 0), 6) / 6 (TFNAS_SE_GATE_HSIGMOID); its derivative is 1/6 where
+ *              0 < gate < 1 and 0 elsewhere, taken from the saved gate itself: no workspace grows
+ *   any undefined value of either nibble and any higher bit is TFNAS_EINVAL.
+ * One style per cell, as `act` is one per cell: it applies to every SE group of the cell whatever its kind (plain, expand-free,
+ * Fused-MBConv, the groups of a TFNAS_CELL_KINDS cell).  A styled cell without SE groups is legal and runs like the unstyled
+ * one.  A descriptor that spells the defaults (TFNAS_SE_HIDDEN(act) with the logistic gate) launches the kernels the unstyled one
+ * launches.  TFNAS_MODE_CELL only (tfnas_mixedop_*, tfnas_mbconv_*, the path level): TFNAS_MODE_STEM and TFNAS_MODE_HEAD refuse a
+ * non-zero style -- the stem keeps the reference's SE.  tfnas_cell_ws, tfnas_cell_route, tfnas_efree_supported and
+ * tfnas_fx_supported do not depend on it.  Checked by tfnas_cell_plan and again by every entry point. */
+#define TFNAS_CELL_SE_STYLE 0x1000
+#define TFNAS_SE_HIDDEN(act) (1 + (act))
+#define TFNAS_SE_HIDDEN_MASK 0xf
+#define TFNAS_SE_GATE_SHIFT 4
+#define TFNAS_SE_GATE_MASK 0xf0
+#define TFNAS_SE_GATE_LOGISTIC 0
+#define TFNAS_SE_GATE_HSIGMOID (1 << TFNAS_SE_GATE_SHIFT)
 #define TFNAS_GROUP_MBCONV 0
 #define TFNAS_GROUP_NOEXPAND 1
 #define TFNAS_GROUP_FUSED 2

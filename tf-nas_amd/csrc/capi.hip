@@ -157,6 +157,21 @@ static int check_act(const TfnasCellDesc* d) {
     return 0;
 }
 
+// the squeeze-excite style of a descriptor (tfnas_hip.h: TFNAS_CELL_SE_STYLE): 0, or -- from a caller that set the bit, in cell mode
+// -- a defined hidden activation (ReLU6 / hard-swish with TFNAS_CELL_ACTS, as in `act`) and a defined gate, nothing above bit 7
+static int check_se_style(const TfnasCellDesc* d) {
+    const int st = d->se_style;
+    if (st == 0) return 0;
+    if (!(d->flags & TFNAS_CELL_SE_STYLE) || d->mode != TFNAS_MODE_CELL) return TFNAS_EINVAL;
+    if (st & ~(TFNAS_SE_HIDDEN_MASK | TFNAS_SE_GATE_MASK)) return TFNAS_EINVAL;
+    const int hid = st & TFNAS_SE_HIDDEN_MASK, gate = st & TFNAS_SE_GATE_MASK;
+    if (hid > TFNAS_SE_HIDDEN(TFNAS_ACT_HSWISH)) return TFNAS_EINVAL;
+    if (gate != TFNAS_SE_GATE_LOGISTIC && gate != TFNAS_SE_GATE_HSIGMOID) return TFNAS_EINVAL;
+    if ((hid == TFNAS_SE_HIDDEN(TFNAS_ACT_RELU6) || hid == TFNAS_SE_HIDDEN(TFNAS_ACT_HSWISH)) && !(d->flags & TFNAS_CELL_ACTS))
+        return TFNAS_EINVAL;
+    return 0;
+}
+
 // the kind bits of a descriptor.  Both newer kinds are ONE block in cell mode; TFNAS_CELL_NOEXPAND: mc == ic channels, no expand
 // weight or gradient pointer; TFNAS_CELL_FUSED: a dense 3 x 3 weight (w_expand), no depthwise pointer; never both bits
 // TFNAS_CELL_KINDS: the same rules per group (TfnasGroup.kind), any G; the two one-block bits must then be clear
@@ -189,9 +204,10 @@ static int check_modes(const TfnasCellDesc* d) {
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
     if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS | TFNAS_CELL_NOEXPAND |
-                     TFNAS_CELL_FUSED | TFNAS_CELL_KINDS))
+                     TFNAS_CELL_FUSED | TFNAS_CELL_KINDS | TFNAS_CELL_SE_STYLE))
         return TFNAS_EINVAL;
     TRY(check_kind(d));
+    TRY(check_se_style(d));
     if (!(d->flags & TFNAS_CELL_K7)) {            // kernel size 7 is opt-in: without the bit it is refused as it always was
         for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g)
             if (d->g[g].k == 7) return TFNAS_EINVAL;
@@ -863,6 +879,7 @@ static int check_head(const TfnasCellDesc* dp) {
     if (dp->mode != TFNAS_MODE_HEAD) return TFNAS_EINVAL;
     if (dp->g[0].mc & 3) return TFNAS_EINVAL;      // (pooled / dpooled rows move in quads: tfnas_cell_plan refuses it too)
     TRY(check_act(dp));
+    TRY(check_se_style(dp));                       // (the head has no squeeze-excite: a non-zero style is refused)
     return check_kind(dp);
 }
 

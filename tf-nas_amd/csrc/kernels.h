@@ -67,6 +67,14 @@ static inline bool any_group_has_E(const TfnasCellDesc& d) {
         if (group_kind(d, g) == TFNAS_KIND_MBCONV) return true;
     return false;
 }
+// TFNAS_CELL_SE_STYLE (TfnasCellDesc.se_style, checked by the entry points): the hidden activation of the cell's squeeze-excite
+// branches resolved to a TFNAS_ACT_* (0 in the low nibble: the cell's own), and their gate function (SE_GATE_*)
+enum SeGate { SE_GATE_LOGISTIC = 0, SE_GATE_HSIGMOID = 1 };
+static inline int se_hidden_act(const TfnasCellDesc& d) {
+    const int h = d.se_style & TFNAS_SE_HIDDEN_MASK;
+    return h ? h - 1 : d.act;
+}
+static inline int se_gate(const TfnasCellDesc& d) { return (d.se_style & TFNAS_SE_GATE_MASK) >> TFNAS_SE_GATE_SHIFT; }
 // the activation fork of a launcher (inside a function returning int): the statements run with ACT = the launch's activation as a
 // compile-time constant; any other value is TFNAS_EINVAL
 #define ACT_DISPATCH(act, ...)                                                                        \
@@ -74,6 +82,11 @@ static inline bool any_group_has_E(const TfnasCellDesc& d) {
     else if ((act) == TFNAS_ACT_SWISH) { constexpr int ACT = TFNAS_ACT_SWISH; __VA_ARGS__; }          \
     else if ((act) == TFNAS_ACT_RELU6) { constexpr int ACT = TFNAS_ACT_RELU6; __VA_ARGS__; }          \
     else if ((act) == TFNAS_ACT_HSWISH) { constexpr int ACT = TFNAS_ACT_HSWISH; __VA_ARGS__; }        \
+    else return TFNAS_EINVAL;
+// the same for the gate function of the squeeze-excite kernels: GATE = SE_GATE_* as a compile-time constant
+#define SE_GATE_DISPATCH(gate, ...)                                                                   \
+    if ((gate) == SE_GATE_LOGISTIC) { constexpr int GATE = SE_GATE_LOGISTIC; __VA_ARGS__; }           \
+    else if ((gate) == SE_GATE_HSIGMOID) { constexpr int GATE = SE_GATE_HSIGMOID; __VA_ARGS__; }      \
     else return TFNAS_EINVAL;
 
 // gemm_kernels.hip

@@ -10,6 +10,10 @@
 //   MODE 3  dpool[N,mc] = dhpre[N,se] W_r                                            (NN)
 //   MODE 4  g_se_e[mc,se] = dgl^T act(hpre)                                          (TN, K = batch)
 //   MODE 5  g_se_r[se,mc] = (pooled^T dhpre)^T                                       (TN, K = batch)
+// TFNAS_CELL_SE_STYLE (TfnasCellDesc.se_style): `act` above is the cell's resolved hidden activation (se_hidden_act: the ACT
+// argument of every kernel here) and `sigmoid` / `gate*(1-gate)` the cell's gate function and its derivative in terms of the
+// gate (se_gate_f / se_gate_bwd, tfnas_dev.h: the GATE argument of the kernels that touch them -- MODE 1, 2, 4, the fused
+// per-image pair, the bias gradients).  GATE = 0 with ACT = d.act is the reference's branch, instruction for instruction.
 #include <cstring>
 #include "gemm_core.h"
 #include "kernels.h"
@@ -33,7 +37,7 @@ __device__ __forceinline__ int se_group_idx(const TfnasCellDesc& d, int idx) {
     return -1;
 }
 
-template <int MODE, int ACT>
+template <int MODE, int ACT, int GATE>
 __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
     constexpr int NT = 4;
     using T = GT<NT>;
@@ -59,6 +63,7 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
     struct Pair { f32x4 a, b; };
     const f32x4 one4 = splat4(1.f);
     XfId id;
+    // (dgl below: the logistic form stays spelled in place, so that this kernel's default code is what it always was)
 
     if (MODE == 0) {
         if (r0 >= N || n0 >= se) return;
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
             return r;
         };
         auto xa = [&](Pair r, int c, int, int row, int kl) -> f32x4 {
-            return (r0 + row < N && (cbase + c) * 16 + kl < mcp) ? r.b * r.a * (one4 - r.a) : zero4();
+            return (r0 + row < N && (cbase + c) * 16 + kl < mcp) ? (GATE == SE_GATE_LOGISTIC ? r.b * r.a * (one4 - r.a) : se_gate_bwd4<GATE>(r.b, r.a)) : zero4();
         };
         auto lb = [&](int c, int, int kl, int nn) -> f32x4 {
             const int k = min((cbase + c) * 16 + kl, mc - 1), j = min(n0 + nn, se - 4);
@@ -152,7 +157,7 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
             return r;
         };
         auto xa = [&](Pair r, int c, int, int kl, int m) -> f32x4 {
-            const f32x4 v = MODE == 4 ? r.b * r.a * (one4 - r.a) : r.a;
+            const f32x4 v = MODE == 4 ? (GATE == SE_GATE_LOGISTIC ? r.b * r.a * (one4 - r.a) : se_gate_bwd4<GATE>(r.b, r.a)) : r.a;
             return (c * 16 + kl < N && r0 + m < mcp) ? v : zero4();
         };
         auto lb = [&](int c, int, int kl, int nn) -> f32x4 {
@@ -182,7 +187,7 @@ __global__ __launch_bounds__(256) void k_se_gemm(TfnasCellDesc d, SeArgs a) {
                     if (row < N && col < se) a.out0[(size_t)row * SE + so + col] = v + d.g[g].b_se_r[col];
                 } else if (MODE == 1) {
                     if (row < N && col < mcp)
-                        a.out0[(size_t)row * M + off + col] = col < mc ? sigmoid_f(v + d.g[g].b_se_e[col]) : 0.f;
+                        a.out0[(size_t)row * M + off + col] = col < mc ? se_gate_f<GATE>(v + d.g[g].b_se_e[col]) : 0.f;
                 } else if (MODE == 2) {
                     if (row < N && col < se)
                         a.out0[(size_t)row * SE + so + col] = v * act_d<ACT>(a.hpre[(size_t)row * SE + so + col]);
@@ -218,6 +223,7 @@ __global__ __launch_bounds__(256) void k_se_finish(TfnasCellDesc d, SeArgs a) {
 
 // bias gradients: gb_se_e[c] = sum_n dgl[n][c] ; gb_se_r[j] = sum_n dhpre[n][j]
 // 64 columns x 4 batch-lanes per workgroup, 8 loads in flight per thread
+template <int GATE>
 __global__ __launch_bounds__(256) void k_se_bias_grad(TfnasCellDesc d, SeArgs a) {
     __shared__ float buf[4][64];
     const int g = se_group_idx(d, blockIdx.y);
@@ -238,7 +244,7 @@ __global__ __launch_bounds__(256) void k_se_bias_grad(TfnasCellDesc d, SeArgs a)
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u)
-                if (n0 + 4 * u < N) s += dg[u] * gt[u] * (1.f - gt[u]);
+                if (n0 + 4 * u < N) s += se_gate_bwd<GATE>(dg[u], gt[u]);
         }
     } else if (idx < mc + se) {
         const int j = idx - mc;
@@ -278,7 +284,7 @@ __device__ __forceinline__ void se_stage_rows(float* wl, const float* __restrict
 
 constexpr int SE_CH = 128;   // channels per staged block of W_e
 
-template <int ACT>
+template <int ACT, int GATE>
 __global__ __launch_bounds__(256) void k_se_fused_fwd(TfnasCellDesc d, const float* __restrict__ pooled,
                                                       float* __restrict__ hpre, float* __restrict__ gate) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -344,12 +350,12 @@ __global__ __launch_bounds__(256) void k_se_fused_fwd(TfnasCellDesc d, const flo
             for (int j = half; j < se; j += 2) sacc += row[j] * hs[j];
         }
         sacc += __shfl_xor(sacc, 1, 64);
-        if (half == 0 && c < mcp) gate[(size_t)n * M + off + c] = c < mc ? sigmoid_f(sacc + d.g[g].b_se_e[c]) : 0.f;
+        if (half == 0 && c < mcp) gate[(size_t)n * M + off + c] = c < mc ? se_gate_f<GATE>(sacc + d.g[g].b_se_e[c]) : 0.f;
     }
 }
 
 // dgl = dgate*gate*(1-gate);  dhpre = (dgl W_e) * act'(hpre);  dpooled = dhpre W_r
-template <int ACT>
+template <int ACT, int GATE>
 __global__ __launch_bounds__(256) void k_se_fused_bwd(TfnasCellDesc d, const float* __restrict__ dgate,
                                                       const float* __restrict__ gate, const float* __restrict__ hpre,
                                                       float* __restrict__ dhpre, float* __restrict__ dpooled) {
@@ -368,7 +374,7 @@ __global__ __launch_bounds__(256) void k_se_fused_bwd(TfnasCellDesc d, const flo
         float v = 0.f;
         if (c < mc) {
             const float gt = gate[(size_t)n * M + off + c];
-            v = dgate[(size_t)n * M + off + c] * gt * (1.f - gt);
+            v = se_gate_bwd<GATE>(dgate[(size_t)n * M + off + c], gt);
         }
         dgl[c] = v;
     }
@@ -447,7 +453,7 @@ __global__ __launch_bounds__(256) void k_se_fused_bwd(TfnasCellDesc d, const flo
 // of W_r; ragged widths keep the GEMM path).  Weights are read once per 16 images instead of once per image.
 #define SEW_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-template <int MODE, int ACT>      // MODE 0: hpre = pooled W_r^T + b_r (K = mc, split over the waves);  MODE 1: gate (K = se)
+template <int MODE, int ACT, int GATE>      // MODE 0: hpre = pooled W_r^T + b_r (K = mc, split over the waves);  MODE 1: gate (K = se)
 __global__ __launch_bounds__(256) void k_se_nt(TfnasCellDesc d, SeArgs a) {
     __shared__ f32x4 red[4][64];
     const int g = se_group_idx(d, blockIdx.z);
@@ -500,11 +506,11 @@ __global__ __launch_bounds__(256) void k_se_nt(TfnasCellDesc d, SeArgs a) {
         const int n = n0 + 4 * lk + r;
         if (n >= N || j >= ncol) continue;
         if (MODE == 0) a.out0[(size_t)n * SE + so + j] = acc[r] + d.g[g].b_se_r[j];
-        else a.out0[(size_t)n * M + off + j] = j < mc ? sigmoid_f(acc[r] + d.g[g].b_se_e[j]) : 0.f;
+        else a.out0[(size_t)n * M + off + j] = j < mc ? se_gate_f<GATE>(acc[r] + d.g[g].b_se_e[j]) : 0.f;
     }
 }
 
-template <int MODE, int ACT>      // MODE 2: dhpre = (dgl W_e) * act'(hpre) (K = mc, split over the waves);  MODE 3: dpooled = dhpre W_r
+template <int MODE, int ACT, int GATE>      // MODE 2: dhpre = (dgl W_e) * act'(hpre) (K = mc, split over the waves);  MODE 3: dpooled = dhpre W_r
 __global__ __launch_bounds__(256) void k_se_nn(TfnasCellDesc d, SeArgs a) {
     __shared__ f32x4 red[MODE == 2 ? 4 : 1][4][64];
     const int g = se_group_idx(d, blockIdx.z);
@@ -542,7 +548,7 @@ __global__ __launch_bounds__(256) void k_se_nn(TfnasCellDesc d, SeArgs a) {
         for (int u = 0; u < UB; ++u) {
             const int k = 16 * (s0 + u * stride) + 4 * lk;
             f32x4 x = av[u];
-            if (MODE == 2) x = x * gv[u] * (splat4(1.f) - gv[u]);
+            if (MODE == 2) x = se_gate_bwd4<GATE>(x, gv[u]);
             x = (k < K) ? x : zero4();
 #pragma unroll
             for (int t = 0; t < 4; ++t)
@@ -617,13 +623,22 @@ static SePlan se_plan(const TfnasCellDesc& d, size_t scratch_floats) {
     return p;
 }
 
+// the two compile-time forks of a launch: ACT = the cell's resolved SE hidden activation, GATE = its gate function -- the latter
+// only for the kernels that touch the gate function (the others exist once per activation, as GATE 0: SE_DISPATCH_UNGATED)
+#define SE_DISPATCH(d, ...) ACT_DISPATCH(se_hidden_act(d), { SE_GATE_DISPATCH(se_gate(d), __VA_ARGS__) })
+#define SE_DISPATCH_UNGATED(d, ...) ACT_DISPATCH(se_hidden_act(d), { constexpr int GATE = SE_GATE_LOGISTIC; __VA_ARGS__; })
+
 template <int MODE>
 static int se_gemm(const TfnasCellDesc& d, const SeArgs& a, int rows, int cols, int ng, hipStream_t s) {
     dim3 grid(cdiv(rows, 128) * ((MODE == 0 || MODE == 2) ? a.ksplit : 1), cdiv(cols, 64), ng);
-    ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_gemm<MODE, ACT>), grid, dim3(256), 0, s, d, a); })
+    if constexpr (MODE == 1 || MODE == 2 || MODE == 4) {
+        SE_DISPATCH(d, { hipLaunchKernelGGL((k_se_gemm<MODE, ACT, GATE>), grid, dim3(256), 0, s, d, a); })
+    } else {
+        SE_DISPATCH_UNGATED(d, { hipLaunchKernelGGL((k_se_gemm<MODE, ACT, GATE>), grid, dim3(256), 0, s, d, a); })
+    }
     if constexpr (MODE == 0 || MODE == 2) {      // (their K-split partials)
         if (a.ksplit > 1) {
-            ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_finish<MODE, ACT>), dim3(cdiv(d.N * d.SE, 256)), dim3(256), 0, s, d, a); })
+            ACT_DISPATCH(se_hidden_act(d), { hipLaunchKernelGGL((k_se_finish<MODE, ACT>), dim3(cdiv(d.N * d.SE, 256)), dim3(256), 0, s, d, a); })
         }
     }
     return 0;
@@ -637,11 +652,11 @@ int launch_se_fc_fwd(const TfnasCellDesc& d, const float* pooled, float* hpre, f
     SeArgs a = {pooled, gate, hpre, nullptr, nullptr, hpre, nullptr, 1};
     if (p.var == SE_TILED) a.scratch = scratch, a.ksplit = p.ksplit;
     if (p.var == SE_WAVE) {
-        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_nt<0, ACT>), dim3(cdiv(d.N, 16), cdiv(p.se_max, 16), p.ng), dim3(256), 0, s, d, a); })
+        SE_DISPATCH_UNGATED(d, { hipLaunchKernelGGL((k_se_nt<0, ACT, GATE>), dim3(cdiv(d.N, 16), cdiv(p.se_max, 16), p.ng), dim3(256), 0, s, d, a); })
         a.out0 = gate;
-        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_nt<1, ACT>), dim3(cdiv(d.N, 16), cdiv(p.mcp_max, 64), p.ng), dim3(256), 0, s, d, a); })
+        SE_DISPATCH(d, { hipLaunchKernelGGL((k_se_nt<1, ACT, GATE>), dim3(cdiv(d.N, 16), cdiv(p.mcp_max, 64), p.ng), dim3(256), 0, s, d, a); })
     } else if (p.var == SE_IMAGE) {
-        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_fused_fwd<ACT>), dim3(d.N, p.ng), dim3(256), p.shm, s, d, pooled, hpre, gate); })
+        SE_DISPATCH(d, { hipLaunchKernelGGL((k_se_fused_fwd<ACT, GATE>), dim3(d.N, p.ng), dim3(256), p.shm, s, d, pooled, hpre, gate); })
     } else {
         if (se_gemm<0>(d, a, d.N, p.se_max, p.ng, s)) return TFNAS_EINVAL;
         a.out0 = gate;
@@ -658,12 +673,12 @@ int launch_se_fc_bwd(const TfnasCellDesc& d, const float* dgate, const float* ga
     SeArgs a = {nullptr, gate, hpre, dgate, dhpre, dhpre, nullptr, 1};
     if (p.var == SE_TILED) a.scratch = scratch, a.ksplit = p.ksplit;
     if (p.var == SE_WAVE) {
-        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_nn<2, ACT>), dim3(cdiv(d.N, 16), cdiv(p.se_max, 64), p.ng), dim3(256), 0, s, d, a); })
+        SE_DISPATCH(d, { hipLaunchKernelGGL((k_se_nn<2, ACT, GATE>), dim3(cdiv(d.N, 16), cdiv(p.se_max, 64), p.ng), dim3(256), 0, s, d, a); })
         a.out0 = dpooled;
-        ACT_DISPATCH(d.act, { hipLaunchKernelGGL((k_se_nn<3, ACT>), dim3(cdiv(d.N, 16), cdiv(p.mcp_max, 256), p.ng), dim3(256), 0, s, d, a); })
+        SE_DISPATCH_UNGATED(d, { hipLaunchKernelGGL((k_se_nn<3, ACT, GATE>), dim3(cdiv(d.N, 16), cdiv(p.mcp_max, 256), p.ng), dim3(256), 0, s, d, a); })
     } else if (p.var == SE_IMAGE) {
-        ACT_DISPATCH(d.act, {
-            hipLaunchKernelGGL((k_se_fused_bwd<ACT>), dim3(d.N, p.ng), dim3(256), p.shm, s, d, dgate, gate, hpre, dhpre, dpooled);
+        SE_DISPATCH(d, {
+            hipLaunchKernelGGL((k_se_fused_bwd<ACT, GATE>), dim3(d.N, p.ng), dim3(256), p.shm, s, d, dgate, gate, hpre, dhpre, dpooled);
         })
     } else {
         if (se_gemm<2>(d, a, d.N, p.se_max, p.ng, s)) return TFNAS_EINVAL;
@@ -681,8 +696,8 @@ int launch_se_wgrad(const TfnasCellDesc& d, const float* dgate, const float* gat
     SeArgs a = {pooled, gate, hpre, dgate, dhpre, nullptr, nullptr, 1};
     // (a wave-level TN formulation of these two, K = batch = 128 images, was built and measured: 51 instead of 36 us per cell
     //  for the three launches -- ~100 waves walking 32 dependent K-steps each; the LDS-tiled GEMMs stay in every variant)
-    se_gemm<4>(d, a, p.mcp_max, p.se_max, p.ng, s);
-    se_gemm<5>(d, a, p.mcp_max, p.se_max, p.ng, s);
-    hipLaunchKernelGGL(k_se_bias_grad, dim3(cdiv(p.mcp_max + p.se_max, 64), p.ng), dim3(256), 0, s, d, a);
+    if (se_gemm<4>(d, a, p.mcp_max, p.se_max, p.ng, s)) return TFNAS_EINVAL;
+    if (se_gemm<5>(d, a, p.mcp_max, p.se_max, p.ng, s)) return TFNAS_EINVAL;
+    SE_GATE_DISPATCH(se_gate(d), hipLaunchKernelGGL(k_se_bias_grad<GATE>, dim3(cdiv(p.mcp_max + p.se_max, 64), p.ng), dim3(256), 0, s, d, a))
     return (int)hipGetLastError();
 }

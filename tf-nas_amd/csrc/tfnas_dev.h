@@ -60,6 +60,34 @@ __device__ __forceinline__ f32x4 act_d4(f32x4 v) {
     r.x = act_d<ACT>(v.x); r.y = act_d<ACT>(v.y); r.z = act_d<ACT>(v.z); r.w = act_d<ACT>(v.w);
     return r;
 }
+// The gate function of the squeeze-excite branch (TfnasCellDesc.se_style, GATE = SE_GATE_* of kernels.h): 0 the logistic function,
+// 1 torch's hardsigmoid min(max(v + 3, 0), 6) / 6.  The backward keeps only the gate itself, so the derivative is written in
+// it: dgl = dgate * gate * (1 - gate), or dgate / 6 strictly inside 0 < gate < 1 (v strictly inside (-3, 3): hardsigmoid's
+// backward), 0 where the gate saturated.
+template <int GATE>
+__device__ __forceinline__ float se_gate_f(float v) {
+    static_assert(GATE == 0 || GATE == 1, "unknown gate");
+    if constexpr (GATE == 0) return sigmoid_f(v);
+    else return fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f);
+}
+template <int GATE>
+__device__ __forceinline__ float se_gate_bwd(float dgate, float gate) {
+    static_assert(GATE == 0 || GATE == 1, "unknown gate");
+    if constexpr (GATE == 0) return dgate * gate * (1.f - gate);
+    else return (gate > 0.f && gate < 1.f) ? dgate * (1.f / 6.f) : 0.f;
+}
+template <int GATE>
+__device__ __forceinline__ f32x4 se_gate_bwd4(f32x4 dgate, f32x4 gate) {
+    if constexpr (GATE == 0) {
+        const f32x4 one4 = {1.f, 1.f, 1.f, 1.f};
+        return dgate * gate * (one4 - gate);
+    } else {
+        f32x4 r;
+        r.x = se_gate_bwd<GATE>(dgate.x, gate.x); r.y = se_gate_bwd<GATE>(dgate.y, gate.y);
+        r.z = se_gate_bwd<GATE>(dgate.z, gate.z); r.w = se_gate_bwd<GATE>(dgate.w, gate.w);
+        return r;
+    }
+}
 
 // ----------------------------------------------------------------------------- batch-norm constants
 // stats layout: [channel][2] doubles = (sum, sum of squares) over `cnt` elements.

@@ -31,6 +31,8 @@ CELL_ACTS = 0x100            # TfnasCellDesc.flags: act may be 'relu6' / 'h-swis
 CELL_NOEXPAND = 0x200        # TfnasCellDesc.flags: the one group has no expand convolution (mid == in channels; refused without the bit)
 CELL_FUSED = 0x400           # TfnasCellDesc.flags: the one group is a Fused-MBConv block (dense 3 x 3 weight in w_expand, no depthwise)
 CELL_KINDS = 0x800           # TfnasCellDesc.flags: every group names its own kind in TfnasGroup.kind (group_kind_id; refused without the bit)
+CELL_SE_STYLE = 0x1000       # TfnasCellDesc.flags: se_style may be non-zero (se_style_id; refused without the bit)
+SE_GATE = {'sigmoid': 0, 'h-sigmoid': 1}      # gate function of a squeeze-excite branch (bits 4-7 of TfnasCellDesc.se_style)
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
 ROUTE_FX_OFF, ROUTE_FOLD_OFF, ROUTE_DWWG_OFF, ROUTE_DWWG2_OFF, ROUTE_XG_OFF, ROUTE_XG_ALL = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 ROUTE_DW = {'auto': 0, 'direct': 1 << 6, 'lds': 2 << 6, 'tiled': 3 << 6}
@@ -52,6 +54,38 @@ def act_flags(act):
     """TfnasCellDesc.flags bit a descriptor with activation id ``act`` needs (the library takes the two newer activations only
     from callers that say they know them)."""
     return CELL_ACTS if act in (ACT['relu6'], ACT['h-swish']) else 0
+
+
+def se_style_id(se_act=None, se_gate='sigmoid'):
+    """TfnasCellDesc.se_style of a squeeze-excite style: ``se_act`` the hidden activation (None: the block's own; else one of
+    ACT's names), ``se_gate`` 'sigmoid' or 'h-sigmoid'.  0 is the reference's branch.  ValueError names the legal spellings."""
+    if se_act is not None and (not isinstance(se_act, str) or se_act not in ACT):
+        raise ValueError('tfnas_amd: unknown squeeze-excite activation %r (None for the block\'s own, or one of %s)'
+                         % (se_act, ', '.join(repr(a) for a in ACT)))
+    if not isinstance(se_gate, str) or se_gate not in SE_GATE:
+        raise ValueError('tfnas_amd: unknown squeeze-excite gate %r (one of %s)' % (se_gate, ', '.join(repr(g) for g in SE_GATE)))
+    return (0 if se_act is None else 1 + ACT[se_act]) | (SE_GATE[se_gate] << 4)
+
+
+def se_style_flags(style):
+    """TfnasCellDesc.flags bits a descriptor with ``se_style == style`` needs: CELL_SE_STYLE, and CELL_ACTS for an explicit
+    'relu6' / 'h-swish' hidden activation."""
+    if not style:
+        return 0
+    hidden = style & 0xf
+    return CELL_SE_STYLE | (act_flags(hidden - 1) if hidden else 0)
+
+
+def se_style_pair(style, what='se_style'):
+    """A caller's ``(se_act, se_gate)`` pair, validated (None: the default pair)."""
+    if style is None:
+        return (None, 'sigmoid')
+    try:
+        se_act, se_gate = style
+    except (TypeError, ValueError):
+        raise ValueError('tfnas_amd: %s must be None or a (se_act, se_gate) pair, got %r' % (what, style)) from None
+    se_style_id(se_act, se_gate)
+    return (se_act, se_gate)
 
 
 class BlockKind(collections.namedtuple('BlockKind', 'name flag fields bn_sites has_E')):
@@ -100,6 +134,10 @@ class TfnasCellDesc(C.Structure):
                    ('stor', C.c_int32), ('gemm_mode', C.c_int32), ('flags', C.c_int32), ('g', TfnasGroup * MAX_GROUPS),
                    ('sync_fn', C.c_void_p), ('sync_user', C.c_void_p), ('sync_world', C.c_int32), ('route', C.c_int32),
                    ('fwd_route', C.c_int32), ('pad_route', C.c_int32), ('wgrad_stream', C.c_void_p * 3)])
+    # TfnasCellDesc.se_style (TFNAS_SE_*: se_style_id) lives in the word that was padding before it.  The mirror keeps that word's
+    # historical field name in _fields_ -- recorded descriptor dumps (tests/golden/block_kind_pin.json) list the int32 fields by
+    # name -- and exposes it under the header's name.
+    se_style = property(lambda self: self.pad_route, lambda self, v: setattr(self, 'pad_route', v))
 
 
 class TfnasCellWs(C.Structure):

@@ -243,7 +243,7 @@ def train_stats(stats, m, epoch, arch_epoch, num_classes):
 def search_epoch(epoch, state_dict, mc_mask_dddict, lat_lookup, train_queue, val_queue, *, num_classes=100, epochs=100,
                  lr=0.025, T=5.0, w_mom=0.9, w_wd=1e-5, a_lr=0.01, a_wd=5e-4, a_betas=(0.5, 0.999), grad_clip=5.0,
                  target_lat=15.0, lambda_lat=0.1, warmup_epochs=10, noise=None, device='cuda', group=None, log=None,
-                 print_freq=100, primitives=None):
+                 print_freq=100, primitives=None, se_style=None):
     """One epoch of the reference's main loop (train_search.py:155-307) on the HIP model.  ``state_dict`` / ``mc_mask_dddict``
     are updated in place and returned together with the epoch's statistics.  ``train_queue`` / ``val_queue``: iterables of
     (x, target) batches (the weight-sharing / arch-step queues of train_w_arch).
@@ -253,7 +253,9 @@ def search_epoch(epoch, state_dict, mc_mask_dddict, lat_lookup, train_queue, val
     ``['train_top5']``, ``['train_objs_w']`` and, in architecture epochs, ``['train_objs_a']``, ``['train_objs_l']``.  With a ``log``
     the reference's TRAIN lines are logged every ``print_freq`` steps from this rank's running sums: one more read, i.e. one host
     synchronisation, per ``print_freq`` steps, and none without a ``log``.
-    ``primitives``: refused unless None / the defaults (require_default_primitives)."""
+    ``primitives``: refused unless None / the defaults (require_default_primitives).  ``se_style``: the squeeze-excite style of the
+    epoch's network (model_search.Network(se_style=...)); it changes no tensor shape, so the store, the masks, the slicing and the
+    re-ranking do not know it."""
     require_default_primitives('search_epoch', primitives)
     from . import search
     from .tail import SearchMeter
@@ -263,7 +265,7 @@ def search_epoch(epoch, state_dict, mc_mask_dddict, lat_lookup, train_queue, val
     lat_keys = geometry.make_lat_lookup_key_dddict()
     mc_max = geometry.get_mc_num_dddict(mc_mask_dddict, is_max=True)
     mc_num = geometry.get_mc_num_dddict(mc_mask_dddict)
-    model = Network(num_classes, mc_num, lat_lookup).to(device)
+    model = Network(num_classes, mc_num, lat_lookup, se_style=se_style).to(device)
     model.set_temperature(T)
     slice_weights_from_max(model, state_dict, mc_mask_dddict)
     state = search.SearchState(model)
@@ -338,7 +340,8 @@ def run_search(save_dir, lat_lookup, make_train_queue, make_val_queue, *, num_cl
     torch.manual_seed(seed)
     if start_epoch == 0:
         mc_mask = geometry.make_mc_mask_dddict()
-        full = TfnasDataParallel(Network(num_classes, geometry.get_mc_num_dddict(mc_mask, is_max=True), lat_lookup),
+        full = TfnasDataParallel(Network(num_classes, geometry.get_mc_num_dddict(mc_mask, is_max=True), lat_lookup,
+                                         se_style=kw.get('se_style')),
                                  device=torch.device(device))
         save_search_checkpoint(save_dir, 0, full.state_dict(), mc_mask)
         del full

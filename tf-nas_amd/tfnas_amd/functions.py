@@ -161,6 +161,22 @@ def adopt_modes(root, modes=None):
     return modes
 
 
+def blocks_se_style(blocks):
+    """TfnasCellDesc.se_style of a cell of ``blocks``: the one style of its blocks with squeeze-excite; ValueError if they differ."""
+    styles = {(getattr(b, 'se_act', None), getattr(b, 'se_gate', 'sigmoid')) for b in blocks if b.se_channels > 0}
+    ids = {_lib.se_style_id(*st) for st in styles}
+    if len(ids) > 1:
+        raise ValueError('tfnas_amd: the squeeze-excite blocks of one cell must share one style (se_act, se_gate); got %s'
+                         % ', '.join(sorted(repr(st) for st in styles)))
+    return ids.pop() if ids else 0
+
+
+def mark_se_style(d, style):
+    """Write a style and its flag bits into a descriptor (after HipModes.apply, which rewrites flags)."""
+    d.se_style = style
+    d.flags |= _lib.se_style_flags(style)
+
+
 class CellPlan:
     """Host-side description of one MixedOP launch: geometry + which candidate blocks take part.
 
@@ -190,6 +206,9 @@ class CellPlan:
         # (what desc() hands HipModes.apply after the descriptor: a plain plan names no kind, so that a subclass which overrides
         # apply(d) alone keeps working -- for such a plan apply's own inference says MBCONV too)
         self._kind_arg = () if self.kind is _lib.MBCONV else (self.kind,)
+        # the squeeze-excite style (TfnasCellDesc.se_style) is one per cell, as the activation is: that of the plan's blocks WITH
+        # squeeze-excite, which must agree (a block without SE has no branch the style could apply to and never conflicts)
+        self.se_style = blocks_se_style(self.blocks) if mode == _lib.MODE_CELL else 0
         # (group, field index) of every parameter bind() is handed, in params() order: a head binds its one weight, the stem all
         # seven fields, a cell's block the fields of its kind
         slots = []
@@ -231,18 +250,20 @@ class CellPlan:
             for g, b in enumerate(self.blocks):
                 d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
             self.modes.apply(d, *self._kind_arg)       # (before the plan: it validates the modes; every launch re-checks them)
-            self._mark_kinds(d)
+            self._mark(d)
             check(_lib.lib().tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
             ws = TfnasCellWs()
             check(_lib.lib().tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
             hit = (d, ws)
             self._desc_cache[key] = hit
         self.modes.apply(hit[0], *self._kind_arg)      # (every launch: the descriptor is cached, the model's modes may change)
-        self._mark_kinds(hit[0])
+        self._mark(hit[0])
         return hit
 
-    def _mark_kinds(self, d):
-        """A plan of blocks of different kinds: CELL_KINDS and every group's own kind (after HipModes.apply, which rewrites flags)."""
+    def _mark(self, d):
+        """What the plan itself knows about its descriptor (after HipModes.apply, which rewrites flags): the squeeze-excite style
+        with its flag bits, and -- a plan of blocks of different kinds -- CELL_KINDS and every group's own kind."""
+        mark_se_style(d, self.se_style)
         if self.group_kinds is not None:
             d.flags |= _lib.CELL_KINDS
             for g, kind in enumerate(self.group_kinds):

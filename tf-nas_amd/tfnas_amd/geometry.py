@@ -41,6 +41,31 @@ def cell_primitives(primitives, stage, block):
     return list(PRIMITIVES) if primitives is None else list(primitives)
 
 
+def cell_se_style(se_style, stage, block):
+    """The (se_act, se_gate) pair of cell (stage, block) under an ``se_style`` argument: None -> the default (None, 'sigmoid');
+    one pair -> that pair for every cell; a {stage: pair} or {stage: {block: pair}} mapping -> its entry, the default where it
+    has none."""
+    if isinstance(se_style, dict):
+        se_style = se_style.get(stage)
+        if isinstance(se_style, dict):
+            se_style = se_style.get(block)
+    if se_style is None:
+        return (None, 'sigmoid')
+    se_act, se_gate = se_style
+    return (se_act, se_gate)
+
+
+def se_style_keys(se_act, se_gate):
+    """The keys a block's config carries for its squeeze-excite style: only what differs from the default, so that the config of
+    an unstyled block is what it always was."""
+    keys = {}
+    if se_act is not None:
+        keys['se_act'] = se_act
+    if se_gate != 'sigmoid':
+        keys['se_gate'] = se_gate
+    return keys
+
+
 def primitive_block(name, ic, mc):
     """(layer class name, mid_channels, se_channels, kernel_size) of primitive ``name`` in a cell of ``ic`` input channels whose
     width table says ``mc``; ValueError (naming the legal ones) for an unknown name."""

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._lib import act_id, MBCONV, NOEXPAND, FUSED
+from ._lib import act_id, se_style_id, MBCONV, NOEXPAND, FUSED
 from .functions import CellPlan, MixedOpFn, BN_EPS
 
 
@@ -91,9 +91,15 @@ class _HipBlock(nn.Module):
 
     kind = MBCONV
 
-    def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead):
+    def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead,
+                 se_act=None, se_gate='sigmoid'):
         super().__init__()
         act_id(act_func)                                   # (ValueError for a name the library has no kernels for)
+        se_style_id(se_act, se_gate)                       # (... or a squeeze-excite style it has none for)
+        # squeeze-excite style (TfnasCellDesc.se_style): hidden activation (None: act_func) and gate of the SE branch; plain
+        # attributes -- no parameter, module or state_dict key depends on them.  MobileNetV3: ('relu', 'h-sigmoid').  (What the
+        # hard-sigmoid gate costs beside the logistic one on the chip has not been measured; the latency tables ignore the style.)
+        self.se_act, self.se_gate = se_act, se_gate
         self.in_channels, self.mid_channels = in_channels, mid_channels
         self.se_channels, self.out_channels = max(se_channels, 0), out_channels
         self.kernel_size, self.stride, self.act_func = kernel_size, stride, act_func
@@ -111,6 +117,13 @@ class _HipBlock(nn.Module):
         self.has_residual = (in_channels == out_channels) and (stride == 1)
         # the conv (+ bn) modules in the order of the library's fields: the leading ones that are there, then the project
         self._convs = [m for m in leading.values() if m is not None] + [self.point_linear]
+        self._plan = None
+
+    def set_se_style(self, style):
+        """Give the block the squeeze-excite style ``(se_act, se_gate)`` (None: the default) -- before its first forward: the
+        plan of a launch reads the style when it is made."""
+        from ._lib import se_style_pair
+        self.se_act, self.se_gate = se_style_pair(style)
         self._plan = None
 
     def bn(self, ch):
@@ -170,7 +183,7 @@ class MBInvertedResBlock(_HipBlock):
     with two BatchNorm sites.  (``Network._stem`` runs ``second_stem`` fused with ``first_stem`` instead.)"""
 
     def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size=3, stride=1,
-                 affine=False, act_func='relu'):
+                 affine=False, act_func='relu', *, se_act=None, se_gate='sigmoid'):
         expand = mid_channels > in_channels
         if not expand:
             mid_channels = in_channels
@@ -181,7 +194,8 @@ class MBInvertedResBlock(_HipBlock):
                 inverted_bottleneck=_seq(conv=nn.Conv2d(in_channels, mc, 1, 1, 0, bias=False), **self.bn(mc)) if expand else None,
                 depth_conv=_seq(conv=nn.Conv2d(mc, mc, kernel_size, stride, get_same_padding(kernel_size), groups=mc,
                                                bias=False), **self.bn(mc)))
-        super().__init__(in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead)
+        super().__init__(in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead,
+                         se_act=se_act, se_gate=se_gate)
 
     @property
     def name(self):
@@ -199,7 +213,7 @@ class FusedMBConvBlock(_HipBlock):
     kind = FUSED
 
     def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size=3, stride=1,
-                 affine=False, act_func='relu'):
+                 affine=False, act_func='relu', *, se_act=None, se_gate='sigmoid'):
         act_id(act_func)                                   # (first, as ever: ValueError for a name the library has no kernels for)
         if kernel_size != 3:
             raise NotImplementedError('tfnas_amd: FusedMBConvBlock has kernel size 3 only (got %r)' % (kernel_size,))
@@ -208,7 +222,8 @@ class FusedMBConvBlock(_HipBlock):
 
         def lead(mc):
             return OrderedDict(fused_conv=_seq(conv=nn.Conv2d(in_channels, mc, 3, stride, 1, bias=False), **self.bn(mc)))
-        super().__init__(in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead)
+        super().__init__(in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead,
+                         se_act=se_act, se_gate=se_gate)
 
     @property
     def name(self):

@@ -114,7 +114,8 @@ class _DerivedBase(nn.Module):
     def _block_config(b):
         return {'name': b.name, 'in_channels': b.in_channels, 'mid_channels': b.mid_channels,
                 'se_channels': b.se_channels, 'out_channels': b.out_channels, 'kernel_size': b.kernel_size, 'stride': b.stride,
-                'groups': 1, 'has_shuffle': False, 'bias': False, 'use_bn': True, 'affine': True, 'act_func': b.act_func}
+                'groups': 1, 'has_shuffle': False, 'bias': False, 'use_bn': True, 'affine': True, 'act_func': b.act_func,
+                **geometry.se_style_keys(b.se_act, b.se_gate)}      # ('se_act' / 'se_gate': only where not the default)
 
     @property
     def config(self):
@@ -141,7 +142,7 @@ class _DerivedBase(nn.Module):
 
 class Network(_DerivedBase):
     def __init__(self, num_classes, parsed_arch, mc_num_dddict, lat_lookup=None, dropout_rate=0.0, drop_connect_rate=0.0,
-                 primitives=None):
+                 primitives=None, se_style=None):
         super().__init__()
         self.lat_lookup, self.mc_num_dddict, self.parsed_arch = lat_lookup, mc_num_dddict, parsed_arch
         self.dropout_rate, self.drop_connect_rate = dropout_rate, drop_connect_rate
@@ -161,7 +162,9 @@ class Network(_DerivedBase):
                 prim = geometry.cell_primitives(primitives, name, block_name)[op]
                 layer, mc, se, k = geometry.primitive_block(prim, ic, mc_num_dddict[name][block_name][op])
                 cls = FusedMBConvBlock if layer == 'FusedMBConvBlock' else MBInvertedResBlock
-                blk = cls(ic, mc, se, oc, k, s, affine=True, act_func=cfg['act'])
+                # (``se_style``: likewise -- None, one (se_act, se_gate) pair or a {stage: pair} mapping; the stems keep theirs)
+                se_act, se_gate = _lib.se_style_pair(geometry.cell_se_style(se_style, name, block_name))
+                blk = cls(ic, mc, se, oc, k, s, affine=True, act_func=cfg['act'], se_act=se_act, se_gate=se_gate)
                 blk.drop_connect_rate = self.drop_connect_rate * self.block_idx / self.block_count
                 stage.append(blk)
             setattr(self, name, stage)
@@ -184,8 +187,12 @@ class NetworkCfg(_DerivedBase):
                 kinds['FusedMBConvBlock'] = FusedMBConvBlock
             if c['name'] not in kinds or c.get('groups', 1) != 1 or c.get('has_shuffle') or c.get('bias'):
                 raise NotImplementedError('only plain MBInvertedResBlock / FusedMBConvBlock configs are supported: %r' % (c,))
+            se_act, se_gate = c.get('se_act'), c.get('se_gate', 'sigmoid')
+            if not fused_ok and _lib.se_style_id(se_act, se_gate) != 0:
+                raise NotImplementedError('second_stem runs fused with first_stem and keeps the default squeeze-excite: %r' % (c,))
             return kinds[c['name']](c['in_channels'], c['mid_channels'], c['se_channels'], c['out_channels'],
-                                      c['kernel_size'], c['stride'], affine=c.get('affine', True), act_func=c['act_func'])
+                                      c['kernel_size'], c['stride'], affine=c.get('affine', True), act_func=c['act_func'],
+                                      se_act=se_act, se_gate=se_gate)
         fs = model_config['first_stem']
         self.first_stem = ConvLayer(fs['in_channels'], fs['out_channels'], fs['kernel_size'], fs['stride'], affine=True,
                                     act_func=fs['act_func'])

@@ -83,13 +83,26 @@ def _cell_primitives(primitives, stage, block):
     return per_stage.get(block)
 
 
+def _cell_se_style(se_style, name):
+    """``se_style`` of a MixedStage / Network for one of its parts: one (se_act, se_gate) pair (or None) for every part, or a
+    {name: pair} mapping -- {block: pair} for a MixedStage, {stage: pair} (or {stage: {block: pair}}) for a Network -- whose
+    missing entries mean the default."""
+    return se_style.get(name) if isinstance(se_style, dict) else se_style
+
+
 _SAMPLE_MODES = {'gumbel': 0, 'gumbel_2': 0, 'min_alphas': 1, 'max_alphas': 2}
 
 
 class MixedOP(nn.Module):
-    def __init__(self, in_channels, out_channels, stride, affine, act_func, num_ops, mc_num_dict, lat_lookup, primitives=None):
+    def __init__(self, in_channels, out_channels, stride, affine, act_func, num_ops, mc_num_dict, lat_lookup, primitives=None,
+                 se_style=None):
         super().__init__()
         self.primitives = check_primitives(primitives)
+        # squeeze-excite style of the cell, one for all its candidates: None (the reference's: hidden activation = act_func,
+        # logistic gate) or a (se_act, se_gate) pair, e.g. MobileNetV3's ('relu', 'h-sigmoid') -- layers._HipBlock.  The latency
+        # tables know no style: a styled candidate is looked up under the key of its logistic twin (nobody has measured the
+        # hard-sigmoid forward beside the logistic one on this chip).
+        self.se_style = _lib.se_style_pair(se_style)
         self.num_ops = num_ops
         self.lat_lookup = lat_lookup
         self.mc_num_dict = mc_num_dict
@@ -98,6 +111,8 @@ class MixedOP(nn.Module):
         for i in range(num_ops):
             self.m_ops.append(OPS[self.primitives[i]](in_channels, self.mc_num_dict[i], out_channels, stride, affine,
                                                  act_func))
+            self.m_ops[-1].set_se_style(self.se_style)     # (the registry's factories keep their signature: applied here,
+                                                           #  before any plan of the cell exists)
         self._initialize_log_alphas()
         self.reset_switches()
         self.T = 1.0
@@ -206,7 +221,8 @@ class MixedOP(nn.Module):
 
 
 class MixedStage(nn.Module):
-    def __init__(self, ics, ocs, ss, affs, acts, mc_num_ddict, lat_lookup, stage_type, primitives=None, stage_name=None):
+    def __init__(self, ics, ocs, ss, affs, acts, mc_num_ddict, lat_lookup, stage_type, primitives=None, stage_name=None,
+                 se_style=None):
         super().__init__()
         self.lat_lookup = lat_lookup
         self.mc_num_ddict = mc_num_ddict
@@ -220,7 +236,8 @@ class MixedStage(nn.Module):
         for b in range(nblocks):
             setattr(self, 'block%d' % (b + 1),
                     MixedOP(ics[b], ocs[b], ss[b], affs[b], acts[b], len(PRIMITIVES), mc_num_ddict['block%d' % (b + 1)],
-                            lat_lookup, primitives=_cell_primitives(primitives, stage_name, 'block%d' % (b + 1))))
+                            lat_lookup, primitives=_cell_primitives(primitives, stage_name, 'block%d' % (b + 1)),
+                            se_style=_cell_se_style(se_style, 'block%d' % (b + 1))))
         self._initialize_betas()
 
     def blocks(self):
@@ -257,8 +274,9 @@ SECOND_PATH_ON_SIDE_STREAM = True       # the 'random' forward of a bi-sampling 
 
 
 class Network(nn.Module):
-    def __init__(self, num_classes, mc_num_dddict, lat_lookup, primitives=None):
+    def __init__(self, num_classes, mc_num_dddict, lat_lookup, primitives=None, se_style=None):
         super().__init__()
+        self.se_style = se_style               # (of the MixedOP cells; the stems keep the reference's squeeze-excite)
         self.lat_lookup = lat_lookup
         self.mc_num_dddict = mc_num_dddict
 
@@ -276,7 +294,7 @@ class Network(nn.Module):
         for name, ics, ocs, ss, act, st in cfg:
             setattr(self, name, MixedStage(ics=ics, ocs=ocs, ss=ss, affs=[False] * len(ics), acts=[act] * len(ics),
                                            mc_num_ddict=mc_num_dddict[name], lat_lookup=lat_lookup, stage_type=st,
-                                           primitives=primitives, stage_name=name))
+                                           primitives=primitives, stage_name=name, se_style=_cell_se_style(se_style, name)))
         self.feature_mix_layer = ConvLayer(320, 1280, kernel_size=1, stride=1, affine=False, act_func='swish')
         self.global_avg_pooling = nn.AdaptiveAvgPool2d(1)
         self.classifier = LinearLayer(1280, num_classes)

@@ -9,7 +9,7 @@ from collections import OrderedDict
 
 import torch
 
-from . import geometry
+from . import _lib, geometry
 from .epoch import get_op_and_depth_weights, parse_architecture          # noqa: F401  (re-exported: parsing_model.py API)
 from .geometry import get_mc_num_dddict                                  # noqa: F401
 from .latency import get_lookup_latency
@@ -29,11 +29,14 @@ def _mbconv_config(ic, mc, se, oc, k, stride, act):
             'affine': True, 'act_func': act}
 
 
-def derived_config(parsed_arch, mc_num_dddict, num_classes=1000, primitives=None):
+def derived_config(parsed_arch, mc_num_dddict, num_classes=1000, primitives=None, se_style=None):
     """``models/model_eval.Network(num_classes, parsed_arch, mc_num_dddict).config`` (model_eval.py:214-228).  ``primitives``:
     what the searched network was built with (model_search.Network(primitives=...): one list, or a {stage: {block: list}}
     mapping); a Fused-MBConv choice is written as a 'FusedMBConvBlock' entry, an expand-free one as the reference records such a
-    block (an 'MBInvertedResBlock' with mid_channels == in_channels) -- both load in model_eval.NetworkCfg."""
+    block (an 'MBInvertedResBlock' with mid_channels == in_channels) -- both load in model_eval.NetworkCfg.  ``se_style``: the
+    squeeze-excite style the searched network was built with (model_search.Network(se_style=...): None, one (se_act, se_gate) pair
+    or a {stage: pair} mapping); a block's entry carries 'se_act' / 'se_gate' keys only where they differ from the default (the
+    block's own activation, 'sigmoid'), so a config without a style is what it always was."""
     cfg = OrderedDict()
     cfg['first_stem'] = _conv_layer_config(3, 32, 3, 2, 'relu')
     cfg['second_stem'] = _mbconv_config(32, 32, 8, 16, 3, 1, 'relu')
@@ -46,7 +49,8 @@ def derived_config(parsed_arch, mc_num_dddict, num_classes=1000, primitives=None
             op = parsed_arch[stage][name]
             prim = geometry.cell_primitives(primitives, stage, name)[op]
             layer, mc, se, k = geometry.primitive_block(prim, ic, mc_num_dddict[stage][name][op])
-            blocks.append(dict(_mbconv_config(ic, mc, se, oc, k, s, st['act']), name=layer))
+            blocks.append(dict(_mbconv_config(ic, mc, se, oc, k, s, st['act']), name=layer,
+                               **geometry.se_style_keys(*_lib.se_style_pair(geometry.cell_se_style(se_style, stage, name)))))
         cfg[stage] = blocks
     cfg['feature_mix_layer'] = _conv_layer_config(320, 1280, 1, 1, 'swish')
     cfg['classifier'] = {'name': 'LinearLayer', 'in_features': 1280, 'out_features': num_classes, 'bias': True,
@@ -125,7 +129,7 @@ def count_params_in_MB(config):
     return n / 1e6
 
 
-def parse_searched_model(model_or_path, lat_lookup=None, num_classes=1000, save_path=None, primitives=None):
+def parse_searched_model(model_or_path, lat_lookup=None, num_classes=1000, save_path=None, primitives=None, se_style=None):
     """parsing_model.py's __main__ (:91-134) as a function: checkpoint / model -> dict(parsed_arch, mc_num_dddict, config,
     lat_lut, params_MB, macs_M); optionally writes the config JSON like ``--save_path``."""
     if isinstance(model_or_path, str):
@@ -135,13 +139,15 @@ def parse_searched_model(model_or_path, lat_lookup=None, num_classes=1000, save_
     else:
         net = getattr(model_or_path, 'module', model_or_path)
         sd, mc_num = net.state_dict(), net.mc_num_dddict
+        if se_style is None:                                   # (a model built with se_style=...: export what it was built with)
+            se_style = getattr(net, 'se_style', None)
         if hasattr(net, 'cells') and hasattr(net, 'plain_candidates') and not net.plain_candidates():
             # (a model built with primitives=...: export what its cells hold)
             primitives = {}
             for (stage, block, *_), cell in zip(geometry.iter_cells(), net.cells()):
                 primitives.setdefault(stage, {})[block] = list(cell.primitives)
     parsed = parse_architecture(*get_op_and_depth_weights(sd))
-    config = derived_config(parsed, mc_num, num_classes, primitives)
+    config = derived_config(parsed, mc_num, num_classes, primitives, se_style)
     out = dict(parsed_arch=parsed, mc_num_dddict=mc_num, config=config, params_MB=count_params_in_MB(config),
                macs_M=count_macs_in_M(config))
     if lat_lookup is not None:

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import TfnasCellDesc, TfnasPathDesc, TfnasPathWs, check, ptr, raw_array
-from .functions import BN_EPS, DEFAULT_MODES, EFREE, EFREE_STRIDE1, _nhwc, _on, _require_cuda
+from .functions import BN_EPS, DEFAULT_MODES, EFREE, EFREE_STRIDE1, _nhwc, _on, _require_cuda, blocks_se_style, mark_se_style
 
 ALIGN = 64          # floats; every parameter starts on a 256-byte boundary of the arenas
 
@@ -159,6 +159,7 @@ class PathRunner:
         t = self._tmpl.get(key)
         if t is not None and t.g[0].w_expand == blocks[0].inverted_bottleneck.conv.weight.data_ptr():
             getattr(cell, 'hip_modes', DEFAULT_MODES).apply(t)          # (the model's launch modes may have changed)
+            mark_se_style(t, blocks_se_style(blocks))                   # (apply rewrites flags; the cell's squeeze-excite style)
             return t
         d = TfnasCellDesc()
         d.N, d.H, d.W, d.ic, d.oc, d.stride = N, H, W, cell.in_channels, cell.out_channels, cell.stride
@@ -178,6 +179,7 @@ class PathRunner:
                 for j, f in enumerate(_lib._G_FIELDS[:len(ps)]):
                     setattr(d.g[g], f, self.weights.grad_ptr(ps[j]))
         getattr(cell, 'hip_modes', DEFAULT_MODES).apply(d)
+        mark_se_style(d, blocks_se_style(blocks))
         check(self.lib.tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
         self._tmpl[key] = d
         return d
