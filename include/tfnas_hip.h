@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-/* 4, additive: TFNAS_CELL_SE_STYLE -- TfnasCellDesc.se_style: the squeeze-excite hidden activation and gate function of a cell.
+/* 4, additive: TFNAS_CELL_SKIP -- TFNAS_GROUP_SKIP: the identity candidate in a residual TFNAS_CELL_KINDS cell.
+ * 4, additive: TFNAS_CELL_SE_STYLE -- TfnasCellDesc.se_style: the squeeze-excite hidden activation and gate function of a cell.
  * 4, additive: TFNAS_CELL_KINDS -- a per-group kind (TfnasGroup.kind): plain, expand-free and Fused-MBConv candidates in ONE cell.
  * 4, additive: TFNAS_CELL_FUSED -- a Fused-MBConv block (dense 3 x 3 convolution, no depthwise) through tfnas_mixedop_* / tfnas_mbconv_*.
  * 4, additive: TFNAS_CELL_NOEXPAND -- a block without expand convolution (mid <= in channels) through tfnas_mixedop_* / tfnas_mbconv_*.
@@ -143,7 +144,8 @@ typedef struct TfnasCellDesc {
                                  TFNAS_CELL_NOEXPAND: the one group has no expand convolution;
                                  TFNAS_CELL_FUSED: the one group is a Fused-MBConv block (dense 3 x 3 convolution);
                                  TFNAS_CELL_KINDS: every group has a kind of its own (TfnasGroup.kind);
-                                 TFNAS_CELL_SE_STYLE: se_style may be non-zero                                           [in]
+                                 TFNAS_CELL_SE_STYLE: se_style may be non-zero;
+                                 TFNAS_CELL_SKIP: groups may be TFNAS_GROUP_SKIP, the identity candidate                 [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -314,6 +316,36 @@ typedef struct TfnasCellDesc {
 #define TFNAS_GROUP_MBCONV 0
 #define TFNAS_GROUP_NOEXPAND 1
 #define TFNAS_GROUP_FUSED 2
+/* TfnasCellDesc.flags: the caller knows the skip (identity) candidate of the MobileNet-family search spaces -- the reference's
+ * commented-out 'skip' primitive (models/model_search.py:16,28; models/layers.py:274-319).  Additive like the bits above: without
+ * the bit every descriptor is accepted, refused, planned, sized, routed and launched exactly as before (TfnasGroup.kind = 3 stays
+ * TFNAS_EINVAL).  With it a group may say TFNAS_GROUP_SKIP in g.kind: the candidate that returns the cell's input.  The cell computes
+ *   out = sum_{g computing} wmix[g] BN3_g(project_g(...)) + (sum_{ALL g} wmix[g]) x
+ * which is the reference's sum_g w_g op_g(x): every MBConv candidate of a residual cell adds x itself, the identity candidate is x.
+ * Backward: dwmix[g] of a computing group as before; dwmix[g] of a skip group = <dout, x> (the per-channel sums the BN3 backward
+ * pass forms anyway, added in double in a fixed order); dx gains (sum of ALL wmix[g]) dout, once.  A skip group is not a kind: it
+ * has no weights, no BatchNorm site, no columns of the [pixels][M] tensors and no Pr slot.  Rules, checked by tfnas_cell_plan and
+ * again by every entry point before any pointer is looked at (TFNAS_EINVAL unless stated):
+ *   - TFNAS_CELL_KINDS must be set too; mode == TFNAS_MODE_CELL; has_res == 1 (hence ic == oc, stride == 1);
+ *   - a SKIP group has mc == 0, k == 0, se == 0 and every weight and gradient pointer NULL; the plan gives it mcp = 0 and no
+ *     columns (M and SE are those of the other groups);
+ *   - SKIP groups come after every other group, so wmix[g] / dwmix[g] of the G' = G - nskip computing groups keep their indices;
+ *     at least one group computes (G' >= 1: a caller that samples the skip alone launches nothing);
+ *   - such a cell is always a mixed cell: it is never folded into the unflagged or one-block form, even when its computing groups
+ *     are all plain or there is one.  tfnas_efree_supported and tfnas_fx_supported return 0, tfnas_cell_route returns
+ *     TFNAS_ROUTE_TAKEN_VALID, and a plain group needs its E buffer (E == NULL is TFNAS_ENULL): the residual gradient is added
+ *     once at the end over all mix weights, which the one-kind routes -- adding it inside their own dgrad kernels -- cannot do;
+ *   - a descriptor that carries the bit but has no SKIP group plans, sizes, routes and runs bit for bit like the same descriptor
+ *     without the bit;
+ *   - tfnas_cell_ws reports, field for field, what the descriptor without its SKIP groups (flags & ~TFNAS_CELL_SKIP, G = G')
+ *     reports: Pr, stats3, red3 and the partial rows are sized by G'; wmix and dwmix are the caller's [G];
+ *   - tfnas_mbconv_fwd/bwd, tfnas_path_plan, TFNAS_MODE_STEM and TFNAS_MODE_HEAD refuse the bit as they refuse TFNAS_CELL_KINDS.
+ * Launch sequence: everything runs on the first G' groups as for any TFNAS_CELL_KINDS cell; four kernels see G -- the forward mix
+ * and the residual-gradient pass (the sum of the mix weights), the BN3-backward sums (the <dout, x> accumulator of a residual cell)
+ * and the dwmix kernel (one wave per entry).  TFNAS_CELL_ACCUM_WGRAD, dx == NULL, need_wgrad == 0, the dwmix-only early return,
+ * wgrad_stream[], the sync-stats hook (table lengths follow G'), se_style, TFNAS_CELL_K7 and TFNAS_CELL_ACTS keep their meaning. */
+#define TFNAS_CELL_SKIP 0x2000
+#define TFNAS_GROUP_SKIP 3
 /* TfnasCellDesc.route (ABI 4; rounds 2-5 read these from TFNAS_* environment variables latched once per process) */
 #define TFNAS_ROUTE_FX_OFF 0x1        /* frozen-weight launches of the 14 x 14 / 7 x 7 cells through the materialised route instead
                                          of the fused per-image kernels (csrc/fx_kernels.hip)                                   */

@@ -175,11 +175,25 @@ static int check_se_style(const TfnasCellDesc* d) {
 // the kind bits of a descriptor.  Both newer kinds are ONE block in cell mode; TFNAS_CELL_NOEXPAND: mc == ic channels, no expand
 // weight or gradient pointer; TFNAS_CELL_FUSED: a dense 3 x 3 weight (w_expand), no depthwise pointer; never both bits
 // TFNAS_CELL_KINDS: the same rules per group (TfnasGroup.kind), any G; the two one-block bits must then be clear
+// TFNAS_CELL_SKIP (with TFNAS_CELL_KINDS only): groups may be TFNAS_GROUP_SKIP, the identity candidate -- a residual cell, the skip
+// groups last and empty (no width, no kernel size, no SE, no pointer), at least one computing group before them
 static int check_kind(const TfnasCellDesc* d) {
+    if (cell_skip(*d) && !cell_mixed(*d)) return TFNAS_EINVAL;
     if (cell_mixed(*d)) {
         if (d->mode != TFNAS_MODE_CELL || cell_noexpand(*d) || cell_fused(*d)) return TFNAS_EINVAL;
+        if (cell_skip(*d) && (d->has_res != 1 || d->ic != d->oc || d->stride != 1)) return TFNAS_EINVAL;
+        bool skips = false;
         for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g) {
             const TfnasGroup& gr = d->g[g];
+            if (cell_skip(*d) && gr.kind == TFNAS_GROUP_SKIP) {
+                if (g == 0 || gr.mc != 0 || gr.k != 0 || gr.se != 0) return TFNAS_EINVAL;
+                if (gr.w_expand || gr.w_dw || gr.w_proj || gr.w_se_r || gr.b_se_r || gr.w_se_e || gr.b_se_e || gr.g_expand ||
+                    gr.g_dw || gr.g_proj || gr.g_se_r || gr.gb_se_r || gr.g_se_e || gr.gb_se_e)
+                    return TFNAS_EINVAL;
+                skips = true;
+                continue;
+            }
+            if (skips) return TFNAS_EINVAL;           // (a computing group after a skip: wmix / dwmix indices would move)
             if (gr.kind < TFNAS_GROUP_MBCONV || gr.kind > TFNAS_GROUP_FUSED) return TFNAS_EINVAL;
             if (gr.kind == TFNAS_GROUP_NOEXPAND && (gr.mc != d->ic || gr.w_expand || gr.g_expand)) return TFNAS_EINVAL;
             if (gr.kind == TFNAS_GROUP_FUSED && (gr.k != 3 || gr.w_dw || gr.g_dw)) return TFNAS_EINVAL;
@@ -204,7 +218,7 @@ static int check_modes(const TfnasCellDesc* d) {
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
     if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS | TFNAS_CELL_NOEXPAND |
-                     TFNAS_CELL_FUSED | TFNAS_CELL_KINDS | TFNAS_CELL_SE_STYLE))
+                     TFNAS_CELL_FUSED | TFNAS_CELL_KINDS | TFNAS_CELL_SE_STYLE | TFNAS_CELL_SKIP))
         return TFNAS_EINVAL;
     TRY(check_kind(d));
     TRY(check_se_style(d));
@@ -223,10 +237,13 @@ static int check_modes(const TfnasCellDesc* d) {
 // The canonical form of a (checked) descriptor, which everything past the checks works on: without TFNAS_CELL_KINDS the
 // descriptor itself.  With it: all groups plain -- the bit dropped; one group -- its one-block bit instead (both then plan,
 // size, route and run exactly like the descriptor a caller without the bit would have written); anything else keeps the bit: a
-// mixed cell (kernels.h: cell_mixed).
+// mixed cell (kernels.h: cell_mixed).  TFNAS_CELL_SKIP: without a skip group the bit is dropped first (the descriptor is the one
+// without the bit); with one the cell is mixed whatever its computing groups are -- never folded.
 static TfnasCellDesc kinds_canon(const TfnasCellDesc& d) {
     TfnasCellDesc c = d;
     if (!cell_mixed(d)) return c;
+    if (skip_groups(d) > 0) return c;
+    c.flags &= ~TFNAS_CELL_SKIP;
     bool plain = true;
     for (int g = 0; g < d.G && g < TFNAS_MAX_GROUPS; ++g) plain = plain && d.g[g].kind == TFNAS_GROUP_MBCONV;
     if (plain || d.G == 1) {
@@ -246,6 +263,14 @@ static int kind_subset(const TfnasCellDesc& d, CellKind kind, TfnasCellDesc& sub
     sub.flags |= kind == TFNAS_KIND_FUSED ? TFNAS_CELL_FUSED : kind == TFNAS_KIND_NOEXPAND ? TFNAS_CELL_NOEXPAND : 0;
     return n;
 }
+// the computing groups of a (canonical) cell as a descriptor of their own: the first G' = G - skip_groups(d) groups, still a mixed
+// cell (TFNAS_CELL_KINDS stays: its launch sequences add the residual once, over all mix weights)
+static TfnasCellDesc skip_strip(const TfnasCellDesc& d) {
+    TfnasCellDesc c = d;
+    c.G -= skip_groups(d);
+    c.flags &= ~TFNAS_CELL_SKIP;
+    return c;
+}
 static TfnasCellDesc group_alone(const TfnasCellDesc& sub, int g) {
     TfnasCellDesc one = sub;
     one.g[0] = sub.g[g];
@@ -254,7 +279,8 @@ static TfnasCellDesc group_alone(const TfnasCellDesc& sub, int g) {
 }
 
 // (a canonical descriptor; a mixed cell: the limits of the one-block kinds hold per kind / per FUSED group)
-static bool wgrad_row_fits(const TfnasCellDesc& d) {
+static bool wgrad_row_fits(const TfnasCellDesc& d0) {
+    const TfnasCellDesc d = skip_strip(d0);
     if (!cell_mixed(d)) return cell_fused(d) ? conv_wgrad_row_fits(d) : dw_wgrad_row_fits(d);
     TfnasCellDesc sub;
     if (kind_subset(d, TFNAS_KIND_MBCONV, sub) && !dw_wgrad_row_fits(sub)) return false;
@@ -294,6 +320,12 @@ extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
     int off = 0, se_off = 0;
     for (int g = 0; g < d->G; ++g) {
         TfnasGroup& gr = d->g[g];
+        if (cell_skip(*d) && gr.kind == TFNAS_GROUP_SKIP) {      // (checked empty and last by check_kind: no columns of anything)
+            gr.mcp = 0;
+            gr.off = (off + 31) & ~31;
+            gr.se_off = se_off;
+            continue;
+        }
         if (gr.mc < 1 || (gr.k != 3 && gr.k != 5 && gr.k != 7) ||      // (7: with TFNAS_CELL_K7 only, check_modes)
             gr.se < 0) return TFNAS_EINVAL;
         if (gr.se & 3) return TFNAS_EINVAL;       // SE widths are in_channels x {1, 2} in the search space; the excite
@@ -324,7 +356,8 @@ extern "C" int tfnas_cell_ws(const TfnasCellDesc* d, TfnasCellWs* ws) {
     if (!d || !ws) return TFNAS_ENULL;
     memset(ws, 0, sizeof(*ws));
     if (cell_mixed(*d) && check_kind(d) != 0) return TFNAS_EINVAL;      // (TfnasGroup.kind is about to be read)
-    const TfnasCellDesc c = kinds_canon(*d);
+    // (skip groups own nothing of the workspace: what the descriptor without them reports, dwmix is the caller's [G])
+    const TfnasCellDesc c = kinds_canon(skip_strip(kinds_canon(*d)));
     return cell_ws_canon(&c, ws);
 }
 static int cell_ws_canon(const TfnasCellDesc* d, TfnasCellWs* ws) {
@@ -447,7 +480,9 @@ int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdB
     // affine / eval BatchNorm: the producers run as usual; their statistics tables are rewritten as effective (mean, rstd)
     // before the consumers -- which then run with eps = -1 (tfnas_dev.h: bn_consts) -- read them
     const TfnasBnAffine* bn = b.bn;
-    TfnasCellDesc dc = d0;
+    // skip groups (kernels.h: cell_skip) take part in the mix alone: everything else runs on the computing groups' descriptor
+    const int nw = d0.G;
+    TfnasCellDesc dc = skip_strip(d0);
     if (bn) dc.eps = -1.f;
     const TfnasCellDesc& d = dc;
     // E-free late cells (14 x 14 / 7 x 7 images, 64..192 input channels): the fused per-image route (fx_kernels.hip)
@@ -485,10 +520,10 @@ int cell_fwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellFwdB
         // drop-connect (tools/utils.py:77-86): out = scale[n] * BN3(.) + x -- the mix kernel without its residual, then one pass
         TfnasCellDesc dn = dc;
         dn.has_res = 0;
-        TRY(launch_mix_fwd(dn, b.Pr, stats3, b.wmix, b.x, b.out, s));
+        TRY(launch_mix_fwd(dn, nw, b.Pr, stats3, b.wmix, b.x, b.out, s));
         return launch_rowscale(b.out, b.out, b.x, b.drop_scale, d.N, (uint64_t)d.Ho * d.Wo * d.oc, s);
     }
-    TRY(launch_mix_fwd(d, b.Pr, stats3, b.wmix, b.x, b.out, s));              // sum_g w_g BN3(.) + residual
+    TRY(launch_mix_fwd(d, nw, b.Pr, stats3, b.wmix, b.x, b.out, s));          // sum_g w_g BN3(.) + residual (all nw weights)
     return 0;
 }
 
@@ -530,7 +565,8 @@ static int expand_dx(const TfnasCellDesc& d, const float* dEh, const float* x, c
 namespace {
 struct CellBwd {
     const TfnasCellDesc& d0;         // the caller's descriptor
-    TfnasCellDesc d;                 // the launch's: eps = -1 with affine BatchNorm
+    TfnasCellDesc d;                 // the launch's: eps = -1 with affine BatchNorm; without the caller's skip groups (skip_strip)
+    int nw;                          // entries of wmix / dwmix: the caller's G
     const TfnasCellWs& ws;
     CellBwdBufs b;
     hipStream_t s;
@@ -564,7 +600,7 @@ int CellBwd::run() {
     }
     TRY(launch_mix_bwd_stats(d, b.dout, b.Pr, stats3, b.x, red3, part, s));           // BN3 backward sums (+ d wmix)
     TRY(stats_sync(d, red3, 2 * (size_t)d.G * d.oc, s));
-    if (b.dwmix) TRY(launch_mix_dw(d, red3, b.red + ws.off_resdot, b.dwmix, s));
+    if (b.dwmix) TRY(launch_mix_dw(d, nw, red3, b.red + ws.off_resdot, b.dwmix, s));    // (skip entries: <dout, x> alone)
     if (bn) TRY(bn_bwd_fix(d0, bn, 2, red3, s));
     // Nothing upstream wants a gradient (first cell of the alpha-step: frozen weights, input = stem output):
     // d wmix is the only product, like autograd pruning the same sub-graph in the reference.
@@ -709,7 +745,7 @@ int CellBwd::tail_mixed() {
             stored = true;
         }
     }
-    if (b.dx && d.has_res) TRY(launch_dx_add_res(d, dout_res, b.wmix, b.dx, s));
+    if (b.dx && d.has_res) TRY(launch_dx_add_res(d, nw, dout_res, b.wmix, b.dx, s));
     return 0;
 }
 }  // namespace
@@ -723,7 +759,7 @@ int cell_bwd_impl(const TfnasCellDesc& d0, const TfnasCellWs& ws, const CellBwdB
     const int taken = route_taken(d0, bn != nullptr);
     if ((fwd_route & TFNAS_ROUTE_TAKEN_VALID) && taken != fwd_route) return TFNAS_EINVAL;
     const CellBwdBufs& b = b0;
-    CellBwd c = {d0, d0, ws, b0, s, so, bn, taken, b0.dout,
+    CellBwd c = {d0, skip_strip(d0), d0.G, ws, b0, s, so, bn, taken, b0.dout,
                  b.stats + ws.off_stats1, b.stats + ws.off_stats2, b.stats + ws.off_stats3,
                  b.fsmall + ws.off_pooled, b.fsmall + ws.off_gate, b.fsmall + ws.off_hpre,
                  b.bsmall + ws.off_dgate, b.bsmall + ws.off_dpooled, b.bsmall + ws.off_dhpre, b.bsmall + ws.off_cb1,

@@ -883,7 +883,7 @@ __global__ __launch_bounds__(256) void k_dx_reduce(TfnasCellDesc d, const float*
 // dx += (sum_g wmix[g]) * dout: the residual gradient of a cell whose groups differ in kind (kernels.h: cell_mixed), added ONCE
 // after the last branch's data gradient (every branch runs with has_res = 0: the branches see sub-descriptors, whose group
 // indices do not index wmix).  One more pass over dx [N*H*W][ic], the narrowest tensor of the backward; each element read and
-// written by one thread.  wmix == NULL: weight 1.
+// written by one thread.  wmix == NULL: weight 1.  G: the entries of wmix, skip groups included (launch_dx_add_res: nw).
 __global__ __launch_bounds__(256) void k_dx_add_res(const float* __restrict__ dout, const float* __restrict__ wmix, int G,
                                                     float* __restrict__ dx, size_t n4) {
     float sumw = 1.f;
@@ -894,12 +894,12 @@ __global__ __launch_bounds__(256) void k_dx_add_res(const float* __restrict__ do
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
         st4(dx + 4 * i, ld4(dx + 4 * i) + splat4(sumw) * ld4(dout + 4 * i));
 }
-int launch_dx_add_res(const TfnasCellDesc& d, const float* dout, const float* wmix, float* dx, hipStream_t s) {
+int launch_dx_add_res(const TfnasCellDesc& d, int nw, const float* dout, const float* wmix, float* dx, hipStream_t s) {
     if (!d.has_res || !dout || !dx) return TFNAS_EINVAL;
     const size_t n4 = (size_t)d.N * d.H * d.W * d.ic / 4;
     size_t gx = (n4 + 255) / 256;
     if (gx > 2048) gx = 2048;
-    hipLaunchKernelGGL(k_dx_add_res, dim3((unsigned)gx), dim3(256), 0, s, dout, wmix, d.G, dx, n4);
+    hipLaunchKernelGGL(k_dx_add_res, dim3((unsigned)gx), dim3(256), 0, s, dout, wmix, nw, dx, n4);
     return (int)hipGetLastError();
 }
 

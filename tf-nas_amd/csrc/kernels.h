@@ -61,6 +61,18 @@ static inline bool cell_mixed(const TfnasCellDesc& d) { return (d.flags & TFNAS_
 static inline CellKind group_kind(const TfnasCellDesc& d, int g) {
     return cell_mixed(d) && !cell_fused(d) && !cell_noexpand(d) ? (CellKind)d.g[g].kind : cell_kind(d);
 }
+// TFNAS_CELL_SKIP: groups of a mixed residual cell may be TFNAS_GROUP_SKIP, the identity candidate.  It is not a kind either: a
+// skip group binds no field, has no BatchNorm site and no columns anywhere; it adds its mix weight to the residual term, one entry
+// to dwmix (<dout, x>) and nothing else.  Skip groups stand last (capi.hip: check_kind), so the launch sequences run on the
+// descriptor of the first G' = G - skip_groups(d) groups (capi.hip: skip_strip) and only the four kernels that sum or emit mix
+// weights are told the caller's G (launch_mix_fwd, launch_mix_dw, launch_dx_add_res: `nw`).
+static inline bool cell_skip(const TfnasCellDesc& d) { return (d.flags & TFNAS_CELL_SKIP) != 0; }
+static inline int skip_groups(const TfnasCellDesc& d) {
+    int n = 0;
+    if (cell_skip(d) && cell_mixed(d))
+        for (int g = d.G < TFNAS_MAX_GROUPS ? d.G : TFNAS_MAX_GROUPS; g > 0 && d.g[g - 1].kind == TFNAS_GROUP_SKIP; --g) ++n;
+    return n;
+}
 // group-aware forms of the two facts: some group has an E buffer / a BatchNorm site 0
 static inline bool any_group_has_E(const TfnasCellDesc& d) {
     for (int g = 0; g < d.G; ++g)
@@ -146,8 +158,9 @@ int launch_expand_dgrad(const TfnasCellDesc& d, const float* dEh, const float* x
                         const float* add_src = nullptr, const float* add_scale = nullptr, int nsl = -1);
 int launch_expand_wgrad(const TfnasCellDesc& d, const float* dEh, const float* E, const float* cb1,
                         const float* x, float* part, hipStream_t s);
-// dx += (sum of the d.G mix weights) * dout: the residual gradient of a mixed residual cell, after its last branch
-int launch_dx_add_res(const TfnasCellDesc& d, const float* dout, const float* wmix, float* dx, hipStream_t s);
+// dx += (sum of the nw mix weights) * dout: the residual gradient of a mixed residual cell, after its last branch
+// (nw: entries of wmix -- d.G, plus the skip groups of the caller's descriptor)
+int launch_dx_add_res(const TfnasCellDesc& d, int nw, const float* dout, const float* wmix, float* dx, hipStream_t s);
 
 // dwconv_kernels.hip: the depthwise k x k convolution in three kernel families, each with the geometry struct its kernels take by
 // value: k = 3 | 5 in all of them, k = 7 in the LDS tile kernels only (a cell with a 7 x 7 group is planned onto those in every
@@ -249,11 +262,13 @@ int launch_conv_dgrad(const TfnasCellDesc& d, const float* dd, const float* dres
 int launch_se_pool(const TfnasCellDesc& d, const float* D, const double* stats2, float* pooled, hipStream_t s);
 int launch_se_fc_fwd(const TfnasCellDesc& d, const float* pooled, float* hpre, float* gate, float* scratch,
                      size_t scratch_floats, hipStream_t s);
-int launch_mix_fwd(const TfnasCellDesc& d, const float* Pr, const double* stats3, const float* wmix,
+// nw: entries of wmix (and of dwmix) -- d.G, plus the skip groups of the caller's descriptor (cell_skip), which stand after the
+// d.G computing groups: they add to the residual weight / get <dout, x> alone
+int launch_mix_fwd(const TfnasCellDesc& d, int nw, const float* Pr, const double* stats3, const float* wmix,
                    const float* x, float* out, hipStream_t s);
 int launch_mix_bwd_stats(const TfnasCellDesc& d, const float* dout, const float* Pr, const double* stats3,
                          const float* x, double* red3, float* part, hipStream_t s);
-int launch_mix_dw(const TfnasCellDesc& d, const double* red3, const double* resdot, float* dwmix, hipStream_t s);
+int launch_mix_dw(const TfnasCellDesc& d, int nw, const double* red3, const double* resdot, float* dwmix, hipStream_t s);
 int launch_se_bwd_reduce(const TfnasCellDesc& d, const float* dZ, const float* D, const double* stats2,
                          float* dgate, hipStream_t s);
 int launch_se_fc_bwd(const TfnasCellDesc& d, const float* dgate, const float* gate, const float* hpre, float* dhpre,

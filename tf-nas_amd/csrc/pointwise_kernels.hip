@@ -97,15 +97,16 @@ __global__ __launch_bounds__(256) void k_se_pool(TfnasCellDesc d, const float* _
 
 // ============================================================================ mixing epilogue (forward)
 // out[p][o] = sum_g wmix[g] * BN3(Pr[g])[p][o]  (+ (sum_g wmix[g]) * x[p][o] for residual cells)
+// nw >= d.G mix weights: those past the d.G computing groups belong to skip (identity) groups -- the residual term alone
 __global__ __launch_bounds__(256) void k_mix_fwd(TfnasCellDesc d, const float* __restrict__ Pr,
                                                  const double* __restrict__ stats3, const float* __restrict__ wmix,
-                                                 const float* __restrict__ x, float* __restrict__ out) {
+                                                 const float* __restrict__ x, float* __restrict__ out, int nw) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float2* tab = reinterpret_cast<float2*>(lds);   // [G*oc] (mean3, rstd3*w)
     const int oc = d.oc, G = d.G, OQ = oc >> 2;
     const int Po = d.N * d.Ho * d.Wo;
     float sumw = 0.f;
-    for (int g = 0; g < G; ++g) sumw += wmix ? wmix[g] : 1.f;
+    for (int g = 0; g < nw; ++g) sumw += wmix ? wmix[g] : 1.f;
     for (int i = threadIdx.x; i < G * oc; i += 256) {
         const float2 c = bn_consts(stats3 + 2 * (size_t)i, 1.0 / (double)Po, d.eps);
         tab[i] = make_float2(c.x, c.y * (wmix ? wmix[i / oc] : 1.f));
@@ -232,6 +233,9 @@ __global__ __launch_bounds__(256) void k_mix_bwd_stats(TfnasCellDesc d, const fl
 
 // dwmix[g] = d loss / d wmix[g] = <dout, phat_g [+ x]> = sum_o S2[g][o] [+ <dout,x>]
 // resdot[o] = per-channel <dout,x> sums (residual cells), stored right after red3
+// SKIPS: the launch has more entries than d.G groups; blockIdx.x >= d.G is the entry of a skip (identity) group -- <dout, x>
+// alone, the same sums in the same order.  (An instantiation of its own: the test costs the plain one two scalar registers.)
+template <bool SKIPS>
 __global__ __launch_bounds__(64) void k_mix_dw(TfnasCellDesc d, const double* __restrict__ red3, const double* __restrict__ resdot,
                                                float* __restrict__ dwmix) {
     // one wave per group (blockIdx.x), lanes stride over the output channels, butterfly sum in double (fixed order).  The
@@ -239,7 +243,7 @@ __global__ __launch_bounds__(64) void k_mix_dw(TfnasCellDesc d, const double* __
     const int g = blockIdx.x, lane = threadIdx.x;
     double s = 0.0;
     for (int o = lane; o < d.oc; o += 64) {
-        s += red3[2 * ((size_t)g * d.oc + o) + 1];
+        if (!SKIPS || g < d.G) s += red3[2 * ((size_t)g * d.oc + o) + 1];
         if (d.has_res) s += resdot[o];
     }
 #pragma unroll
@@ -862,7 +866,7 @@ int launch_se_bwd_reduce(const TfnasCellDesc& d, const float* dZ, const float* D
     return (int)hipGetLastError();
 }
 
-int launch_mix_fwd(const TfnasCellDesc& d, const float* Pr, const double* stats3, const float* wmix,
+int launch_mix_fwd(const TfnasCellDesc& d, int nw, const float* Pr, const double* stats3, const float* wmix,
                    const float* x, float* out, hipStream_t s) {
     ProfScope _prof(TK_MIX_FWD, s);
     const size_t total = (size_t)d.N * d.Ho * d.Wo * (d.oc / 4);
@@ -870,7 +874,7 @@ int launch_mix_fwd(const TfnasCellDesc& d, const float* Pr, const double* stats3
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
     const size_t shm = (size_t)2 * d.G * d.oc * sizeof(float);
-    hipLaunchKernelGGL(k_mix_fwd, dim3((unsigned)blocks), dim3(256), shm, s, d, Pr, stats3, wmix, x, out);
+    hipLaunchKernelGGL(k_mix_fwd, dim3((unsigned)blocks), dim3(256), shm, s, d, Pr, stats3, wmix, x, out, nw);
     return (int)hipGetLastError();
 }
 
@@ -905,9 +909,10 @@ int launch_mix_bwd_stats(const TfnasCellDesc& d, const float* dout, const float*
     return launch_reduce_rows(part, gx, ncols, (size_t)ncols, red3, nullptr, s);
 }
 
-int launch_mix_dw(const TfnasCellDesc& d, const double* red3, const double* resdot, float* dwmix, hipStream_t s) {
+int launch_mix_dw(const TfnasCellDesc& d, int nw, const double* red3, const double* resdot, float* dwmix, hipStream_t s) {
     ProfScope _prof(TK_SMALL, s);
-    hipLaunchKernelGGL(k_mix_dw, dim3(d.G), dim3(64), 0, s, d, red3, resdot, dwmix);
+    if (nw > d.G) hipLaunchKernelGGL(k_mix_dw<true>, dim3(nw), dim3(64), 0, s, d, red3, resdot, dwmix);
+    else hipLaunchKernelGGL(k_mix_dw<false>, dim3(d.G), dim3(64), 0, s, d, red3, resdot, dwmix);
     return (int)hipGetLastError();
 }
 

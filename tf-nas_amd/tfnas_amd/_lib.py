@@ -32,6 +32,8 @@ CELL_NOEXPAND = 0x200        # TfnasCellDesc.flags: the one group has no expand 
 CELL_FUSED = 0x400           # TfnasCellDesc.flags: the one group is a Fused-MBConv block (dense 3 x 3 weight in w_expand, no depthwise)
 CELL_KINDS = 0x800           # TfnasCellDesc.flags: every group names its own kind in TfnasGroup.kind (group_kind_id; refused without the bit)
 CELL_SE_STYLE = 0x1000       # TfnasCellDesc.flags: se_style may be non-zero (se_style_id; refused without the bit)
+CELL_SKIP = 0x2000           # TfnasCellDesc.flags: groups may be GROUP_SKIP, the identity candidate (with CELL_KINDS, residual cells only)
+GROUP_SKIP = 3               # TfnasGroup.kind of a skip group: no width, no weights, no columns -- not a BlockKind (KINDS stays three)
 SE_GATE = {'sigmoid': 0, 'h-sigmoid': 1}      # gate function of a squeeze-excite branch (bits 4-7 of TfnasCellDesc.se_style)
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
 ROUTE_FX_OFF, ROUTE_FOLD_OFF, ROUTE_DWWG_OFF, ROUTE_DWWG2_OFF, ROUTE_XG_OFF, ROUTE_XG_ALL = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20

@@ -195,7 +195,20 @@ class CellPlan:
         # the kind is decided HERE, once: a one-block cell is what its block is (_lib.BlockKind), every other plan is plain --
         # unless the caller allows blocks of different kinds in one plan (``mixed_kinds``: MixedOP._plan), where every group keeps
         # its block's kind (TfnasGroup.kind under CELL_KINDS) as soon as one of them is not plain
+        # A block without a kind (kind None: layers.IdentityLayer) is a skip candidate -- a TFNAS_GROUP_SKIP group under CELL_SKIP:
+        # ``mixed_kinds`` plans only, residual cells only, after every computing block, never alone
         kinds = [getattr(b, 'kind', _lib.MBCONV) for b in self.blocks]
+        nskip = sum(k is None for k in kinds)
+        if nskip:
+            if not (mixed_kinds and mode == _lib.MODE_CELL):
+                raise NotImplementedError('tfnas_amd: an IdentityLayer runs only as a skip candidate of a MixedOP launch '
+                                          '(CellPlan(..., mixed_kinds=True))')
+            if nskip == len(kinds):
+                raise ValueError('tfnas_amd: a plan of identity blocks alone has nothing to launch')
+            if any(k is not None for k in kinds[len(kinds) - nskip:]):
+                raise ValueError('tfnas_amd: skip candidates stand after every computing candidate of a cell')
+            if not (ic == oc and stride == 1):
+                raise ValueError('tfnas_amd: a skip candidate needs a residual cell (in_channels == out_channels, stride 1)')
         many = len(self.blocks) != 1 or mode != _lib.MODE_CELL
         mixed = bool(mixed_kinds) and mode == _lib.MODE_CELL and len(self.blocks) > 1 and any(k is not _lib.MBCONV for k in kinds)
         if _lib.FUSED in kinds and many and not mixed:
@@ -213,6 +226,8 @@ class CellPlan:
         # seven fields, a cell's block the fields of its kind
         slots = []
         for g, (b, kind) in enumerate(zip(self.blocks, kinds)):
+            if kind is None:                           # (a skip group binds nothing)
+                continue
             fields = (0,) if mode == _lib.MODE_HEAD else (kind if mode == _lib.MODE_CELL else _lib.MBCONV).bound(b.se_channels > 0)
             slots += [(g, k) for k in fields]
         self._w_slots = [(g, _lib._W_FIELDS[k]) for g, k in slots]
@@ -267,7 +282,11 @@ class CellPlan:
         if self.group_kinds is not None:
             d.flags |= _lib.CELL_KINDS
             for g, kind in enumerate(self.group_kinds):
-                d.g[g].kind = _lib.group_kind_id(kind)
+                if kind is None:                       # (a skip candidate: no BlockKind, constants of its own)
+                    d.flags |= _lib.CELL_SKIP
+                    d.g[g].kind = _lib.GROUP_SKIP
+                else:
+                    d.g[g].kind = _lib.group_kind_id(kind)
 
     def bind(self, d, params, grads=None):
         """Write current weight (and gradient) pointers into the descriptor."""

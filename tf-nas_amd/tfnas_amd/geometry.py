@@ -33,6 +33,10 @@ PRIMITIVE_SPECS = OrderedDict(
     + [('DS_k%d%s' % (k, '_se' if se else ''), ('MBInvertedResBlock', k, se, True)) for k in (3, 5) for se in (0, 1)])
 
 
+SKIP = 'skip'        # the identity candidate (the reference's commented-out primitive): recognised NEXT to PRIMITIVE_SPECS -- it
+                     # has no layer spec (no kernel, no width, no SE) and only residual cells can hold it (residual_cells)
+
+
 def cell_primitives(primitives, stage, block):
     """The 8 candidate names of cell (stage, block) under a ``primitives`` argument: None -> PRIMITIVES; one list -> that list for
     every cell; a {stage: {block: list}} mapping -> its entry, PRIMITIVES where it has none."""
@@ -68,7 +72,10 @@ def se_style_keys(se_act, se_gate):
 
 def primitive_block(name, ic, mc):
     """(layer class name, mid_channels, se_channels, kernel_size) of primitive ``name`` in a cell of ``ic`` input channels whose
-    width table says ``mc``; ValueError (naming the legal ones) for an unknown name."""
+    width table says ``mc``; ValueError (naming the legal ones) for an unknown name.  'skip': ('IdentityLayer', 0, 0, 0) -- the
+    same four words with nothing in them, so callers that unpack the answer keep working and fork on the layer name."""
+    if name == SKIP:
+        return 'IdentityLayer', 0, 0, 0
     if name not in PRIMITIVE_SPECS:
         raise ValueError('tfnas_amd: unknown primitive %r (one of %s)' % (name, ', '.join(sorted(PRIMITIVE_SPECS))))
     layer, k, se_mult, own = PRIMITIVE_SPECS[name]
@@ -95,6 +102,14 @@ def iter_cells(input_size=INPUT_SIZE_AFTER_STEMS):
         for b, (ic, oc, s) in enumerate(zip(cfg['ics'], cfg['ocs'], cfg['ss']), start=1):
             yield stage, 'block%d' % b, ic, oc, s, cfg['act'], size
             size = (size + s - 1) // s if s > 1 else size
+
+
+def residual_cells():
+    """Yield the (stage, block) pairs whose cell has a residual connection (in == out channels, stride 1): the cells that can hold
+    a 'skip' candidate.  {st: {b: names} for st, b in residual_cells()}-style mappings are what ``primitives=`` takes."""
+    for stage, block, ic, oc, s, act, size in iter_cells():
+        if ic == oc and s == 1:
+            yield stage, block
 
 
 def max_mid_channels(ic, op_idx):

@@ -10,6 +10,8 @@ Only what the search hot path touches is provided:
                       ``squeeze_excite.conv_reduce/conv_expand``, ``point_linear.conv``.
   ConvLayer / LinearLayer (models/layers.py:190-271, :322-428) -- parameter containers of the stems and the head; inside
                       Network they run as HIP cells (TFNAS_MODE_STEM / _HEAD), the classifier is an nn.Linear.
+  IdentityLayer       (models/layers.py:274-319) -- the skip candidate of a residual cell and the skipped block of a derived
+                      network: no parameters, ``forward(x)`` is ``x``.
   Swish               (models/layers.py:26-35)
 BatchNorm of the search net has no affine and no running statistics (layers.py:101-103,469,498,533): it is
 a pure function of the batch and therefore has no module/state here.
@@ -76,6 +78,41 @@ class LinearLayer(nn.Module):
 
     def forward(self, x):
         return self.linear(x)
+
+
+class IdentityLayer(nn.Module):
+    """The reference's IdentityLayer (models/layers.py:274-319) as it stands in a MixedOP: no parameters, no buffers, ``forward``
+    returns its input itself.  As a candidate of a residual cell it is the library's TFNAS_GROUP_SKIP group (a mix weight that adds
+    to the residual term, nothing else); it has no ``kind`` (_lib.BlockKind) because it binds no field and has no BatchNorm site."""
+
+    kind = None
+    mid_channels = se_channels = kernel_size = 0       # (what a TfnasGroup of it holds)
+    stride = 1
+    act_func = None
+
+    def __init__(self, in_channels, out_channels, use_bn=False, affine=False, act_func=None, ops_order='weight_bn_act'):
+        super().__init__()
+        if use_bn or affine or act_func is not None or ops_order != 'weight_bn_act':
+            raise NotImplementedError('tfnas_amd: IdentityLayer is the plain identity (no BatchNorm, no activation)')
+        self.in_channels, self.out_channels = in_channels, out_channels
+
+    @property
+    def name(self):
+        return 'IdentityLayer'
+
+    @property
+    def config(self):
+        return {'name': 'IdentityLayer', 'in_channels': self.in_channels, 'out_channels': self.out_channels,
+                'use_bn': False, 'affine': False, 'act_func': None, 'ops_order': 'weight_bn_act'}
+
+    def forward(self, x):
+        return x
+
+    def hip_params(self):
+        return []
+
+    def set_se_style(self, style):
+        """No squeeze-excite branch: a style never conflicts with it."""
 
 
 def _seq(**mods):

@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from . import _lib, geometry
 from .functions import CellPlan, HeadAffineFn, MBConvAffineFn
-from .layers import ConvLayer, FusedMBConvBlock, LinearLayer, MBInvertedResBlock
+from .layers import ConvLayer, FusedMBConvBlock, IdentityLayer, LinearLayer, MBInvertedResBlock
 from .parsing import derived_config
 
 
@@ -104,6 +104,8 @@ class _DerivedBase(nn.Module):
         size = (x.size(-1) - 1) // 2 + 1                    # after first_stem (stride 2); second_stem keeps it
         for stage in self._stages():
             for b in stage:
+                if isinstance(b, IdentityLayer):           # a skipped block costs nothing and keeps the resolution
+                    continue
                 key = '{}_{}_{}_{}_{}_k{}_s{}_{}'.format(b.name, size, b.in_channels, b.se_channels, b.out_channels,
                                                          b.kernel_size, b.stride, b.act_func)
                 lat += self.lat_lookup[key][b.mid_channels]
@@ -112,6 +114,8 @@ class _DerivedBase(nn.Module):
 
     @staticmethod
     def _block_config(b):
+        if isinstance(b, IdentityLayer):
+            return b.config
         return {'name': b.name, 'in_channels': b.in_channels, 'mid_channels': b.mid_channels,
                 'se_channels': b.se_channels, 'out_channels': b.out_channels, 'kernel_size': b.kernel_size, 'stride': b.stride,
                 'groups': 1, 'has_shuffle': False, 'bias': False, 'use_bn': True, 'affine': True, 'act_func': b.act_func,
@@ -160,6 +164,9 @@ class Network(_DerivedBase):
                 ic, oc, s = cfg['ics'][i], cfg['ocs'][i], cfg['ss'][i]
                 # (``primitives``: what the searched network was built with, model_search.Network(primitives=...))
                 prim = geometry.cell_primitives(primitives, name, block_name)[op]
+                if prim == geometry.SKIP:              # a chosen skip: counted like any block, nothing to drop-connect
+                    stage.append(IdentityLayer(ic, oc))
+                    continue
                 layer, mc, se, k = geometry.primitive_block(prim, ic, mc_num_dddict[name][block_name][op])
                 cls = FusedMBConvBlock if layer == 'FusedMBConvBlock' else MBInvertedResBlock
                 # (``se_style``: likewise -- None, one (se_act, se_gate) pair or a {stage: pair} mapping; the stems keep theirs)
@@ -203,6 +210,9 @@ class NetworkCfg(_DerivedBase):
             stage = nn.ModuleList()
             for c in model_config['stage%d' % i]:
                 self.block_idx += 1
+                if c['name'] == 'IdentityLayer':       # (counted, as the reference's loop over the entries does; no drop-connect)
+                    stage.append(IdentityLayer(**{k: v for k, v in c.items() if k != 'name'}))
+                    continue
                 blk = mb(c)
                 blk.drop_connect_rate = self.drop_connect_rate * self.block_idx / self.block_count
                 stage.append(blk)

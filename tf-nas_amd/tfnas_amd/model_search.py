@@ -22,7 +22,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .functions import ArchFn, CellPlan, HeadFn, MixedOpFn, SinkFn, StemFn, arch_sample
-from .layers import ConvLayer, FusedMBConvBlock, LinearLayer, MBInvertedResBlock
+from .geometry import SKIP
+from .layers import ConvLayer, FusedMBConvBlock, IdentityLayer, LinearLayer, MBInvertedResBlock
 
 PRIMITIVES = [
     'MBI_k3_e3', 'MBI_k3_e6', 'MBI_k5_e3', 'MBI_k5_e6',
@@ -68,9 +69,24 @@ def check_primitives(primitives):
     if len(names) != len(PRIMITIVES):
         raise ValueError('tfnas_amd: a MixedOP takes exactly %d primitives, got %d' % (len(PRIMITIVES), len(names)))
     for n in names:
-        if n not in OPS:
-            raise ValueError('tfnas_amd: unknown primitive %r (one of %s)' % (n, ', '.join(sorted(OPS))))
+        if n not in OPS and n != SKIP:
+            raise ValueError('tfnas_amd: unknown primitive %r (one of %s, or %r in a residual cell)'
+                             % (n, ', '.join(sorted(OPS)), SKIP))
     return names
+
+
+def _check_skips(names, in_channels, out_channels, stride):
+    """What a cell asks of its 'skip' candidates (the library's rules for TFNAS_GROUP_SKIP groups); ValueError names the reason."""
+    if SKIP not in names:
+        return
+    if stride != 1 or in_channels != out_channels:
+        raise ValueError('tfnas_amd: a %r candidate needs a residual cell (stride 1, in_channels == out_channels); this one has '
+                         'stride %d, %d -> %d channels' % (SKIP, stride, in_channels, out_channels))
+    if all(n == SKIP for n in names):
+        raise ValueError('tfnas_amd: a cell needs at least one candidate that is not %r' % SKIP)
+    first = names.index(SKIP)
+    if any(n != SKIP for n in names[first:]):
+        raise ValueError('tfnas_amd: %r candidates stand after every other candidate of a cell (got %s)' % (SKIP, ', '.join(names)))
 
 
 def _cell_primitives(primitives, stage, block):
@@ -107,8 +123,12 @@ class MixedOP(nn.Module):
         self.lat_lookup = lat_lookup
         self.mc_num_dict = mc_num_dict
         self.in_channels, self.out_channels, self.stride, self.act_func = in_channels, out_channels, stride, act_func
+        _check_skips(self.primitives[:num_ops], in_channels, out_channels, stride)
         self.m_ops = nn.ModuleList()
         for i in range(num_ops):
+            if self.primitives[i] == SKIP:                 # (no width: mc_num_dict[i] is ignored)
+                self.m_ops.append(IdentityLayer(in_channels, out_channels))
+                continue
             self.m_ops.append(OPS[self.primitives[i]](in_channels, self.mc_num_dict[i], out_channels, stride, affine,
                                                  act_func))
             self.m_ops[-1].set_se_style(self.se_style)     # (the registry's factories keep their signature: applied here,
@@ -133,6 +153,9 @@ class MixedOP(nn.Module):
     def get_lookup_latency(self, size):
         lats = []
         for op in self.m_ops:
+            if op.name == 'IdentityLayer':                 # (models/model_search.py:96-97: the skip costs nothing)
+                lats.append(0)
+                continue
             key = '{}_{}_{}_{}_{}_k{}_s{}_{}'.format(op.name, size, op.in_channels, op.se_channels, op.out_channels,
                                                      op.kernel_size, op.stride, op.act_func)
             lats.append(self.lat_lookup[key][op.mid_channels])
@@ -163,7 +186,7 @@ class MixedOP(nn.Module):
 
     def lat_tensor(self, size, device):
         """Looked-up latencies of the 8 candidates as a device tensor (cached per input size / widths)."""
-        key = (size, str(device), tuple(op.mid_channels for op in self.m_ops))
+        key = (size, str(device), tuple(getattr(op, 'mid_channels', 0) for op in self.m_ops))
         t = self._lat_cache.get(key)
         if t is None:
             t = torch.tensor(self.get_lookup_latency(size), dtype=torch.float32, device=device)
@@ -205,6 +228,8 @@ class MixedOP(nn.Module):
             idx = pre if pre is not None else self.sample_index(mode, exp_noise, rand_pos)
             self.last_idx = idx
             op = self.m_ops[idx]
+            if op.kind is None:                            # a sampled skip: the input itself, no launch (as the reference)
+                return x, 0
             return MixedOpFn.apply(self._plan((idx,)), x, None, *op.hip_params()), 0
         if pre is not None:
             w, out_lat = pre
@@ -234,9 +259,18 @@ class MixedStage(nn.Module):
             raise ValueError('invalid stage_type...')
         self.nblocks = nblocks
         for b in range(nblocks):
+            names = _cell_primitives(primitives, stage_name, 'block%d' % (b + 1))
+            try:
+                _check_skips(check_primitives(names), ics[b], ocs[b], ss[b])
+            except ValueError as e:
+                if names is None or SKIP not in list(names):
+                    raise
+                # (the first block of a stage that changes width or stride cannot hold a skip: one list for every cell cannot work)
+                raise ValueError('%s -- %s block%d; give the skip to the residual cells only: primitives={stage: {block: list}}, '
+                                 'e.g. from geometry.residual_cells()' % (e, stage_name or 'stage', b + 1)) from None
             setattr(self, 'block%d' % (b + 1),
                     MixedOP(ics[b], ocs[b], ss[b], affs[b], acts[b], len(PRIMITIVES), mc_num_ddict['block%d' % (b + 1)],
-                            lat_lookup, primitives=_cell_primitives(primitives, stage_name, 'block%d' % (b + 1)),
+                            lat_lookup, primitives=names,
                             se_style=_cell_se_style(se_style, 'block%d' % (b + 1))))
         self._initialize_betas()
 
@@ -371,7 +405,7 @@ class Network(nn.Module):
         cells = self.cells()
         if exp_noise is None:
             exp_noise = torch.empty(len(cells), 8, device=dev).exponential_()
-        key = (size, str(dev), tuple(op.mid_channels for c in cells for op in c.m_ops))
+        key = (size, str(dev), tuple(getattr(op, 'mid_channels', 0) for c in cells for op in c.m_ops))
         if self._lat_stack is None or self._lat_stack[0] != key:
             lats = []
             for st in self.stages():
@@ -452,9 +486,12 @@ class Network(nn.Module):
                 ia = blk.sample_index('gumbel', pos=int(pos_g[ci]))
                 ib = blk.sample_index('random', rand_pos=rand_pos[ci])
                 blk.last_idx = ib                          # (what two sequential forwards leave behind)
-                ra.append(MixedOpFn.apply(blk._plan((ia,)), ra[-1], None, *blk.m_ops[ia].hip_params()))
+                # (a sampled skip is the path's input itself: no launch)
+                ra.append(ra[-1] if blk.m_ops[ia].kind is None else
+                          MixedOpFn.apply(blk._plan((ia,)), ra[-1], None, *blk.m_ops[ia].hip_params()))
                 with torch.cuda.stream(side_stream):
-                    rb.append(MixedOpFn.apply(blk._plan((ib,)), rb[-1], None, *blk.m_ops[ib].hip_params()))
+                    rb.append(rb[-1] if blk.m_ops[ib].kind is None else
+                              MixedOpFn.apply(blk._plan((ib,)), rb[-1], None, *blk.m_ops[ib].hip_params()))
                 ci += 1
             xa, _ = SinkFn.apply(st.betas, None, *ra[st.start_res:])
             with torch.cuda.stream(side_stream):

@@ -29,11 +29,19 @@ def _mbconv_config(ic, mc, se, oc, k, stride, act):
             'affine': True, 'act_func': act}
 
 
+def _identity_config(ic, oc):
+    """models/layers.py IdentityLayer.config (:304-309 + BasicLayer.config :169-177): what the reference's own
+    model_eval.Network.config would hold for a chosen 'skip'."""
+    return {'name': 'IdentityLayer', 'in_channels': ic, 'out_channels': oc, 'use_bn': False, 'affine': False, 'act_func': None,
+            'ops_order': 'weight_bn_act'}
+
+
 def derived_config(parsed_arch, mc_num_dddict, num_classes=1000, primitives=None, se_style=None):
     """``models/model_eval.Network(num_classes, parsed_arch, mc_num_dddict).config`` (model_eval.py:214-228).  ``primitives``:
     what the searched network was built with (model_search.Network(primitives=...): one list, or a {stage: {block: list}}
     mapping); a Fused-MBConv choice is written as a 'FusedMBConvBlock' entry, an expand-free one as the reference records such a
-    block (an 'MBInvertedResBlock' with mid_channels == in_channels) -- both load in model_eval.NetworkCfg.  ``se_style``: the
+    block (an 'MBInvertedResBlock' with mid_channels == in_channels), a chosen 'skip' as the reference's 'IdentityLayer' entry
+    -- all load in model_eval.NetworkCfg.  ``se_style``: the
     squeeze-excite style the searched network was built with (model_search.Network(se_style=...): None, one (se_act, se_gate) pair
     or a {stage: pair} mapping); a block's entry carries 'se_act' / 'se_gate' keys only where they differ from the default (the
     block's own activation, 'sigmoid'), so a config without a style is what it always was."""
@@ -48,6 +56,9 @@ def derived_config(parsed_arch, mc_num_dddict, num_classes=1000, primitives=None
                 continue
             op = parsed_arch[stage][name]
             prim = geometry.cell_primitives(primitives, stage, name)[op]
+            if prim == geometry.SKIP:                           # (no width: mc_num_dddict is not asked)
+                blocks.append(_identity_config(ic, oc))
+                continue
             layer, mc, se, k = geometry.primitive_block(prim, ic, mc_num_dddict[stage][name][op])
             blocks.append(dict(_mbconv_config(ic, mc, se, oc, k, s, st['act']), name=layer,
                                **geometry.se_style_keys(*_lib.se_style_pair(geometry.cell_se_style(se_style, stage, name)))))
@@ -77,6 +88,8 @@ def count_macs_in_M(config, input_size=224):
         if c['name'] == 'ConvLayer':
             size = (size - 1) // c['stride'] + 1
             total += c['kernel_size'] ** 2 * c['in_channels'] * c['out_channels'] * size * size
+        elif c['name'] == 'IdentityLayer':                         # nothing to count, the resolution stays
+            continue
         else:
             ic, mc, se, oc, k, s = (c[n] for n in ('in_channels', 'mid_channels', 'se_channels', 'out_channels',
                                                     'kernel_size', 'stride'))
@@ -109,6 +122,8 @@ def count_params_in_MB(config):
     for c in _layers(config):
         if c['name'] == 'ConvLayer':
             n += c['kernel_size'] ** 2 * c['in_channels'] * c['out_channels'] + 2 * c['out_channels']
+        elif c['name'] == 'IdentityLayer':
+            continue
         else:
             ic, mc, se, oc, k = (c[x] for x in ('in_channels', 'mid_channels', 'se_channels', 'out_channels', 'kernel_size'))
             if c['name'] == 'FusedMBConvBlock':
@@ -151,7 +166,11 @@ def parse_searched_model(model_or_path, lat_lookup=None, num_classes=1000, save_
     out = dict(parsed_arch=parsed, mc_num_dddict=mc_num, config=config, params_MB=count_params_in_MB(config),
                macs_M=count_macs_in_M(config))
     if lat_lookup is not None:
-        out['lat_lut'] = get_lookup_latency(parsed, mc_num, geometry.make_lat_lookup_key_dddict(), lat_lookup)
+        # (a chosen 'skip' has no latency row: it costs nothing, models/model_search.py:96-97)
+        priced = OrderedDict((st, OrderedDict((b, op) for b, op in blocks.items()
+                                              if geometry.cell_primitives(primitives, st, b)[op] != geometry.SKIP))
+                             for st, blocks in parsed.items())
+        out['lat_lut'] = get_lookup_latency(priced, mc_num, geometry.make_lat_lookup_key_dddict(), lat_lookup)
     if save_path:
         with open(save_path, 'w') as f:
             json.dump(config, f, indent=4)

@@ -83,7 +83,10 @@ class WeightArena:
         return self.g.data_ptr() + 4 * self.slot[id(p)][0]
 
     def span(self, params):
-        """(offset, length) of the smallest range covering ``params`` (which must be adjacent in the arena)."""
+        """(offset, length) of the smallest range covering ``params`` (which must be adjacent in the arena); no parameters (a skip
+        candidate): the empty range (0, 0)."""
+        if not params:
+            return 0, 0
         offs = [self.slot[id(p)] for p in params]
         lo = min(o for o, _ in offs)
         hi = max(o + (n + ALIGN - 1) // ALIGN * ALIGN for o, n in offs)

@@ -173,11 +173,19 @@ class SearchState:
                 and not g[0].get('maximize'))
 
     def op_span(self, ci, idx):
+        """(offset, length) of candidate ``idx`` of cell ``ci`` in the weight / gradient / momentum arena; a skip candidate owns
+        the empty span (0, 0), which every list of ranges handed to a kernel leaves out (_live)."""
         key = (ci, idx)
         sp = self._op_span.get(key)
         if sp is None:
             sp = self._op_span[key] = self.arena.span(self.op_params(ci, idx))
         return sp
+
+    @staticmethod
+    def _live(spans):
+        """the spans that hold something: a skip candidate's empty span (and a cell where both bi-sampling paths picked the skip)
+        contributes nothing to a message or an optimizer step"""
+        return [sp for sp in spans if sp[1] > 0]
 
     def _dp_active(self, group):
         import torch.distributed as dist
@@ -201,8 +209,8 @@ class SearchState:
         first_late = sum(st.nblocks for st in self.model.stages()[:k])
         cells = [(ci, idx) for idxs in idx_lists for ci, idx in enumerate(idxs)]
         stem_first = self.arena.slot[id(self._shared[0])][0]
-        r1 = [sp for sp in self._shared_spans if sp[0] != stem_first] + [self.op_span(ci, i) for ci, i in cells if ci >= first_late]
-        r2 = [sp for sp in self._shared_spans if sp[0] == stem_first] + [self.op_span(ci, i) for ci, i in cells if ci < first_late]
+        r1 = [sp for sp in self._shared_spans if sp[0] != stem_first] + self._live(self.op_span(ci, i) for ci, i in cells if ci >= first_late)
+        r2 = [sp for sp in self._shared_spans if sp[0] == stem_first] + self._live(self.op_span(ci, i) for ci, i in cells if ci < first_late)
         n1, n2 = sum(sp[1] for sp in r1), sum(sp[1] for sp in r2)
         if self._msg is None or self._msg.numel() < n1 + n2:
             self._msg = torch.empty(int((n1 + n2) * 1.5), device=a.device, dtype=torch.float32)
@@ -278,7 +286,7 @@ class SearchState:
         else:
             spans = list(self._shared_spans)
             for idxs in idx_lists:
-                spans.extend(self.op_span(ci, idx) for ci, idx in enumerate(idxs))
+                spans.extend(self._live(self.op_span(ci, idx) for ci, idx in enumerate(idxs)))
             n = len(spans)
             off = (C.c_uint64 * n)(*[sp[0] for sp in spans])
             ln = (C.c_uint64 * n)(*[sp[1] for sp in spans])
