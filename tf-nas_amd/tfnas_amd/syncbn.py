@@ -14,8 +14,16 @@ different number of steps (a short last batch, uneven validation shards) leaves 
 ``drop_last=False``).  The hook is removed at interpreter exit and must be removed (``disable()``) before its process group is
 destroyed.
 
-Cost: 6 small all-reduces per cell and direction pair (<= 2 x 1536 doubles each) on the step's critical path -- an opt-in mode,
-not the throughput default.  E-free mode is switched off by the library while the hook is installed.
+Cost: up to 6 small all-reduces per cell and direction pair (<= 2 x 1536 doubles each) on the step's critical path -- an opt-in
+mode, not the throughput default.  Six for a cell with a plain MBConv group (three BatchNorm sites, forward and backward); four for
+a cell without one -- expand-free and Fused-MBConv blocks have no BatchNorm site 0 --; a backward that produces d wmix alone makes
+one call instead of three; the head makes two.  INTEGRATION.md lists the sites, their lengths and which rows of each table mean
+something (tests/test_gpu_sync_cells.py holds them to the float64 global batch).  The E-free and the fused per-image routes are
+switched off by the library while the hook is installed.
+
+Weight gradients stay per-rank contributions (sum them over the ranks as without the hook); of d wmix the part read from the
+reduced BatchNorm-backward table is already global / world, the residual term <dout, x> is local: the sum over the ranks is the
+global-batch gradient either way.
 """
 import ctypes as C
 
