@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-/* 4, additive: TFNAS_CELL_SKIP -- TFNAS_GROUP_SKIP: the identity candidate in a residual TFNAS_CELL_KINDS cell.
+/* 4, additive: TFNAS_CELL_DILATION -- TfnasGroup.dil: depthwise candidates with taps two pixels apart (3 x 3 and 5 x 5).
+ * 4, additive: TFNAS_CELL_SKIP -- TFNAS_GROUP_SKIP: the identity candidate in a residual TFNAS_CELL_KINDS cell.
  * 4, additive: TFNAS_CELL_SE_STYLE -- TfnasCellDesc.se_style: the squeeze-excite hidden activation and gate function of a cell.
  * 4, additive: TFNAS_CELL_KINDS -- a per-group kind (TfnasGroup.kind): plain, expand-free and Fused-MBConv candidates in ONE cell.
  * 4, additive: TFNAS_CELL_FUSED -- a Fused-MBConv block (dense 3 x 3 convolution, no depthwise) through tfnas_mixedop_* / tfnas_mbconv_*.
@@ -111,7 +112,8 @@ typedef struct TfnasGroup {
     int32_t off;      /* first column of this group in the [.][M] tensors (multiple of 32) [plan] */
     int32_t se_off;   /* first column in the [N][SE] hidden tensors         [plan] */
     int32_t kind;     /* TFNAS_GROUP_*: read only from a descriptor whose flags carry TFNAS_CELL_KINDS [in]  */
-    int32_t pad1;
+    int32_t dil;      /* depthwise dilation: 0 or 1 = none, 2 = taps two pixels apart (pad 2 * (k / 2), k 3 or 5); read only
+                         from a descriptor whose flags carry TFNAS_CELL_DILATION (this word was padding, pad1, before) [in]  */
     const float *w_expand, *w_dw, *w_proj, *w_se_r, *b_se_r, *w_se_e, *b_se_e;
     float *g_expand, *g_dw, *g_proj, *g_se_r, *gb_se_r, *g_se_e, *gb_se_e;
 } TfnasGroup;
@@ -145,7 +147,8 @@ typedef struct TfnasCellDesc {
                                  TFNAS_CELL_FUSED: the one group is a Fused-MBConv block (dense 3 x 3 convolution);
                                  TFNAS_CELL_KINDS: every group has a kind of its own (TfnasGroup.kind);
                                  TFNAS_CELL_SE_STYLE: se_style may be non-zero;
-                                 TFNAS_CELL_SKIP: groups may be TFNAS_GROUP_SKIP, the identity candidate                 [in]
+                                 TFNAS_CELL_SKIP: groups may be TFNAS_GROUP_SKIP, the identity candidate;
+                                 TFNAS_CELL_DILATION: groups may have depthwise dilation 2 (TfnasGroup.dil)              [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -346,6 +349,27 @@ typedef struct TfnasCellDesc {
  * wgrad_stream[], the sync-stats hook (table lengths follow G'), se_style, TFNAS_CELL_K7 and TFNAS_CELL_ACTS keep their meaning. */
 #define TFNAS_CELL_SKIP 0x2000
 #define TFNAS_GROUP_SKIP 3
+/* TfnasCellDesc.flags: the caller knows dilated depthwise convolutions (TfnasGroup.dil) -- the dil_conv_3x3 / dil_conv_5x5 candidates
+ * of the DARTS-family spaces and the dilated late stages of MobileNet-family backbones: a 3 x 3 with its taps two pixels apart
+ * covers 5 x 5 with 9 taps, a 5 x 5 covers 9 x 9 with 25.  Additive like TFNAS_CELL_K7: without the bit TfnasGroup.dil is not read
+ * and every descriptor is accepted, refused, planned, sized, routed and launched exactly as before (0x4000 stays undefined and
+ * refused).  With the bit a descriptor whose groups all have dil 0 or 1 plans, sizes, routes and launches identically, and a group
+ * may have dil == 2 with k 3 or 5: padding 2 * (k / 2), so the output size stays (H - 1) / stride + 1 as for every k.  Rules,
+ * checked by tfnas_cell_plan and again by every entry point (TFNAS_EINVAL):
+ *   - dil outside {0, 1, 2}; k == 7 with dil == 2; a dilated TFNAS_GROUP_FUSED or TFNAS_GROUP_SKIP group; a dilated TFNAS_CELL_FUSED
+ *     cell; a dilated group in TFNAS_MODE_STEM or TFNAS_MODE_HEAD;
+ *   - allowed: plain MBConv groups and expand-free groups (TFNAS_CELL_NOEXPAND, or TFNAS_GROUP_NOEXPAND of a TFNAS_CELL_KINDS cell), in
+ *     sampled and soft launches of tfnas_mixedop_fwd/bwd, in tfnas_mbconv_fwd/bwd, in tfnas_path_plan and the path level; all four
+ *     activations, both strides, SE or none, every se_style.
+ * A cell with a dilated group follows the 7 x 7 rule: it always materialises E (tfnas_efree_supported and tfnas_fx_supported return
+ * 0, tfnas_cell_route returns TFNAS_ROUTE_TAKEN_VALID), runs every depthwise pass on the LDS tile kernels whatever TFNAS_ROUTE_DW_*
+ * asks, and keeps the depthwise weight gradient in a launch of its own.  Dilation changes neither the workspace (tfnas_cell_ws)
+ * nor the weight-gradient partial row (sum of mc * k * k) nor any planned word (M, SE, off, mcp, se_off): the weight stays
+ * [mc][k * k].  At stride 2 every tap of a dilated group lands on an even input row and column: the odd pixels of its data
+ * gradient (dEh; dx of an expand-free group) are exactly zero and are stored as such.  TFNAS_CELL_ACCUM_WGRAD,
+ * TFNAS_CELL_LAZY_JOIN, wgrad_stream[], the sync-stats hook and the GEMM modes keep their meaning.  The Python mirror sets the bit
+ * for every descriptor that holds a dilated group, and only those (functions.HipModes.apply). */
+#define TFNAS_CELL_DILATION 0x8000
 /* TfnasCellDesc.route (ABI 4; rounds 2-5 read these from TFNAS_* environment variables latched once per process) */
 #define TFNAS_ROUTE_FX_OFF 0x1        /* frozen-weight launches of the 14 x 14 / 7 x 7 cells through the materialised route instead
                                          of the fused per-image kernels (csrc/fx_kernels.hip)                                   */
@@ -358,7 +382,8 @@ typedef struct TfnasCellDesc {
 #define TFNAS_ROUTE_XG_ALL 0x20       /* ... in Gram form wherever the shape allows (default: where E >= 100 MB)                */
 #define TFNAS_ROUTE_DW_SHIFT 6        /* 2 bits: 0 per-launch policy, 1 register-window kernels wherever the geometry allows,   */
 #define TFNAS_ROUTE_DW_MASK 0xc0      /*         2 LDS ring / tile kernels only, 3 tile kernels only (7 x 7 cells,
-                                         TFNAS_ACT_RELU6 / _HSWISH cells and TFNAS_CELL_NOEXPAND cells: always 3)                                             */
+                                         TFNAS_ACT_RELU6 / _HSWISH cells, TFNAS_CELL_NOEXPAND cells and cells with a
+                                         dilated group, TFNAS_CELL_DILATION: always 3)                                        */
 #define TFNAS_ROUTE_SE_SHIFT 8        /* 2 bits: 0 wave-level MFMA kernels for the excite FCs, 1 one fused per-image kernel,    */
 #define TFNAS_ROUTE_SE_MASK 0x300     /*         2 LDS-tiled GEMMs                                                              */
 #define TFNAS_ROUTE_WGRAD_INLINE 0x400 /* weight-gradient kernels on the caller's stream (no side stream)                       */
@@ -430,7 +455,7 @@ int tfnas_cell_ws(const TfnasCellDesc *d, TfnasCellWs *ws);
 /* 1 when the cell can run without the expanded tensor E ("E-free" mode: pass E = NULL to tfnas_mixedop_fwd AND to the
  * matching tfnas_mixedop_bwd; the depthwise kernels then recompute act(BN1(x W_expand^T)) from the narrow cell input,
  * and BN1's batch statistics come from the ic x ic Gram matrix of x).  Currently: TFNAS_MODE_CELL, need_wgrad = 0
- * (the alpha-step: frozen weights), ic in {16, 24, 40}, kernel sizes 3 / 5, ReLU / Swish.  Same arithmetic contract as the E path (fp32, <= 1e-3). */
+ * (the alpha-step: frozen weights), ic in {16, 24, 40}, kernel sizes 3 / 5 without dilation, ReLU / Swish.  Same arithmetic contract as the E path (fp32, <= 1e-3). */
 int tfnas_efree_supported(const TfnasCellDesc *d);
 /* What a forward of the (planned) descriptor does with the saved buffers -- a pure function of the descriptor (geometry,
  * need_wgrad, route, sync hook): TFNAS_ROUTE_TAKEN_VALID | TFNAS_ROUTE_TAKEN_*.  Callers that plan the backward with a descriptor
@@ -441,7 +466,8 @@ int tfnas_cell_route(const TfnasCellDesc *d);
  * most 14 x 14 pixels, 64 <= ic <= 192 (a multiple of 16), frozen weights -- the supernet's cells at 14 x 14 and 7 x 7.  One kernel
  * per direction runs expand 1x1 + BN1 + activation + depthwise k x k (models/layers.py:542-552) for a group of whole images x a
  * slice of mid channels; neither E nor its gradient is ever written (the dEh buffer of tfnas_mixedop_bwd is used as scratch for
- * partial sums of dx).  Implies tfnas_efree_supported (so: 0 for a cell with a 7 x 7 group or with TFNAS_ACT_RELU6 / _HSWISH). */
+ * partial sums of dx).  Implies tfnas_efree_supported (so: 0 for a cell with a 7 x 7 group, a dilated group or
+ * TFNAS_ACT_RELU6 / _HSWISH). */
 int tfnas_fx_supported(const TfnasCellDesc *d);
 
 /* MixedOP forward.

@@ -210,6 +210,22 @@ static int check_kind(const TfnasCellDesc* d) {
     return 0;
 }
 
+// the depthwise dilations of a descriptor (tfnas_hip.h: TFNAS_CELL_DILATION; after check_kind: TfnasGroup.kind is read).  Without
+// the bit TfnasGroup.dil is not read.  With it: 0 | 1 | 2 per group, and a dilated group has k 3 or 5, is a plain or an expand-free
+// one (never Fused-MBConv, never a skip) and stands in a cell-mode descriptor
+static int check_dilation(const TfnasCellDesc* d) {
+    if (!(d->flags & TFNAS_CELL_DILATION)) return 0;
+    for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g) {
+        const TfnasGroup& gr = d->g[g];
+        if (gr.dil < 0 || gr.dil > 2) return TFNAS_EINVAL;
+        if (gr.dil != 2) continue;
+        if (gr.k != 3 && gr.k != 5) return TFNAS_EINVAL;
+        if (d->mode != TFNAS_MODE_CELL || cell_fused(*d)) return TFNAS_EINVAL;
+        if (cell_mixed(*d) && (gr.kind == TFNAS_GROUP_FUSED || gr.kind == TFNAS_GROUP_SKIP)) return TFNAS_EINVAL;
+    }
+    return 0;
+}
+
 // the per-launch modes of a descriptor (callers may change them between tfnas_cell_plan and a launch: every entry point re-checks)
 static int check_modes(const TfnasCellDesc* d) {
     TRY(check_act(d));
@@ -218,10 +234,11 @@ static int check_modes(const TfnasCellDesc* d) {
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
     if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS | TFNAS_CELL_NOEXPAND |
-                     TFNAS_CELL_FUSED | TFNAS_CELL_KINDS | TFNAS_CELL_SE_STYLE | TFNAS_CELL_SKIP))
+                     TFNAS_CELL_FUSED | TFNAS_CELL_KINDS | TFNAS_CELL_SE_STYLE | TFNAS_CELL_SKIP | TFNAS_CELL_DILATION))
         return TFNAS_EINVAL;
     TRY(check_kind(d));
     TRY(check_se_style(d));
+    TRY(check_dilation(d));
     if (!(d->flags & TFNAS_CELL_K7)) {            // kernel size 7 is opt-in: without the bit it is refused as it always was
         for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g)
             if (d->g[g].k == 7) return TFNAS_EINVAL;

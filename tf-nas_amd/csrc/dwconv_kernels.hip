@@ -30,11 +30,14 @@ __device__ __forceinline__ int xcd_first_tile() {
     return (gx & 7) ? bx : (bx & 7) * (gx >> 3) + (bx >> 3);
 }
 
-// locate (group, first channel) of channel-chunk `cy` among the groups whose kernel size is K
-template <int K>
+// locate (group, first channel) of channel-chunk `cy` among the groups whose kernel size is K.  DIL = 0 (the register-window and
+// ring kernels: never planned for a cell with a dilated group, dw_tile_only): the dilation is not looked at; DIL = 1 | 2 (the tile
+// kernels): the groups of that kernel size AND that dilation (kernels.h: group_dil) -- one launch per (K, DIL) pair
+template <int K, int DIL = 0>
 __device__ __forceinline__ bool dw_locate(const TfnasCellDesc& d, int cy, int CC, int& g, int& c0) {
     for (g = 0; g < d.G; ++g) {
         if (d.g[g].k != K) continue;
+        if (DIL != 0 && group_dil(d, g) != DIL) continue;
         const int t = (d.g[g].mcp + CC - 1) / CC;
         if (cy < t) {
             c0 = cy * CC;
@@ -148,15 +151,20 @@ __device__ __forceinline__ void load_tile(float* tile, int L0, int L1, int CC, i
 // KQ = 0: the tile is loaded from E.  KQ = ic/4 > 0 (E-free, efree.h): the tile is recomputed from the cell input x.
 // RAW (TFNAS_CELL_NOEXPAND: a block without expand convolution, mc == ic): the tile is the cell input x itself, rows of ic floats,
 // neither normalised nor activated -- no BN1 table is built or read (stats1 and E are not touched), ACT is unused (instantiated 0).
-template <int K, int S, int ACT, int KQ, bool RAW = false>
+// DIL (TFNAS_CELL_DILATION): taps DIL pixels apart, padding DIL * (K / 2) -- the window covers KE = DIL * (K - 1) + 1 pixels each
+// way, the tile origin moves out to ho0 * S - DIL * (K / 2), tap row ky is tile row oh * S + ky * DIL and tap kx of output j reads
+// win[j * S + kx * DIL] of a 3 * S + KE wide register window (window entries no tap reads are never loaded: all indices are
+// compile-time).  DIL = 2: K 3 | 5, KQ = 0 only.
+template <int K, int S, int ACT, int KQ, bool RAW = false, int DIL = 1>
 __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float* __restrict__ E,
                                                    const float* __restrict__ x,
                                                    const double* __restrict__ stats1, float* __restrict__ D,
                                                    float* __restrict__ part, DwGeom gm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int g, c0, lane = blockIdx.x, cy = blockIdx.y;
+    static_assert(DIL == 1 || (DIL == 2 && KQ == 0 && (K == 3 || K == 5)), "dilation 2: 3 x 3 / 5 x 5 from E or raw x");
     if (KQ > 0) efree_lane_chunk(lane, cy);
-    if (!dw_locate<K>(d, cy, gm.CC, g, c0)) return;
+    if (!dw_locate<K, DIL>(d, cy, gm.CC, g, c0)) return;
     const int mc = d.g[g].mc, mcp = d.g[g].mcp, off = d.g[g].off;
     const int CC = gm.CC, CQ = CC >> 2, TH = gm.T0, TW = gm.T1;
     const int H = d.H, W = d.W, Ho = d.Ho, Wo = d.Wo, M = d.M;
@@ -180,13 +188,13 @@ __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float*
         expand_b_load(xb, d.g[g].w_expand, d.ic, c0, mc, cst);
     }
 
-    constexpr int WIN = 3 * S + K;
+    constexpr int KE = DIL * (K - 1) + 1, WIN = 3 * S + KE;
     const int nsw = TW >> 2, nstrips = TH * nsw;
     f32x4 ssum = zero4(), ssq = zero4();
     for (int t = KQ > 0 ? lane : xcd_first_tile(); t < gm.ntiles; t += gridDim.x) {
         const int tw = t % gm.tilesW, th = (t / gm.tilesW) % gm.tilesH, n = t / (gm.tilesW * gm.tilesH);
         const int ho0 = th * TH, wo0 = tw * TW;
-        const int hi0 = ho0 * S - K / 2, wi0 = wo0 * S - K / 2;
+        const int hi0 = ho0 * S - DIL * (K / 2), wi0 = wo0 * S - DIL * (K / 2);
         __syncthreads();     // previous tile fully consumed (and cst/wts visible on the first pass)
         if (KQ > 0) {
             const float inv_iw = 1.f / (float)IW;
@@ -226,7 +234,7 @@ __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float*
             f32x4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
 #pragma unroll 1
             for (int ky = 0; ky < K; ++ky) {
-                const float* rowp = in_tile + ((oh * S + ky) * IW + ow0 * S) * CC + 4 * cq;
+                const float* rowp = in_tile + ((oh * S + ky * DIL) * IW + ow0 * S) * CC + 4 * cq;
                 const float* wp = wts + ky * K * CC + 4 * cq;
                 f32x4 win[WIN];
 #pragma unroll
@@ -235,7 +243,7 @@ __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float*
                 for (int kx = 0; kx < K; ++kx) {
                     const f32x4 wv = ld4(wp + kx * CC);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] += win[j * S + kx] * wv;
+                    for (int j = 0; j < 4; ++j) acc[j] += win[j * S + kx * DIL] * wv;
                 }
             }
             const int ho = ho0 + oh;
@@ -268,7 +276,11 @@ __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float*
 // stride 1), in the same store.  No BN1-backward sums: E, stats1 and `part` are not touched.  dx_accum: dx already holds the data
 // gradient of the cell's earlier branches (a mixed cell) and the same store adds it -- read and written by the one thread that
 // owns the element, its load issued with the residual's before the tap loop.
-template <int K, int S, int ACT, int KQ, bool RAW = false>
+// DIL: PAD = DIL * (K / 2) and tap (ky, kx) of input (hi, wi) reads output ((hi + PAD - ky * DIL) / S, (wi + PAD - kx * DIL) / S).
+// Stride 2 with DIL = 2: PAD and every tap offset are even, so only even input rows and columns receive anything -- the odd
+// pixels pass the parity tests of no tap, keep acc = 0 and are STORED as zero like every other element of the tile (dEh, and the dx
+// of the RAW form, are written everywhere the pass owns).
+template <int K, int S, int ACT, int KQ, bool RAW = false, int DIL = 1>
 __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const float* __restrict__ dZ,
                                                         const float* __restrict__ gate, const float* __restrict__ dpooled,
                                                         const float* __restrict__ D, const double* __restrict__ stats2,
@@ -278,12 +290,13 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
                                                         float* __restrict__ part, DwGeom gm, int dx_accum) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int g, c0, lane = blockIdx.x, cy = blockIdx.y;
+    static_assert(DIL == 1 || (DIL == 2 && KQ == 0 && (K == 3 || K == 5)), "dilation 2: 3 x 3 / 5 x 5 from E or raw x");
     if (KQ > 0) efree_lane_chunk(lane, cy);
-    if (!dw_locate<K>(d, cy, gm.CC, g, c0)) return;
+    if (!dw_locate<K, DIL>(d, cy, gm.CC, g, c0)) return;
     const int mc = d.g[g].mc, mcp = d.g[g].mcp, off = d.g[g].off;
     const int CC = gm.CC, CQ = CC >> 2, TIH = gm.T0, TIW = gm.T1;
     const int H = d.H, W = d.W, Ho = d.Ho, Wo = d.Wo, M = d.M;
-    constexpr int PAD = K / 2;
+    constexpr int PAD = DIL * (K / 2), KE = DIL * (K - 1) + 1;
     const int tid = threadIdx.x;
     const int OH = gm.L0, OW = gm.L1;      // LDS tile extent (host: worst case over tile origins)
 
@@ -314,7 +327,7 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
     for (int t = KQ > 0 ? lane : xcd_first_tile(); t < gm.ntiles; t += gridDim.x) {
         const int tw = t % gm.tilesW, th = (t / gm.tilesW) % gm.tilesH, n = t / (gm.tilesW * gm.tilesH);
         const int hi0 = th * TIH, wi0 = tw * TIW;
-        const int oh0 = floordiv(hi0 + PAD - (K - 1), S), ow0 = floordiv(wi0 + PAD - (K - 1), S);
+        const int oh0 = floordiv(hi0 + PAD - (KE - 1), S), ow0 = floordiv(wi0 + PAD - (KE - 1), S);
         __syncthreads();
         // this thread always stages the same channel quad (256 % CQ == 0): its SE gate / pool-path terms of image n
         const int mycq = tid & (CQ - 1);
@@ -366,27 +379,27 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
                 else ev[j] = okj ? ld4_nt(E + (((size_t)(n * H + hi) * W + wi) * M + off + c0 + 4 * cq)) : zero4();
             }
             if (S == 1) {
-                // column of output (wi + PAD - kx) relative to ow0 = wi0 + PAD - (K-1):  iw0 + j - kx + K - 1
+                // column of output (wi + PAD - kx * DIL) relative to ow0 = wi0 + PAD - (KE-1):  iw0 + j - kx * DIL + KE - 1
 #pragma unroll 1
                 for (int ky = 0; ky < K; ++ky) {
-                    const int r = hi + PAD - ky - oh0;
+                    const int r = hi + PAD - ky * DIL - oh0;
                     const float* rowp = dd_tile + (r * OW + iw0) * CC + 4 * cq;
                     const float* wp = wts + ky * K * CC + 4 * cq;
-                    f32x4 win[K + 3];
+                    f32x4 win[KE + 3];
 #pragma unroll
-                    for (int u = 0; u < K + 3; ++u) win[u] = ld4(rowp + u * CC);
+                    for (int u = 0; u < KE + 3; ++u) win[u] = ld4(rowp + u * CC);
 #pragma unroll
                     for (int kx = 0; kx < K; ++kx) {
                         const f32x4 wv = ld4(wp + kx * CC);
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[j] += win[j - kx + K - 1] * wv;
+                        for (int j = 0; j < 4; ++j) acc[j] += win[j - kx * DIL + KE - 1] * wv;
                     }
                 }
             } else {
                 const int base = wi0 + iw0;   // multiple of 4 -> even
 #pragma unroll 1
                 for (int ky = 0; ky < K; ++ky) {
-                    const int tt = hi + PAD - ky;
+                    const int tt = hi + PAD - ky * DIL;
                     if (tt & 1) continue;
                     const int r = tt / 2 - oh0;   // tt even: exact also for negatives
                     const float* wp = wts + ky * K * CC + 4 * cq;
@@ -395,8 +408,8 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
                         const f32x4 wv = ld4(wp + kx * CC);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            if ((j + PAD - kx) & 1) continue;   // compile-time after unrolling
-                            const int c = base / 2 + (j + PAD - kx) / 2 - ow0;
+                            if ((j + PAD - kx * DIL) & 1) continue;   // compile-time after unrolling
+                            const int c = base / 2 + (j + PAD - kx * DIL) / 2 - ow0;
                             acc[j] += ld4(dd_tile + (r * OW + c) * CC + 4 * cq) * wv;
                         }
                     }
@@ -440,7 +453,8 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
 // every channel's K * K block of the partial row.
 // (KY0, KR as template arguments: tap rows [KY0, KY0 + KR) with every accumulator index a compile-time constant)
 // RAW (TFNAS_CELL_NOEXPAND): a1 is the cell input itself -- `E` = x [N*H*W][ic], row stride ic; stats1 is not touched.
-template <int K, int S, int ACT, int KY0, int KR, bool RAW>
+// DIL: as in k_dw_fwd (a1 at [ho*S + ky*DIL - DIL*p][wo*S + kx*DIL - DIL*p]); the partial row keeps its mc * K * K layout.
+template <int K, int S, int ACT, int KY0, int KR, bool RAW, int DIL>
 __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const float* __restrict__ dZ,
                                               const float* __restrict__ gate, const float* __restrict__ dpooled,
                                               const float* __restrict__ D, const double* __restrict__ stats2,
@@ -449,7 +463,7 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
                                               size_t out_size, const DwGeom& gm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int g, c0;
-    if (!dw_locate<K>(d, blockIdx.y, gm.CC, g, c0)) return;
+    if (!dw_locate<K, DIL>(d, blockIdx.y, gm.CC, g, c0)) return;
     const int mc = d.g[g].mc, mcp = d.g[g].mcp, off = d.g[g].off;
     size_t poff = 0;
     for (int gg = 0; gg < g; ++gg) poff += (size_t)d.g[gg].mc * d.g[gg].k * d.g[gg].k;
@@ -471,7 +485,7 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
                                     : make_float2(0.f, 0.f);
     }
 
-    constexpr int WIN = 3 * S + K;
+    constexpr int KE = DIL * (K - 1) + 1, WIN = 3 * S + KE;
     const int nsw = TW >> 2, nstrips = TH * nsw;
     const bool has_se = d.g[g].se > 0;
     const float inv_hw = 1.f / (float)(Ho * Wo);
@@ -481,7 +495,7 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
     for (int t = xcd_first_tile(); t < gm.ntiles; t += gridDim.x) {
         const int tw = t % gm.tilesW, th = (t / gm.tilesW) % gm.tilesH, n = t / (gm.tilesW * gm.tilesH);
         const int ho0 = th * TH, wo0 = tw * TW;
-        const int hi0 = ho0 * S - K / 2, wi0 = wo0 * S - K / 2;
+        const int hi0 = ho0 * S - DIL * (K / 2), wi0 = wo0 * S - DIL * (K / 2);
         const int mycq = tid & (CQ - 1);
         f32x4 g4 = zero4(), dp4 = zero4();
         if (has_se && c0 + 4 * mycq < mcp) {
@@ -560,14 +574,14 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
             for (int j = 0; j < 4; ++j) dd[j] = ok[j] ? bn2_dd<ACT>(cst2, 4 * cq, dd[j], dv[j], has_se, g4, dp4) : zero4();
 #pragma unroll
             for (int r = 0; r < KR; ++r) {
-                const float* rowp = in_tile + ((oh * S + KY0 + r) * IW + ow0 * S) * CC + 4 * cq;
+                const float* rowp = in_tile + ((oh * S + (KY0 + r) * DIL) * IW + ow0 * S) * CC + 4 * cq;
                 f32x4 win[WIN];
 #pragma unroll
                 for (int u = 0; u < WIN; ++u) win[u] = ld4(rowp + u * CC);
 #pragma unroll
                 for (int kx = 0; kx < K; ++kx)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) wacc[r * K + kx] += dd[j] * win[j * S + kx];
+                    for (int j = 0; j < 4; ++j) wacc[r * K + kx] += dd[j] * win[j * S + kx * DIL];
             }
         }
     }
@@ -597,7 +611,7 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
         }
     }
 }
-template <int K, int S, int ACT, int KR = K, bool RAW = false>
+template <int K, int S, int ACT, int KR = K, bool RAW = false, int DIL = 1>
 __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const float* __restrict__ dZ,
                                                      const float* __restrict__ gate, const float* __restrict__ dpooled,
                                                      const float* __restrict__ D, const double* __restrict__ stats2,
@@ -605,12 +619,13 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
                                                      const double* __restrict__ stats1, float* __restrict__ part,
                                                      size_t out_size, DwGeom gm) {
     static_assert(KR == K || (KR < K && 2 * KR >= K), "one part, or two over blockIdx.z");
+    static_assert(DIL == 1 || (DIL == 2 && (K == 3 || K == 5)), "dilation 2: 3 x 3 / 5 x 5");
     if constexpr (KR == K) {
-        dw_wgrad_rows<K, S, ACT, 0, K, RAW>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
+        dw_wgrad_rows<K, S, ACT, 0, K, RAW, DIL>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
     } else if (blockIdx.z == 0) {
-        dw_wgrad_rows<K, S, ACT, 0, KR, RAW>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
+        dw_wgrad_rows<K, S, ACT, 0, KR, RAW, DIL>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
     } else {
-        dw_wgrad_rows<K, S, ACT, KR, K - KR, RAW>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
+        dw_wgrad_rows<K, S, ACT, KR, K - KR, RAW, DIL>(d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, out_size, gm);
     }
 }
 
@@ -628,12 +643,16 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
 // geometry allows | 2 ring / tile kernels only | 3 tile kernels only: every choice is compared with the oracle
 // (tests/test_gpu_cell.py::test_variant_against_oracle)
 
-static int dw_chunks(const TfnasCellDesc& d, int K, int CC) {
+// channel chunks of the groups with kernel size K and dilation dil (the kernels' twin: dw_locate)
+static int dw_chunks(const TfnasCellDesc& d, int K, int CC, int dil = 1) {
     int t = 0;
     for (int g = 0; g < d.G; ++g)
-        if (d.g[g].k == K) t += cdiv(d.g[g].mcp, CC);
+        if (d.g[g].k == K && group_dil(d, g) == dil) t += cdiv(d.g[g].mcp, CC);
     return t;
 }
+// the (kernel size, dilation) pair of launch slot i of a pass (kernels.h: DW_NK): 3, 5, 7 undilated, then 3 and 5 with dilation 2
+static int dw_slot_k(int i) { return i < 3 ? 3 + 2 * i : 3 + 2 * (i - 3); }
+static int dw_slot_dil(int i) { return i < 3 ? 1 : 2; }
 
 // floats of one weight-gradient partial row: the groups' mc x K x K blocks in group order
 static size_t dw_wout_size(const TfnasCellDesc& d) {
@@ -646,9 +665,10 @@ static size_t dw_wout_size(const TfnasCellDesc& d) {
 // taps or accumulators in registers and are built for 3 and 5 only: such a cell takes the tile kernels in every pass, whatever
 // TFNAS_ROUTE_DW_* asks, never fuses the weight gradient into the backward-data pass, and always has E (efree_supported).
 // The same holds for a cell with TFNAS_ACT_RELU6 / TFNAS_ACT_HSWISH: only the tile kernels are instantiated for them, and for a
-// cell without expand convolution (TFNAS_CELL_NOEXPAND): only the tile kernels have the raw-input form.
+// cell without expand convolution (TFNAS_CELL_NOEXPAND): only the tile kernels have the raw-input form; and for a cell with a
+// dilated group (TFNAS_CELL_DILATION): only the tile kernels have the tap spacing as a template argument.
 static bool dw_tile_only(const TfnasCellDesc& d) {
-    if (act_tile_only(d.act) || cell_noexpand(d)) return true;
+    if (act_tile_only(d.act) || cell_noexpand(d) || cell_dilated(d)) return true;
     for (int g = 0; g < d.G; ++g)
         if (d.g[g].k != 3 && d.g[g].k != 5) return true;
     return false;
@@ -667,6 +687,10 @@ static bool dw_groups_k(const TfnasCellDesc& d, bool k5) {
 
 // ---------------------------------------------------------------------------------------------------- tile kernels
 // force32: the E-free producer (efree.h) works on 32-channel chunks
+// K: the EFFECTIVE extent of the taps, dil * (k - 1) + 1 -- all the tile geometry knows of a kernel size is the halo.  The two
+// dilated extents, 5 and 9: 5 has the geometry of a 5 x 5; 9 lands in the 16-channel regime of the 7 x 7 at stride 2 forward
+// (15 x 39 pixels x 32 channels = 73 KB) and stays at 32 channels at stride 1 backward (17 x 25 pixels x 32 channels = 53.1 KB,
+// under the 56 KB switch; 57.0 KB with the taps and the constant tables) -- every launcher checks its total against 64 KB.
 static void pick_tile(int N, int Th, int Tw, int K, int S, bool fwd_like, DwGeom& gm, bool force32) {
     // T1 (width) multiple of 4 (strips), up to 16; T0 so that a tile has ~128 (64 for stride 2) pixels
     gm.T1 = Tw >= 16 ? 16 : ((Tw + 3) / 4) * 4;
@@ -699,14 +723,15 @@ static int dw_grid_x(const DwGeom& gm, int chunks, int target_blocks) {
     return gx < 1 ? 1 : gx;
 }
 
-// Tiles of Th x Tw (outputs for fwd_like, inputs otherwise).  The kernel-size launches (3, 5, 7) of one pass share grid.x so that
-// they fill the same rows of the partials matrix.
+// Tiles of Th x Tw (outputs for fwd_like, inputs otherwise).  The launches of one pass (3, 5, 7, dilated 3, dilated 5) share grid.x
+// so that they fill the same rows of the partials matrix.
 static void dw_tile_plan(const TfnasCellDesc& d, int Th, int Tw, bool fwd_like, int target_blocks, size_t row_floats,
                          bool force32, DwPlan& p) {
     int gx = 1 << 30;
     for (int i = 0; i < DW_NK; ++i) {
-        pick_tile(d.N, Th, Tw, 3 + 2 * i, d.stride, fwd_like, p.tile[i], force32);
-        p.chunks[i] = dw_chunks(d, 3 + 2 * i, p.tile[i].CC);
+        const int kk = dw_slot_k(i), dil = dw_slot_dil(i);
+        pick_tile(d.N, Th, Tw, dil * (kk - 1) + 1, d.stride, fwd_like, p.tile[i], force32);
+        p.chunks[i] = dw_chunks(d, kk, p.tile[i].CC, dil);
         if (!p.chunks[i]) continue;
         const int g1 = dw_grid_x(p.tile[i], p.chunks[i], target_blocks);
         if (g1 < gx) gx = g1;
@@ -916,6 +941,7 @@ static DwPlan dw_plan_wgrad(const TfnasCellDesc& d) {
 }
 
 // ---------------------------------------------------------------------------------------------------- launchers
+// (A tile launch also has a dilation, 1 | 2: dw_tile_dispatch_d below.)
 // Template arguments of a launch from its runtime kernel size (3 | 5, and 7 where TILE), stride (1 | 2), activation (ReLU | Swish,
 // and ReLU6 | hard-swish where TILE) and variant (one of Vs): calls f(K, S, ACT, V) with std::integral_constant arguments.  False
 // if the kernel size, the activation or the variant is not among them -- the launchers return TFNAS_EINVAL.  (Every combination
@@ -954,6 +980,19 @@ template <int... Vs, class F>
 static bool dw_tile_dispatch(int k, int stride, int act, int v, F&& f) {
     return dw_dispatch_k<true, Vs...>(k, stride, act, v, f);
 }
+// the tile launch of slot (k, dil): f(K, S, ACT, V, DIL).  Dilation 2: kernel sizes 3 | 5 and the variant 0 (KQ = 0: E or the raw
+// input is read) only -- anything else is not instantiated and returns false
+template <int... Vs, class F>
+static bool dw_tile_dispatch_d(int k, int dil, int stride, int act, int v, F&& f) {
+    if (dil == 1)
+        return dw_tile_dispatch<Vs...>(k, stride, act, v, [&](auto K, auto S, auto A, auto V) {
+            f(K, S, A, V, std::integral_constant<int, 1>{});
+        });
+    if (dil != 2 || (k != 3 && k != 5) || v != 0) return false;
+    return dw_tile_dispatch<0>(k, stride, act, 0, [&](auto K, auto S, auto A, auto V) {
+        if constexpr (K != 7) f(K, S, A, V, std::integral_constant<int, 2>{});
+    });
+}
 // variant of the launches with the weight gradient fused into the backward-data pass (k_dwd_bwd<.., WG>, k_dws_bwd<.., WGR>)
 constexpr int DW_WG = -1;
 // variant of a ring launch: 0 plain, 1 register prefetch (PIPE), KQ (6 | 10: E-free), DW_WG
@@ -978,7 +1017,7 @@ int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const 
     const DwPlan p = dw_plan_fwd(d, !raw && E == nullptr, x != nullptr);
     for (int i = 0; i < DW_NK; ++i) {
         if (!p.chunks[i]) continue;
-        const int kk = 3 + 2 * i;
+        const int kk = dw_slot_k(i), dil = dw_slot_dil(i);
         ProfScope _prof(TK_DW_FWD, s, d.G > 2);
         bool ok = false;
         if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_tile_only)
@@ -1000,15 +1039,15 @@ int launch_dw_fwd(const TfnasCellDesc& d, const float* E, const float* x, const 
             const size_t shm = (size_t)(tile + kk * kk * gm.CC + 2 * gm.CC) * sizeof(float);
             if (shm > 64 * 1024) return TFNAS_ERANGE;
             if (raw)        // (no activation before the depthwise: one instantiation per K, S)
-                ok = dw_tile_dispatch<0>(kk, d.stride, TFNAS_ACT_RELU, 0, [&](auto K, auto S, auto, auto) {
-                    hipLaunchKernelGGL((k_dw_fwd<K, S, TFNAS_ACT_RELU, 0, true>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d,
-                                       nullptr, x, nullptr, D, part, gm);
+                ok = dw_tile_dispatch_d<0>(kk, dil, d.stride, TFNAS_ACT_RELU, 0, [&](auto K, auto S, auto, auto, auto DIL) {
+                    hipLaunchKernelGGL((k_dw_fwd<K, S, TFNAS_ACT_RELU, 0, true, DIL>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s,
+                                       d, nullptr, x, nullptr, D, part, gm);
                 });
             else
-            ok = dw_tile_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
+            ok = dw_tile_dispatch_d<0, 4, 6, 10>(kk, dil, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ, auto DIL) {
                 if constexpr ((K != 7 && !act_tile_only(A)) || KQ == 0)     // (no E-free 7 x 7 / ReLU6 / hard-swish kernels: refused above)
-                    hipLaunchKernelGGL((k_dw_fwd<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, E, x, stats1, D,
-                                       part, gm);
+                    hipLaunchKernelGGL((k_dw_fwd<K, S, A, KQ, false, DIL>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, E, x,
+                                       stats1, D, part, gm);
             });
         }
         if (!ok) return TFNAS_EINVAL;
@@ -1025,7 +1064,7 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
     float* wpart = part + (((size_t)p.rows * 2 * d.M + 63) & ~(size_t)63);    // (fuse_wgrad: behind the statistics partials)
     for (int i = 0; i < DW_NK; ++i) {
         if (!p.chunks[i]) continue;
-        const int kk = 3 + 2 * i;
+        const int kk = dw_slot_k(i), dil = dw_slot_dil(i);
         ProfScope _prof(TK_DW_BWD_DATA, s, d.G > 2);
         bool ok = false;
         if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_tile_only)
@@ -1061,10 +1100,10 @@ int launch_dw_bwd_data(const DwPlan& p, const TfnasCellDesc& d, const float* dZ,
             const size_t shm = (size_t)(tile + kk * kk * gm.CC + 4 * gm.CC + 2 * gm.CC + (p.kq ? gm.T0 * gm.T1 * gm.CC : 0)) *
                                sizeof(float);
             if (shm > 64 * 1024) return TFNAS_ERANGE;
-            ok = dw_tile_dispatch<0, 4, 6, 10>(kk, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ) {
+            ok = dw_tile_dispatch_d<0, 4, 6, 10>(kk, dil, d.stride, d.act, p.kq, [&](auto K, auto S, auto A, auto KQ, auto DIL) {
                 if constexpr ((K != 7 && !act_tile_only(A)) || KQ == 0)
-                    hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, KQ>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate,
-                                       dpooled, D, stats2, red2, E, x, stats1, dEh, part, gm, 0);
+                    hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, KQ, false, DIL>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ,
+                                       gate, dpooled, D, stats2, red2, E, x, stats1, dEh, part, gm, 0);
             });
         }
         if (!ok) return TFNAS_EINVAL;
@@ -1089,20 +1128,25 @@ int launch_dw_bwd_dx(const TfnasCellDesc& d, const float* dZ, const float* gate,
     if (p.fam != DW_TILE) return TFNAS_EINVAL;       // (never planned: dw_tile_only)
     for (int i = 0; i < DW_NK; ++i) {
         if (!p.chunks[i]) continue;
-        const int kk = 3 + 2 * i;
+        const int kk = dw_slot_k(i), dil = dw_slot_dil(i);
         ProfScope _prof(TK_DW_BWD_DATA, s, false);
         const DwGeom gm = p.tile[i];
         const int tile = gm.L0 * gm.L1 * gm.CC > 2048 ? gm.L0 * gm.L1 * gm.CC : 2048;
         const size_t shm = (size_t)(tile + kk * kk * gm.CC + 4 * gm.CC + 2 * gm.CC) * sizeof(float);
         if (shm > 64 * 1024) return TFNAS_ERANGE;
-        const bool ok = dw_tile_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
-            hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, 0, true>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate, dpooled,
-                               D, stats2, red2, nullptr, dres, nullptr, dx, nullptr, gm, (int)accum);
+        const bool ok = dw_tile_dispatch_d<0>(kk, dil, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto, auto DIL) {
+            hipLaunchKernelGGL((k_dw_bwd_data<K, S, A, 0, true, DIL>), dim3(p.rows, p.chunks[i]), dim3(256), shm, s, d, dZ, gate,
+                               dpooled, D, stats2, red2, nullptr, dres, nullptr, dx, nullptr, gm, (int)accum);
         });
         if (!ok) return TFNAS_EINVAL;
     }
     return (int)hipGetLastError();
 }
+
+// tap rows of one k_dw_wgrad workgroup (KR).  All K of them, except: 7 x 7 -- 4 (rows 0-3 | 4-6); the dilated 5 x 5 at stride 1
+// -- 3 (rows 0-2 | 3-4): its 25 accumulators beside the 12-wide register window (stride + 9 taps' extent) spill 36-48 bytes of
+// scratch at 256 registers, 15 do not.  (At stride 2 the window holds only the 8 even entries and all 25 fit: 249-251 registers.)
+static constexpr int dw_wgrad_kr(int k, int stride, int dil) { return k == 7 ? 4 : (k == 5 && dil == 2 && stride == 1) ? 3 : k; }
 
 int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, const float* dpooled, const float* D,
                     const double* stats2, const double* red2, const float* E, const double* stats1, float* part,
@@ -1112,7 +1156,7 @@ int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, 
     const size_t wout = dw_wout_size(d);
     for (int i = 0; i < DW_NK; ++i) {
         if (!p.chunks[i]) continue;
-        const int kk = 3 + 2 * i;
+        const int kk = dw_slot_k(i), dil = dw_slot_dil(i);
         ProfScope _prof(TK_DW_WGRAD, s);
         if (p.fam != DW_TILE && i >= 2) return TFNAS_EINVAL;     // (never planned: dw_tile_only)
         if (p.fam == DW_DIRECT) {
@@ -1132,22 +1176,22 @@ int launch_dw_wgrad(const TfnasCellDesc& d, const float* dZ, const float* gate, 
             });
         } else {
             const DwGeom gm = p.tile[i];
-            const int kr = kk == 7 ? 4 : kk;       // tap rows per workgroup (k_dw_wgrad: KR), parts over blockIdx.z
+            const int kr = dw_wgrad_kr(kk, d.stride, dil);     // tap rows per workgroup (k_dw_wgrad: KR), parts over blockIdx.z
             int tile = gm.L0 * gm.L1 * gm.CC;
             if (tile < 4 * kr * kk * gm.CC) tile = 4 * kr * kk * gm.CC;
             const size_t shm = (size_t)(tile + 4 * gm.CC + 2 * gm.CC) * sizeof(float);
             if (shm > 64 * 1024) return TFNAS_ERANGE;
             if (cell_noexpand(d))        // (E = the cell input x, raw)
-                dw_tile_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
-                    constexpr int KR = K == 7 ? 4 : (int)K;
-                    hipLaunchKernelGGL((k_dw_wgrad<K, S, A, KR, true>), dim3(p.rows, p.chunks[i], (K + KR - 1) / KR), dim3(256), shm,
-                                       s, d, dZ, gate, dpooled, D, stats2, red2, E, nullptr, part, wout, gm);
+                dw_tile_dispatch_d<0>(kk, dil, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto, auto DIL) {
+                    constexpr int KR = dw_wgrad_kr(K, S, DIL);
+                    hipLaunchKernelGGL((k_dw_wgrad<K, S, A, KR, true, DIL>), dim3(p.rows, p.chunks[i], (K + KR - 1) / KR), dim3(256),
+                                       shm, s, d, dZ, gate, dpooled, D, stats2, red2, E, nullptr, part, wout, gm);
                 });
             else
-            dw_tile_dispatch<0>(kk, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto) {
-                constexpr int KR = K == 7 ? 4 : (int)K;
-                hipLaunchKernelGGL((k_dw_wgrad<K, S, A, KR>), dim3(p.rows, p.chunks[i], (K + KR - 1) / KR), dim3(256), shm, s, d,
-                                   dZ, gate, dpooled, D, stats2, red2, E, stats1, part, wout, gm);
+            dw_tile_dispatch_d<0>(kk, dil, d.stride, d.act, 0, [&](auto K, auto S, auto A, auto, auto DIL) {
+                constexpr int KR = dw_wgrad_kr(K, S, DIL);
+                hipLaunchKernelGGL((k_dw_wgrad<K, S, A, KR, false, DIL>), dim3(p.rows, p.chunks[i], (K + KR - 1) / KR), dim3(256), shm,
+                                   s, d, dZ, gate, dpooled, D, stats2, red2, E, stats1, part, wout, gm);
             });
         }
     }

@@ -73,6 +73,18 @@ static inline int skip_groups(const TfnasCellDesc& d) {
         for (int g = d.G < TFNAS_MAX_GROUPS ? d.G : TFNAS_MAX_GROUPS; g > 0 && d.g[g - 1].kind == TFNAS_GROUP_SKIP; --g) ++n;
     return n;
 }
+// TFNAS_CELL_DILATION: the depthwise dilation of group g (TfnasGroup.dil) -- 1, or 2 = taps two pixels apart.  Without the bit the
+// word is not read (it was padding): every group is undilated.  The entry points refuse any other value (capi.hip: check_dilation).
+__host__ __device__ static inline int group_dil(const TfnasCellDesc& d, int g) {
+    return ((d.flags & TFNAS_CELL_DILATION) && d.g[g].dil == 2) ? 2 : 1;
+}
+// a cell with a dilated group follows the 7 x 7 rule: E materialised, LDS tile kernels in every depthwise pass, the depthwise weight
+// gradient in a launch of its own (dwconv_kernels.hip: dw_tile_only; efree_supported, fx_plan)
+static inline bool cell_dilated(const TfnasCellDesc& d) {
+    for (int g = 0; g < d.G && g < TFNAS_MAX_GROUPS; ++g)
+        if (group_dil(d, g) != 1) return true;
+    return false;
+}
 // group-aware forms of the two facts: some group has an E buffer / a BatchNorm site 0
 static inline bool any_group_has_E(const TfnasCellDesc& d) {
     for (int g = 0; g < d.G; ++g)
@@ -163,8 +175,8 @@ int launch_expand_wgrad(const TfnasCellDesc& d, const float* dEh, const float* E
 int launch_dx_add_res(const TfnasCellDesc& d, int nw, const float* dout, const float* wmix, float* dx, hipStream_t s);
 
 // dwconv_kernels.hip: the depthwise k x k convolution in three kernel families, each with the geometry struct its kernels take by
-// value: k = 3 | 5 in all of them, k = 7 in the LDS tile kernels only (a cell with a 7 x 7 group is planned onto those in every
-// pass); ReLU | Swish in all of them, ReLU6 | hard-swish in the tile kernels only (act_tile_only: the same rule).
+// value: k = 3 | 5 in all of them, k = 7 and dilation 2 (k = 3 | 5) in the LDS tile kernels only (a cell with such a group is
+// planned onto those in every pass); ReLU | Swish in all of them, ReLU6 | hard-swish in the tile kernels only (act_tile_only: the same rule).
 // Register-window kernels (dw_direct.inc):
 struct DwDirect {
     int chunks;      // 32-channel chunks of the groups with this kernel size
@@ -190,14 +202,14 @@ struct DwGeom {
     int L0, L1;        // LDS tile extent (rows, cols)
 };
 // What one depthwise pass launches, chosen once by the pass's planner from the descriptor (route bits included), whether E is
-// present and whether x is given; the launcher carries it out: the k = 3 launch, the k = 5 launch, the k = 7 launch (DW_TILE
-// only), then the reductions of the `rows` partial rows.
+// present and whether x is given; the launcher carries it out: the k = 3 launch, the k = 5 launch, the k = 7 launch, the dilated
+// k = 3 and k = 5 launches (the last three: DW_TILE only), then the reductions of the `rows` partial rows.
 enum DwFamily { DW_DIRECT, DW_RING, DW_TILE };
-constexpr int DW_NK = 3;  // kernel sizes 3 + 2 * i of a pass
+constexpr int DW_NK = 5;  // launch slots of a pass, one per (kernel size, dilation): (3, 1) (5, 1) (7, 1) (3, 2) (5, 2)
 struct DwPlan {
     DwFamily fam;
     int rows;             // partial rows of the pass
-    int chunks[DW_NK];    // channel chunks of the k = 3 / k = 5 / k = 7 launch (0: not launched)
+    int chunks[DW_NK];    // channel chunks of each slot's launch (0: not launched)
     DwDirect direct[2];   // geometry of the k = 3 / k = 5 launch: the planned family's member
     DwSlide ring[2];
     DwGeom tile[DW_NK];

@@ -33,6 +33,7 @@ CELL_FUSED = 0x400           # TfnasCellDesc.flags: the one group is a Fused-MBC
 CELL_KINDS = 0x800           # TfnasCellDesc.flags: every group names its own kind in TfnasGroup.kind (group_kind_id; refused without the bit)
 CELL_SE_STYLE = 0x1000       # TfnasCellDesc.flags: se_style may be non-zero (se_style_id; refused without the bit)
 CELL_SKIP = 0x2000           # TfnasCellDesc.flags: groups may be GROUP_SKIP, the identity candidate (with CELL_KINDS, residual cells only)
+CELL_DILATION = 0x8000       # TfnasCellDesc.flags: groups may have depthwise dilation 2 (TfnasGroup.dil; not read without the bit)
 GROUP_SKIP = 3               # TfnasGroup.kind of a skip group: no width, no weights, no columns -- not a BlockKind (KINDS stays three)
 SE_GATE = {'sigmoid': 0, 'h-sigmoid': 1}      # gate function of a squeeze-excite branch (bits 4-7 of TfnasCellDesc.se_style)
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
@@ -113,19 +114,29 @@ def group_kind_id(kind):
     return KINDS.index(kind)
 
 
-def describe_block(kind, N, H, W, ic, mc, se, oc, k, stride, act):
+def dilation_flags(dils):
+    """TfnasCellDesc.flags bit a descriptor whose groups have the depthwise dilations ``dils`` needs: CELL_DILATION when one of
+    them is dilated, nothing otherwise (an undilated descriptor is what it always was)."""
+    return CELL_DILATION if any(int(v) > 1 for v in dils) else 0
+
+
+def describe_block(kind, N, H, W, ic, mc, se, oc, k, stride, act, dilation=1):
     """A one-block TFNAS_MODE_CELL descriptor of ``kind``, before tfnas_cell_plan: the geometry words, has_res, eps and the flags
-    the geometry itself asks for (CELL_K7, the activation's bit, the kind's bit).  ``act``: a TFNAS_ACT_* id.  Pure host code."""
+    the geometry itself asks for (CELL_K7, CELL_DILATION, the activation's bit, the kind's bit).  ``act``: a TFNAS_ACT_* id.  Pure
+    host code."""
     d = TfnasCellDesc()
     d.N, d.H, d.W, d.ic, d.oc, d.stride, d.act, d.G, d.mode = N, H, W, ic, oc, stride, act, 1, MODE_CELL
     d.has_res, d.eps = int(ic == oc and stride == 1), BN_EPS
     d.g[0].mc, d.g[0].k, d.g[0].se = mc, k, se
     d.flags = (CELL_K7 if k == 7 else 0) | act_flags(act) | kind.flag
+    if dilation != 1:
+        d.g[0].dil = dilation
+        d.flags |= dilation_flags((dilation,))
     return d
 
 
 class TfnasGroup(C.Structure):
-    _fields_ = ([(n, C.c_int32) for n in ('mc', 'k', 'se', 'mcp', 'off', 'se_off', 'kind', 'pad1')]
+    _fields_ = ([(n, C.c_int32) for n in ('mc', 'k', 'se', 'mcp', 'off', 'se_off', 'kind', 'dil')]
                 + [(n, C.c_void_p) for n in _W_FIELDS] + [(n, C.c_void_p) for n in _G_FIELDS])
 
 

@@ -140,6 +140,7 @@ class HipModes:
         if any(d.g[g].k == 7 for g in range(min(d.G, _lib.MAX_GROUPS))):
             d.flags |= _lib.CELL_K7                    # (the library takes 7 x 7 groups only from callers that say they know them)
         d.flags |= _lib.act_flags(d.act)               # (... and 'relu6' / 'h-swish')
+        d.flags |= _lib.dilation_flags(d.g[g].dil for g in range(min(d.G, _lib.MAX_GROUPS)))     # (... and dilated groups)
         if kind is None:
             kind = _lib.NOEXPAND if (d.mode == _lib.MODE_CELL and d.G == 1 and d.g[0].mc == d.ic) else _lib.MBCONV
         d.flags |= kind.flag                           # (... and the two newer block kinds)
@@ -264,6 +265,8 @@ class CellPlan:
             d.act, d.has_res, d.G, d.need_wgrad, d.eps = _lib.act_id(self.act), self.has_res, len(self.blocks), 0, BN_EPS
             for g, b in enumerate(self.blocks):
                 d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
+                dil = getattr(b, 'dilation', 1)
+                d.g[g].dil = dil if dil != 1 else 0    # (an undilated group keeps the word at 0, as before the field had a name)
             self.modes.apply(d, *self._kind_arg)       # (before the plan: it validates the modes; every launch re-checks them)
             self._mark(d)
             check(_lib.lib().tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')

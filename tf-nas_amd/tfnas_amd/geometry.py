@@ -32,6 +32,18 @@ PRIMITIVE_SPECS = OrderedDict(
     + [('FMB_k3_%s%s' % (e, '_se' if se else ''), ('FusedMBConvBlock', 3, se, False)) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))]
     + [('DS_k%d%s' % (k, '_se' if se else ''), ('MBInvertedResBlock', k, se, True)) for k in (3, 5) for se in (0, 1)])
 
+# The dilated primitives (model_search.DILATED_OPS builds the modules): depthwise taps two pixels apart, everything else like their
+# undilated twins -- 'MBI_k3d2_e6_se' is 'MBI_k3_e6_se' with dilation 2, 'DS_k5d2' is 'DS_k5' with dilation 2 (the dil_conv_3x3 /
+# dil_conv_5x5 of the DARTS-family spaces).  They have the same four words in PRIMITIVE_SPECS as every primitive; the dilation is
+# a table of its own (primitive_dilation), 1 for every name that is not in it.
+PRIMITIVE_DILATION = OrderedDict(
+    [('MBI_k%dd2_%s%s' % (k, e, '_se' if se else ''), 2) for k in (3, 5) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))]
+    + [('DS_k%dd2%s' % (k, '_se' if se else ''), 2) for k in (3, 5) for se in (0, 1)])
+PRIMITIVE_SPECS.update(
+    [('MBI_k%dd2_%s%s' % (k, e, '_se' if se else ''), ('MBInvertedResBlock', k, se, False))
+     for k in (3, 5) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))]
+    + [('DS_k%dd2%s' % (k, '_se' if se else ''), ('MBInvertedResBlock', k, se, True)) for k in (3, 5) for se in (0, 1)])
+
 
 SKIP = 'skip'        # the identity candidate (the reference's commented-out primitive): recognised NEXT to PRIMITIVE_SPECS -- it
                      # has no layer spec (no kernel, no width, no SE) and only residual cells can hold it (residual_cells)
@@ -80,6 +92,24 @@ def primitive_block(name, ic, mc):
         raise ValueError('tfnas_amd: unknown primitive %r (one of %s)' % (name, ', '.join(sorted(PRIMITIVE_SPECS))))
     layer, k, se_mult, own = PRIMITIVE_SPECS[name]
     return layer, (ic if own else mc), ic * se_mult, k
+
+
+def primitive_dilation(name):
+    """Depthwise dilation of primitive ``name``: 2 for the dilated ones (PRIMITIVE_DILATION), 1 for every other registered name
+    and for 'skip'; ValueError for an unknown name, as primitive_block."""
+    primitive_block(name, 4, 4)
+    return PRIMITIVE_DILATION.get(name, 1)
+
+
+def dilation_keys(dilation):
+    """The key a block's config carries for its depthwise dilation: only where it is not 1, so that the config of an undilated
+    block is what it always was (se_style_keys is the pattern)."""
+    return {'dilation': dilation} if dilation != 1 else {}
+
+
+def kernel_tag(k, dilation=1):
+    """How a latency-table key spells a depthwise kernel: 'k3', 'k5', 'k7'; 'k3d2' / 'k5d2' with dilation 2."""
+    return 'k%d' % k if dilation == 1 else 'k%dd%d' % (k, dilation)
 
 
 # stage -> (in_channels[], out_channels[], strides[], act, stage_type)   (model_search.py:221-275)
@@ -138,9 +168,10 @@ def make_mc_mask_dddict():
     return d
 
 
-def lut_key(size, ic, se, oc, k, stride, act):
-    """LUT key format of MixedOP.get_lookup_latency (model_search.py:99-107)."""
-    return 'MBInvertedResBlock_{}_{}_{}_{}_k{}_s{}_{}'.format(size, ic, se, oc, k, stride, act)
+def lut_key(size, ic, se, oc, k, stride, act, dilation=1):
+    """LUT key format of MixedOP.get_lookup_latency (model_search.py:99-107); a dilated block writes 'k3d2' / 'k5d2' where an
+    undilated one writes 'k3' / 'k5'."""
+    return 'MBInvertedResBlock_{}_{}_{}_{}_{}_s{}_{}'.format(size, ic, se, oc, kernel_tag(k, dilation), stride, act)
 
 
 def make_lat_lookup_key_dddict():

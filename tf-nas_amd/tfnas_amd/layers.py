@@ -217,10 +217,19 @@ class MBInvertedResBlock(_HipBlock):
     ``forward`` runs the fused HIP path (sampled mode of ``tfnas_mixedop_fwd``; ``affine=True``: ``tfnas_mbconv_fwd``).  With
     ``mid_channels <= in_channels`` there is no expand convolution (``inverted_bottleneck is None``, mid normalised to in: the
     reference's layers.py:463-482): depthwise -> BN -> act -> [SE] -> project -> BN [+ x], the library's TFNAS_CELL_NOEXPAND cell
-    with two BatchNorm sites.  (``Network._stem`` runs ``second_stem`` fused with ``first_stem`` instead.)"""
+    with two BatchNorm sites.  (``Network._stem`` runs ``second_stem`` fused with ``first_stem`` instead.)
+
+    ``dilation`` (1 | 2; 2 with kernel size 3 or 5 only): the spacing of the depthwise taps, padding ``dilation * (k // 2)`` so the
+    output size does not depend on it -- TfnasGroup.dil under TFNAS_CELL_DILATION.  The weight stays [mc, 1, k, k]: no parameter,
+    module or state_dict key depends on it."""
 
     def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size=3, stride=1,
-                 affine=False, act_func='relu', *, se_act=None, se_gate='sigmoid'):
+                 affine=False, act_func='relu', *, se_act=None, se_gate='sigmoid', dilation=1):
+        if type(dilation) is not int or dilation not in (1, 2):
+            raise ValueError('tfnas_amd: depthwise dilation is 1 or 2 (got %r)' % (dilation,))
+        if dilation == 2 and kernel_size == 7:
+            raise ValueError('tfnas_amd: dilation 2 goes with kernel size 3 or 5, not 7')
+        self.dilation = dilation
         expand = mid_channels > in_channels
         if not expand:
             mid_channels = in_channels
@@ -229,8 +238,8 @@ class MBInvertedResBlock(_HipBlock):
         def lead(mc):
             return OrderedDict(
                 inverted_bottleneck=_seq(conv=nn.Conv2d(in_channels, mc, 1, 1, 0, bias=False), **self.bn(mc)) if expand else None,
-                depth_conv=_seq(conv=nn.Conv2d(mc, mc, kernel_size, stride, get_same_padding(kernel_size), groups=mc,
-                                               bias=False), **self.bn(mc)))
+                depth_conv=_seq(conv=nn.Conv2d(mc, mc, kernel_size, stride, padding=dilation * get_same_padding(kernel_size),
+                                               dilation=dilation, groups=mc, bias=False), **self.bn(mc)))
         super().__init__(in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead,
                          se_act=se_act, se_gate=se_gate)
 

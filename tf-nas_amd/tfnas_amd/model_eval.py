@@ -106,8 +106,9 @@ class _DerivedBase(nn.Module):
             for b in stage:
                 if isinstance(b, IdentityLayer):           # a skipped block costs nothing and keeps the resolution
                     continue
-                key = '{}_{}_{}_{}_{}_k{}_s{}_{}'.format(b.name, size, b.in_channels, b.se_channels, b.out_channels,
-                                                         b.kernel_size, b.stride, b.act_func)
+                key = '{}_{}_{}_{}_{}_{}_s{}_{}'.format(b.name, size, b.in_channels, b.se_channels, b.out_channels,
+                                                        geometry.kernel_tag(b.kernel_size, getattr(b, 'dilation', 1)), b.stride,
+                                                        b.act_func)
                 lat += self.lat_lookup[key][b.mid_channels]
                 size = (size - 1) // b.stride + 1
         return lat
@@ -119,7 +120,8 @@ class _DerivedBase(nn.Module):
         return {'name': b.name, 'in_channels': b.in_channels, 'mid_channels': b.mid_channels,
                 'se_channels': b.se_channels, 'out_channels': b.out_channels, 'kernel_size': b.kernel_size, 'stride': b.stride,
                 'groups': 1, 'has_shuffle': False, 'bias': False, 'use_bn': True, 'affine': True, 'act_func': b.act_func,
-                **geometry.se_style_keys(b.se_act, b.se_gate)}      # ('se_act' / 'se_gate': only where not the default)
+                **geometry.se_style_keys(b.se_act, b.se_gate),      # ('se_act' / 'se_gate': only where not the default)
+                **geometry.dilation_keys(getattr(b, 'dilation', 1))}  # ('dilation': only where not 1)
 
     @property
     def config(self):
@@ -171,7 +173,8 @@ class Network(_DerivedBase):
                 cls = FusedMBConvBlock if layer == 'FusedMBConvBlock' else MBInvertedResBlock
                 # (``se_style``: likewise -- None, one (se_act, se_gate) pair or a {stage: pair} mapping; the stems keep theirs)
                 se_act, se_gate = _lib.se_style_pair(geometry.cell_se_style(se_style, name, block_name))
-                blk = cls(ic, mc, se, oc, k, s, affine=True, act_func=cfg['act'], se_act=se_act, se_gate=se_gate)
+                dil = geometry.dilation_keys(geometry.primitive_dilation(prim))      # (FusedMBConvBlock has no such argument)
+                blk = cls(ic, mc, se, oc, k, s, affine=True, act_func=cfg['act'], se_act=se_act, se_gate=se_gate, **dil)
                 blk.drop_connect_rate = self.drop_connect_rate * self.block_idx / self.block_count
                 stage.append(blk)
             setattr(self, name, stage)
@@ -197,9 +200,13 @@ class NetworkCfg(_DerivedBase):
             se_act, se_gate = c.get('se_act'), c.get('se_gate', 'sigmoid')
             if not fused_ok and _lib.se_style_id(se_act, se_gate) != 0:
                 raise NotImplementedError('second_stem runs fused with first_stem and keeps the default squeeze-excite: %r' % (c,))
+            dil = geometry.dilation_keys(c.get('dilation', 1))
+            if dil and (not fused_ok or c['name'] != 'MBInvertedResBlock'):
+                raise NotImplementedError('only an MBInvertedResBlock of a stage may be dilated (second_stem runs fused with '
+                                          'first_stem, FusedMBConvBlock has no depthwise convolution): %r' % (c,))
             return kinds[c['name']](c['in_channels'], c['mid_channels'], c['se_channels'], c['out_channels'],
                                       c['kernel_size'], c['stride'], affine=c.get('affine', True), act_func=c['act_func'],
-                                      se_act=se_act, se_gate=se_gate)
+                                      se_act=se_act, se_gate=se_gate, **dil)
         fs = model_config['first_stem']
         self.first_stem = ConvLayer(fs['in_channels'], fs['out_channels'], fs['kernel_size'], fs['stride'], affine=True,
                                     act_func=fs['act_func'])

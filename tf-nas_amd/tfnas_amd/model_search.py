@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .functions import ArchFn, CellPlan, HeadFn, MixedOpFn, SinkFn, StemFn, arch_sample
-from .geometry import SKIP
+from .geometry import SKIP, kernel_tag
 from .layers import ConvLayer, FusedMBConvBlock, IdentityLayer, LinearLayer, MBInvertedResBlock
 
 PRIMITIVES = [
@@ -60,6 +60,26 @@ OPS.update({
     for k in (3, 5) for se in (0, 1)})
 
 
+# The dilated primitives, in a table of their own with the same signature (OPS keeps exactly the names it had): the taps of the
+# depthwise convolution two pixels apart -- a 3 x 3 covers 5 x 5 with 9 taps, a 5 x 5 covers 9 x 9 with 25.
+#   MBI_k3d2_* / MBI_k5d2_*  the dilated twins of the defaults (width from mc_num_dict[i], SE = ic x {1, 2})
+#   DS_k3d2* / DS_k5d2*      expand-free: the dil_conv_3x3 / dil_conv_5x5 of the DARTS-family spaces
+DILATED_OPS = {
+    'MBI_k%dd2_%s%s' % (k, e, '_se' if se else ''): (lambda ic, mc, oc, s, aff, act, _k=k, _se=se:
+                                                     MBInvertedResBlock(ic, mc, ic * _se, oc, _k, s, affine=aff, act_func=act,
+                                                                        dilation=2))
+    for k in (3, 5) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))}
+DILATED_OPS.update({
+    'DS_k%dd2%s' % (k, '_se' if se else ''): (lambda ic, mc, oc, s, aff, act, _k=k, _se=se:
+                                              MBInvertedResBlock(ic, ic, ic * _se, oc, _k, s, affine=aff, act_func=act, dilation=2))
+    for k in (3, 5) for se in (0, 1)})
+
+
+def primitive_factory(name):
+    """The factory (ic, mc, oc, stride, affine, act) -> block of a registered primitive, from either table."""
+    return OPS[name] if name in OPS else DILATED_OPS[name]
+
+
 def check_primitives(primitives):
     """The candidate names of one MixedOP: None -> the defaults; else a list of exactly len(PRIMITIVES) registered names
     (the architecture kernels and noise tensors are 8 wide).  ValueError names the legal ones."""
@@ -69,9 +89,9 @@ def check_primitives(primitives):
     if len(names) != len(PRIMITIVES):
         raise ValueError('tfnas_amd: a MixedOP takes exactly %d primitives, got %d' % (len(PRIMITIVES), len(names)))
     for n in names:
-        if n not in OPS and n != SKIP:
+        if n not in OPS and n not in DILATED_OPS and n != SKIP:
             raise ValueError('tfnas_amd: unknown primitive %r (one of %s, or %r in a residual cell)'
-                             % (n, ', '.join(sorted(OPS)), SKIP))
+                             % (n, ', '.join(sorted(list(OPS) + list(DILATED_OPS))), SKIP))
     return names
 
 
@@ -129,8 +149,8 @@ class MixedOP(nn.Module):
             if self.primitives[i] == SKIP:                 # (no width: mc_num_dict[i] is ignored)
                 self.m_ops.append(IdentityLayer(in_channels, out_channels))
                 continue
-            self.m_ops.append(OPS[self.primitives[i]](in_channels, self.mc_num_dict[i], out_channels, stride, affine,
-                                                 act_func))
+            self.m_ops.append(primitive_factory(self.primitives[i])(in_channels, self.mc_num_dict[i], out_channels, stride,
+                                                                    affine, act_func))
             self.m_ops[-1].set_se_style(self.se_style)     # (the registry's factories keep their signature: applied here,
                                                            #  before any plan of the cell exists)
         self._initialize_log_alphas()
@@ -156,8 +176,8 @@ class MixedOP(nn.Module):
             if op.name == 'IdentityLayer':                 # (models/model_search.py:96-97: the skip costs nothing)
                 lats.append(0)
                 continue
-            key = '{}_{}_{}_{}_{}_k{}_s{}_{}'.format(op.name, size, op.in_channels, op.se_channels, op.out_channels,
-                                                     op.kernel_size, op.stride, op.act_func)
+            key = '{}_{}_{}_{}_{}_{}_s{}_{}'.format(op.name, size, op.in_channels, op.se_channels, op.out_channels,
+                                                    kernel_tag(op.kernel_size, getattr(op, 'dilation', 1)), op.stride, op.act_func)
             lats.append(self.lat_lookup[key][op.mid_channels])
         return lats
 

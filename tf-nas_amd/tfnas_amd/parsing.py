@@ -41,7 +41,8 @@ def derived_config(parsed_arch, mc_num_dddict, num_classes=1000, primitives=None
     what the searched network was built with (model_search.Network(primitives=...): one list, or a {stage: {block: list}}
     mapping); a Fused-MBConv choice is written as a 'FusedMBConvBlock' entry, an expand-free one as the reference records such a
     block (an 'MBInvertedResBlock' with mid_channels == in_channels), a chosen 'skip' as the reference's 'IdentityLayer' entry
-    -- all load in model_eval.NetworkCfg.  ``se_style``: the
+    -- all load in model_eval.NetworkCfg.  A dilated choice ('MBI_k3d2_*', 'DS_k5d2', ...) carries a 'dilation' key; an undilated
+    entry has none, so a config without dilation is what it always was.  ``se_style``: the
     squeeze-excite style the searched network was built with (model_search.Network(se_style=...): None, one (se_act, se_gate) pair
     or a {stage: pair} mapping); a block's entry carries 'se_act' / 'se_gate' keys only where they differ from the default (the
     block's own activation, 'sigmoid'), so a config without a style is what it always was."""
@@ -61,7 +62,8 @@ def derived_config(parsed_arch, mc_num_dddict, num_classes=1000, primitives=None
                 continue
             layer, mc, se, k = geometry.primitive_block(prim, ic, mc_num_dddict[stage][name][op])
             blocks.append(dict(_mbconv_config(ic, mc, se, oc, k, s, st['act']), name=layer,
-                               **geometry.se_style_keys(*_lib.se_style_pair(geometry.cell_se_style(se_style, stage, name)))))
+                               **geometry.se_style_keys(*_lib.se_style_pair(geometry.cell_se_style(se_style, stage, name))),
+                               **geometry.dilation_keys(geometry.primitive_dilation(prim))))
         cfg[stage] = blocks
     cfg['feature_mix_layer'] = _conv_layer_config(320, 1280, 1, 1, 'swish')
     cfg['classifier'] = {'name': 'LinearLayer', 'in_features': 1280, 'out_features': num_classes, 'bias': True,
@@ -156,7 +158,8 @@ def parse_searched_model(model_or_path, lat_lookup=None, num_classes=1000, save_
         sd, mc_num = net.state_dict(), net.mc_num_dddict
         if se_style is None:                                   # (a model built with se_style=...: export what it was built with)
             se_style = getattr(net, 'se_style', None)
-        if hasattr(net, 'cells') and hasattr(net, 'plain_candidates') and not net.plain_candidates():
+        if hasattr(net, 'cells') and hasattr(net, 'plain_candidates') and (
+                not net.plain_candidates() or any(list(c.primitives) != geometry.PRIMITIVES for c in net.cells())):
             # (a model built with primitives=...: export what its cells hold)
             primitives = {}
             for (stage, block, *_), cell in zip(geometry.iter_cells(), net.cells()):

@@ -171,6 +171,7 @@ class PathRunner:
         d.has_res = int(cell.in_channels == cell.out_channels and cell.stride == 1)
         for g, b in enumerate(blocks):
             d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
+            d.g[g].dil = b.dilation if getattr(b, 'dilation', 1) != 1 else 0     # (HipModes.apply sets the bit for a dilated group)
             ps = b.hip_params()
             for p in ps:
                 _require_cuda(p, 'MBConv weight')

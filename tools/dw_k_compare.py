@@ -3,7 +3,11 @@
 candidate with k = 5 (default route, and tile kernels only) and k = 7 (tile kernels) at two benchmark geometries, HIP-event time per
 launch from the library's tfnas_prof_* timers.  Weight gradients run on the caller's stream (route bit) so that no launch overlaps
 another; the variants alternate and the median over the rounds is printed (DESIGN.md section 4, 7 x 7 table).
-   python tools/dw_k_compare.py [batch] [rounds]"""
+   python tools/dw_k_compare.py [batch] [rounds]
+With a third argument ``dil``: the dilated candidates beside their undilated twins -- k3, k3d2, k5, k5d2 (the undilated ones on
+the default route and on the tile kernels the dilated ones always take) in a late cell (14 x 14, 80 -> 80) and an early cell
+(56 x 56, 24 -> 24), both at six times the input width (dilation table).
+   python tools/dw_k_compare.py 128 7 dil"""
 import ctypes as C
 import os
 import statistics
@@ -19,6 +23,11 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 ROUNDS = int(sys.argv[2]) if len(sys.argv) > 2 else 7
 GEOMS = [('56 x 56 x 144', 24, 144, 24, 1, 'relu', 56), ('14 x 14 x 672', 112, 672, 112, 1, 'swish', 14)]
 VARIANTS = [('k5 default route', 5, {}), ('k5 tile kernels', 5, dict(dw='tiled', dwwg=False)), ('k7 tile kernels', 7, {})]
+if len(sys.argv) > 3 and sys.argv[3] == 'dil':
+    GEOMS = [('14 x 14 x 480', 80, 480, 80, 1, 'swish', 14), ('56 x 56 x 144', 24, 144, 24, 1, 'relu', 56)]
+    TILE = dict(dw='tiled', dwwg=False)
+    VARIANTS = [('k3 default route', 3, {}), ('k3 tile kernels', 3, TILE), ('k3d2 tile kernels', (3, 2), {}),
+                ('k5 default route', 5, {}), ('k5 tile kernels', 5, TILE), ('k5d2 tile kernels', (5, 2), {})]
 FAMS = ('k_dw_fwd', 'k_dw_bwd_data', 'k_dw_wgrad')
 
 lib = _lib.lib()
@@ -37,7 +46,8 @@ for name, ic, mc, oc, s, act, hw in GEOMS:
     x = torch.randn(B, ic, hw, hw, device=dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
     blocks = []
     for label, k, route in VARIANTS:
-        blk = MBInvertedResBlock(ic, mc, 0, oc, k, s, affine=False, act_func=act).to(dev)
+        k, dil = k if isinstance(k, tuple) else (k, 1)
+        blk = MBInvertedResBlock(ic, mc, 0, oc, k, s, affine=False, act_func=act, dilation=dil).to(dev)
         F.adopt_modes(blk, F.HipModes(route=F.route_bits(wgrad_stream=False, **route)))
         blocks.append(blk)
 
@@ -60,4 +70,4 @@ for name, ic, mc, oc, s, act, hw in GEOMS:
                 times[i][f].append(collect(f))
     print('%s, B = %d, median of %d alternating rounds (ms per launch)' % (name, B, ROUNDS))
     for (label, k, route), t in zip(VARIANTS, times):
-        print('  %-18s' % label + '  '.join('%s %.3f' % (f, statistics.median(t[f])) for f in FAMS))
+        print('  %-19s' % label + '  '.join('%s %.3f' % (f, statistics.median(t[f])) for f in FAMS))
