@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-/* 4, additive: TFNAS_CELL_DILATION -- TfnasGroup.dil: depthwise candidates with taps two pixels apart (3 x 3 and 5 x 5).
+/* 4, additive: TFNAS_CELL_MIXK -- a packed TfnasGroup.k: MixConv candidates, one depthwise whose channel segments are 3 x 3 | 5 x 5 | 7 x 7.
+ * 4, additive: TFNAS_CELL_DILATION -- TfnasGroup.dil: depthwise candidates with taps two pixels apart (3 x 3 and 5 x 5).
  * 4, additive: TFNAS_CELL_SKIP -- TFNAS_GROUP_SKIP: the identity candidate in a residual TFNAS_CELL_KINDS cell.
  * 4, additive: TFNAS_CELL_SE_STYLE -- TfnasCellDesc.se_style: the squeeze-excite hidden activation and gate function of a cell.
  * 4, additive: TFNAS_CELL_KINDS -- a per-group kind (TfnasGroup.kind): plain, expand-free and Fused-MBConv candidates in ONE cell.
@@ -106,7 +107,8 @@ extern "C" {
  * (tfnas_cell_plan, tfnas_cell_ws); eight 7 x 7 groups of 1536 channels fit. */
 typedef struct TfnasGroup {
     int32_t mc;       /* mid channels (any integer > 0, e.g. 53)            [in]  */
-    int32_t k;        /* depthwise kernel size: 3 or 5; 7 with TFNAS_CELL_K7 [in]  */
+    int32_t k;        /* depthwise kernel size: 3 or 5; 7 with TFNAS_CELL_K7; with TFNAS_CELL_MIXK also a packed word
+                         (0x53, 0x73, 0x75, 0x753: one nibble per channel segment)  [in]  */
     int32_t se;       /* squeeze-excite width (a multiple of 4), 0 = no SE   [in]  */
     int32_t mcp;      /* mc rounded up to a multiple of 4                   [plan] */
     int32_t off;      /* first column of this group in the [.][M] tensors (multiple of 32) [plan] */
@@ -148,7 +150,8 @@ typedef struct TfnasCellDesc {
                                  TFNAS_CELL_KINDS: every group has a kind of its own (TfnasGroup.kind);
                                  TFNAS_CELL_SE_STYLE: se_style may be non-zero;
                                  TFNAS_CELL_SKIP: groups may be TFNAS_GROUP_SKIP, the identity candidate;
-                                 TFNAS_CELL_DILATION: groups may have depthwise dilation 2 (TfnasGroup.dil)              [in]
+                                 TFNAS_CELL_DILATION: groups may have depthwise dilation 2 (TfnasGroup.dil);
+                                 TFNAS_CELL_MIXK: TfnasGroup.k may be a packed word of two or three kernel sizes          [in]
                                  (bit 4 was TFNAS_CELL_FXP, the fused per-image project dgrad of round 5: measured equal to the
                                  default kernels over two rounds and deleted in round 6) */
     TfnasGroup g[TFNAS_MAX_GROUPS];
@@ -370,6 +373,34 @@ typedef struct TfnasCellDesc {
  * TFNAS_CELL_LAZY_JOIN, wgrad_stream[], the sync-stats hook and the GEMM modes keep their meaning.  The Python mirror sets the bit
  * for every descriptor that holds a dilated group, and only those (functions.HipModes.apply). */
 #define TFNAS_CELL_DILATION 0x8000
+/* TfnasCellDesc.flags: the caller knows MixConv groups (Tan & Le, "MixConv: Mixed Depthwise Convolutional Kernels", the MixNet
+ * family): ONE depthwise convolution whose channels are split into two or three contiguous segments, segment 0 3 x 3 (or 5 x 5),
+ * the next 5 x 5 (or 7 x 7), an optional third 7 x 7; everything else of the block is the ordinary MBConv.  Additive like
+ * TFNAS_CELL_K7: without the bit (0x10000; 0x4000 stays undefined and refused, as the dilation bit left it) every descriptor is
+ * accepted, refused, planned, sized, routed and launched exactly as before.  With the bit TfnasGroup.k may be a PACKED word: nibble s (bits 4s .. 4s+3) is the
+ * kernel size of channel segment s -- two or three non-zero nibbles, strictly ascending, each 3, 5 or 7, everything above zero:
+ * 0x53, 0x73, 0x75, 0x753.  A plain k (3, 5, 7) under the bit means what it means without it, and a descriptor that carries the
+ * bit but has no packed group plans, sizes, routes and runs bit for bit like the same descriptor without the bit.
+ * Segments: q = mcp / 4 channel quads, n segments; segment s gets q / n quads, segment 0 the q % n remaining ones as well;
+ * segment s covers channels [4 Q_s, min(4 Q_s+1, mc)).  Where mc is a multiple of 4 n this is MixNet's own _split_channels
+ * (equal parts, remainder to the first); for ragged widths the split points stay 16-byte aligned (the kernels' float4 accesses).
+ * Weights: w_dw / g_dw point to ONE packed buffer, segment s [mc_s][k_s * k_s] at float offset sum_{t<s} mc_t k_t^2, in all
+ * sum_s mc_s k_s^2 floats; the weight-gradient partial row (TFNAS_ERANGE when it does not fit) has exactly this layout.
+ * Rules, checked by tfnas_cell_plan and again by every entry point (TFNAS_EINVAL):
+ *   - any other packed word; a word with a 7 without TFNAS_CELL_K7; q < n (a segment without a quad); a packed k in a group with
+ *     dil == 2, in a TFNAS_GROUP_FUSED or TFNAS_GROUP_SKIP group, in a TFNAS_CELL_FUSED cell, in TFNAS_MODE_STEM or
+ *     TFNAS_MODE_HEAD; tfnas_path_plan on a cell with a packed group;
+ *   - allowed: plain MBConv groups and expand-free groups (TFNAS_CELL_NOEXPAND, or TFNAS_GROUP_NOEXPAND of a TFNAS_CELL_KINDS cell), in
+ *     sampled and soft launches of tfnas_mixedop_fwd/bwd and in tfnas_mbconv_fwd/bwd; all four activations, both strides, SE or
+ *     none, every se_style; a soft cell may hold packed groups beside plain 3 / 5 / 7, dilated, FUSED and SKIP groups.
+ * A cell with a packed group follows the 7 x 7 rule: it always materialises E (tfnas_efree_supported and tfnas_fx_supported return
+ * 0, tfnas_cell_route returns TFNAS_ROUTE_TAKEN_VALID), runs every depthwise pass on the LDS tile kernels whatever TFNAS_ROUTE_DW_*
+ * asks -- each segment in the launch of its own kernel size -- and keeps the depthwise weight gradient in a launch of its own.
+ * tfnas_cell_ws and every planned word (M, SE, off, mcp, se_off) are what they are for the same group with a plain k.
+ * TFNAS_CELL_ACCUM_WGRAD, TFNAS_CELL_LAZY_JOIN, wgrad_stream[], the sync-stats hook, the GEMM modes, need_wgrad == 0 and
+ * dx == NULL keep their meaning.  The Python mirror sets the bit for every descriptor that holds a packed group, and only those
+ * (functions.HipModes.apply). */
+#define TFNAS_CELL_MIXK 0x10000
 /* TfnasCellDesc.route (ABI 4; rounds 2-5 read these from TFNAS_* environment variables latched once per process) */
 #define TFNAS_ROUTE_FX_OFF 0x1        /* frozen-weight launches of the 14 x 14 / 7 x 7 cells through the materialised route instead
                                          of the fused per-image kernels (csrc/fx_kernels.hip)                                   */
@@ -383,7 +414,7 @@ typedef struct TfnasCellDesc {
 #define TFNAS_ROUTE_DW_SHIFT 6        /* 2 bits: 0 per-launch policy, 1 register-window kernels wherever the geometry allows,   */
 #define TFNAS_ROUTE_DW_MASK 0xc0      /*         2 LDS ring / tile kernels only, 3 tile kernels only (7 x 7 cells,
                                          TFNAS_ACT_RELU6 / _HSWISH cells, TFNAS_CELL_NOEXPAND cells and cells with a
-                                         dilated group, TFNAS_CELL_DILATION: always 3)                                        */
+                                         dilated or a packed group, TFNAS_CELL_DILATION / _MIXK: always 3)                                        */
 #define TFNAS_ROUTE_SE_SHIFT 8        /* 2 bits: 0 wave-level MFMA kernels for the excite FCs, 1 one fused per-image kernel,    */
 #define TFNAS_ROUTE_SE_MASK 0x300     /*         2 LDS-tiled GEMMs                                                              */
 #define TFNAS_ROUTE_WGRAD_INLINE 0x400 /* weight-gradient kernels on the caller's stream (no side stream)                       */

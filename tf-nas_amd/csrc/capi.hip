@@ -226,6 +226,26 @@ static int check_dilation(const TfnasCellDesc* d) {
     return 0;
 }
 
+// the packed kernel-size words of a descriptor (tfnas_hip.h: TFNAS_CELL_MIXK; after check_kind and check_dilation).  Without the bit
+// no word is packed: a k above 7 is refused by tfnas_cell_plan as it always was.  With it a plain k means what it means without,
+// and a packed word is one of 0x53, 0x73, 0x75, 0x753 (two or three nibbles, strictly ascending, each 3 | 5 | 7, nothing above), in
+// a plain or an expand-free group (never Fused-MBConv, never a skip, never dilated) of a cell-mode descriptor wide enough to give
+// every segment a channel quad; a 7 needs TFNAS_CELL_K7 like a plain one
+static int check_mixk(const TfnasCellDesc* d) {
+    if (!(d->flags & TFNAS_CELL_MIXK)) return 0;
+    for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g) {
+        const TfnasGroup& gr = d->g[g];
+        if (gr.k >= 0 && gr.k <= 0xf) continue;           // (a plain word: tfnas_cell_plan's own rules)
+        if (gr.k != 0x53 && gr.k != 0x73 && gr.k != 0x75 && gr.k != 0x753) return TFNAS_EINVAL;
+        if (gr.k != 0x53 && !(d->flags & TFNAS_CELL_K7)) return TFNAS_EINVAL;
+        if (d->mode != TFNAS_MODE_CELL || cell_fused(*d)) return TFNAS_EINVAL;
+        if (cell_mixed(*d) && (gr.kind == TFNAS_GROUP_FUSED || gr.kind == TFNAS_GROUP_SKIP)) return TFNAS_EINVAL;
+        if (group_dil(*d, g) != 1) return TFNAS_EINVAL;
+        if (gr.mc < 1 || (gr.mc + 3) / 4 < (gr.k > 0xff ? 3 : 2)) return TFNAS_EINVAL;      // (q < n: a segment without a quad)
+    }
+    return 0;
+}
+
 // the per-launch modes of a descriptor (callers may change them between tfnas_cell_plan and a launch: every entry point re-checks)
 static int check_modes(const TfnasCellDesc* d) {
     TRY(check_act(d));
@@ -234,14 +254,16 @@ static int check_modes(const TfnasCellDesc* d) {
         if (!(d->gemm_mode & TFNAS_GEMM_EXPLICIT) || (gm != 0 && gm != 1 && gm != 3 && gm != 6)) return TFNAS_EINVAL;
     }
     if (d->flags & ~(TFNAS_CELL_LAZY_JOIN | TFNAS_CELL_ACCUM_WGRAD | TFNAS_CELL_K7 | TFNAS_CELL_ACTS | TFNAS_CELL_NOEXPAND |
-                     TFNAS_CELL_FUSED | TFNAS_CELL_KINDS | TFNAS_CELL_SE_STYLE | TFNAS_CELL_SKIP | TFNAS_CELL_DILATION))
+                     TFNAS_CELL_FUSED | TFNAS_CELL_KINDS | TFNAS_CELL_SE_STYLE | TFNAS_CELL_SKIP | TFNAS_CELL_DILATION |
+                     TFNAS_CELL_MIXK))
         return TFNAS_EINVAL;
     TRY(check_kind(d));
     TRY(check_se_style(d));
     TRY(check_dilation(d));
+    TRY(check_mixk(d));
     if (!(d->flags & TFNAS_CELL_K7)) {            // kernel size 7 is opt-in: without the bit it is refused as it always was
         for (int g = 0; g < d->G && g < TFNAS_MAX_GROUPS; ++g)
-            if (d->g[g].k == 7) return TFNAS_EINVAL;
+            if (d->g[g].k == 7) return TFNAS_EINVAL;          // (a packed word with a 7: check_mixk)
     }
     if (d->route & ~TFNAS_ROUTE_ALL) return TFNAS_EINVAL;
     if ((d->route & TFNAS_ROUTE_XG_OFF) && (d->route & TFNAS_ROUTE_XG_ALL)) return TFNAS_EINVAL;
@@ -343,7 +365,8 @@ extern "C" int tfnas_cell_plan(TfnasCellDesc* d) {
             gr.se_off = se_off;
             continue;
         }
-        if (gr.mc < 1 || (gr.k != 3 && gr.k != 5 && gr.k != 7) ||      // (7: with TFNAS_CELL_K7 only, check_modes)
+        if (gr.mc < 1 || (gr.k != 3 && gr.k != 5 && gr.k != 7 &&      // (7: with TFNAS_CELL_K7 only, check_modes)
+                          !group_packed(*d, g)) ||                     // (a packed word, TFNAS_CELL_MIXK: legal by check_mixk)
             gr.se < 0) return TFNAS_EINVAL;
         if (gr.se & 3) return TFNAS_EINVAL;       // SE widths are in_channels x {1, 2} in the search space; the excite
                                                   // GEMMs move hidden units in quads

@@ -48,6 +48,40 @@ __device__ __forceinline__ bool dw_locate(const TfnasCellDesc& d, int cy, int CC
     return false;
 }
 
+// The channel chunk of a TILE kernel: a chunk of one SEGMENT (TFNAS_CELL_MIXK; a plain group is one segment: the group).  c0: its
+// first channel in the group; mc / mcp: the segment's own end, min(4 Q_s+1, mc) and 4 Q_s+1 (kernels.h: seg_quad0) -- everything
+// a tile kernel bounds by the group's width it bounds by these, because the overhanging lanes of a segment's last chunk are the
+// NEXT segment's columns, written by another workgroup of another launch; cs: the segment's first channel and woff: the float
+// offset of the segment's [mc_s][K * K] block in the group's packed depthwise weight (and in its block of the partial row).
+struct DwSeg {
+    int g, c0, mc, mcp, cs, woff;
+};
+// locate chunk `cy` among the segments whose kernel size is K, in group order then segment order (the host's twin: dw_chunks); a
+// chunk never straddles a segment.  DIL = 1 | 2: the groups of that dilation (a packed group is never dilated).  All of it is
+// wave-uniform (kernel arguments and blockIdx.y): scalar code.
+template <int K, int DIL>
+__device__ __forceinline__ bool dw_locate_seg(const TfnasCellDesc& d, int cy, int CC, DwSeg& sg) {
+    for (int g = 0; g < d.G; ++g) {
+        if (group_dil(d, g) != DIL) continue;
+        const int n = group_nseg(d, g), q = d.g[g].mcp >> 2, mc = d.g[g].mc;
+        int woff = 0;
+        for (int s = 0; s < n; ++s) {
+            const int ks = seg_k(d, g, s), lo = 4 * seg_quad0(q, n, s), hi = 4 * seg_quad0(q, n, s + 1);
+            const int top = hi < mc ? hi : mc;
+            if (ks == K) {
+                const int t = (hi - lo + CC - 1) / CC;
+                if (cy < t) {
+                    sg = DwSeg{g, lo + cy * CC, top, hi, lo, woff};
+                    return true;
+                }
+                cy -= t;
+            }
+            woff += (top - lo) * ks * ks;
+        }
+    }
+    return false;
+}
+
 // sum the per-thread float4 partials of all threads that share a channel quad (tid % CQ) and store the CC
 // per-channel totals as this workgroup's partial pair: acc[2*c + which] (acc = row blockIdx.x of the partials
 // matrix, already offset to the group's first channel); k_reduce_rows sums the rows afterwards
@@ -78,10 +112,11 @@ __device__ __forceinline__ void dw_flush_stats(f32x4 a, f32x4 b, float* lds, int
     dw_flush_pair(a, b, lds, CC, c0, mcp, part + (size_t)lane * 2 * M + 2 * (size_t)off);
 }
 
-__device__ __forceinline__ void stage_weights(float* wts, const float* __restrict__ w, int KK, int CC, int c0, int mc) {
+// (w: row 0 = channel `cs`, the first of the chunk's segment -- DwSeg; mc: the segment's end)
+__device__ __forceinline__ void stage_weights(float* wts, const float* __restrict__ w, int KK, int CC, int c0, int mc, int cs = 0) {
     for (int idx = threadIdx.x; idx < KK * CC; idx += 256) {
         const int cl = idx % CC, t = idx / CC;
-        wts[t * CC + cl] = (c0 + cl < mc) ? w[(size_t)(c0 + cl) * KK + t] : 0.f;
+        wts[t * CC + cl] = (c0 + cl < mc) ? w[(size_t)(c0 + cl - cs) * KK + t] : 0.f;
     }
 }
 
@@ -164,8 +199,15 @@ __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float*
     int g, c0, lane = blockIdx.x, cy = blockIdx.y;
     static_assert(DIL == 1 || (DIL == 2 && KQ == 0 && (K == 3 || K == 5)), "dilation 2: 3 x 3 / 5 x 5 from E or raw x");
     if (KQ > 0) efree_lane_chunk(lane, cy);
-    if (!dw_locate<K, DIL>(d, cy, gm.CC, g, c0)) return;
-    const int mc = d.g[g].mc, mcp = d.g[g].mcp, off = d.g[g].off;
+    DwSeg sg;
+    if constexpr (KQ > 0) {      // (E-free: never a packed group -- efree_supported)
+        if (!dw_locate<K, DIL>(d, cy, gm.CC, g, c0)) return;
+        sg = DwSeg{g, c0, d.g[g].mc, d.g[g].mcp, 0, 0};
+    } else {
+        if (!dw_locate_seg<K, DIL>(d, cy, gm.CC, sg)) return;
+        g = sg.g, c0 = sg.c0;
+    }
+    const int mc = sg.mc, mcp = sg.mcp, off = d.g[g].off;      // (the SEGMENT's end: DwSeg)
     const int CC = gm.CC, CQ = CC >> 2, TH = gm.T0, TW = gm.T1;
     const int H = d.H, W = d.W, Ho = d.Ho, Wo = d.Wo, M = d.M;
     const int tid = threadIdx.x;
@@ -181,7 +223,7 @@ __global__ __launch_bounds__(256, 4) void k_dw_fwd(TfnasCellDesc d, const float*
         cst[tid] = (c0 + tid < mc) ? bn_consts(stats1 + 2 * (size_t)(off + c0 + tid), 1.0 / ((double)d.N * H * W), d.eps)
                                    : make_float2(0.f, 0.f);
     }
-    stage_weights(wts, d.g[g].w_dw, K * K, CC, c0, mc);
+    stage_weights(wts, d.g[g].w_dw + sg.woff, K * K, CC, c0, mc, sg.cs);
     ExpandB<(KQ > 0 ? KQ : 2)> xb;
     if (KQ > 0) {
         __syncthreads();
@@ -292,8 +334,15 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
     int g, c0, lane = blockIdx.x, cy = blockIdx.y;
     static_assert(DIL == 1 || (DIL == 2 && KQ == 0 && (K == 3 || K == 5)), "dilation 2: 3 x 3 / 5 x 5 from E or raw x");
     if (KQ > 0) efree_lane_chunk(lane, cy);
-    if (!dw_locate<K, DIL>(d, cy, gm.CC, g, c0)) return;
-    const int mc = d.g[g].mc, mcp = d.g[g].mcp, off = d.g[g].off;
+    DwSeg sg;
+    if constexpr (KQ > 0) {      // (E-free: never a packed group -- efree_supported)
+        if (!dw_locate<K, DIL>(d, cy, gm.CC, g, c0)) return;
+        sg = DwSeg{g, c0, d.g[g].mc, d.g[g].mcp, 0, 0};
+    } else {
+        if (!dw_locate_seg<K, DIL>(d, cy, gm.CC, sg)) return;
+        g = sg.g, c0 = sg.c0;
+    }
+    const int mc = sg.mc, mcp = sg.mcp, off = d.g[g].off;      // (the SEGMENT's end: DwSeg)
     const int CC = gm.CC, CQ = CC >> 2, TIH = gm.T0, TIW = gm.T1;
     const int H = d.H, W = d.W, Ho = d.Ho, Wo = d.Wo, M = d.M;
     constexpr int PAD = DIL * (K / 2), KE = DIL * (K - 1) + 1;
@@ -312,7 +361,7 @@ __global__ __launch_bounds__(256, 4) void k_dw_bwd_data(TfnasCellDesc d, const f
         cst1[tid] = (c0 + tid < mc) ? bn_consts(stats1 + 2 * (size_t)(off + c0 + tid), 1.0 / ((double)d.N * H * W), d.eps)
                                     : make_float2(0.f, 0.f);
     }
-    stage_weights(wts, d.g[g].w_dw, K * K, CC, c0, mc);
+    stage_weights(wts, d.g[g].w_dw + sg.woff, K * K, CC, c0, mc, sg.cs);
     float* eh_tile = reinterpret_cast<float*>(cst1 + CC);     // [TIH*TIW][CC] (E-free only)
     ExpandB<(KQ > 0 ? KQ : 2)> xb;
     if (KQ > 0) {
@@ -462,11 +511,12 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
                                               const double* __restrict__ stats1, float* __restrict__ part,
                                               size_t out_size, const DwGeom& gm) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    int g, c0;
-    if (!dw_locate<K, DIL>(d, blockIdx.y, gm.CC, g, c0)) return;
-    const int mc = d.g[g].mc, mcp = d.g[g].mcp, off = d.g[g].off;
-    size_t poff = 0;
-    for (int gg = 0; gg < g; ++gg) poff += (size_t)d.g[gg].mc * d.g[gg].k * d.g[gg].k;
+    DwSeg sg;
+    if (!dw_locate_seg<K, DIL>(d, blockIdx.y, gm.CC, sg)) return;
+    const int g = sg.g, c0 = sg.c0;
+    const int mc = sg.mc, mcp = sg.mcp, off = d.g[g].off;      // (the SEGMENT's end: DwSeg)
+    size_t poff = sg.woff;                                     // (the segment's block inside the group's block of the row)
+    for (int gg = 0; gg < g; ++gg) poff += group_dw_floats(d, gg);
     float* __restrict__ gw = part + (size_t)blockIdx.x * out_size + poff;
     const int CC = gm.CC, CQ = CC >> 2, TH = gm.T0, TW = gm.T1;
     const int H = d.H, W = d.W, Ho = d.Ho, Wo = d.Wo, M = d.M;
@@ -607,7 +657,7 @@ __device__ __forceinline__ void dw_wgrad_rows(const TfnasCellDesc& d, const floa
             float s = 0.f;
 #pragma unroll
             for (int ww = 0; ww < 4; ++ww) s += wred[(ww * KR * K + u) * CC + cl];
-            gw[(size_t)(c0 + cl) * (K * K) + KY0 * K + u] = s;
+            gw[(size_t)(c0 + cl - sg.cs) * (K * K) + KY0 * K + u] = s;
         }
     }
 }
@@ -644,10 +694,16 @@ __global__ __launch_bounds__(256, 2) void k_dw_wgrad(TfnasCellDesc d, const floa
 // (tests/test_gpu_cell.py::test_variant_against_oracle)
 
 // channel chunks of the groups with kernel size K and dilation dil (the kernels' twin: dw_locate)
+// -- in segments (TFNAS_CELL_MIXK, dw_locate_seg): a plain group is one segment of mcp channels, a packed group hands each of its
+// segments to the slot of that segment's kernel size
 static int dw_chunks(const TfnasCellDesc& d, int K, int CC, int dil = 1) {
     int t = 0;
-    for (int g = 0; g < d.G; ++g)
-        if (d.g[g].k == K && group_dil(d, g) == dil) t += cdiv(d.g[g].mcp, CC);
+    for (int g = 0; g < d.G; ++g) {
+        if (group_dil(d, g) != dil) continue;
+        const int n = group_nseg(d, g), q = d.g[g].mcp >> 2;
+        for (int s = 0; s < n; ++s)
+            if (seg_k(d, g, s) == K) t += cdiv(4 * (seg_quad0(q, n, s + 1) - seg_quad0(q, n, s)), CC);
+    }
     return t;
 }
 // the (kernel size, dilation) pair of launch slot i of a pass (kernels.h: DW_NK): 3, 5, 7 undilated, then 3 and 5 with dilation 2
@@ -657,7 +713,7 @@ static int dw_slot_dil(int i) { return i < 3 ? 1 : 2; }
 // floats of one weight-gradient partial row: the groups' mc x K x K blocks in group order
 static size_t dw_wout_size(const TfnasCellDesc& d) {
     size_t n = 0;
-    for (int g = 0; g < d.G; ++g) n += (size_t)d.g[g].mc * d.g[g].k * d.g[g].k;
+    for (int g = 0; g < d.G; ++g) n += group_dw_floats(d, g);       // (a packed group: the sum over its segments)
     return n;
 }
 
@@ -668,7 +724,7 @@ static size_t dw_wout_size(const TfnasCellDesc& d) {
 // cell without expand convolution (TFNAS_CELL_NOEXPAND): only the tile kernels have the raw-input form; and for a cell with a
 // dilated group (TFNAS_CELL_DILATION): only the tile kernels have the tap spacing as a template argument.
 static bool dw_tile_only(const TfnasCellDesc& d) {
-    if (act_tile_only(d.act) || cell_noexpand(d) || cell_dilated(d)) return true;
+    if (act_tile_only(d.act) || cell_noexpand(d) || cell_dilated(d) || cell_packed(d)) return true;     // (packed: segments)
     for (int g = 0; g < d.G; ++g)
         if (d.g[g].k != 3 && d.g[g].k != 5) return true;
     return false;
@@ -680,6 +736,7 @@ bool dw_wgrad_row_fits(const TfnasCellDesc& d) { return dw_wout_size(d) <= TFNAS
 
 // every group has kernel size 3 (or 5 where k5 is set)
 static bool dw_groups_k(const TfnasCellDesc& d, bool k5) {
+    if (cell_packed(d)) return false;     // (a packed word is not a kernel size: never a fused weight gradient)
     for (int g = 0; g < d.G; ++g)
         if (d.g[g].k != 3 && !(k5 && d.g[g].k == 5)) return false;
     return true;
@@ -1002,7 +1059,7 @@ static int dws_variant(const DwPlan& p) { return p.fuse_wgrad ? DW_WG : p.kq ? p
 static int dw_reduce_wgrad(const TfnasCellDesc& d, const float* wpart, int rows, size_t wout, hipStream_t s) {
     size_t poff = 0;
     for (int g = 0; g < d.G; ++g) {
-        const int n = d.g[g].mc * d.g[g].k * d.g[g].k;
+        const int n = (int)group_dw_floats(d, g);      // (a packed group: its segments' blocks are contiguous, one reduction)
         const int rc = launch_reduce_rows(wpart + poff, rows, n, wout, nullptr, d.g[g].g_dw, s, wgrad_accum(d));
         if (rc) return rc;
         poff += n;

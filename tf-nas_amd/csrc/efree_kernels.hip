@@ -139,6 +139,7 @@ bool efree_supported(const TfnasCellDesc& d) {
     if (cell_noexpand(d) || cell_fused(d)) return false;       // (no expand convolution / a dense one: there is no E to leave out)
     if (cell_mixed(d)) return false;                           // (the plain groups of a mixed cell always materialise E)
     if (cell_dilated(d)) return false;                         // (a dilated group: the LDS tile kernels with E, the 7 x 7 rule)
+    if (cell_packed(d)) return false;                          // (a packed group, TFNAS_CELL_MIXK: likewise; before any read of k)
     if (!efree_ic_ok(d.ic)) return fx_supported(d);            // late cells: the fused per-image route (fx_kernels.hip)
     if (stats_sync_on(d)) return false;          // (cross-rank statistics are reduced on the (sum, sumsq) tables of E)
     if ((size_t)d.N * d.H * d.W * d.ic >= ((size_t)1 << 31)) return false;

@@ -35,6 +35,7 @@ bool fx_plan(const TfnasCellDesc& d, FxPlan& pl, bool bwd) {
     if (d.act != TFNAS_ACT_RELU && d.act != TFNAS_ACT_SWISH) return false;     // (the kernels are instantiated for these two)
     if (stats_sync_on(d)) return false;                     // (BN1 statistics come from the Gram matrix of x: efree_kernels.hip)
     if (cell_dilated(d)) return false;                      // (taps one pixel apart only: a dilated group materialises E)
+    if (cell_packed(d)) return false;                       // (one kernel size per group only: a packed group, TFNAS_CELL_MIXK, materialises E)
     if (d.ic < 64 || d.ic > 192 || (d.ic & 15)) return false;
     if (d.stride != 1) return false;                       // (stride-2 cells keep the materialised route)
     const int HW = d.H * d.W;

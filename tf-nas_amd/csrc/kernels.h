@@ -85,6 +85,44 @@ static inline bool cell_dilated(const TfnasCellDesc& d) {
         if (group_dil(d, g) != 1) return true;
     return false;
 }
+// TFNAS_CELL_MIXK: TfnasGroup.k of group g may be a PACKED word -- a MixConv group, one depthwise convolution whose channels are
+// split into two or three contiguous segments of ascending kernel size, nibble s = the kernel size of segment s (0x53, 0x73,
+// 0x75, 0x753: capi.hip, check_mixk).  Without the bit no word is packed (a value above 7 is refused as it always was).  Every
+// reader of TfnasGroup.k past the entry points asks these, never the raw word.
+__host__ __device__ static inline bool group_packed(const TfnasCellDesc& d, int g) {
+    return (d.flags & TFNAS_CELL_MIXK) && d.g[g].k > 0xf;
+}
+__host__ __device__ static inline int group_nseg(const TfnasCellDesc& d, int g) {
+    return group_packed(d, g) ? ((d.g[g].k >> 8) ? 3 : 2) : 1;
+}
+__host__ __device__ static inline int seg_k(const TfnasCellDesc& d, int g, int s) {
+    return group_packed(d, g) ? ((d.g[g].k >> (4 * s)) & 0xf) : d.g[g].k;
+}
+// first channel QUAD of segment s of an n-segment group of q = mcp / 4 quads (s = n: q itself): q / n quads each, the q % n
+// remaining ones to segment 0 -- where mc is a multiple of 4 n MixNet's own _split_channels; every split point a multiple of 4
+// channels (16 bytes: the kernels' float4 accesses).  Segment s covers channels [4 Q_s, min(4 Q_s+1, mc)).
+__host__ __device__ static inline int seg_quad0(int q, int n, int s) {
+    const int base = n == 1 ? q : n == 2 ? (q >> 1) : q / 3;       // (q / n with constant divisors: no division sequence in the kernels)
+    return s == 0 ? 0 : s * base + (q - n * base);
+}
+// floats of group g's depthwise weight (and of its block of the weight-gradient partial row): mc * k * k, a packed group the sum
+// over its segments [mc_s][k_s * k_s], in segment order
+__host__ __device__ static inline size_t group_dw_floats(const TfnasCellDesc& d, int g) {
+    const int n = group_nseg(d, g), q = d.g[g].mcp >> 2, mc = d.g[g].mc;
+    if (n == 1) return (size_t)mc * d.g[g].k * d.g[g].k;       // (a plain group: what it always was, planned or not)
+    size_t f = 0;
+    for (int s = 0; s < n; ++s) {
+        const int lo = 4 * seg_quad0(q, n, s), hi4 = 4 * seg_quad0(q, n, s + 1), hi = hi4 < mc ? hi4 : mc, ks = seg_k(d, g, s);
+        f += (size_t)(hi - lo) * ks * ks;
+    }
+    return f;
+}
+// a cell with a packed group follows the 7 x 7 rule like a dilated one: only the tile kernels take their chunk from a segment
+static inline bool cell_packed(const TfnasCellDesc& d) {
+    for (int g = 0; g < d.G && g < TFNAS_MAX_GROUPS; ++g)
+        if (group_packed(d, g)) return true;
+    return false;
+}
 // group-aware forms of the two facts: some group has an E buffer / a BatchNorm site 0
 static inline bool any_group_has_E(const TfnasCellDesc& d) {
     for (int g = 0; g < d.G; ++g)

@@ -77,6 +77,7 @@ int plan_path(PathCtx& c, const TfnasPathDesc& in, TfnasPathWs* out) {
         TfnasCellDesc& d = pd.cell[i];
         if (d.mode != TFNAS_MODE_CELL) return TFNAS_EINVAL;
         if (cell_kind(d) != TFNAS_KIND_MBCONV || cell_mixed(d)) return TFNAS_EINVAL;   // (the other kinds, and cells of several: per-cell entry points only)
+        if (cell_packed(d)) return TFNAS_EINVAL;                  // (a MixConv group, TFNAS_CELL_MIXK: per-cell entry points only)
         if (!pd.soft && d.G != 1) return TFNAS_EINVAL;            // a sampled path evaluates one candidate per cell
         if (i > 0) {
             const TfnasCellDesc& p = pd.cell[i - 1];

@@ -34,6 +34,7 @@ CELL_KINDS = 0x800           # TfnasCellDesc.flags: every group names its own ki
 CELL_SE_STYLE = 0x1000       # TfnasCellDesc.flags: se_style may be non-zero (se_style_id; refused without the bit)
 CELL_SKIP = 0x2000           # TfnasCellDesc.flags: groups may be GROUP_SKIP, the identity candidate (with CELL_KINDS, residual cells only)
 CELL_DILATION = 0x8000       # TfnasCellDesc.flags: groups may have depthwise dilation 2 (TfnasGroup.dil; not read without the bit)
+CELL_MIXK = 0x10000          # TfnasCellDesc.flags: TfnasGroup.k may be a packed word -- a MixConv group (mix_k_word; refused without the bit)
 GROUP_SKIP = 3               # TfnasGroup.kind of a skip group: no width, no weights, no columns -- not a BlockKind (KINDS stays three)
 SE_GATE = {'sigmoid': 0, 'h-sigmoid': 1}      # gate function of a squeeze-excite branch (bits 4-7 of TfnasCellDesc.se_style)
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
@@ -120,15 +121,60 @@ def dilation_flags(dils):
     return CELL_DILATION if any(int(v) > 1 for v in dils) else 0
 
 
-def describe_block(kind, N, H, W, ic, mc, se, oc, k, stride, act, dilation=1):
+MIX_KERNELS = ((3, 5), (3, 7), (5, 7), (3, 5, 7))      # the kernel sizes of a MixConv depthwise, segment by segment (ascending)
+
+
+def check_mix_kernels(mix_kernels):
+    """``mix_kernels`` as a tuple of ints, one of MIX_KERNELS; ValueError otherwise."""
+    try:
+        ks = tuple(mix_kernels)
+    except TypeError:
+        ks = None
+    if ks not in MIX_KERNELS or not all(type(k) is int for k in ks):
+        raise ValueError('tfnas_amd: mix_kernels is one of %s (got %r)' % (', '.join(map(repr, MIX_KERNELS)), mix_kernels))
+    return ks
+
+
+def mix_k_word(mix_kernels):
+    """The packed TfnasGroup.k of a MixConv group: nibble s = the kernel size of channel segment s (0x53, 0x73, 0x75, 0x753)."""
+    return sum(k << (4 * s) for s, k in enumerate(check_mix_kernels(mix_kernels)))
+
+
+def mix_split(mc, n):
+    """Channels of the ``n`` segments of a MixConv depthwise of ``mc`` channels (include/tfnas_hip.h, TFNAS_CELL_MIXK): the
+    (mc + 3) // 4 channel quads in equal parts, the remaining quads to segment 0, the last segment cut at mc.  Where mc is a
+    multiple of 4 n this is MixNet's _split_channels.  ValueError when a segment would get no quad."""
+    q = (mc + 3) // 4
+    if q < n:
+        raise ValueError('tfnas_amd: %d channels are too few for %d kernel-size segments (a segment is at least 4 channels)' % (mc, n))
+    bounds = [0] + [min(4 * (s * (q // n) + q % n), mc) for s in range(1, n + 1)]
+    return [bounds[s + 1] - bounds[s] for s in range(n)]
+
+
+def mixk_flags(ks):
+    """TfnasCellDesc.flags bit a descriptor whose groups have the TfnasGroup.k words ``ks`` needs: CELL_MIXK when one of them is
+    packed, nothing otherwise (a descriptor of plain kernel sizes is what it always was)."""
+    return CELL_MIXK if any(int(k) > 0xf for k in ks) else 0
+
+
+def block_k_word(block):
+    """TfnasGroup.k of a block module: its kernel size, the packed word of a MixConv block (``mix_kernels``)."""
+    mk = getattr(block, 'mix_kernels', None)
+    return block.kernel_size if mk is None else mix_k_word(mk)
+
+
+def describe_block(kind, N, H, W, ic, mc, se, oc, k, stride, act, dilation=1, mix_kernels=None):
     """A one-block TFNAS_MODE_CELL descriptor of ``kind``, before tfnas_cell_plan: the geometry words, has_res, eps and the flags
-    the geometry itself asks for (CELL_K7, CELL_DILATION, the activation's bit, the kind's bit).  ``act``: a TFNAS_ACT_* id.  Pure
-    host code."""
+    the geometry itself asks for (CELL_K7, CELL_DILATION, CELL_MIXK, the activation's bit, the kind's bit).  ``act``: a TFNAS_ACT_*
+    id; ``mix_kernels``: a MixConv block, ``k`` its largest kernel size.  Pure host code."""
     d = TfnasCellDesc()
     d.N, d.H, d.W, d.ic, d.oc, d.stride, d.act, d.G, d.mode = N, H, W, ic, oc, stride, act, 1, MODE_CELL
     d.has_res, d.eps = int(ic == oc and stride == 1), BN_EPS
     d.g[0].mc, d.g[0].k, d.g[0].se = mc, k, se
     d.flags = (CELL_K7 if k == 7 else 0) | act_flags(act) | kind.flag
+    if mix_kernels is not None:                    # (``k`` is then the largest of them: CELL_K7 above where it is 7)
+        d.g[0].k = mix_k_word(mix_kernels)
+        d.flags |= CELL_MIXK
     if dilation != 1:
         d.g[0].dil = dilation
         d.flags |= dilation_flags((dilation,))

@@ -137,8 +137,10 @@ class HipModes:
         d.gemm_mode = 0 if self.gemm is None else (_lib.GEMM_EXPLICIT | _lib.GEMM_MODES[self.gemm]
                                                    | (_lib.GEMM_EVERYWHERE if self.everywhere else 0))
         d.flags = _lib.CELL_LAZY_JOIN if self.lazy_join else 0
-        if any(d.g[g].k == 7 for g in range(min(d.G, _lib.MAX_GROUPS))):
+        ks = [d.g[g].k for g in range(min(d.G, _lib.MAX_GROUPS))]
+        if any(k == 7 or (k > 0xf and 7 in (k & 0xf, (k >> 4) & 0xf, (k >> 8) & 0xf)) for k in ks):
             d.flags |= _lib.CELL_K7                    # (the library takes 7 x 7 groups only from callers that say they know them)
+        d.flags |= _lib.mixk_flags(ks)                 # (... and MixConv groups: a packed k, with a 7 x 7 segment CELL_K7 as well)
         d.flags |= _lib.act_flags(d.act)               # (... and 'relu6' / 'h-swish')
         d.flags |= _lib.dilation_flags(d.g[g].dil for g in range(min(d.G, _lib.MAX_GROUPS)))     # (... and dilated groups)
         if kind is None:
@@ -264,7 +266,7 @@ class CellPlan:
                 d.Hi, d.Wi = H, W
             d.act, d.has_res, d.G, d.need_wgrad, d.eps = _lib.act_id(self.act), self.has_res, len(self.blocks), 0, BN_EPS
             for g, b in enumerate(self.blocks):
-                d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
+                d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, _lib.block_k_word(b), b.se_channels     # (a MixConv block: packed)
                 dil = getattr(b, 'dilation', 1)
                 d.g[g].dil = dil if dil != 1 else 0    # (an undilated group keeps the word at 0, as before the field had a name)
             self.modes.apply(d, *self._kind_arg)       # (before the plan: it validates the modes; every launch re-checks them)

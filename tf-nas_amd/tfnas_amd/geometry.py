@@ -44,6 +44,20 @@ PRIMITIVE_SPECS.update(
      for k in (3, 5) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))]
     + [('DS_k%dd2%s' % (k, '_se' if se else ''), ('MBInvertedResBlock', k, se, True)) for k in (3, 5) for se in (0, 1)])
 
+# The MixConv primitives (model_search.MIX_OPS builds the modules): one depthwise convolution whose channel segments have the kernel
+# sizes of PRIMITIVE_MIX -- 'MBI_k35_e6_se' is 'MBI_k5_e6_se' with channel segments 3 x 3 | 5 x 5, 'DS_k357' an expand-free block
+# with 3 x 3 | 5 x 5 | 7 x 7.  The same four words in PRIMITIVE_SPECS as every primitive (the kernel size: the largest of them);
+# the segments are a table of its own (primitive_mix_kernels), None for every name that is not in it.
+PRIMITIVE_MIX = OrderedDict(
+    [('MBI_k%s_%s%s' % (tag, e, '_se' if se else ''), ks)
+     for tag, ks in (('35', (3, 5)), ('357', (3, 5, 7))) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))]
+    + [('DS_k%s%s' % (tag, '_se' if se else ''), ks) for tag, ks in (('35', (3, 5)), ('357', (3, 5, 7))) for se in (0, 1)])
+PRIMITIVE_SPECS.update(
+    [('MBI_k%s_%s%s' % (tag, e, '_se' if se else ''), ('MBInvertedResBlock', max(ks), se, False))
+     for tag, ks in (('35', (3, 5)), ('357', (3, 5, 7))) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))]
+    + [('DS_k%s%s' % (tag, '_se' if se else ''), ('MBInvertedResBlock', max(ks), se, True))
+       for tag, ks in (('35', (3, 5)), ('357', (3, 5, 7))) for se in (0, 1)])
+
 
 SKIP = 'skip'        # the identity candidate (the reference's commented-out primitive): recognised NEXT to PRIMITIVE_SPECS -- it
                      # has no layer spec (no kernel, no width, no SE) and only residual cells can hold it (residual_cells)
@@ -107,8 +121,24 @@ def dilation_keys(dilation):
     return {'dilation': dilation} if dilation != 1 else {}
 
 
-def kernel_tag(k, dilation=1):
-    """How a latency-table key spells a depthwise kernel: 'k3', 'k5', 'k7'; 'k3d2' / 'k5d2' with dilation 2."""
+def primitive_mix_kernels(name):
+    """Kernel sizes of the channel segments of primitive ``name``: (3, 5) / (3, 5, 7) for the MixConv ones (PRIMITIVE_MIX), None
+    for every other registered name and for 'skip'; ValueError for an unknown name, as primitive_block."""
+    primitive_block(name, 4, 4)
+    return PRIMITIVE_MIX.get(name)
+
+
+def mix_keys(mix_kernels):
+    """The key a block's config carries for its MixConv segments: only where it has them, so that the config of every other block
+    is what it always was (dilation_keys is the pattern)."""
+    return {'mix_kernels': [int(k) for k in mix_kernels]} if mix_kernels is not None else {}
+
+
+def kernel_tag(k, dilation=1, mix_kernels=None):
+    """How a latency-table key spells a depthwise kernel: 'k3', 'k5', 'k7'; 'k3d2' / 'k5d2' with dilation 2; 'k35' / 'k357' (the
+    segments' sizes in a row) for a MixConv block."""
+    if mix_kernels is not None:
+        return 'k' + ''.join('%d' % v for v in mix_kernels)
     return 'k%d' % k if dilation == 1 else 'k%dd%d' % (k, dilation)
 
 
@@ -168,10 +198,10 @@ def make_mc_mask_dddict():
     return d
 
 
-def lut_key(size, ic, se, oc, k, stride, act, dilation=1):
+def lut_key(size, ic, se, oc, k, stride, act, dilation=1, mix_kernels=None):
     """LUT key format of MixedOP.get_lookup_latency (model_search.py:99-107); a dilated block writes 'k3d2' / 'k5d2' where an
-    undilated one writes 'k3' / 'k5'."""
-    return 'MBInvertedResBlock_{}_{}_{}_{}_{}_s{}_{}'.format(size, ic, se, oc, kernel_tag(k, dilation), stride, act)
+    undilated one writes 'k3' / 'k5', a MixConv block 'k35' / 'k357'."""
+    return 'MBInvertedResBlock_{}_{}_{}_{}_{}_s{}_{}'.format(size, ic, se, oc, kernel_tag(k, dilation, mix_kernels), stride, act)
 
 
 def make_lat_lookup_key_dddict():

@@ -17,12 +17,13 @@ BatchNorm of the search net has no affine and no running statistics (layers.py:1
 a pure function of the batch and therefore has no module/state here.
 """
 from collections import OrderedDict
+import math
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._lib import act_id, se_style_id, MBCONV, NOEXPAND, FUSED
+from ._lib import act_id, se_style_id, check_mix_kernels, mix_split, MBCONV, NOEXPAND, FUSED
 from .functions import CellPlan, MixedOpFn, BN_EPS
 
 
@@ -117,6 +118,47 @@ class IdentityLayer(nn.Module):
 
 def _seq(**mods):
     return nn.Sequential(OrderedDict(mods))
+
+
+class MixDepthwiseConv2d(nn.Module):
+    """The depthwise convolution of a MixConv block (Tan & Le, MixNet): the channels in two or three contiguous segments, segment s
+    a depthwise ``kernels[s]`` x ``kernels[s]`` convolution (padding ``k // 2``, no bias).  ONE 1-D parameter ``weight`` holds the
+    segments back to back, segment s as [mc_s][k_s * k_s] -- the packed w_dw of a TFNAS_CELL_MIXK group (include/tfnas_hip.h), so
+    the state_dict key stays ``...depth_conv.conv.weight``.  ``segment_weights()`` are its views [mc_s, 1, k_s, k_s];
+    ``splits`` the segment widths (_lib.mix_split).  ``forward`` is the stock-torch CPU form (split -> grouped conv2d per segment
+    -> cat): inside a block the HIP library runs it, this is what a test or an export compares with."""
+
+    def __init__(self, channels, kernels, stride=1):
+        super().__init__()
+        self.kernels = check_mix_kernels(kernels)
+        self.channels, self.stride = channels, stride
+        self.splits = mix_split(channels, len(self.kernels))
+        self.weight = nn.Parameter(torch.empty(sum(c * k * k for c, k in zip(self.splits, self.kernels))))
+        self.bias = None
+        self.reset_parameters()
+
+    def segment_weights(self, weight=None):
+        w = self.weight if weight is None else weight
+        out, o = [], 0
+        for c, k in zip(self.splits, self.kernels):
+            out.append(w[o:o + c * k * k].view(c, 1, k, k))
+            o += c * k * k
+        return out
+
+    def reset_parameters(self):
+        """Every segment as nn.Conv2d initialises a depthwise convolution of its size (the networks' _initialization leaves
+        convolution weights at that default)."""
+        with torch.no_grad():
+            for w in self.segment_weights():
+                nn.init.kaiming_uniform_(w, a=math.sqrt(5))
+
+    def forward(self, x):
+        xs = torch.split(x, self.splits, dim=1)
+        return torch.cat([F.conv2d(xi, w, None, self.stride, k // 2, 1, c)
+                          for xi, w, c, k in zip(xs, self.segment_weights(), self.splits, self.kernels)], dim=1)
+
+    def extra_repr(self):
+        return '%d, kernels=%r, splits=%r, stride=%d' % (self.channels, self.kernels, self.splits, self.stride)
 
 
 class _HipBlock(nn.Module):
@@ -221,10 +263,20 @@ class MBInvertedResBlock(_HipBlock):
 
     ``dilation`` (1 | 2; 2 with kernel size 3 or 5 only): the spacing of the depthwise taps, padding ``dilation * (k // 2)`` so the
     output size does not depend on it -- TfnasGroup.dil under TFNAS_CELL_DILATION.  The weight stays [mc, 1, k, k]: no parameter,
-    module or state_dict key depends on it."""
+    module or state_dict key depends on it.
+
+    ``mix_kernels`` ((3, 5) | (3, 7) | (5, 7) | (3, 5, 7); not with dilation 2): a MixConv block -- ``depth_conv.conv`` is a
+    MixDepthwiseConv2d whose channel segments have these kernel sizes (a packed TfnasGroup.k under TFNAS_CELL_MIXK);
+    ``kernel_size`` is then the largest of them.  A block without it is what it always was, down to every state_dict key."""
 
     def __init__(self, in_channels, mid_channels, se_channels, out_channels, kernel_size=3, stride=1,
-                 affine=False, act_func='relu', *, se_act=None, se_gate='sigmoid', dilation=1):
+                 affine=False, act_func='relu', *, se_act=None, se_gate='sigmoid', dilation=1, mix_kernels=None):
+        if mix_kernels is not None:
+            mix_kernels = check_mix_kernels(mix_kernels)
+            if dilation != 1:
+                raise ValueError('tfnas_amd: a MixConv block (mix_kernels) has no dilation')
+            kernel_size = max(mix_kernels)
+        self.mix_kernels = mix_kernels
         if type(dilation) is not int or dilation not in (1, 2):
             raise ValueError('tfnas_amd: depthwise dilation is 1 or 2 (got %r)' % (dilation,))
         if dilation == 2 and kernel_size == 7:
@@ -235,11 +287,16 @@ class MBInvertedResBlock(_HipBlock):
             mid_channels = in_channels
             self.kind = NOEXPAND
 
-        def lead(mc):
+        def depthwise(mc):
+            if mix_kernels is not None:
+                return MixDepthwiseConv2d(mc, mix_kernels, stride)
+            return nn.Conv2d(mc, mc, kernel_size, stride, padding=dilation * get_same_padding(kernel_size), dilation=dilation,
+                             groups=mc, bias=False)
+
+        def lead(mc):       # (modules are made in the order of the fields: a seeded construction draws its weights in that order)
             return OrderedDict(
                 inverted_bottleneck=_seq(conv=nn.Conv2d(in_channels, mc, 1, 1, 0, bias=False), **self.bn(mc)) if expand else None,
-                depth_conv=_seq(conv=nn.Conv2d(mc, mc, kernel_size, stride, padding=dilation * get_same_padding(kernel_size),
-                                               dilation=dilation, groups=mc, bias=False), **self.bn(mc)))
+                depth_conv=_seq(conv=depthwise(mc), **self.bn(mc)))
         super().__init__(in_channels, mid_channels, se_channels, out_channels, kernel_size, stride, affine, act_func, lead,
                          se_act=se_act, se_gate=se_gate)
 

@@ -46,7 +46,7 @@ class _BlockTimer:
         return t
 
     @staticmethod
-    def _describe(ic, mc, se, oc, k, stride, act, H, W, batch, block, dilation=1):
+    def _describe(ic, mc, se, oc, k, stride, act, H, W, batch, block, dilation=1, mix_kernels=None):
         """Pure host: the planned descriptor of one block (no pointers yet), its workspace, its _lib.BlockKind, the width after
         normalisation, {weight field: float offset} into one weight buffer of ``nw`` floats (4-float rounding) and
         {BatchNorm site: channel offset} into the 2 mc + oc channels of the affine tables."""
@@ -55,14 +55,14 @@ class _BlockTimer:
         if block == 'FusedMBConvBlock':              # (a dense 3 x 3 convolution: its weight in the expand field, no depthwise)
             if k != 3:
                 raise NotImplementedError('tfnas_amd: FusedMBConvBlock has kernel size 3 only (got %r)' % (k,))
-            if dilation != 1:
-                raise NotImplementedError('tfnas_amd: FusedMBConvBlock has no depthwise convolution to dilate')
+            if dilation != 1 or mix_kernels is not None:
+                raise NotImplementedError('tfnas_amd: FusedMBConvBlock has no depthwise convolution to dilate or to mix')
             kind = _lib.FUSED
         elif mc <= ic:                               # (no expand convolution, mid normalised to in: layers.MBInvertedResBlock)
             kind, mc = _lib.NOEXPAND, ic
         else:
             kind = _lib.MBCONV
-        d = _lib.describe_block(kind, batch, H, W, ic, mc, se, oc, k, stride, _lib.act_id(act), dilation)
+        d = _lib.describe_block(kind, batch, H, W, ic, mc, se, oc, k, stride, _lib.act_id(act), dilation, mix_kernels)
         lib = _lib.lib()
         _lib.check(lib.tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
         ws = _lib.TfnasCellWs()
@@ -77,11 +77,14 @@ class _BlockTimer:
         return d, ws, kind, mc, woff, sum(sizes) + 64, {site: site_off[site] for site in kind.bn_sites}
 
     def measure(self, ic, mc, se, oc, k, stride, act, size, batch=32, warmup=3, iters=10, reps=3, mode='inference',
-                block='MBInvertedResBlock', dilation=1):
+                block='MBInvertedResBlock', dilation=1, mix_kernels=None):
         lib, dev = self.lib, self.dev
         if mode not in ('inference', 'search'):
             raise ValueError(mode)
-        d, ws, kind, mc, woff, nw, boff = self._describe(ic, mc, se, oc, k, stride, act, size, size, batch, block, dilation)
+        if mix_kernels is not None:
+            k = max(_lib.check_mix_kernels(mix_kernels))     # (a MixConv block: ``k`` is the largest of its kernel sizes)
+        d, ws, kind, mc, woff, nw, boff = self._describe(ic, mc, se, oc, k, stride, act, size, size, batch, block, dilation,
+                                                         mix_kernels)
         w = self._buf('w', nw)
         w.normal_(0, 0.1)
         for f, o in woff.items():
@@ -138,7 +141,8 @@ BLOCK_KINDS = ('MBInvertedResBlock', 'FusedMBConvBlock')      # ``block`` of mea
 Measurer = _BlockTimer          # public name: Measurer(device).measure(ic, mc, se, oc, k, stride, act, size, ...), k in {3, 5, 7},
                                 # act in 'relu' | 'swish' | 'relu6' | 'h-swish'; mc <= ic: the block without expand convolution;
                                 # block='FusedMBConvBlock' (k = 3): the dense 3 x 3 block of the same (ic, mc, se, oc);
-                                # dilation=2 (k in {3, 5}): the depthwise taps two pixels apart
+                                # dilation=2 (k in {3, 5}): the depthwise taps two pixels apart;
+                                # mix_kernels=(3, 5) | (3, 7) | (5, 7) | (3, 5, 7): a MixConv block (k is then ignored)
 
 
 def lut_keys():
@@ -186,17 +190,23 @@ def measure_base(device, batch=32, iters=10, mode='inference'):
 
 
 def build_latency_lookup(device='cuda', step=8, batch=32, iters=10, progress=None, keys=None, mode='inference',
-                         block='MBInvertedResBlock', dilation=1):
+                         block='MBInvertedResBlock', dilation=1, mix_kernels=None):
     """Measure the table on the current GPU.  ``step``: measure every step-th width (1 = every width, ~40 k measurements);
     ``mode``: 'inference' (the reference's meaning) or 'search' (see the module docstring); ``block``: the block kind that is
     timed -- 'FusedMBConvBlock' times the fused block of every k = 3 geometry (every width from 1 up: it has no expand-free
     form) and writes keys that begin with that name, the ones model_eval.NetworkCfg.get_lookup_latency looks up.  ``dilation``:
     2 times every geometry with its depthwise taps two pixels apart and writes the keys of the dilated blocks ('k3d2' / 'k5d2'
-    where the undilated key says 'k3' / 'k5': geometry.lut_key) -- the shipped tables hold none of them."""
+    where the undilated key says 'k3' / 'k5': geometry.lut_key) -- the shipped tables hold none of them.
+    ``mix_kernels``: times every geometry whose kernel size is the largest of them as a MixConv block and writes its key ('k35' /
+    'k357'); the shipped tables hold none of those either: no MixConv block has been measured for them."""
     if block not in BLOCK_KINDS:
         raise ValueError(block)
     if dilation not in (1, 2):
         raise ValueError(dilation)
+    if mix_kernels is not None:
+        mix_kernels = _lib.check_mix_kernels(mix_kernels)
+        if dilation != 1:
+            raise ValueError('a MixConv block has no dilation')
     fused = block == 'FusedMBConvBlock'
     dev = torch.device(device)
     timer = _BlockTimer(dev)
@@ -211,10 +221,14 @@ def build_latency_lookup(device='cuda', step=8, batch=32, iters=10, progress=Non
             if fused or gm['k'] not in (3, 5):
                 continue
             key = geometry.lut_key(gm['size'], gm['ic'], gm['se'], gm['oc'], gm['k'], gm['stride'], gm['act'], dilation)
+        if mix_kernels is not None:
+            if fused or gm['k'] != max(mix_kernels):
+                continue
+            key = geometry.lut_key(gm['size'], gm['ic'], gm['se'], gm['oc'], gm['k'], gm['stride'], gm['act'], 1, mix_kernels)
         lo, hi = (1 if fused else gm['ic'] + 1), gm['max_mc']
         widths = sorted(set(list(range(lo, hi + 1, step)) + [hi]))
         ms = [timer.measure(gm['ic'], w, gm['se'], gm['oc'], gm['k'], gm['stride'], gm['act'], gm['size'], batch,
-                            iters=iters, mode=mode, block=block, dilation=dilation) for w in widths]
+                            iters=iters, mode=mode, block=block, dilation=dilation, mix_kernels=mix_kernels) for w in widths]
         dense = np.interp(np.arange(1, hi + 1), widths, ms)          # (clamps to the end values outside [lo, hi])
         lut[key] = OrderedDict((w + 1, float(dense[w])) for w in range(hi))
         if progress:

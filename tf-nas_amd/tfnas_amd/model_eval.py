@@ -107,7 +107,8 @@ class _DerivedBase(nn.Module):
                 if isinstance(b, IdentityLayer):           # a skipped block costs nothing and keeps the resolution
                     continue
                 key = '{}_{}_{}_{}_{}_{}_s{}_{}'.format(b.name, size, b.in_channels, b.se_channels, b.out_channels,
-                                                        geometry.kernel_tag(b.kernel_size, getattr(b, 'dilation', 1)), b.stride,
+                                                        geometry.kernel_tag(b.kernel_size, getattr(b, 'dilation', 1),
+                                                                            getattr(b, 'mix_kernels', None)), b.stride,
                                                         b.act_func)
                 lat += self.lat_lookup[key][b.mid_channels]
                 size = (size - 1) // b.stride + 1
@@ -121,7 +122,8 @@ class _DerivedBase(nn.Module):
                 'se_channels': b.se_channels, 'out_channels': b.out_channels, 'kernel_size': b.kernel_size, 'stride': b.stride,
                 'groups': 1, 'has_shuffle': False, 'bias': False, 'use_bn': True, 'affine': True, 'act_func': b.act_func,
                 **geometry.se_style_keys(b.se_act, b.se_gate),      # ('se_act' / 'se_gate': only where not the default)
-                **geometry.dilation_keys(getattr(b, 'dilation', 1))}  # ('dilation': only where not 1)
+                **geometry.dilation_keys(getattr(b, 'dilation', 1)),  # ('dilation': only where not 1)
+                **geometry.mix_keys(getattr(b, 'mix_kernels', None))}  # ('mix_kernels': only a MixConv block)
 
     @property
     def config(self):
@@ -174,6 +176,9 @@ class Network(_DerivedBase):
                 # (``se_style``: likewise -- None, one (se_act, se_gate) pair or a {stage: pair} mapping; the stems keep theirs)
                 se_act, se_gate = _lib.se_style_pair(geometry.cell_se_style(se_style, name, block_name))
                 dil = geometry.dilation_keys(geometry.primitive_dilation(prim))      # (FusedMBConvBlock has no such argument)
+                mk = geometry.primitive_mix_kernels(prim)
+                if mk is not None:
+                    dil['mix_kernels'] = mk
                 blk = cls(ic, mc, se, oc, k, s, affine=True, act_func=cfg['act'], se_act=se_act, se_gate=se_gate, **dil)
                 blk.drop_connect_rate = self.drop_connect_rate * self.block_idx / self.block_count
                 stage.append(blk)
@@ -204,6 +209,11 @@ class NetworkCfg(_DerivedBase):
             if dil and (not fused_ok or c['name'] != 'MBInvertedResBlock'):
                 raise NotImplementedError('only an MBInvertedResBlock of a stage may be dilated (second_stem runs fused with '
                                           'first_stem, FusedMBConvBlock has no depthwise convolution): %r' % (c,))
+            if c.get('mix_kernels') is not None:
+                if not fused_ok or c['name'] != 'MBInvertedResBlock':
+                    raise NotImplementedError('only an MBInvertedResBlock of a stage may be a MixConv block (second_stem runs '
+                                              'fused with first_stem, FusedMBConvBlock has no depthwise convolution): %r' % (c,))
+                dil['mix_kernels'] = tuple(c['mix_kernels'])
             return kinds[c['name']](c['in_channels'], c['mid_channels'], c['se_channels'], c['out_channels'],
                                       c['kernel_size'], c['stride'], affine=c.get('affine', True), act_func=c['act_func'],
                                       se_act=se_act, se_gate=se_gate, **dil)

@@ -75,9 +75,26 @@ DILATED_OPS.update({
     for k in (3, 5) for se in (0, 1)})
 
 
+# The MixConv primitives (Tan & Le, the MixNet family), in a table of their own with the same signature: ONE depthwise whose channel
+# segments are 3 x 3 | 5 x 5 (k35) or 3 x 3 | 5 x 5 | 7 x 7 (k357) -- the 5 x 5 / 7 x 7 receptive field on a part of the channels at
+# 17 / 27.7 taps per channel on average instead of 25 / 49.
+#   MBI_k35_* / MBI_k357_*   width from mc_num_dict[i], SE = ic x {1, 2}
+#   DS_k35* / DS_k357*       expand-free
+MIX_OPS = {
+    'MBI_k%s_%s%s' % (tag, e, '_se' if se else ''): (lambda ic, mc, oc, s, aff, act, _ks=ks, _se=se:
+                                                     MBInvertedResBlock(ic, mc, ic * _se, oc, max(_ks), s, affine=aff, act_func=act,
+                                                                        mix_kernels=_ks))
+    for tag, ks in (('35', (3, 5)), ('357', (3, 5, 7))) for e, se in (('e3', 0), ('e6', 0), ('e3', 1), ('e6', 2))}
+MIX_OPS.update({
+    'DS_k%s%s' % (tag, '_se' if se else ''): (lambda ic, mc, oc, s, aff, act, _ks=ks, _se=se:
+                                              MBInvertedResBlock(ic, ic, ic * _se, oc, max(_ks), s, affine=aff, act_func=act,
+                                                                 mix_kernels=_ks))
+    for tag, ks in (('35', (3, 5)), ('357', (3, 5, 7))) for se in (0, 1)})
+
+
 def primitive_factory(name):
-    """The factory (ic, mc, oc, stride, affine, act) -> block of a registered primitive, from either table."""
-    return OPS[name] if name in OPS else DILATED_OPS[name]
+    """The factory (ic, mc, oc, stride, affine, act) -> block of a registered primitive, from any of the three tables."""
+    return OPS[name] if name in OPS else DILATED_OPS[name] if name in DILATED_OPS else MIX_OPS[name]
 
 
 def check_primitives(primitives):
@@ -89,9 +106,9 @@ def check_primitives(primitives):
     if len(names) != len(PRIMITIVES):
         raise ValueError('tfnas_amd: a MixedOP takes exactly %d primitives, got %d' % (len(PRIMITIVES), len(names)))
     for n in names:
-        if n not in OPS and n not in DILATED_OPS and n != SKIP:
+        if n not in OPS and n not in DILATED_OPS and n not in MIX_OPS and n != SKIP:
             raise ValueError('tfnas_amd: unknown primitive %r (one of %s, or %r in a residual cell)'
-                             % (n, ', '.join(sorted(list(OPS) + list(DILATED_OPS))), SKIP))
+                             % (n, ', '.join(sorted(list(OPS) + list(DILATED_OPS) + list(MIX_OPS))), SKIP))
     return names
 
 
@@ -177,7 +194,8 @@ class MixedOP(nn.Module):
                 lats.append(0)
                 continue
             key = '{}_{}_{}_{}_{}_{}_s{}_{}'.format(op.name, size, op.in_channels, op.se_channels, op.out_channels,
-                                                    kernel_tag(op.kernel_size, getattr(op, 'dilation', 1)), op.stride, op.act_func)
+                                                    kernel_tag(op.kernel_size, getattr(op, 'dilation', 1), getattr(op, 'mix_kernels', None)),
+                                                    op.stride, op.act_func)
             lats.append(self.lat_lookup[key][op.mid_channels])
         return lats
 
@@ -700,7 +718,8 @@ class Network(nn.Module):
         """Every candidate of every cell is a plain MBConv block (what the path level and the epoch boundary are built for)."""
         hit = self.__dict__.get('_plain')
         if hit is None:
-            hit = self.__dict__['_plain'] = all(op.kind is _lib.MBCONV for c in self.cells() for op in c.m_ops)
+            hit = self.__dict__['_plain'] = all(op.kind is _lib.MBCONV and getattr(op, 'mix_kernels', None) is None
+                                                for c in self.cells() for op in c.m_ops)      # (a MixConv block: per-cell route)
         return hit
 
     def set_temperature(self, T):

@@ -42,7 +42,8 @@ def derived_config(parsed_arch, mc_num_dddict, num_classes=1000, primitives=None
     mapping); a Fused-MBConv choice is written as a 'FusedMBConvBlock' entry, an expand-free one as the reference records such a
     block (an 'MBInvertedResBlock' with mid_channels == in_channels), a chosen 'skip' as the reference's 'IdentityLayer' entry
     -- all load in model_eval.NetworkCfg.  A dilated choice ('MBI_k3d2_*', 'DS_k5d2', ...) carries a 'dilation' key; an undilated
-    entry has none, so a config without dilation is what it always was.  ``se_style``: the
+    entry has none, so a config without dilation is what it always was.  A MixConv choice ('MBI_k35_*', 'DS_k357', ...)
+    carries 'mix_kernels': [3, 5] / [3, 5, 7] (its 'kernel_size' is the largest); no other entry has the key.  ``se_style``: the
     squeeze-excite style the searched network was built with (model_search.Network(se_style=...): None, one (se_act, se_gate) pair
     or a {stage: pair} mapping); a block's entry carries 'se_act' / 'se_gate' keys only where they differ from the default (the
     block's own activation, 'sigmoid'), so a config without a style is what it always was."""
@@ -63,7 +64,8 @@ def derived_config(parsed_arch, mc_num_dddict, num_classes=1000, primitives=None
             layer, mc, se, k = geometry.primitive_block(prim, ic, mc_num_dddict[stage][name][op])
             blocks.append(dict(_mbconv_config(ic, mc, se, oc, k, s, st['act']), name=layer,
                                **geometry.se_style_keys(*_lib.se_style_pair(geometry.cell_se_style(se_style, stage, name))),
-                               **geometry.dilation_keys(geometry.primitive_dilation(prim))))
+                               **geometry.dilation_keys(geometry.primitive_dilation(prim)),
+                               **geometry.mix_keys(geometry.primitive_mix_kernels(prim))))
         cfg[stage] = blocks
     cfg['feature_mix_layer'] = _conv_layer_config(320, 1280, 1, 1, 'swish')
     cfg['classifier'] = {'name': 'LinearLayer', 'in_features': 1280, 'out_features': num_classes, 'bias': True,
@@ -78,6 +80,14 @@ def _layers(config):
         for blk in config[k]:
             yield blk
     yield config['feature_mix_layer']
+
+
+def _dw_taps(c, mc, k):
+    """Weights of the depthwise convolution of block config ``c``: mc k^2; a MixConv block ('mix_kernels') the sum over its segments."""
+    mk = c.get('mix_kernels')
+    if mk is None:
+        return k * k * mc
+    return sum(w * kk * kk for w, kk in zip(_lib.mix_split(mc, len(mk)), mk))
 
 
 def count_macs_in_M(config, input_size=224):
@@ -107,7 +117,7 @@ def count_macs_in_M(config, input_size=224):
             else:
                 mc = ic
             size = (size - 1) // s + 1
-            total += k * k * mc * size * size                  # depthwise
+            total += _dw_taps(c, mc, k) * size * size          # depthwise
             if se > 0:
                 total += (mc * se + se) + (se * mc + mc)        # 1x1 convs on the pooled vector, with bias
             total += mc * oc * size * size
@@ -137,7 +147,7 @@ def count_params_in_MB(config):
                 n += ic * mc + 2 * mc
             else:
                 mc = ic
-            n += k * k * mc + 2 * mc
+            n += _dw_taps(c, mc, k) + 2 * mc
             if se > 0:
                 n += mc * se + se + se * mc + mc
             n += mc * oc + 2 * oc

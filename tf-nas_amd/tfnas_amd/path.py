@@ -170,7 +170,8 @@ class PathRunner:
         d.act, d.G, d.need_wgrad, d.eps = _lib.act_id(cell.act_func), len(blocks), 0, BN_EPS
         d.has_res = int(cell.in_channels == cell.out_channels and cell.stride == 1)
         for g, b in enumerate(blocks):
-            d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, b.kernel_size, b.se_channels
+            d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, _lib.block_k_word(b), b.se_channels     # (a MixConv block: packed, and
+                                                                                                     #  tfnas_path_plan refuses it)
             d.g[g].dil = b.dilation if getattr(b, 'dilation', 1) != 1 else 0     # (HipModes.apply sets the bit for a dilated group)
             ps = b.hip_params()
             for p in ps:

@@ -7,7 +7,11 @@ another; the variants alternate and the median over the rounds is printed (DESIG
 With a third argument ``dil``: the dilated candidates beside their undilated twins -- k3, k3d2, k5, k5d2 (the undilated ones on
 the default route and on the tile kernels the dilated ones always take) in a late cell (14 x 14, 80 -> 80) and an early cell
 (56 x 56, 24 -> 24), both at six times the input width (dilation table).
-   python tools/dw_k_compare.py 128 7 dil"""
+   python tools/dw_k_compare.py 128 7 dil
+With ``mix``: the MixConv candidates beside their plain twins on the tile kernels they always take -- k3, k5, k7, k35, k357 at
+14 x 14 x 480 and 56 x 56 x 144.  A MixConv pass is two or three launches (one per kernel size of its segments), so this mode
+prints the time of the whole PASS, the sum over its launches (MixConv table).
+   python tools/dw_k_compare.py 128 7 mix"""
 import ctypes as C
 import os
 import statistics
@@ -28,6 +32,12 @@ if len(sys.argv) > 3 and sys.argv[3] == 'dil':
     TILE = dict(dw='tiled', dwwg=False)
     VARIANTS = [('k3 default route', 3, {}), ('k3 tile kernels', 3, TILE), ('k3d2 tile kernels', (3, 2), {}),
                 ('k5 default route', 5, {}), ('k5 tile kernels', 5, TILE), ('k5d2 tile kernels', (5, 2), {})]
+PER_PASS = len(sys.argv) > 3 and sys.argv[3] == 'mix'
+if PER_PASS:
+    GEOMS = [('14 x 14 x 480', 80, 480, 80, 1, 'swish', 14), ('56 x 56 x 144', 24, 144, 24, 1, 'relu', 56)]
+    TILE = dict(dw='tiled', dwwg=False)
+    VARIANTS = [('k3 tile kernels', 3, TILE), ('k5 tile kernels', 5, TILE), ('k7 tile kernels', 7, {}),
+                ('k35 tile kernels', 'mix35', {}), ('k357 tile kernels', 'mix357', {})]
 FAMS = ('k_dw_fwd', 'k_dw_bwd_data', 'k_dw_wgrad')
 
 lib = _lib.lib()
@@ -38,7 +48,7 @@ dev = torch.device('cuda', 0)
 def collect(fam):
     n, ms = C.c_uint64(), C.c_double()
     _lib.check(lib.tfnas_prof_collect(ids[fam], C.byref(n), C.byref(ms)), 'tfnas_prof_collect')
-    return ms.value / max(1, n.value)
+    return ms.value if PER_PASS else ms.value / max(1, n.value)      # (one forward + backward per collection: a pass's total)
 
 
 for name, ic, mc, oc, s, act, hw in GEOMS:
@@ -46,8 +56,9 @@ for name, ic, mc, oc, s, act, hw in GEOMS:
     x = torch.randn(B, ic, hw, hw, device=dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
     blocks = []
     for label, k, route in VARIANTS:
-        k, dil = k if isinstance(k, tuple) else (k, 1)
-        blk = MBInvertedResBlock(ic, mc, 0, oc, k, s, affine=False, act_func=act, dilation=dil).to(dev)
+        mix = {'mix35': (3, 5), 'mix357': (3, 5, 7)}.get(k) if isinstance(k, str) else None
+        k, dil = (max(mix), 1) if mix else k if isinstance(k, tuple) else (k, 1)
+        blk = MBInvertedResBlock(ic, mc, 0, oc, k, s, affine=False, act_func=act, dilation=dil, mix_kernels=mix).to(dev)
         F.adopt_modes(blk, F.HipModes(route=F.route_bits(wgrad_stream=False, **route)))
         blocks.append(blk)
 
@@ -68,6 +79,6 @@ for name, ic, mc, oc, s, act, hw in GEOMS:
             lib.tfnas_prof_enable(0)
             for f in FAMS:
                 times[i][f].append(collect(f))
-    print('%s, B = %d, median of %d alternating rounds (ms per launch)' % (name, B, ROUNDS))
+    print('%s, B = %d, median of %d alternating rounds (ms per %s)' % (name, B, ROUNDS, 'pass' if PER_PASS else 'launch'))
     for (label, k, route), t in zip(VARIANTS, times):
         print('  %-19s' % label + '  '.join('%s %.3f' % (f, statistics.median(t[f])) for f in FAMS))
