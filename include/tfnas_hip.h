@@ -36,7 +36,10 @@
 extern "C" {
 #endif
 
-/* 4, additive: TFNAS_CELL_MIXK -- a packed TfnasGroup.k: MixConv candidates, one depthwise whose channel segments are 3 x 3 | 5 x 5 | 7 x 7.
+/* 4, additive: TFNAS_PATH_EXTENDED (TfnasPathDesc.path_flags, the word that had to be 0) -- tfnas_path_plan takes every cell
+ * tfnas_cell_plan takes in cell mode (the three kinds, TFNAS_CELL_KINDS with or without TFNAS_CELL_SKIP groups, packed groups) and
+ * the pass-through cell of a sampled skip; without the bit it refuses them as before.  No struct, no entry point changed.
+ * 4, additive: TFNAS_CELL_MIXK -- a packed TfnasGroup.k: MixConv candidates, one depthwise whose channel segments are 3 x 3 | 5 x 5 | 7 x 7.
  * 4, additive: TFNAS_CELL_DILATION -- TfnasGroup.dil: depthwise candidates with taps two pixels apart (3 x 3 and 5 x 5).
  * 4, additive: TFNAS_CELL_SKIP -- TFNAS_GROUP_SKIP: the identity candidate in a residual TFNAS_CELL_KINDS cell.
  * 4, additive: TFNAS_CELL_SE_STYLE -- TfnasCellDesc.se_style: the squeeze-excite hidden activation and gate function of a cell.
@@ -213,7 +216,7 @@ typedef struct TfnasCellDesc {
  * describes ONE such block:
  *   geometry   mode == TFNAS_MODE_CELL, G == 1, g[0].mc == ic, g[0].w_expand == NULL and g[0].g_expand == NULL; anything else --
  *              G > 1, mc != ic, an expand pointer, stem or head mode -- is TFNAS_EINVAL, and so is tfnas_path_plan on a cell that
- *              carries the bit.  A mixed cell in which only SOME candidates lack the expand convolution is deliberately out of scope.
+ *              carries the bit (unless the path says TFNAS_PATH_EXTENDED).  A mixed cell in which only SOME candidates lack the expand convolution is deliberately out of scope.
  *              k in {3, 5, 7 (TFNAS_CELL_K7)}, all four activations (two with TFNAS_CELL_ACTS), stride 1 | 2, se 0 or a multiple of
  *              4, ic any multiple of 4 >= 4, has_res as for any cell.
  *   arithmetic D = dw(x) on the raw cell input: no BatchNorm and no activation before the depthwise convolution; `act` applies after
@@ -243,7 +246,8 @@ typedef struct TfnasCellDesc {
  *              included), se 0 or a multiple of 4, all four activations (two with TFNAS_CELL_ACTS), has_res as for any cell.
  *              g[0].w_expand / g_expand hold the dense weight / its gradient in torch's OIHW order [mc][ic][3][3]; g[0].w_dw and
  *              g[0].g_dw are NULL.  Two groups, k != 3, a depthwise pointer, the bit together with TFNAS_CELL_NOEXPAND, stem or
- *              head mode are TFNAS_EINVAL, and so is tfnas_path_plan on a cell that carries the bit.  A width whose
+ *              head mode are TFNAS_EINVAL, and so is tfnas_path_plan on a cell that carries the bit (unless the path says
+ *              TFNAS_PATH_EXTENDED).  A width whose
  *              weight-gradient partial row (9 ic mc floats) does not fit the partial-row scratch, or whose repacked weight
  *              (9 ic mcp floats) does not fit it next to 128 statistics rows of 2 M floats, is TFNAS_ERANGE at plan time (the
  *              widest block of the supernet, 192 -> 1536, fits); the depthwise-only limits do not apply.
@@ -281,7 +285,7 @@ typedef struct TfnasCellDesc {
  *   - TFNAS_CELL_K7 / TFNAS_CELL_ACTS apply as before; the size limits of the one-block kinds hold per group (the dense weight's
  *     partial row and repacked copy of every FUSED group; the depthwise weight-gradient row of the MBCONV groups and of the
  *     NOEXPAND groups): TFNAS_ERANGE;
- *   - tfnas_mbconv_fwd/bwd and tfnas_path_plan refuse the bit (TFNAS_EINVAL); tfnas_efree_supported and tfnas_fx_supported return
+ *   - tfnas_mbconv_fwd/bwd and tfnas_path_plan (without TFNAS_PATH_EXTENDED) refuse the bit (TFNAS_EINVAL); tfnas_efree_supported and tfnas_fx_supported return
  *     0 when any group is not plain: the plain groups of such a cell always materialise E (E == NULL is TFNAS_ENULL);
  *   - tfnas_cell_ws reports E = 0 when no group is plain (E, stats1, red1, cb1 are then never touched);
  *   - a descriptor whose groups are ALL TFNAS_GROUP_MBCONV, and a ONE-group descriptor of any kind, plan, size, route and run
@@ -345,7 +349,10 @@ typedef struct TfnasCellDesc {
  *     without the bit;
  *   - tfnas_cell_ws reports, field for field, what the descriptor without its SKIP groups (flags & ~TFNAS_CELL_SKIP, G = G')
  *     reports: Pr, stats3, red3 and the partial rows are sized by G'; wmix and dwmix are the caller's [G];
- *   - tfnas_mbconv_fwd/bwd, tfnas_path_plan, TFNAS_MODE_STEM and TFNAS_MODE_HEAD refuse the bit as they refuse TFNAS_CELL_KINDS.
+ *   - tfnas_mbconv_fwd/bwd, tfnas_path_plan, TFNAS_MODE_STEM and TFNAS_MODE_HEAD refuse the bit as they refuse TFNAS_CELL_KINDS.  A
+ *     path that says TFNAS_PATH_EXTENDED takes it, and takes a ONE-group descriptor whose group is TFNAS_GROUP_SKIP as the
+ *     pass-through cell of a sampled path (below: the path level) -- the per-cell entry points keep refusing that descriptor (a skip
+ *     needs a computing group before it).
  * Launch sequence: everything runs on the first G' groups as for any TFNAS_CELL_KINDS cell; four kernels see G -- the forward mix
  * and the residual-gradient pass (the sum of the mix weights), the BN3-backward sums (the <dout, x> accumulator of a residual cell)
  * and the dwmix kernel (one wave per entry).  TFNAS_CELL_ACCUM_WGRAD, dx == NULL, need_wgrad == 0, the dwmix-only early return,
@@ -389,7 +396,7 @@ typedef struct TfnasCellDesc {
  * Rules, checked by tfnas_cell_plan and again by every entry point (TFNAS_EINVAL):
  *   - any other packed word; a word with a 7 without TFNAS_CELL_K7; q < n (a segment without a quad); a packed k in a group with
  *     dil == 2, in a TFNAS_GROUP_FUSED or TFNAS_GROUP_SKIP group, in a TFNAS_CELL_FUSED cell, in TFNAS_MODE_STEM or
- *     TFNAS_MODE_HEAD; tfnas_path_plan on a cell with a packed group;
+ *     TFNAS_MODE_HEAD; tfnas_path_plan on a cell with a packed group (unless the path says TFNAS_PATH_EXTENDED);
  *   - allowed: plain MBConv groups and expand-free groups (TFNAS_CELL_NOEXPAND, or TFNAS_GROUP_NOEXPAND of a TFNAS_CELL_KINDS cell), in
  *     sampled and soft launches of tfnas_mixedop_fwd/bwd and in tfnas_mbconv_fwd/bwd; all four activations, both strides, SE or
  *     none, every se_style; a soft cell may hold packed groups beside plain 3 / 5 / 7, dilated, FUSED and SKIP groups.
@@ -705,6 +712,9 @@ int tfnas_sink_bwd(int K, const float *bw, const float *const *res, const float 
  *   - several paths (the two bi-sampling paths) are enqueued interleaved, cell by cell, on their own streams.
  * ================================================================================================================ */
 #define TFNAS_MAX_STAGES 8
+/* TfnasPathDesc.path_flags: the caller knows the cells beside the plain ones -- the other kinds, cells of several kinds, skip and
+ * packed groups, the pass-through cell (tfnas_path_plan).  Without the bit such a path is TFNAS_EINVAL, as it always was. */
+#define TFNAS_PATH_EXTENDED 0x1
 
 typedef struct TfnasStage {
     int32_t ncell;          /* MixedOP blocks of this stage (model_search.py:126-155: 2,3,4,4,4,1)            [in] */
@@ -720,7 +730,7 @@ typedef struct TfnasPathDesc {
     int32_t soft;           /* 1: cells carry G = 8 groups, wmix/cell_lat are consumed and d wmix / d cell_lat produced */
     int32_t need_dx0;       /* backward produces the gradient of the path input                               */
     int32_t efree_mask_lo;  /* bit c set: cell c runs E-free (E never materialised; needs tfnas_efree_supported) */
-    int32_t reserved0;      /* must be 0 (ABI 1: dual) */
+    int32_t path_flags;     /* 0 or TFNAS_PATH_EXTENDED; any other bit: TFNAS_EINVAL (ABI 1: dual; then a word that had to be 0) */
     TfnasStage stage[TFNAS_MAX_STAGES];
     TfnasCellDesc cell[TFNAS_MAX_CELLS];   /* [in] fields + weight / gradient pointers bound; N, H, W chained by plan */
 } TfnasPathDesc;
@@ -743,7 +753,21 @@ int tfnas_path_destroy(void *ctx);
  * really run concurrently (tfnas_amd/streams.py) hands the good ones in here. */
 int tfnas_path_set_side_stream(void *ctx, void *stream);
 /* Validate + plan every cell (tfnas_cell_plan), chain the geometry (cell i+1's input extent = cell i's output), lay out
- * the arena.  May be called again on the same context with different candidates / widths (every weight step does). */
+ * the arena.  May be called again on the same context with different candidates / widths (every weight step does).
+ * Cells: plain TFNAS_MODE_CELL descriptors (dilated groups included); anything below is TFNAS_EINVAL in a path without
+ * TFNAS_PATH_EXTENDED, as it always was.  With the bit: TFNAS_MODE_CELL descriptors of every kind -- plain, TFNAS_CELL_NOEXPAND, TFNAS_CELL_FUSED, TFNAS_CELL_KINDS with or without
+ * TFNAS_CELL_SKIP groups, packed (TFNAS_CELL_MIXK) and dilated groups: the rules of tfnas_cell_plan are the rules.  A sampled path
+ * (soft == 0) keeps G == 1 in every cell.  The E slot of the arena is laid out for the cells that have an E; an efree_mask_lo bit
+ * is legal only where tfnas_efree_supported says so (plain cells), TFNAS_EINVAL elsewhere.  The sink-connecting gradient
+ * dx += bw[k] * dsink of a cell whose input is a depth choice is the LAST term of dx on every tail: in the epilogue of the expand
+ * dgrad (plain cells), in one pass over dx behind the depthwise backward-data pass / the dense dgrad / the residual pass (the
+ * other kinds, cells of several kinds), each product rounded on its own.
+ * The pass-through cell -- a sampled skip: flags = TFNAS_CELL_KINDS | TFNAS_CELL_SKIP (| TFNAS_CELL_ACCUM_WGRAD, ignored), G == 1,
+ * g[0].kind == TFNAS_GROUP_SKIP and nothing else in the group, ic == oc, stride 1, in a sampled path only (anything else:
+ * TFNAS_EINVAL).  It is planned here, never by tfnas_cell_plan; it owns no workspace; its output IS its input (the stage's sink
+ * and the next cell read the tensor it was handed); forward: no launch; backward: one launch for a whole run of such cells,
+ * dx = dout + (bw[a] dsink + bw[a+1] dsink + ...) over the sink slots the tensor fills, the shares summed in slot order; no
+ * weight-gradient fork, no event. */
 int tfnas_path_plan(void *ctx, const TfnasPathDesc *pd, TfnasPathWs *ws);
 /* Set (bit c of cell_mask = 1) or clear TFNAS_CELL_ACCUM_WGRAD on planned cell c of the context, without re-planning: the arena
  * and every offset stay where they are, so a caller may decide between a forward and its backward whether that backward

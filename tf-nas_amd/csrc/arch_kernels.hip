@@ -290,6 +290,48 @@ int launch_scale_copy(float* dst, const float* src, const float* scale, uint64_t
     return (int)hipGetLastError();
 }
 
+// dx = src + ((w_0 g + w_1 g) + ...): the sink-connecting gradient of a tensor that feeds K >= 1 slots of its stage's sink, added
+// to `src` as the LAST term.  Every product is rounded on its own and the products are summed in slot order before the sum meets
+// `src` (sink_add, tfnas_dev.h) -- the order in which autograd accumulates the sink's gradients of one tensor before the gradient
+// of the cell that consumes it arrives.  K = 1, src == dx: dx += w_0 g in place, the pass behind the data gradient of a cell
+// whose tail has no epilogue for the term (expand-free, Fused-MBConv, mixed kinds).  K >= 1, src = the gradient of the last cell
+// of a run of sampled skips: the whole backward of that run (path.hip).  src and dx may alias: each element is read, then
+// written, by one thread.
+struct SinkTerms {
+    const float* w[TFNAS_MAX_SINK];
+};
+__global__ __launch_bounds__(256) void k_dx_add_sink(float* dx, const float* src, const float* __restrict__ g, SinkTerms t,
+                                                     int K, uint64_t count4) {
+    float w[TFNAS_MAX_SINK];
+#pragma unroll
+    for (int k = 0; k < TFNAS_MAX_SINK; ++k) w[k] = k < K ? t.w[k][0] : 0.f;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count4; i += (uint64_t)gridDim.x * 256) {
+        const f32x4 gv = ld4(g + 4 * i), v = ld4(src + 4 * i);
+        if (K == 1) {
+            st4(dx + 4 * i, sink_add(v, w[0], gv));
+            continue;
+        }
+        f32x4 sum = sink_add(zero4(), w[0], gv);
+#pragma unroll
+        for (int k = 1; k < TFNAS_MAX_SINK; ++k)
+            if (k < K) sum = sink_add(sum, w[k], gv);
+        st4(dx + 4 * i, v + sum);
+    }
+}
+
+int launch_dx_add_sink(float* dx, const float* src, const float* g, int K, const float* const* w, uint64_t count, hipStream_t s) {
+    if (K < 1 || K > TFNAS_MAX_SINK || (count & 3)) return TFNAS_EINVAL;
+    if (!dx || !src || !g || !w) return TFNAS_ENULL;
+    ProfScope _prof(TK_SMALL, s);
+    SinkTerms t = {};
+    for (int k = 0; k < K; ++k) {
+        if (!w[k]) return TFNAS_ENULL;
+        t.w[k] = w[k];
+    }
+    hipLaunchKernelGGL(k_dx_add_sink, dim3(stream_blocks(count / 4)), dim3(256), 0, s, dx, src, g, t, K, count / 4);
+    return (int)hipGetLastError();
+}
+
 int launch_sink_bwd(int K, const float* bw, const float* const* res, const float* cell_lat, const float* dout,
                     const float* dlat, uint64_t count, float* const* dres, float* dbetas, float* dcell_lat,
                     double* dots, hipStream_t s) {

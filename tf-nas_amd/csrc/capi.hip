@@ -291,6 +291,7 @@ static TfnasCellDesc kinds_canon(const TfnasCellDesc& d) {
     }
     return c;
 }
+TfnasCellDesc cell_canon(const TfnasCellDesc& d) { return kinds_canon(d); }     // (cell_impl.h: the path level's plan)
 // the groups of one kind of a mixed cell as a sub-descriptor (kernels.h: cell_mixed): same geometry, M and offsets, the kind's
 // one-block bit; returns how many there are.  group_alone: group g of a (sub-)descriptor as a one-group descriptor.
 static int kind_subset(const TfnasCellDesc& d, CellKind kind, TfnasCellDesc& sub) {
@@ -621,7 +622,8 @@ struct CellBwd {
     float *part, *part_w, *part_w1, *part_w2;
 
     int run();
-    int chain_mbconv(const TfnasCellDesc& d, bool se_wgrad);
+    int chain_mbconv(const TfnasCellDesc& d, bool whole);
+    int add_sink();
     int tail_mixed();
     int tail_fused();
     int tail_noexpand();
@@ -678,6 +680,16 @@ int CellBwd::run() {
     return tail_mbconv();
 }
 
+// dx += add_scale[0] * add_src, the sink-connecting gradient (path level: the cell's input is a depth choice of its stage), for the
+// tails whose last store of dx has no epilogue for it -- the depthwise backward-data pass, the dense dgrad, the residual pass of a
+// mixed cell: one more pass over dx [N*H*W][ic], the narrowest tensor of the backward, with k_dx_reduce's rounding (sink_add) and
+// as the LAST term, after the branch sum and after the residual term.  The plain tail keeps its epilogue (expand_dx).
+int CellBwd::add_sink() {
+    if (!b.add_src || !b.dx) return 0;
+    if (!b.add_scale) return TFNAS_ENULL;
+    return launch_dx_add_sink(b.dx, b.dx, b.add_src, 1, &b.add_scale, (uint64_t)d.N * d.H * d.W * d.ic, s);
+}
+
 int CellBwd::tail_fused() {
     // Fused-MBConv: dd, the gradient w.r.t. D, goes to dEh once (free since the SE backward above); the convolution's weight
     // gradient and its data gradient (which writes dx, + the unscaled residual gradient) both read it
@@ -688,7 +700,7 @@ int CellBwd::tail_fused() {
         TRY(launch_conv_wgrad(d, b.dEh, b.x, part_w1, sw));
     }
     if (b.dx) TRY(launch_conv_dgrad(d, b.dEh, d.has_res ? dout_res : nullptr, b.dx, part, s));
-    return 0;
+    return add_sink();
 }
 
 int CellBwd::tail_noexpand() {
@@ -701,7 +713,7 @@ int CellBwd::tail_noexpand() {
     }
     if (b.dx)
         TRY(launch_dw_bwd_dx(d, b.dZ, gate, dpooled, b.D, stats2, red2, d.has_res ? dout_res : nullptr, b.dx, s));
-    return 0;
+    return add_sink();
 }
 
 int CellBwd::tail_mbconv() {
@@ -716,10 +728,10 @@ int CellBwd::tail_mbconv() {
     return chain_mbconv(d, true);
 }
 
-// the materialised route of plain groups from the depthwise backward on: the cell's own descriptor, or the plain groups of a mixed
-// cell (se_wgrad = false: tail_mixed launched the SE weight gradients of ALL groups itself)
-int CellBwd::chain_mbconv(const TfnasCellDesc& d, bool se_wgrad) {
-    const bool se = se_wgrad && d.SE > 0;
+// the materialised route of plain groups from the depthwise backward on: the cell's own descriptor (`whole`), or the plain groups of
+// a mixed cell (tail_mixed launched the SE weight gradients of ALL groups itself, and adds the sink gradient after its last branch)
+int CellBwd::chain_mbconv(const TfnasCellDesc& d, bool whole) {
+    const bool se = whole && d.SE > 0;
     // the depthwise backward-data pass below, planned once; on the stride-1 ring cells and the stride-2 register-window cells
     // it also produces the depthwise weight gradient (same dd window, same E elements: no second read of E, dZ and D)
     const DwPlan dw_bwd = dw_plan_bwd_data(d, b.E == nullptr, b.x != nullptr);
@@ -745,7 +757,8 @@ int CellBwd::chain_mbconv(const TfnasCellDesc& d, bool se_wgrad) {
     }
     if (d.need_wgrad) TRY(launch_expand_wgrad(d, b.dEh, b.E, cb1, b.x, part_w2, fork_to(so, 2, s)));
     if (b.dx && d.mode != TFNAS_MODE_STEM)
-        TRY(expand_dx(d, b.dEh, b.x, cb1, part, dout_res, b.wmix, b.dx, b.dxp, s, b.add_src, b.add_scale));
+        TRY(expand_dx(d, b.dEh, b.x, cb1, part, dout_res, b.wmix, b.dx, b.dxp, s, whole ? b.add_src : nullptr,
+                      whole ? b.add_scale : nullptr));
     return 0;
 }
 
@@ -758,7 +771,7 @@ int CellBwd::chain_mbconv(const TfnasCellDesc& d, bool se_wgrad) {
 // Fork 1 carries, in stream order, the SE weight gradients of all groups, then each kind's depthwise / dense weight gradients
 // (they share that fork's scratch); fork 2 the plain groups' expand weight gradient.
 int CellBwd::tail_mixed() {
-    if (bn || b.add_src) return TFNAS_EINVAL;         // (no affine form; the path level, which adds the sink gradient, refuses the bit)
+    if (bn) return TFNAS_EINVAL;                      // (no affine form)
     TfnasCellDesc full = d, sub;
     full.has_res = 0;
     bool stored = false;                              // dx holds the sum of the branches so far
@@ -786,7 +799,7 @@ int CellBwd::tail_mixed() {
         }
     }
     if (b.dx && d.has_res) TRY(launch_dx_add_res(d, nw, dout_res, b.wmix, b.dx, s));
-    return 0;
+    return add_sink();                                // (the path level's sink gradient: last, behind the residual term)
 }
 }  // namespace
 

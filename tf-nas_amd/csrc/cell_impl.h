@@ -50,6 +50,9 @@ struct CellSide {
 // Each launch decides its route ONCE (capi.hip: route_taken -- TFNAS_ROUTE_TAKEN_VALID | the routes that change what the saved
 // buffers MEAN).  route != NULL: the forward stores that word there; fwd_route: the word of the forward whose buffers this backward
 // reads (0: not recorded) -- a backward whose own word differs returns TFNAS_EINVAL before it launches anything.
+// Both take the CANONICAL form of a planned descriptor (capi.hip: kinds_canon -- a TFNAS_CELL_KINDS descriptor of plain groups or of
+// one group is the descriptor without the bit); cell_canon gives it to the path level's plan.
+TfnasCellDesc cell_canon(const TfnasCellDesc& d);
 int cell_fwd_impl(const TfnasCellDesc& d, const TfnasCellWs& ws, const CellFwdBufs& b, hipStream_t s, int* route = nullptr);
 int cell_bwd_impl(const TfnasCellDesc& d, const TfnasCellWs& ws, const CellBwdBufs& b, hipStream_t s, const CellSide* so,
                   int fwd_route);

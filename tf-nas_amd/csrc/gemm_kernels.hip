@@ -723,18 +723,7 @@ __device__ __forceinline__ f32x4 bn1_de(const f32x4* cb, f32x4 deh, f32x4 e) {
     return r;
 }
 
-// dx + w*g with the product rounded separately (what the sink's scaled copy followed by autograd's add computed before the
-// two were folded into this epilogue): keeps the path level bit-identical to the per-cell route
-__device__ __forceinline__ f32x4 sink_add(f32x4 v, float w, f32x4 g) {
-    // the product must be rounded on its own: -ffp-contract=fast would fuse it into the add (HIP's __fmul_rn / __fadd_rn
-    // are plain * and +, and `#pragma clang fp contract(off)` did not survive inlining here) -- the empty asm makes each
-    // product opaque to the contraction pass
-    float px = w * g.x, py = w * g.y, pz = w * g.z, pw = w * g.w;
-    asm volatile("" : "+v"(px), "+v"(py), "+v"(pz), "+v"(pw));
-    f32x4 r;
-    r.x = v.x + px; r.y = v.y + py; r.z = v.z + pz; r.w = v.w + pw;
-    return r;
-}
+// (sink_add, the separately rounded dx + w*g of the sink-connecting gradient: tfnas_dev.h)
 
 // ============================================================================ expand dgrad, without reading E
 // dx[p][c] = sum_m de[p][m] * W[m][c]  (+ sumw * dout[p][c] for residual cells),  m over all mid channels of all groups,

@@ -373,6 +373,8 @@ int launch_arch_sample(int ncell, const float* const* la, const uint8_t* mask, c
 int launch_sink_fwd(int K, const float* betas, const float* const* res, const float* cell_lat, uint64_t count,
                     float* out, float* out_lat, float* bw, hipStream_t s);
 int launch_scale_copy(float* dst, const float* src, const float* scale, uint64_t count, hipStream_t s);
+// dx = src + ((w[0][0] g + w[1][0] g) + ...), K <= TFNAS_MAX_SINK terms, `count` floats (a multiple of 4); src may be dx
+int launch_dx_add_sink(float* dx, const float* src, const float* g, int K, const float* const* w, uint64_t count, hipStream_t s);
 // dres[k] may be NULL (that depth output's share is added elsewhere: path level)
 int launch_sink_bwd(int K, const float* bw, const float* const* res, const float* cell_lat, const float* dout,
                     const float* dlat, uint64_t count, float* const* dres, float* dbetas, float* dcell_lat,

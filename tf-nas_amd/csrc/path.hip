@@ -50,7 +50,37 @@ struct PathCtx {
     hipEvent_t join = nullptr;
     bool events_ok = false;
     int fwd_route[TFNAS_MAX_CELLS] = {};   // the route word each cell's last forward took (cell_impl.h; 0: none since the plan)
+    bool pass[TFNAS_MAX_CELLS] = {};       // a pass-through cell (a sampled skip): no workspace, no launch, out aliases its input
 };
+
+// A sampled skip at the path level: a one-group cell whose flags carry TFNAS_CELL_KINDS | TFNAS_CELL_SKIP and whose group is
+// TFNAS_GROUP_SKIP (the per-cell entry points refuse such a descriptor: a skip needs a computing group before it there).
+inline bool pass_through(const TfnasCellDesc& d) {
+    return d.mode == TFNAS_MODE_CELL && cell_mixed(d) && cell_skip(d) && d.G == 1 && d.g[0].kind == TFNAS_GROUP_SKIP;
+}
+// Planned without tfnas_cell_plan: a residual position of a sampled path, an empty group; it keeps the extent and owns nothing but
+// its share of the gradient ring
+int plan_pass(TfnasCellDesc& d, TfnasCellWs& ws, bool soft, bool efree) {
+    if (soft || efree) return TFNAS_EINVAL;
+    if (d.flags & ~(TFNAS_CELL_KINDS | TFNAS_CELL_SKIP | TFNAS_CELL_ACCUM_WGRAD)) return TFNAS_EINVAL;
+    if (d.ic != d.oc || d.stride != 1) return TFNAS_EINVAL;
+    if (d.N < 1 || d.H < 1 || d.W < 1 || d.ic < 4 || (d.ic & 3) || d.ic > 1024) return TFNAS_EINVAL;
+    if ((double)d.N * d.H * d.W >= 2147483647.0) return TFNAS_ERANGE;
+    const TfnasGroup& gr = d.g[0];
+    if (gr.mc != 0 || gr.k != 0 || gr.se != 0 || gr.dil != 0) return TFNAS_EINVAL;
+    if (gr.w_expand || gr.w_dw || gr.w_proj || gr.w_se_r || gr.b_se_r || gr.w_se_e || gr.b_se_e || gr.g_expand || gr.g_dw ||
+        gr.g_proj || gr.g_se_r || gr.gb_se_r || gr.g_se_e || gr.gb_se_e)
+        return TFNAS_EINVAL;
+    d.has_res = 1;
+    d.need_wgrad = 0;
+    d.route = 0;
+    d.Ho = d.H;
+    d.Wo = d.W;
+    d.M = d.SE = 0;
+    memset(&ws, 0, sizeof(ws));
+    ws.out = ws.dx = (uint64_t)d.N * d.H * d.W * d.ic;
+    return 0;
+}
 
 int plan_path(PathCtx& c, const TfnasPathDesc& in, TfnasPathWs* out) {
     if (in.ncell < 1 || in.ncell > TFNAS_MAX_CELLS || in.nstage < 1 || in.nstage > TFNAS_MAX_STAGES) return TFNAS_ERANGE;
@@ -71,13 +101,16 @@ int plan_path(PathCtx& c, const TfnasPathDesc& in, TfnasPathWs* out) {
         nc += sg.ncell;
     }
     if (nc != pd.ncell) return TFNAS_EINVAL;
-    if (pd.reserved0 != 0) return TFNAS_EINVAL;          // (was `dual`: both bi-sampling paths in one descriptor; removed)
+    if (pd.path_flags & ~TFNAS_PATH_EXTENDED) return TFNAS_EINVAL;   // (the word was `dual`, then had to be 0)
+    const bool ext = (pd.path_flags & TFNAS_PATH_EXTENDED) != 0;
     // cells: chain the geometry, plan, size
     for (int i = 0; i < pd.ncell; ++i) {
         TfnasCellDesc& d = pd.cell[i];
+        // TFNAS_PATH_EXTENDED: every cell tfnas_cell_plan accepts in cell mode -- the three one-block kinds, cells of several kinds
+        // with or without skip groups, packed and dilated groups: its rules are the rules -- and the pass-through cell of a sampled
+        // skip.  Without the bit: plain cells, as it always was
         if (d.mode != TFNAS_MODE_CELL) return TFNAS_EINVAL;
-        if (cell_kind(d) != TFNAS_KIND_MBCONV || cell_mixed(d)) return TFNAS_EINVAL;   // (the other kinds, and cells of several: per-cell entry points only)
-        if (cell_packed(d)) return TFNAS_EINVAL;                  // (a MixConv group, TFNAS_CELL_MIXK: per-cell entry points only)
+        if (!ext && (cell_kind(d) != TFNAS_KIND_MBCONV || cell_mixed(d) || cell_packed(d))) return TFNAS_EINVAL;
         if (!pd.soft && d.G != 1) return TFNAS_EINVAL;            // a sampled path evaluates one candidate per cell
         if (i > 0) {
             const TfnasCellDesc& p = pd.cell[i - 1];
@@ -86,10 +119,16 @@ int plan_path(PathCtx& c, const TfnasPathDesc& in, TfnasPathWs* out) {
             d.H = p.Ho;
             d.W = p.Wo;
         }
-        TRY(tfnas_cell_plan(&d));
-        TRY(tfnas_cell_ws(&d, &c.cws[i]));
         const bool efree = (pd.efree_mask_lo >> i) & 1;
-        if (efree && (d.need_wgrad || !efree_supported(d))) return TFNAS_EINVAL;
+        c.pass[i] = pass_through(d);
+        if (c.pass[i]) {
+            TRY(plan_pass(d, c.cws[i], pd.soft != 0, efree));
+            continue;
+        }
+        TRY(tfnas_cell_plan(&d));
+        d = cell_canon(d);                                        // (what the per-cell entry points launch on)
+        TRY(tfnas_cell_ws(&d, &c.cws[i]));
+        if (efree && (d.need_wgrad || !efree_supported(d))) return TFNAS_EINVAL;   // (plain cells only: efree_supported)
     }
     // a stage whose input is a depth choice must keep the extent (ic == oc, stride 1 in its first cell)
     for (int st = 0; st < pd.nstage; ++st) {
@@ -116,7 +155,11 @@ int plan_path(PathCtx& c, const TfnasPathDesc& in, TfnasPathWs* out) {
         const bool efree = (pd.efree_mask_lo >> i) & 1;
         CellOff& o = c.co[i];
         o.E = ~(uint64_t)0;
-        if (!efree) { o.E = off; off += up(w.E); }
+        if (c.pass[i]) {                                          // (no workspace; its out is its input: cell_out)
+            o.D = o.Pr = o.fsmall = o.stats = o.out = ~(uint64_t)0;
+            continue;
+        }
+        if (!efree && w.E > 0) { o.E = off; off += up(w.E); }     // (a cell without expand convolution has no E)
         o.D = off; off += up(w.D);
         o.Pr = off; off += up(w.Pr);
         o.fsmall = off; off += up(w.fsmall);
@@ -179,13 +222,22 @@ inline const float* stage_input(const PathCtx& c, int st, const float* x0, const
     return st == 0 ? x0 : arena + c.so[st - 1].sink_out;
 }
 
+// input / output of cell i: a pass-through cell's output is its input, however many of them stand in a row
+inline const float* cell_in(const PathCtx& c, int i, const float* x0, const float* arena) {
+    const int st = c.stage_of[i], first = c.pd.stage[st].first_cell;
+    while (i > first && c.pass[i - 1]) --i;
+    return i == first ? stage_input(c, st, x0, arena) : arena + c.co[i - 1].out;
+}
+inline const float* cell_out(const PathCtx& c, int i, const float* x0, const float* arena) {
+    return c.pass[i] ? cell_in(c, i, x0, arena) : arena + c.co[i].out;
+}
+
 int fwd_cell(PathCtx& c, int i, const float* x0, const float* wmix, float* arena, hipStream_t s) {
     const TfnasPathDesc& pd = c.pd;
-    const int st = c.stage_of[i];
-    const TfnasStage& sg = pd.stage[st];
     const CellOff& o = c.co[i];
+    if (c.pass[i]) return 0;                             // (a sampled skip: no launch)
     CellFwdBufs b;
-    b.x = (i == sg.first_cell) ? stage_input(c, st, x0, arena) : arena + c.co[i - 1].out;
+    b.x = cell_in(c, i, x0, arena);
     b.wmix = wmix ? wmix + (size_t)i * TFNAS_MAX_GROUPS : nullptr;
     b.E = o.E == ~(uint64_t)0 ? nullptr : arena + o.E;
     b.D = arena + o.D;
@@ -202,7 +254,7 @@ void sink_res(const PathCtx& c, int st, const float* x0, const float* arena, con
     const TfnasStage& sg = c.pd.stage[st];
     for (int k = 0; k < sg.nres; ++k) {
         const int r = sg.start_res + k;                    // index into [stage input, out_1, ..., out_K]
-        res[k] = r == 0 ? stage_input(c, st, x0, arena) : arena + c.co[sg.first_cell + r - 1].out;
+        res[k] = r == 0 ? stage_input(c, st, x0, arena) : cell_out(c, sg.first_cell + r - 1, x0, arena);
     }
 }
 
@@ -362,7 +414,7 @@ struct BwdRun {
 // weight-gradient kernels of cell i + NSET -- the last ones that read them -- must be done (side stream, <= LAG cells behind)
 int wait_wgrads(BwdRun& r, int i) {
     const int j = i + NSET;
-    if (!r.side_on || j >= r.c->pd.ncell || !r.c->pd.cell[j].need_wgrad) return 0;
+    if (!r.side_on || j >= r.c->pd.ncell || r.c->pass[j] || !r.c->pd.cell[j].need_wgrad) return 0;
     return (int)hipStreamWaitEvent(r.s, r.c->wdone[j], 0);
 }
 
@@ -386,8 +438,48 @@ int bwd_sink(BwdRun& r, int st, int lat_off) {
                            r.s);
 }
 
+// where the input gradient of cell i goes: the ring (the previous cell's dout), the previous stage's boundary buffer, or the caller
+float* dx_dest(BwdRun& r, int i) {
+    PathCtx& c = *r.c;
+    const int st = c.stage_of[i];
+    if (i > c.pd.stage[st].first_cell) return r.arena + c.ring[i % NRING];
+    if (st > 0) return r.arena + c.so[st - 1].bound;
+    return c.pd.need_dx0 ? r.dx0 : nullptr;
+}
+
+// Backward of a run of pass-through cells a..b (sampled skips in a row): ONE tensor is the input of a and the output of each of
+// them, so its gradient is the gradient arriving at b plus the sink's share of every slot the tensor fills -- res_list[a - first]
+// (where that is a depth choice) .. res_list[b + 1 - first].  One launch, by the run's first cell (the last one the walk
+// reaches); the others launch nothing.  The shares are summed in slot order and the sum is added last: the order in which autograd
+// accumulates them on the per-cell route.  (The last slot of a stage is not in the sum: bwd_sink has stored it as the gradient of
+// the stage's last cell.)  The cell behind the run leaves its own sink share to this launch (bwd_cell).  No weight gradients: no
+// fork, no wdone event.
+int bwd_pass(BwdRun& r, int i) {
+    PathCtx& c = *r.c;
+    const int st = c.stage_of[i];
+    const TfnasStage& sg = c.pd.stage[st];
+    const int last = sg.first_cell + sg.ncell - 1;
+    if (i > sg.first_cell && c.pass[i - 1]) return 0;    // (not the first of its run)
+    int b = i;
+    while (b < last && c.pass[b + 1]) ++b;
+    if (i != last) TRY(wait_wgrads(r, i));               // (this launch writes ring slot i % NRING)
+    float* dx = dx_dest(r, i);
+    if (!dx) return 0;
+    const float* src = r.arena + c.ring[(b + 1) % NRING];
+    const float* dsink = (st + 1 < c.pd.nstage) ? r.arena + c.so[st].bound : r.dout;
+    const int lo = (i - sg.first_cell) > sg.start_res ? (i - sg.first_cell) : sg.start_res;
+    const int hi = b == last ? sg.ncell - 1 : b + 1 - sg.first_cell;      // res_list slots lo .. hi
+    const float* w[TFNAS_MAX_SINK];
+    int K = 0;
+    for (int q = lo; q <= hi && K < TFNAS_MAX_SINK; ++q) w[K++] = r.arena + c.so[st].bw + (q - sg.start_res);
+    const uint64_t count = c.cws[i].dx;
+    if (K == 0) return (int)hipMemcpyAsync(dx, src, sizeof(float) * count, hipMemcpyDeviceToDevice, r.s);
+    return launch_dx_add_sink(dx, src, dsink, K, w, count, r.s);
+}
+
 int bwd_cell(BwdRun& r, int i) {
     PathCtx& c = *r.c;
+    if (c.pass[i]) return bwd_pass(r, i);
     const TfnasPathDesc& pd = c.pd;
     const int st = c.stage_of[i];
     const TfnasStage& sg = pd.stage[st];
@@ -396,7 +488,7 @@ int bwd_cell(BwdRun& r, int i) {
     const ScratchSet& ss = c.set[i % NSET];
     if (j != sg.ncell - 1) TRY(wait_wgrads(r, i));       // (the stage's last cell waited in bwd_sink)
     CellBwdBufs b;
-    b.x = (j == 0) ? stage_input(c, st, r.x0, r.arena) : r.arena + c.co[i - 1].out;
+    b.x = cell_in(c, i, r.x0, r.arena);
     b.wmix = (r.wmix && pd.soft) ? r.wmix + (size_t)i * TFNAS_MAX_GROUPS : nullptr;
     b.E = o.E == ~(uint64_t)0 ? nullptr : r.arena + o.E;
     b.D = r.arena + o.D;
@@ -412,14 +504,13 @@ int bwd_cell(BwdRun& r, int i) {
     b.part_w = r.arena + ss.part_w;
     b.dxp = r.arena + c.dxp;
     b.dwmix = (r.dwmix && pd.soft) ? r.dwmix + (size_t)i * TFNAS_MAX_GROUPS : nullptr;
-    // where the input gradient goes: the ring (next cell's dout), the previous stage's boundary buffer, or the caller
-    if (j > 0) b.dx = r.arena + c.ring[i % NRING];
-    else if (st > 0) b.dx = r.arena + c.so[st - 1].bound;
-    else b.dx = pd.need_dx0 ? r.dx0 : nullptr;
-    // the cell's input also feeds the stage's sink when it is a depth choice: fold bw * dsink into the dx epilogue
+    b.dx = dx_dest(r, i);
+    // the cell's input also feeds the stage's sink when it is a depth choice: bw * dsink is the last term of dx (the plain tail's
+    // epilogue, one pass behind the other tails: capi.hip) -- unless the input is the tensor of a run of pass-through cells,
+    // whose one launch adds the shares of all its slots (bwd_pass)
     b.add_src = nullptr;
     b.add_scale = nullptr;
-    if (j >= sg.start_res && b.dx) {
+    if (j >= sg.start_res && b.dx && !(j > 0 && c.pass[i - 1])) {
         b.add_src = (st + 1 < pd.nstage) ? r.arena + c.so[st].bound : r.dout;
         b.add_scale = r.arena + c.so[st].bw + (j - sg.start_res);
     }

@@ -118,6 +118,19 @@ __device__ __forceinline__ void st4_nt(float* p, f32x4 v) { __builtin_nontempora
 __device__ __forceinline__ f32x4 zero4() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
 __device__ __forceinline__ f32x4 splat4(float a) { f32x4 z = {a, a, a, a}; return z; }
 
+// dx + w*g with the product rounded separately (what the sink's scaled copy followed by autograd's add computed before the
+// two were folded into this epilogue): keeps the path level bit-identical to the per-cell route
+__device__ __forceinline__ f32x4 sink_add(f32x4 v, float w, f32x4 g) {
+    // the product must be rounded on its own: -ffp-contract=fast would fuse it into the add (HIP's __fmul_rn / __fadd_rn
+    // are plain * and +, and `#pragma clang fp contract(off)` did not survive inlining here) -- the empty asm makes each
+    // product opaque to the contraction pass
+    float px = w * g.x, py = w * g.y, pz = w * g.z, pw = w * g.w;
+    asm volatile("" : "+v"(px), "+v"(py), "+v"(pz), "+v"(pw));
+    f32x4 r;
+    r.x = v.x + px; r.y = v.y + py; r.z = v.z + pz; r.w = v.w + pw;
+    return r;
+}
+
 // load 4 consecutive floats that may be unaligned / partially out of range [0, lim)
 __device__ __forceinline__ f32x4 ld4_guard(const float* base, int idx, int lim, bool aligned) {
     f32x4 r = zero4();

@@ -35,6 +35,7 @@ CELL_SE_STYLE = 0x1000       # TfnasCellDesc.flags: se_style may be non-zero (se
 CELL_SKIP = 0x2000           # TfnasCellDesc.flags: groups may be GROUP_SKIP, the identity candidate (with CELL_KINDS, residual cells only)
 CELL_DILATION = 0x8000       # TfnasCellDesc.flags: groups may have depthwise dilation 2 (TfnasGroup.dil; not read without the bit)
 CELL_MIXK = 0x10000          # TfnasCellDesc.flags: TfnasGroup.k may be a packed word -- a MixConv group (mix_k_word; refused without the bit)
+PATH_EXTENDED = 1            # TfnasPathDesc.path_flags: the path may hold cells beside the plain ones (tfnas_path_plan refuses them without)
 GROUP_SKIP = 3               # TfnasGroup.kind of a skip group: no width, no weights, no columns -- not a BlockKind (KINDS stays three)
 SE_GATE = {'sigmoid': 0, 'h-sigmoid': 1}      # gate function of a squeeze-excite branch (bits 4-7 of TfnasCellDesc.se_style)
 # TfnasCellDesc.route (include/tfnas_hip.h: TFNAS_ROUTE_*) -- every kernel-variant switch of a launch; 0 = the library's policy
@@ -215,7 +216,7 @@ class TfnasStage(C.Structure):
 
 
 class TfnasPathDesc(C.Structure):
-    _fields_ = ([(n, C.c_int32) for n in ('ncell', 'nstage', 'soft', 'need_dx0', 'efree_mask_lo', 'reserved0')]
+    _fields_ = ([(n, C.c_int32) for n in ('ncell', 'nstage', 'soft', 'need_dx0', 'efree_mask_lo', 'path_flags')]
                 + [('stage', TfnasStage * MAX_STAGES), ('cell', TfnasCellDesc * MAX_CELLS)])
 
 

@@ -259,26 +259,19 @@ class CellPlan:
         key = (N, H, W)
         hit = self._desc_cache.get(key)
         if hit is None:
-            d = TfnasCellDesc()
-            d.N, d.H, d.W, d.ic, d.oc, d.stride = N, H, W, self.ic, self.oc, self.stride
-            d.mode = self.mode
-            if self.mode == _lib.MODE_STEM:            # (H, W) given = image size; plan derives the conv output size
-                d.Hi, d.Wi = H, W
-            d.act, d.has_res, d.G, d.need_wgrad, d.eps = _lib.act_id(self.act), self.has_res, len(self.blocks), 0, BN_EPS
-            for g, b in enumerate(self.blocks):
-                d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, _lib.block_k_word(b), b.se_channels     # (a MixConv block: packed)
-                dil = getattr(b, 'dilation', 1)
-                d.g[g].dil = dil if dil != 1 else 0    # (an undilated group keeps the word at 0, as before the field had a name)
-            self.modes.apply(d, *self._kind_arg)       # (before the plan: it validates the modes; every launch re-checks them)
-            self._mark(d)
+            d = fill_cell_desc(TfnasCellDesc(), self, N, H, W)
             check(_lib.lib().tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
             ws = TfnasCellWs()
             check(_lib.lib().tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
             hit = (d, ws)
             self._desc_cache[key] = hit
-        self.modes.apply(hit[0], *self._kind_arg)      # (every launch: the descriptor is cached, the model's modes may change)
-        self._mark(hit[0])
+        self.refresh(hit[0])                           # (every launch: the descriptor is cached, the model's modes may change)
         return hit
+
+    def refresh(self, d):
+        """The words of a filled descriptor that may change between launches: the model's modes, then what the plan marks."""
+        self.modes.apply(d, *self._kind_arg)
+        self._mark(d)
 
     def _mark(self, d):
         """What the plan itself knows about its descriptor (after HipModes.apply, which rewrites flags): the squeeze-excite style
@@ -301,6 +294,35 @@ class CellPlan:
             for (g, f), t in zip(self._g_slots, grads):
                 setattr(d.g[g], f, t.data_ptr())
         d.need_wgrad = int(grads is not None)
+
+
+def fill_cell_desc(d, plan, N, H, W):
+    """Fill ``d`` from a CellPlan's blocks, up to (not including) tfnas_cell_plan: the geometry, per group its width, kernel-size
+    word (a MixConv block: packed), SE width and dilation, the owning model's modes with the flags the content asks for, the
+    squeeze-excite style, and -- a plan of blocks of different kinds -- CELL_KINDS with every group's kind and the skip groups.
+    THE filler of a cell descriptor: the per-cell route (CellPlan.desc) and the path level (path.PathRunner._template) both call
+    it; weight and gradient pointers are CellPlan.bind's (by _W_FIELDS / _G_FIELDS).  Returns ``d``."""
+    d.N, d.H, d.W, d.ic, d.oc, d.stride = N, H, W, plan.ic, plan.oc, plan.stride
+    d.mode = plan.mode
+    if plan.mode == _lib.MODE_STEM:                    # (H, W) given = image size; plan derives the conv output size
+        d.Hi, d.Wi = H, W
+    d.act, d.has_res, d.G, d.need_wgrad, d.eps = _lib.act_id(plan.act), plan.has_res, len(plan.blocks), 0, BN_EPS
+    for g, b in enumerate(plan.blocks):
+        d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, _lib.block_k_word(b), b.se_channels     # (a MixConv block: packed)
+        dil = getattr(b, 'dilation', 1)
+        d.g[g].dil = dil if dil != 1 else 0            # (an undilated group keeps the word at 0, as before the field had a name)
+    plan.refresh(d)                                    # (before the plan: it validates the modes; every launch re-checks them)
+    return d
+
+
+def fill_pass_desc(d, channels, N, H, W):
+    """The descriptor of a sampled skip in a TfnasPathDesc (include/tfnas_hip.h: the pass-through cell): one empty TFNAS_GROUP_SKIP
+    group under CELL_KINDS | CELL_SKIP in a residual position.  tfnas_path_plan plans it itself (never tfnas_cell_plan)."""
+    d.N, d.H, d.W, d.ic, d.oc, d.stride = N, H, W, channels, channels, 1
+    d.mode, d.G, d.has_res, d.need_wgrad, d.eps = _lib.MODE_CELL, 1, 1, 0, BN_EPS
+    d.flags = _lib.CELL_KINDS | _lib.CELL_SKIP
+    d.g[0].kind = _lib.GROUP_SKIP
+    return d
 
 
 def _cell_forward(ctx, plan, xh, N, H, W, wmix, params):

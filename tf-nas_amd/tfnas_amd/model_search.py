@@ -346,9 +346,13 @@ SECOND_PATH_ON_SIDE_STREAM = True       # the 'random' forward of a bi-sampling 
 
 
 class Network(nn.Module):
-    def __init__(self, num_classes, mc_num_dddict, lat_lookup, primitives=None, se_style=None):
+    def __init__(self, num_classes, mc_num_dddict, lat_lookup, primitives=None, se_style=None, extended_paths=False):
         super().__init__()
         self.se_style = se_style               # (of the MixedOP cells; the stems keep the reference's squeeze-excite)
+        # extended_paths=True: a network with candidates beside the plain MBConv ones (other kinds, MixConv, dilated, skip) runs on
+        # the path level and the weight arena too (path_capable).  Off by default: such a network then takes the per-cell route in
+        # every step, as it always did.  A routing switch of this object alone: not handed to the stages, not in state_dict.
+        self.extended_paths = bool(extended_paths)
         self.lat_lookup = lat_lookup
         self.mc_num_dddict = mc_num_dddict
 
@@ -574,7 +578,7 @@ class Network(nn.Module):
         from . import search
         if not (MODULE_PATHS and search.USE_PATHS and x.is_cuda):
             return False
-        if not self.plain_candidates():               # (the path level runs plain candidates only)
+        if not self.path_capable():                   # (plain candidates; every candidate with extended_paths)
             return False
         p = self.first_stem.conv.weight
         return p.is_cuda and p.is_leaf and p.device == x.device
@@ -720,6 +724,18 @@ class Network(nn.Module):
         if hit is None:
             hit = self.__dict__['_plain'] = all(op.kind is _lib.MBCONV and getattr(op, 'mix_kernels', None) is None
                                                 for c in self.cells() for op in c.m_ops)      # (a MixConv block: per-cell route)
+        return hit
+
+    def path_capable(self):
+        """The path level (tfnas_path_plan) takes this network: every candidate plain -- or, with ``extended_paths``, every cell one
+        the library's path plan accepts: candidates of the three block kinds (MixConv and dilated ones included) and skips."""
+        if self.plain_candidates():
+            return True
+        if not self.extended_paths:
+            return False
+        hit = self.__dict__.get('_path_ok')
+        if hit is None:
+            hit = self.__dict__['_path_ok'] = all(op.kind is None or op.kind in _lib.KINDS for c in self.cells() for op in c.m_ops)
         return hit
 
     def set_temperature(self, T):

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import TfnasCellDesc, TfnasPathDesc, TfnasPathWs, check, ptr, raw_array
-from .functions import BN_EPS, DEFAULT_MODES, EFREE, EFREE_STRIDE1, _nhwc, _on, _require_cuda, blocks_se_style, mark_se_style
+from .functions import EFREE, EFREE_STRIDE1, _nhwc, _on, _require_cuda, fill_cell_desc, fill_pass_desc
 
 ALIGN = 64          # floats; every parameter starts on a 256-byte boundary of the arenas
 
@@ -117,10 +117,15 @@ class PathRunner:
         self.weights = weights                      # WeightArena or None (then need_wgrad paths are refused)
         self._slots = {}
         self._tmpl = {}
+        self._tmeta = {}
+        self._wide = {}                             # input shape -> per cell the candidate with the largest planned workspace
         self.wgrad_streams = {}                     # slot name -> torch stream for that path's weight-gradient kernels
         self.segment_hook = None                    # callable(cur_stream, side_stream) between the two backward segments
         self.split_stage = 3                        # stages [3, 6) = stage4..stage6 hold 89 % of the parameters
         self.device = next(model.parameters()).device
+        # TfnasPathDesc.path_flags: a network with candidates beside the plain ones says so (a plain network's paths are what they
+        # always were)
+        self.path_flags = 0 if getattr(model, 'plain_candidates', lambda: True)() else _lib.PATH_EXTENDED
         nres = [st.num_res for st in self.stages]
         self.nres_total = sum(nres)
         # stage-expanded latency layout: per stage its nres entries, a leading 0 where the stage input is a depth choice
@@ -155,39 +160,62 @@ class PathRunner:
 
     # ---- descriptor templates ---------------------------------------------------------------------------------
     def _template(self, ci, idx, N, H, W):
-        """Planned TfnasCellDesc of cell ``ci`` with candidate ``idx`` (None: all 8), weight / gradient pointers bound."""
+        """Planned TfnasCellDesc of cell ``ci`` with candidate ``idx`` (None: all 8), weight / gradient pointers bound: the cell's
+        own CellPlan (the per-cell route's: MixedOP._plan) filled by functions.fill_cell_desc -- every kind, packed and dilated
+        groups, skip groups.  A sampled skip is the pass-through descriptor (functions.fill_pass_desc): no plan, no pointers."""
+        return self._template_entry(ci, idx, N, H, W)[0]
+
+    def _template_entry(self, ci, idx, N, H, W):
+        """(descriptor, gradient pointers are bound); ``_tmpl`` maps the key to the descriptor, ``_tmeta`` to (data pointer of the
+        first bound weight, gradient pointers are bound, the plan that filled it)"""
         cell = self.cells[ci]
         key = (ci, idx, N, H, W)
-        blocks = list(cell.m_ops) if idx is None else [cell.m_ops[idx]]
         t = self._tmpl.get(key)
-        if t is not None and t.g[0].w_expand == blocks[0].inverted_bottleneck.conv.weight.data_ptr():
-            getattr(cell, 'hip_modes', DEFAULT_MODES).apply(t)          # (the model's launch modes may have changed)
-            mark_se_style(t, blocks_se_style(blocks))                   # (apply rewrites flags; the cell's squeeze-excite style)
-            return t
-        d = TfnasCellDesc()
-        d.N, d.H, d.W, d.ic, d.oc, d.stride = N, H, W, cell.in_channels, cell.out_channels, cell.stride
-        d.mode = _lib.MODE_CELL
-        d.act, d.G, d.need_wgrad, d.eps = _lib.act_id(cell.act_func), len(blocks), 0, BN_EPS
-        d.has_res = int(cell.in_channels == cell.out_channels and cell.stride == 1)
-        for g, b in enumerate(blocks):
-            d.g[g].mc, d.g[g].k, d.g[g].se = b.mid_channels, _lib.block_k_word(b), b.se_channels     # (a MixConv block: packed, and
-                                                                                                     #  tfnas_path_plan refuses it)
-            d.g[g].dil = b.dilation if getattr(b, 'dilation', 1) != 1 else 0     # (HipModes.apply sets the bit for a dilated group)
-            ps = b.hip_params()
-            for p in ps:
-                _require_cuda(p, 'MBConv weight')
-                if not p.is_contiguous():
-                    raise RuntimeError('tfnas_amd: MBConv weights must be contiguous')
-            for j, f in enumerate(_lib._W_FIELDS[:len(ps)]):
-                setattr(d.g[g], f, ps[j].data_ptr())
-            if self.weights is not None and all(self.weights.owns(p) for p in ps):
-                for j, f in enumerate(_lib._G_FIELDS[:len(ps)]):
-                    setattr(d.g[g], f, self.weights.grad_ptr(ps[j]))
-        getattr(cell, 'hip_modes', DEFAULT_MODES).apply(d)
-        mark_se_style(d, blocks_se_style(blocks))
+        if idx is not None and cell.m_ops[idx].kind is None:
+            if t is None:                                   # (a skip binds nothing: always fresh)
+                t = self._tmpl[key] = fill_pass_desc(TfnasCellDesc(), cell.in_channels, N, H, W)
+            return t, True
+        plan = cell._plan(tuple(range(len(cell.m_ops))) if idx is None else (idx,))
+        ps = plan.params()
+        first = ps[0].data_ptr()                            # (the first of hip_params(): skips stand last, a plan never starts with one)
+        meta = self._tmeta.get(key)
+        if t is not None and meta is not None and meta[0] == first and meta[2] is plan:
+            plan.refresh(t)                                 # (the model's launch modes may have changed)
+            return t, meta[1]
+        for p in ps:
+            _require_cuda(p, 'MBConv weight')
+            if not p.is_contiguous():
+                raise RuntimeError('tfnas_amd: MBConv weights must be contiguous')
+        d = fill_cell_desc(TfnasCellDesc(), plan, N, H, W)
+        owned = self.weights is not None and all(self.weights.owns(p) for p in ps)
+        plan.bind(d, ps, [self.weights.grad_view(p) for p in ps] if owned else None)
+        d.need_wgrad = 0
         check(self.lib.tfnas_cell_plan(C.byref(d)), 'tfnas_cell_plan')
-        self._tmpl[key] = d
-        return d
+        self._tmpl[key], self._tmeta[key] = d, (first, owned, plan)
+        return d, owned
+
+    def _cell_need(self, ci, idx, N, H, W):
+        """Floats of workspace the library plans for candidate ``idx`` of cell ``ci`` (tfnas_cell_ws: saved + scratch tensors); a
+        sampled skip owns none."""
+        d = self._template(ci, idx, N, H, W)
+        if self.cells[ci].m_ops[idx].kind is None:
+            return 0
+        ws = _lib.TfnasCellWs()
+        check(self.lib.tfnas_cell_ws(C.byref(d), C.byref(ws)), 'tfnas_cell_ws')
+        return int(ws.E + ws.D + ws.Pr + ws.fsmall + 2 * ws.stats + ws.out + ws.dZ + ws.dEh + ws.bsmall + 2 * ws.red + ws.dx + ws.dxp)
+
+    def _widest(self, N, H, W):
+        """Per cell the candidate whose planned workspace is the largest, asked of the library once per input shape (a Fused-MBConv
+        candidate is not sized by its mid width, an expand-free one has no E, a skip nothing at all)."""
+        key = (N, H, W)
+        hit = self._wide.get(key)
+        if hit is None:
+            hit, h, w = [], H, W
+            for ci, cell in enumerate(self.cells):
+                hit.append(max(range(len(cell.m_ops)), key=lambda i: self._cell_need(ci, i, N, h, w)))
+                h, w = (h - 1) // cell.stride + 1, (w - 1) // cell.stride + 1
+            self._wide[key] = hit
+        return hit
 
     def _slot(self, name):
         s = self._slots.get(name)
@@ -206,11 +234,12 @@ class PathRunner:
         soft = idxs is None
         pd = s.pd
         pd.ncell, pd.nstage, pd.soft, pd.need_dx0 = len(self.cells), len(self.stages), int(soft), int(need_dx0)
+        pd.path_flags = self.path_flags
         mask = 0
         h, w = H, W
         for i, cell in enumerate(self.cells):
-            t = self._template(i, None if soft else idxs[i], N, h, w)
-            if need_wgrad and not t.g[0].g_expand:
+            t, owned = self._template_entry(i, None if soft else idxs[i], N, h, w)
+            if need_wgrad and not owned:
                 raise RuntimeError('tfnas_amd: weight gradients at the path level need a WeightArena that owns the weights')
             pd.cell[i] = t
             pd.cell[i].need_wgrad = int(need_wgrad)
@@ -235,9 +264,7 @@ class PathRunner:
             if not soft:
                 # size the arena for the widest candidate of every cell once, instead of growing it (device sync + GBs of
                 # hipMalloc) whenever a step samples a wider sub-network than any before
-                def widest(c):
-                    return max(range(len(c.m_ops)), key=lambda i: (c.m_ops[i].mid_channels, c.m_ops[i].se_channels))
-                wide = [widest(c) for c in self.cells]
+                wide = self._widest(N, H, W)
                 if list(idxs) != wide:
                     need = max(need, self._sampled_need(name, wide, x0h, need_wgrad, need_dx0))
                     return self._plan_with_arena(name, idxs, x0h, need_wgrad, need_dx0, need_dbetas, need)
@@ -260,6 +287,7 @@ class PathRunner:
         N, H, W, _ = x0h.shape
         pd = s.pd
         pd.ncell, pd.nstage, pd.soft, pd.need_dx0, pd.efree_mask_lo = len(self.cells), len(self.stages), 0, int(need_dx0), 0
+        pd.path_flags = self.path_flags
         h, w = H, W
         for i, cell in enumerate(self.cells):
             pd.cell[i] = self._template(i, wide[i], N, h, w)
@@ -310,7 +338,11 @@ class PathRunner:
         return SoftPathFn.apply(self, x0, W.contiguous(), self.expand_lat(CL), *betas)
 
     def _wants_wgrad(self, idxs):
-        return torch.is_grad_enabled() and self.cells[0].m_ops[idxs[0]].point_linear.conv.weight.requires_grad
+        for c, i in zip(self.cells, idxs):
+            ps = c.m_ops[i].hip_params()                    # (a sampled skip has none: the first cell that computes decides)
+            if ps:
+                return torch.is_grad_enabled() and ps[-1].requires_grad
+        return False
 
     def sampled(self, x0, idxs, name='A', expose=None, main_stream=None):
         """One sampled path (train_wo_arch / validate / a single bi-sampling path).  ``expose``: a SearchState -- the backward

@@ -79,10 +79,12 @@ class SearchState:
         self._op_params = {}
         self._shared = None
         self._graded = []                  # parameters whose .grad was pointed into the arena by the last w-step
-        # (the path level, its weight arena and the fused optimizer tails are built for plain candidates: a network with an
-        #  expand-free or Fused-MBConv candidate -- model_search.Network(primitives=...) -- takes the per-cell route in every step)
+        # (the path level, its weight arena and the fused optimizer tails take plain candidates -- and, from a network built with
+        #  extended_paths=True, every other candidate: Network.path_capable.  Without the keyword a network with an expand-free, a
+        #  Fused-MBConv, ... candidate -- model_search.Network(primitives=...) -- takes the per-cell route in every step)
+        capable = getattr(model, 'path_capable', None) or getattr(model, 'plain_candidates', lambda: True)
         if USE_PATHS and hasattr(model, 'cells') and self.weights and self.weights[0].is_cuda \
-                and hasattr(model, 'arch_weights') and getattr(model, 'plain_candidates', lambda: True)():
+                and hasattr(model, 'arch_weights') and capable():
             self.build_paths()
 
     def build_paths(self):
