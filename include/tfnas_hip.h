@@ -814,6 +814,24 @@ int tfnas_sgd_clip_step(float *w, float *g, float *m, int nranges, const uint64_
                         float max_norm, float lr, float momentum, float wd, float grad_scale, double *scratch,
                         uint64_t scratch_doubles, float *norm_out, void *stream);
 
+/* The same step with an exponential moving average of the weights kept in the pass that stores them (the retrain path: the
+ * MobileNetV3 / MixNet / EfficientNet / FBNet recipes report the EMA's accuracy).  ema: a fourth arena with the layout of w;
+ * ema_alpha = 1 - decay, the step weight itself (so that 1 - 0.9999 is never formed in fp32).  Launches, norm, clip and SGD update
+ * are those of tfnas_sgd_clip_step, bit for bit; where w' is stored, ema <- fma(ema_alpha, w' - ema, ema) is stored too.  Two
+ * launches, no atomics, deterministic.  Refused before anything is launched: ema NULL (TFNAS_ENULL); ema_alpha outside [0, 1] or
+ * not finite (TFNAS_EINVAL); ema == w, g or m (TFNAS_EINVAL); and everything tfnas_sgd_clip_step refuses. */
+int tfnas_sgd_clip_ema_step(float *w, float *g, float *m, int nranges, const uint64_t *off, const uint64_t *goff,
+                            const uint64_t *len, float max_norm, float lr, float momentum, float wd, float grad_scale, float *ema,
+                            float ema_alpha, double *scratch, uint64_t scratch_doubles, float *norm_out, void *stream);
+
+/* ema[off[i] .. +len[i]) <- fma(ema_alpha, src[same] - ema[same], ema[same]) for nranges <= 64 disjoint ranges (multiples of 4) of
+ * two buffers with one layout, in one launch: the EMA formula above on its own -- for the BatchNorm running statistics, which no
+ * optimizer pass touches, and for the weights after a step that torch's optimizer made.  src is only read.  Refused before the
+ * launch: a NULL pointer (TFNAS_ENULL); ema_alpha outside [0, 1] or not finite, ema == src, overlapping or misaligned ranges
+ * (TFNAS_EINVAL); nranges outside [1, 64] (TFNAS_ERANGE). */
+int tfnas_ema_lerp(float *ema, const float *src, int nranges, const uint64_t *off, const uint64_t *len, float ema_alpha,
+                   void *stream);
+
 /* dst[doff[i] .. +len[i]) = src[off[i] .. +len[i]) for nranges <= 64 ranges (one launch): gathers the sampled candidates'
  * gradient ranges into ONE contiguous buffer = one RCCL all-reduce message (no torch.cat, no copy back: the SGD step reads
  * the reduced message through `goff`).  The ranges must be disjoint, in src and in dst: overlapping (off[i], len[i]) or

@@ -1076,6 +1076,21 @@ extern "C" int tfnas_sgd_clip_step(float* w, float* g, float* m, int nranges, co
                                 norm_out, S(stream));
 }
 
+extern "C" int tfnas_sgd_clip_ema_step(float* w, float* g, float* m, int nranges, const uint64_t* off, const uint64_t* goff,
+                                       const uint64_t* len, float max_norm, float lr, float momentum, float wd, float grad_scale,
+                                       float* ema, float ema_alpha, double* scratch, uint64_t scratch_doubles, float* norm_out,
+                                       void* stream) {
+    if (!w || !g || !m || !off || !len || !scratch || !ema) return TFNAS_ENULL;
+    return launch_sgd_clip_ema_step(w, g, m, nranges, off, goff, len, max_norm, lr, momentum, wd, grad_scale, ema, ema_alpha,
+                                    scratch, scratch_doubles, norm_out, S(stream));
+}
+
+extern "C" int tfnas_ema_lerp(float* ema, const float* src, int nranges, const uint64_t* off, const uint64_t* len,
+                              float ema_alpha, void* stream) {
+    if (!ema || !src || !off || !len) return TFNAS_ENULL;
+    return launch_ema_lerp(ema, src, nranges, off, len, ema_alpha, S(stream));
+}
+
 extern "C" int tfnas_arch_adam_project(int n, float* const* p, const float* const* g, const int32_t* len, float* m, float* v,
                                        float max_norm, float lr, float beta1, float beta2, float eps, float wd, int step,
                                        float grad_scale, float* norm_out, void* stream) {

@@ -89,6 +89,58 @@ __global__ __launch_bounds__(256) void k_opt_sgd(float* __restrict__ w, float* _
     }
 }
 
+__device__ __forceinline__ f32x4 ema_lerp4(f32x4 e, f32x4 v, float alpha) {
+    f32x4 r;
+    r.x = __builtin_fmaf(alpha, v.x - e.x, e.x);
+    r.y = __builtin_fmaf(alpha, v.y - e.y, e.y);
+    r.z = __builtin_fmaf(alpha, v.z - e.z, e.z);
+    r.w = __builtin_fmaf(alpha, v.w - e.w, e.w);
+    return r;
+}
+
+// k_opt_sgd with an exponential moving average of the weights (tfnas_sgd_clip_ema_step): where w' is stored -- it sits in a
+// register there -- e' = fma(alpha, w' - e, e) is stored too: one more read and one more write of an arena-sized buffer, no
+// launch.  A sibling and not a template parameter of k_opt_sgd: as the <false> instantiation of a shared body that kernel came
+// out with its address set-up scheduled differently, and its device code is to stay what it was.  The test that
+// holds w' / g' / m' / norm of the two kernels to the same bits (tests/test_gpu_ema_kernels.py) keeps the copies together.
+__global__ __launch_bounds__(256) void k_opt_sgd_ema(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m,
+                                                     OptRanges R, const double* __restrict__ partial, float max_norm, float lr,
+                                                     float momentum, float wd, float grad_scale, float* __restrict__ norm_out,
+                                                     float* __restrict__ ema, float ema_alpha) {
+    __shared__ double sh[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < R.nblocks; i += 256) acc += partial[i];
+    acc = block_sum_d(acc, sh);
+    const float total = (float)sqrt(acc) * grad_scale;
+    float coef = max_norm > 0.f ? max_norm / (total + 1e-6f) : 1.f;
+    coef = coef > 1.f ? 1.f : coef;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) *norm_out = total;
+    const float gs = grad_scale * coef;
+    uint64_t beg, end, gbeg;
+    if (!opt_locate(R, blockIdx.x, beg, end, gbeg)) return;
+    for (uint64_t k = 4 * (uint64_t)threadIdx.x; k < end - beg; k += 1024) {
+        const uint64_t i = beg + k;
+        f32x4 gv = ld4(g + gbeg + k), wv = ld4(w + i), mv = ld4(m + i);
+        gv = gv * splat4(gs);
+        st4(g + gbeg + k, gv);
+        const f32x4 d = gv + splat4(wd) * wv;
+        mv = splat4(momentum) * mv + d;
+        wv = wv - splat4(lr) * mv;
+        st4(m + i, mv);
+        st4(w + i, wv);
+        st4(ema + i, ema_lerp4(ld4(ema + i), wv, ema_alpha));
+    }
+}
+
+// ema[ranges] = fma(alpha, src - ema, ema): the same formula on its own (BatchNorm running statistics, which no optimizer pass
+// touches; the parameters of a step that torch's optimizer made)
+__global__ __launch_bounds__(256) void k_ema_lerp(float* __restrict__ ema, const float* __restrict__ src, OptRanges R, float alpha) {
+    uint64_t beg, end, gbeg;
+    if (!opt_locate(R, blockIdx.x, beg, end, gbeg)) return;
+    for (uint64_t k = 4 * (uint64_t)threadIdx.x; k < end - beg; k += 1024)
+        st4(ema + beg + k, ema_lerp4(ld4(ema + beg + k), ld4(src + beg + k), alpha));
+}
+
 // dst[packed] = src[ranges]: the sampled candidates' gradient ranges as ONE contiguous message for the all-reduce
 __global__ __launch_bounds__(256) void k_opt_pack(const float* __restrict__ src, float* __restrict__ dst, OptRanges R) {
     uint64_t beg, end, gbeg;
@@ -143,6 +195,39 @@ int launch_sgd_clip_step(float* w, float* g, float* m, int nranges, const uint64
     hipLaunchKernelGGL(k_opt_sqnorm, dim3(nb), dim3(256), 0, s, g, R, scratch);
     hipLaunchKernelGGL(k_opt_sgd, dim3(nb), dim3(256), 0, s, w, g, m, R, scratch, max_norm, lr, momentum, wd, grad_scale,
                        norm_out);
+    return (int)hipGetLastError();
+}
+
+// the step weight of an EMA: 1 - decay as the caller formed it, in [0, 1] (a NaN fails both comparisons)
+static bool ema_alpha_ok(float a) { return a >= 0.f && a <= 1.f; }
+
+int launch_sgd_clip_ema_step(float* w, float* g, float* m, int nranges, const uint64_t* off, const uint64_t* goff,
+                             const uint64_t* len, float max_norm, float lr, float momentum, float wd, float grad_scale,
+                             float* ema, float ema_alpha, double* scratch, uint64_t scratch_doubles, float* norm_out,
+                             hipStream_t s) {
+    if (!ema_alpha_ok(ema_alpha)) return TFNAS_EINVAL;
+    if (ema == w || ema == g || ema == m) return TFNAS_EINVAL;
+    OptRanges R;
+    int rc = fill_ranges(R, nranges, off, goff, len);
+    if (rc) return rc;
+    const int nb = R.nblocks;
+    if ((uint64_t)nb > scratch_doubles) return TFNAS_ERANGE;
+    ProfScope _prof(TK_SMALL, s);
+    hipLaunchKernelGGL(k_opt_sqnorm, dim3(nb), dim3(256), 0, s, g, R, scratch);
+    hipLaunchKernelGGL(k_opt_sgd_ema, dim3(nb), dim3(256), 0, s, w, g, m, R, scratch, max_norm, lr, momentum, wd, grad_scale,
+                       norm_out, ema, ema_alpha);
+    return (int)hipGetLastError();
+}
+
+int launch_ema_lerp(float* ema, const float* src, int nranges, const uint64_t* off, const uint64_t* len, float ema_alpha,
+                    hipStream_t s) {
+    if (!ema_alpha_ok(ema_alpha)) return TFNAS_EINVAL;
+    if (ema == src) return TFNAS_EINVAL;
+    OptRanges R;
+    int rc = fill_ranges(R, nranges, off, nullptr, len);
+    if (rc) return rc;
+    ProfScope _prof(TK_SMALL, s);
+    hipLaunchKernelGGL(k_ema_lerp, dim3(R.nblocks), dim3(256), 0, s, ema, src, R, ema_alpha);
     return (int)hipGetLastError();
 }
 

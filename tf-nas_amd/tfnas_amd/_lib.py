@@ -265,6 +265,10 @@ _PROTOS = {
     'tfnas_sgd_clip_step': (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint64), C.c_float, C.c_float,
                                       C.c_float, C.c_float, C.c_float, _P, C.c_uint64, _P, _P]),
+    'tfnas_sgd_clip_ema_step': (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                          _P, C.c_float, _P, C.c_uint64, _P, _P]),
+    'tfnas_ema_lerp': (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_float, _P]),
     'tfnas_arch_adam_project': (C.c_int, [C.c_int, _PP, _PP, C.POINTER(C.c_int32), _P, _P, C.c_float, C.c_float, C.c_float,
                                           C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P]),
     'tfnas_arch_fwd': (C.c_int, [C.c_int, C.POINTER(_P), _P, _P, C.c_float, _P, _P, _P]),

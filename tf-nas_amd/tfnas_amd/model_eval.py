@@ -400,7 +400,12 @@ class RetrainState:
             functions.retrain_join(self.arena.device)
         functions.retrain_context(False, False, owner)
 
-    def step(self, opt, grad_clip, group=None):
+    def step(self, opt, grad_clip, group=None, ema=None):
+        """Join, all-reduce (with a group), then clip + SGD over the whole arena in two launches.  ``ema`` (a WeightEma): the SGD
+        pass keeps the parameters' average as it stores them (``tfnas_sgd_clip_ema_step``, same two launches), ONE further launch
+        averages the floating-point buffers, and the EMA's count goes up by one.  The average is taken after the all-reduce, so the
+        parameter shadows are identical on all ranks; the buffer shadows are per rank, as the running statistics themselves are
+        without sync-stats."""
         import ctypes as C
         import torch.distributed as dist
         a = self.arena
@@ -418,22 +423,234 @@ class RetrainState:
             self._gnorm = torch.zeros(2, device=dev, dtype=torch.float32)
         off, ln = (C.c_uint64 * 1)(0), (C.c_uint64 * 1)(a.total)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().tfnas_sgd_clip_step(_lib.ptr(a.w), _lib.ptr(a.g), _lib.ptr(a.m), 1, off, None, ln, float(grad_clip),
-                                                  float(hp['lr']), float(hp['momentum']), float(hp['weight_decay']), float(scale),
-                                                  _lib.ptr(self._scratch), self._scratch.numel(), _lib.ptr(self._gnorm), stream),
-                   'tfnas_sgd_clip_step')
+        if ema is None:
+            _lib.check(_lib.lib().tfnas_sgd_clip_step(_lib.ptr(a.w), _lib.ptr(a.g), _lib.ptr(a.m), 1, off, None, ln, float(grad_clip),
+                                                      float(hp['lr']), float(hp['momentum']), float(hp['weight_decay']), float(scale),
+                                                      _lib.ptr(self._scratch), self._scratch.numel(), _lib.ptr(self._gnorm), stream),
+                       'tfnas_sgd_clip_step')
+        else:
+            _, bufs = ema._sync(self.model)
+            if ema._arena is not a:
+                raise RuntimeError('RetrainState.step: the EMA could not lay its parameter shadow out on this arena')
+            alpha = ema.alpha()
+            _lib.check(_lib.lib().tfnas_sgd_clip_ema_step(_lib.ptr(a.w), _lib.ptr(a.g), _lib.ptr(a.m), 1, off, None, ln,
+                                                          float(grad_clip), float(hp['lr']), float(hp['momentum']),
+                                                          float(hp['weight_decay']), float(scale), _lib.ptr(ema._pflat), alpha,
+                                                          _lib.ptr(self._scratch), self._scratch.numel(), _lib.ptr(self._gnorm),
+                                                          stream), 'tfnas_sgd_clip_ema_step')
+            ema._update_buffers(bufs, alpha)
+            ema.updates += 1
         # what optimizer.step() would have recorded: learning-rate schedulers check these before their own step()
         if hasattr(opt, '_step_count'):
             opt._step_count += 1
         opt._opt_called = True
 
 
-def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None, fused=True, meter=None):
+class WeightEma:
+    """Exponential moving average of a derived network's weights -- what the MobileNetV3 / MixNet / EfficientNet / FBNet recipes
+    evaluate and publish.  Shadows every parameter and every floating-point buffer of ``model`` (the shadow starts as a copy);
+    integer buffers (``num_batches_tracked``) are copied at each update, not averaged.  One update is
+    ``shadow <- fma(alpha_t, live - shadow, shadow)`` with ``alpha_t = 1 - min(decay, (1 + t) / (10 + t))`` (``warmup``; else
+    ``1 - decay``), t = the updates done so far, formed in Python floats and handed to the kernels as the step weight itself.
+
+    Parameters: where the model has an intact ``RetrainState`` the shadow is ONE flat tensor with the arena's layout (gaps zero, and
+    they stay zero), and ``RetrainState.step(..., ema=self)`` keeps it inside the SGD pass (``tfnas_sgd_clip_ema_step``: no launch).
+    When the arena is rebuilt (``model.to()``, ``p.data = ...``) the shadow re-lays itself by parameter name and keeps its values.
+    Float buffers: on a CUDA model they are moved into one flat tensor (path.BufferArena) when the EMA is attached, so that their
+    average is ONE ``tfnas_ema_lerp`` launch per step.  Without an arena (CPU; an optimizer that is not ``RetrainState.fusable``
+    before any fused step) the shadows are per tensor and the update is ``torch._foreach_lerp_``.
+
+    Known property of any fp32 EMA (timm's ModelEmaV2 alike): at alpha = 1e-4 an element stops moving once
+    |w - ema| < 2^-24 |ema| / alpha, about 6e-4 |ema|."""
+
+    COUNT_KEY = '.ema_updates'     # in state_dict()._metadata: no module path has an empty first component
+
+    def __init__(self, model, decay=0.9999, warmup=True):
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError('WeightEma: decay must lie in [0, 1], got %r' % (decay,))
+        self.decay, self.warmup, self.updates = decay, bool(warmup), 0
+        self._arena = self._barena = None          # the WeightArena / BufferArena the flat shadows are laid out for
+        self._pflat = self._bflat = None
+        self._shadow = {}                          # name -> shadow tensor (a view of a flat one where there is an arena)
+        self._sync(model)
+
+    def alpha(self, t=None):
+        """Step weight of update number ``t`` (default: the next one), a Python float."""
+        t = self.updates if t is None else t
+        return 1.0 - (min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay)
+
+    # ---------------------------------------------------------------------------------------------------------- layout
+    def _sync(self, model):
+        """Bring the shadows' layout in line with the model's: new names start as copies, known names keep their values."""
+        from .path import BufferArena
+        with torch.no_grad():
+            st = getattr(model, '_retrain_state', None)
+            arena = st.arena if st is not None and st.intact() else None
+            params = dict(model.named_parameters())
+            if arena is not None and set(arena.names) != set(params):
+                arena = None
+            relaid = False
+            if arena is not self._arena or any(k not in self._shadow for k in params):
+                relaid = True
+                flat = None if arena is None else torch.zeros(arena.total, device=arena.device, dtype=torch.float32)
+                for k, p in params.items():
+                    if flat is not None:
+                        o, n = arena.slot[id(p)]
+                        new = flat[o:o + n].view(p.shape)
+                    else:
+                        new = torch.empty_like(p.data, memory_format=torch.contiguous_format)
+                    new.copy_(self._shadow[k] if k in self._shadow else p.data)
+                    self._shadow[k] = new
+                self._arena, self._pflat = arena, flat
+            bufs = dict(model.named_buffers())
+            fb = {k: b for k, b in bufs.items() if b.is_floating_point()}
+            ba = None
+            if fb and all(b.is_cuda and b.dtype == torch.float32 for b in fb.values()) and len({b.device for b in fb.values()}) == 1:
+                ba = getattr(model, '_buffer_arena', None)
+                if ba is None or not ba.intact(model):
+                    ba = BufferArena(model)
+                    object.__setattr__(model, '_buffer_arena', ba)      # (like _retrain_state: stays out of state_dict)
+            if ba is not self._barena or any(k not in self._shadow for k in bufs):
+                relaid = True
+                flat = None if ba is None else torch.zeros(ba.total, device=ba.device, dtype=torch.float32)
+                for k, b in bufs.items():
+                    if flat is not None and k in fb:
+                        o, n = ba.slot[k]
+                        new = flat[o:o + n].view(b.shape)
+                    else:
+                        new = torch.empty_like(b.data, memory_format=torch.contiguous_format)
+                    new.copy_(self._shadow[k] if k in self._shadow else b.data)
+                    self._shadow[k] = new
+                self._barena, self._bflat = ba, flat
+            if relaid:
+                for k in [k for k in self._shadow if k not in params and k not in bufs]:
+                    del self._shadow[k]
+                sd = model.state_dict()
+                self._keys = list(sd.keys())
+                self._metadata = dict(getattr(sd, '_metadata', None) or {})
+        return params, bufs
+
+    def _pairs(self, model):
+        """([live], [shadow]) over everything shadowed -- the flat tensors where both sides have one."""
+        params, bufs = self._sync(model)
+        live, shadow = [], []
+        if self._pflat is not None:
+            live.append(self._arena.w)
+            shadow.append(self._pflat)
+        else:
+            live += [p.data for p in params.values()]
+            shadow += [self._shadow[k] for k in params]
+        for k, b in bufs.items():
+            if self._bflat is None or not b.is_floating_point():
+                live.append(b.data)
+                shadow.append(self._shadow[k])
+        if self._bflat is not None:
+            live.append(self._barena.b)
+            shadow.append(self._bflat)
+        return live, shadow
+
+    # --------------------------------------------------------------------------------------------------------- updates
+    @staticmethod
+    def _lerp_launch(shadow, live, alpha):
+        """shadow <- fma(alpha, live - shadow, shadow) over two whole flat CUDA tensors: one launch."""
+        import ctypes as C
+        dev = shadow.device
+        off, ln = (C.c_uint64 * 1)(0), (C.c_uint64 * 1)(shadow.numel())
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(_lib.lib().tfnas_ema_lerp(_lib.ptr(shadow), _lib.ptr(live), 1, off, ln, float(alpha), stream), 'tfnas_ema_lerp')
+
+    def _update_buffers(self, bufs, alpha):
+        """The buffers' share of one update: ONE launch for the floating-point ones where they are flat, a copy of the integers."""
+        with torch.no_grad():
+            fl = [k for k, b in bufs.items() if b.is_floating_point()]
+            if self._bflat is not None:
+                if self._bflat.numel():
+                    self._lerp_launch(self._bflat, self._barena.b, alpha)
+            elif fl:
+                torch._foreach_lerp_([self._shadow[k] for k in fl], [bufs[k].data for k in fl], alpha)
+            ints = [k for k, b in bufs.items() if not b.is_floating_point()]
+            if ints:
+                torch._foreach_copy_([self._shadow[k] for k in ints], [bufs[k].data for k in ints])
+
+    def update(self, model):
+        """The stand-alone update, after any optimizer's step: ``tfnas_ema_lerp`` over the weight arena and over the buffer tensor
+        on a CUDA model that has them, ``torch._foreach_lerp_`` otherwise."""
+        params, bufs = self._sync(model)
+        alpha = self.alpha()
+        with torch.no_grad():
+            if self._pflat is not None:
+                self._lerp_launch(self._pflat, self._arena.w, alpha)
+            else:
+                torch._foreach_lerp_([self._shadow[k] for k in params], [p.data for p in params.values()], alpha)
+        self._update_buffers(bufs, alpha)
+        self.updates += 1
+
+    # ----------------------------------------------------------------------------------------------------------- state
+    def state_dict(self):
+        """The averaged network, keyed exactly like ``model.state_dict()`` (clones: it loads straight into a fresh ``NetworkCfg``
+        and is what one deploys).  The update count travels in the dict's ``_metadata`` under ``COUNT_KEY``, where torch keeps the
+        modules' versions: no tensor key is added, so ``load_state_dict(strict=True)`` of a model accepts it."""
+        from collections import OrderedDict
+        out = OrderedDict((k, self._shadow[k].detach().clone()) for k in self._keys)
+        out._metadata = OrderedDict(self._metadata)
+        out._metadata[self.COUNT_KEY] = {'updates': int(self.updates)}
+        return out
+
+    def load_state_dict(self, state, updates=None):
+        """Values from a dict keyed like ``state_dict()`` (every key must be there); the update count from its ``_metadata``, or from
+        ``updates`` (a checkpoint that stores it beside the dict)."""
+        missing = [k for k in self._keys if k not in state]
+        if missing:
+            raise KeyError('WeightEma.load_state_dict: missing %s' % missing[:5])
+        with torch.no_grad():
+            for k in self._keys:
+                self._shadow[k].copy_(state[k])
+        meta = (getattr(state, '_metadata', None) or {}).get(self.COUNT_KEY)
+        if updates is not None:
+            self.updates = int(updates)
+        elif meta is not None:
+            self.updates = int(meta['updates'])
+
+    def copy_to(self, model):
+        """Overwrite the model's parameters and buffers with the averaged ones."""
+        live, shadow = self._pairs(model)
+        with torch.no_grad():
+            for l, s in zip(live, shadow):
+                l.copy_(s)
+
+    def swapped(self, model):
+        """Context manager: inside, the model holds the averaged values and the shadow holds the live ones (exchanged in place,
+        plain torch copies -- the arenas' pointers stay what they are); they are exchanged back on exit, on an exception too."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            live, shadow = self._pairs(model)
+
+            def exchange():
+                with torch.no_grad():
+                    for l, s in zip(live, shadow):
+                        t = l.clone()
+                        l.copy_(s)
+                        s.copy_(t)
+            exchange()
+            try:
+                yield model
+            finally:
+                exchange()
+        return ctx()
+
+
+def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None, fused=True, meter=None, ema=None):
     """One iteration of train_eval.py:228-252 (forward, label-smoothed loss, backward, clip, SGD); with a process group the
     gradients are averaged with ONE all-reduce of the flat gradient arena before clipping (one process per GPU instead of apex
     DDP).  ``fused`` (GPU models with a plain torch.optim.SGD): RetrainState -- gradient arena + tfnas_sgd_clip_step; otherwise
     torch's clip_grad_norm_ + optimizer.step().  Classifier + loss run on the fused retrain tail when ``FUSED_TAIL`` and
-    ``fused_tail_eligible``; ``meter`` (a tail.DeviceMeter) collects loss / top-1 / top-5 of the step on the device."""
+    ``fused_tail_eligible``; ``meter`` (a tail.DeviceMeter) collects loss / top-1 / top-5 of the step on the device.  ``ema`` (a
+    WeightEma of this model): updated once per step -- inside the fused SGD pass, or with ``ema.update(model)`` after
+    ``optimizer.step()`` on the torch route."""
     import torch.distributed as dist
     model.train()
     tail_plan = _fused_tail_plan(model, criterion) if FUSED_TAIL and x.is_cuda else None
@@ -463,7 +680,7 @@ def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None
             st.end()
         raise
     if st is not None:
-        st.step(optimizer, grad_clip, group)
+        st.step(optimizer, grad_clip, group, ema)
         return loss.detach(), logits.detach()
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
         grads = [p.grad for p in model.parameters() if p.grad is not None]
@@ -474,11 +691,21 @@ def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None
     if grad_clip > 0:
         nn.utils.clip_grad_norm_(model.parameters(), grad_clip)
     optimizer.step()
+    if ema is not None:
+        ema.update(model)
     return loss.detach(), logits.detach()
 
 
-def validate(model, val_queue, criterion=None):
-    """train_eval.py:271-293: eval mode (running statistics), top-1 / top-5 / loss."""
+def validate(model, val_queue, criterion=None, ema=None):
+    """train_eval.py:271-293: eval mode (running statistics), top-1 / top-5 / loss.  ``ema`` (a WeightEma of this model): the
+    averaged weights and statistics are evaluated -- exchanged into the model for the loop (``ema.swapped``) and out again."""
+    if ema is not None:
+        with ema.swapped(model):
+            return _validate(model, val_queue, criterion)
+    return _validate(model, val_queue, criterion)
+
+
+def _validate(model, val_queue, criterion):
     from .tail import DeviceMeter, retrain_tail_forward
     model.eval()
     dev = next(model.parameters()).device
@@ -518,11 +745,18 @@ def build_derived_network(num_classes, model_path=None, config_path=None, dropou
 
 
 def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250, lr=0.2, momentum=0.9, weight_decay=4e-5,
-                label_smooth=0.1, grad_clip=5.0, batch_size=256, snapshot=None, device='cuda', group=None, log=print):
+                label_smooth=0.1, grad_clip=5.0, batch_size=256, snapshot=None, device='cuda', group=None, log=print,
+                ema_decay=None, ema_warmup=True):
     """The retrain schedule of train_eval.py:118-226: SGD + cosine learning rate (5 warm-up epochs of linearly increasing rate
     when batch_size > 256), label-smoothed training loss, plain cross-entropy validation every epoch, ``checkpoint.pth.tar`` /
     ``model_best.pth.tar`` with the reference's keys ('epoch', 'state_dict' with DataParallel's ``module.`` prefix,
-    'best_acc_top1', 'best_acc_top5', 'optimizer'), resume from ``snapshot``, ``model.config`` written next to them."""
+    'best_acc_top1', 'best_acc_top5', 'optimizer'), resume from ``snapshot``, ``model.config`` written next to them.
+
+    ``ema_decay`` (None: nothing below happens, the checkpoints keep exactly those five keys): a ``WeightEma(model, ema_decay,
+    ema_warmup)`` is updated at every step; each epoch validates the raw weights and the average (history rows gain
+    ``val_top1_ema`` / ``val_top5_ema`` / ``val_obj_ema``, the log line shows both); ``best_acc_top1`` / ``top5`` and
+    ``model_best.pth.tar`` follow the AVERAGE's top-1; checkpoints gain 'state_dict_ema' (``module.`` prefix, like 'state_dict')
+    and 'ema_updates', which ``snapshot`` restores -- a snapshot without them starts the average from the loaded weights."""
     import json
     import math
     import os
@@ -543,6 +777,12 @@ def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250
         start, best1, best5 = ck['epoch'], ck['best_acc_top1'], ck['best_acc_top5']
         model.load_state_dict({k[len('module.'):] if k.startswith('module.') else k: v for k, v in ck['state_dict'].items()})
         opt.load_state_dict(ck['optimizer'])
+    ema = None
+    if ema_decay is not None:
+        ema = WeightEma(model, ema_decay, ema_warmup)                   # (after the snapshot's weights are in: starts as their copy)
+        if snapshot and 'state_dict_ema' in ck:
+            ema.load_state_dict({k[len('module.'):] if k.startswith('module.') else k: v for k, v in ck['state_dict_ema'].items()},
+                                updates=ck.get('ema_updates', 0))
     history = []
     meter = DeviceMeter(dev)
     for epoch in range(start, epochs):
@@ -553,21 +793,32 @@ def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250
         meter.reset()
         for x, y in make_train_queue(epoch):
             x, y = x.to(dev, non_blocking=True), y.to(dev, non_blocking=True)
-            train_step(model, x, y, crit_smooth, opt, grad_clip, group, meter=meter)
+            train_step(model, x, y, crit_smooth, opt, grad_clip, group, meter=meter, ema=ema)
         train_obj, train_acc, _, _, bad = meter.read()      # the epoch's only device -> host copy of the training loop
         if bad:
             raise ValueError('run_retrain: epoch %d saw %d training target(s) outside [0, %d)' % (epoch, bad, num_classes))
         v1, v5, vobj = validate(model, make_val_queue(epoch))
-        is_best = v1 > best1
+        if ema is not None:
+            e1, e5, eobj = validate(model, make_val_queue(epoch), ema=ema)
+        sel1, sel5 = (v1, v5) if ema is None else (e1, e5)
+        is_best = sel1 > best1
         if is_best:
-            best1, best5 = v1, v5
+            best1, best5 = sel1, sel5
         state = {'epoch': epoch + 1, 'state_dict': {'module.' + k: v for k, v in model.state_dict().items()},
                  'best_acc_top1': best1, 'best_acc_top5': best5, 'optimizer': opt.state_dict()}
+        if ema is not None:
+            state['state_dict_ema'] = {'module.' + k: v for k, v in ema.state_dict().items()}
+            state['ema_updates'] = ema.updates
         path = os.path.join(save_dir, 'checkpoint.pth.tar')
         torch.save(state, path)
         if is_best:
             shutil.copyfile(path, os.path.join(save_dir, 'model_best.pth.tar'))
         history.append(dict(epoch=epoch, lr=opt.param_groups[0]['lr'], train_acc=train_acc, train_obj=train_obj, val_top1=v1,
                             val_top5=v5, val_obj=vobj))
-        log('Epoch %d lr %e train_acc %f val_top1 %f val_top5 %f' % (epoch, opt.param_groups[0]['lr'], train_acc, v1, v5))
+        if ema is None:
+            log('Epoch %d lr %e train_acc %f val_top1 %f val_top5 %f' % (epoch, opt.param_groups[0]['lr'], train_acc, v1, v5))
+        else:
+            history[-1].update(val_top1_ema=e1, val_top5_ema=e5, val_obj_ema=eobj)
+            log('Epoch %d lr %e train_acc %f val_top1 %f val_top5 %f ema_top1 %f ema_top5 %f' % (
+                epoch, opt.param_groups[0]['lr'], train_acc, v1, v5, e1, e5))
     return history

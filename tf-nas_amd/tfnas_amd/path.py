@@ -96,6 +96,43 @@ class WeightArena:
         return lo, hi - lo
 
 
+class BufferArena:
+    """Flat storage of a model's floating-point buffers (the BatchNorm running statistics), as WeightArena is of its parameters:
+    ``buf.data`` of every fp32 buffer becomes a view into ``b`` (values preserved, ``state_dict`` / ``load_state_dict`` keep
+    working, the kernels that update the statistics are handed the views' pointers at every call).  Built only where something
+    wants all buffers in ONE launch -- model_eval.WeightEma.  Slots are keyed by NAME: ``model.to()`` replaces the buffer
+    objects themselves.  The aligning gaps are zero and stay zero."""
+
+    def __init__(self, model):
+        named = [(k, b) for k, b in model.named_buffers() if b.is_floating_point()]
+        self.slot = {}
+        off = 0
+        for k, b in named:
+            _require_cuda(b, 'buffer %s' % k)
+            self.slot[k] = (off, b.numel())
+            off += (b.numel() + ALIGN - 1) // ALIGN * ALIGN
+        self.total = off
+        self.device = named[0][1].device if named else None
+        self.b = torch.zeros(off, device=self.device, dtype=torch.float32)
+        with torch.no_grad():
+            for k, b in named:
+                o, n = self.slot[k]
+                v = self.b[o:o + n].view(b.shape)
+                v.copy_(b.data)
+                b.data = v
+        self._base = self.b.data_ptr()
+
+    def intact(self, model):
+        seen = 0
+        for k, b in model.named_buffers():
+            if b.is_floating_point():
+                s = self.slot.get(k)
+                if s is None or b.numel() != s[1] or b.data_ptr() != self._base + 4 * s[0]:
+                    return False
+                seen += 1
+        return seen == len(self.slot)
+
+
 class _Slot:
     """One concurrently running path: C context + descriptor + arena."""
 

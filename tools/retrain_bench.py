@@ -2,6 +2,10 @@
 """Throughput of the derived-network retrain step (BASELINE configs[4]: 224x224, batch 256 per GPU) on the HIP path
 (tfnas_amd/model_eval.py): forward + label-smoothed loss + backward + clip + SGD, synthetic data.
   python tools/retrain_bench.py [--batch 256] [--steps 20]           (one rank per GPU under torch.distributed.run for N > 1)
+  --ema off | fused | foreach: no weight EMA (default); model_eval.WeightEma kept inside the fused SGD pass; or the user-side
+  stand-in, ``torch._foreach_lerp_`` over ``state_dict()`` after every step (what timm's ModelEmaV2 does).  With --ema fused /
+  foreach, or --sync-steps, the line also carries the median of device-synchronised steps and the library's launch count of one step (tfnas_prof_collect; torch's
+  own multi-tensor launches of the foreach stand-in are not the library's and are not in it).
 The architecture is the all-candidate-1 (k3 e6) full-depth network scaled to the 18 ms target of SURVEY 8(c).6 -- the TF-NAS-A
 config itself is not in the reference repository."""
 import argparse
@@ -22,6 +26,9 @@ def main():
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--ema', choices=('off', 'fused', 'foreach'), default='off')
+    ap.add_argument('--ema-decay', type=float, default=0.9999)
+    ap.add_argument('--sync-steps', action='store_true', help='the median / launch-count figures of --ema, also with --ema off')
     args = ap.parse_args()
     from tfnas_amd import geometry as g, model_eval as me
     from tfnas_amd.elasticity import fit_mc_num_by_latency
@@ -44,23 +51,60 @@ def main():
     crit = me.CrossEntropyLabelSmooth(1000, 0.1)
     x = torch.randn(args.batch, 3, 224, 224, device=dev)
     y = torch.randint(0, 1000, (args.batch,), device=dev)
+    ema = me.WeightEma(model, args.ema_decay) if args.ema == 'fused' else None
+    shadow = live = None
+    if args.ema == 'foreach':
+        live = [v for v in model.state_dict().values() if v.is_floating_point()]
+        shadow = [v.detach().clone() for v in live]
+
+    def step():
+        me.train_step(model, x, y, crit, opt, 5.0, ema=ema)
+        if shadow is not None:
+            if live[0].data_ptr() != next(iter(model.state_dict().values())).data_ptr():      # (the first step built the arena)
+                live[:] = [v for v in model.state_dict().values() if v.is_floating_point()]
+            torch._foreach_lerp_(shadow, live, 1.0 - args.ema_decay)
+
     for _ in range(args.warmup):
-        me.train_step(model, x, y, crit, opt, 5.0)
+        step()
     torch.cuda.synchronize()
     if dist.is_initialized():
         dist.barrier(device_ids=[local])
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        me.train_step(model, x, y, crit, opt, 5.0)
+        step()
     torch.cuda.synchronize()
     if dist.is_initialized():
         dist.barrier(device_ids=[local])
     dt = time.perf_counter() - t0
+    extra = {}
+    if args.ema != 'off' or args.sync_steps:
+        import ctypes as C
+        from tfnas_amd import _lib
+        each = []
+        for _ in range(args.steps):                                  # device-synchronised steps: their median
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            each.append(time.perf_counter() - t1)
+        lib = _lib.lib()
+        nfam = lib.tfnas_prof_count()
+        lib.tfnas_prof_enable((1 << nfam) - 1)
+        step()
+        torch.cuda.synchronize()
+        total = 0
+        for i in range(nfam):
+            cnt, ms = C.c_uint64(0), C.c_double(0.0)
+            _lib.check(lib.tfnas_prof_collect(i, C.byref(cnt), C.byref(ms)), 'tfnas_prof_collect')
+            total += cnt.value
+        lib.tfnas_prof_enable(0)
+        extra = dict(ema=args.ema, median_sync_step_ms=round(sorted(each)[len(each) // 2] * 1e3, 3), library_launches_per_step=total,
+                     ema_tensors=len(shadow) if shadow is not None else None)
     if rank == 0:
         print(json.dumps(dict(metric='derived-network retrain images/sec', value=round(args.batch * world * args.steps / dt, 1),
                               ms_per_step=round(dt / args.steps * 1e3, 2), n_gpus=world, batch_per_gpu=args.batch, dtype='fp32',
                               arch='all-op-1 full depth, widths scaled to 18 ms (%.3f ms in the LUT)' % lat,
-                              params_MB=round(sum(p.numel() for p in model.parameters()) / 1e6, 3))))
+                              params_MB=round(sum(p.numel() for p in model.parameters()) / 1e6, 3), **extra)))
     if dist.is_initialized():
         dist.destroy_process_group()
 
