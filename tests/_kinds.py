@@ -278,37 +278,55 @@ class RawMixed(_rawcell.RawCell):
                 setattr(self.d.g[g], lb._W_FIELDS[k], t.data_ptr())
         self.bufs = OrderedDict()
 
+    # What a launch pair allocates, one method per kind of buffer, so that a subclass (tests/_wsprobe.py) changes the buffers
+    # without restating the launches.
+    fwd_need_wgrad = 0             # TfnasCellDesc.need_wgrad of the forward
+
     def _gbuf(self, name, n, dtype=torch.float32):
         t = self.bufs[name] = (self._buf(n, self.guard, dtype), int(n))
         return t[0]
+
+    def _partbuf(self, name, floats):
+        from tfnas_amd.functions import _part
+        return _part(floats, self.dev)
+
+    def _gradbufs(self, accum_into):
+        return [g.clone() for g in accum_into] if accum_into is not None else [torch.full_like(w, 3.5) for w in self.w]
+
+    def _keeps_E(self):
+        return bool(self.ws.E)
 
     def guards_ok(self):
         return {k: self.guard_ok(t, n) for k, (t, n) in self.bufs.items()}
 
     def forward(self):
-        from tfnas_amd.functions import _part, _stream
+        from tfnas_amd.functions import _stream
         d, ws, ptr = self.d, self.ws, self._lib.ptr
-        d.need_wgrad = 0
-        self.E = self._gbuf('E', ws.E) if ws.E else None
+        d.need_wgrad = self.fwd_need_wgrad
+        self.E = self._gbuf('E', ws.E) if self._keeps_E() else None
         self.D, self.Pr, self.fsmall = self._gbuf('D', ws.D), self._gbuf('Pr', ws.Pr), self._gbuf('fsmall', ws.fsmall)
         self.stats = self._gbuf('stats', ws.stats, torch.float64)
         self.out = self._gbuf('out', ws.out)
-        part = _part(ws.part, self.dev)
-        self._lib.check(self.lib.tfnas_mixedop_fwd(C.byref(d), ptr(self.xh), ptr(self.wmix), ptr(self.E), ptr(self.D),
-                                                   ptr(self.Pr), ptr(self.fsmall), ptr(self.stats), ptr(part), ptr(self.out),
-                                                   _stream(self.dev)), 'tfnas_mixedop_fwd')
-        torch.cuda.synchronize()
+        part = self._partbuf('part_fwd', ws.part)
+        try:
+            self._lib.check(self.lib.tfnas_mixedop_fwd(C.byref(d), ptr(self.xh), ptr(self.wmix), ptr(self.E), ptr(self.D),
+                                                       ptr(self.Pr), ptr(self.fsmall), ptr(self.stats), ptr(part), ptr(self.out),
+                                                       _stream(self.dev)), 'tfnas_mixedop_fwd')
+            torch.cuda.synchronize()
+        finally:
+            d.need_wgrad = 0
         return self.out[:ws.out].view(d.N, d.Ho, d.Wo, d.oc).permute(0, 3, 1, 2)
 
     def backward(self, r, need_wgrad=True, want_dx=True, accum_into=None):
-        """(rc, dx or None, dwmix, {name: gradient} or None); accum_into: gradients are ADDED to copies of these tensors"""
-        from tfnas_amd.functions import _part, _stream
+        """(rc, dx or None, dwmix (None without mix weights), {name: gradient} or None); accum_into: gradients are ADDED to copies
+        of these tensors"""
+        from tfnas_amd.functions import _stream
         d, ws, ptr = self.d, self.ws, self._lib.ptr
         d.need_wgrad = int(need_wgrad)
         base = d.flags
         grads = None
         if need_wgrad:
-            grads = [g.clone() for g in accum_into] if accum_into is not None else [torch.full_like(w, 3.5) for w in self.w]
+            grads = self._gradbufs(accum_into)
             for (g, k), t in zip(self.slots, grads):
                 setattr(d.g[g], self._lib._G_FIELDS[k], t.data_ptr())
             if accum_into is not None:
@@ -320,8 +338,8 @@ class RawMixed(_rawcell.RawCell):
         dxp = self._gbuf('dxp', ws.dxp) if want_dx else None
         dZ, dEh = self._gbuf('dZ', 4 if light else ws.dZ), self._gbuf('dEh', 4 if light else ws.dEh)
         bsmall, red = self._gbuf('bsmall', ws.bsmall), self._gbuf('red', ws.red, torch.float64)
-        dwmix = self._gbuf('dwmix', d.G)
-        part = _part(ws.part * 2, self.dev)
+        dwmix = self._gbuf('dwmix', d.G) if self.wmix is not None else None
+        part = self._partbuf('part_bwd', ws.part * 2)
         try:
             rc = self.lib.tfnas_mixedop_bwd(C.byref(d), ptr(self.xh), ptr(self.wmix), ptr(self.E), ptr(self.D), ptr(self.Pr),
                                             ptr(self.fsmall), ptr(self.stats), ptr(rh), ptr(dZ), ptr(dEh), ptr(bsmall), ptr(red),
@@ -333,7 +351,8 @@ class RawMixed(_rawcell.RawCell):
                 for f in self._lib._G_FIELDS:
                     setattr(d.g[g], f, None)
         dxo = None if dx is None else dx[:P * d.ic].view(d.N, d.H, d.W, d.ic).permute(0, 3, 1, 2)
-        return rc, dxo, dwmix[:d.G], (None if grads is None else OrderedDict(zip(self.names, grads)))
+        return (rc, dxo, None if dwmix is None else dwmix[:d.G],
+                None if grads is None else OrderedDict(zip(self.names, grads)))
 
 
 # ------------------------------------------------------------------------------------------------ pin (float64)
