@@ -480,8 +480,8 @@ int tfnas_set_stats_sync(tfnas_stats_sync_fn fn, void *user, int world);
 int tfnas_shutdown(void);
 
 /* sizeof() of the ABI structs, for binding self-checks: which = 0 TfnasGroup, 1 TfnasCellDesc, 2 TfnasCellWs,
- * 3 TfnasStage, 4 TfnasPathDesc, 5 TfnasPathWs, 6 TfnasBnAffine;  7 = floats of one `part` scratch piece, 8 = reserved
- * words at the end of each piece (TfnasCellWs.part). */
+ * 3 TfnasStage, 4 TfnasPathDesc, 5 TfnasPathWs, 6 TfnasBnAffine, 9 TfnasOptGroups;  7 = floats of one `part` scratch piece,
+ * 8 = reserved words at the end of each piece (TfnasCellWs.part). */
 uint64_t tfnas_sizeof(int which);
 
 /* Fill the [plan] fields of a descriptor from its [in] fields.  Returns TFNAS_E* on bad geometry. */
@@ -831,6 +831,59 @@ int tfnas_sgd_clip_ema_step(float *w, float *g, float *m, int nranges, const uin
  * (TFNAS_EINVAL); nranges outside [1, 64] (TFNAS_ERANGE). */
 int tfnas_ema_lerp(float *ema, const float *src, int nranges, const uint64_t *off, const uint64_t *len, float ema_alpha,
                    void *stream);
+
+/* ---- retrain step tail for parameter groups, Nesterov SGD and RMSprop ---------------------------------------------------
+ * What the published MobileNetV3 / MixNet / EfficientNet / FBNet recipes train with: no weight decay on BatchNorm gamma / beta
+ * and on biases (two parameter groups), and Nesterov SGD or RMSprop, torch's form or TensorFlow's.  w / g / m / v / ema: flat fp32
+ * arenas of `total` floats with one layout (weights, gradients, momentum, squared-gradient average, weight EMA); total is a
+ * multiple of 64 because every arena slot is padded to 64 floats.  A group's parameters are not contiguous in the arena, so the
+ * groups are not ranges: gmap holds ONE byte per 64-float block of the arena (total / 64 bytes of device memory, built once per
+ * arena by the caller), the group id of that block.  Block b is updated with lr[gmap[b]] and wd[gmap[b]]; momentum, alpha, eps
+ * and the flags are one value per call.  A map byte >= ngroups means "leave this block alone": nothing of w, m, v or ema in it
+ * is stored (its gradient is still scaled, and still counts in the norm).
+ *
+ *   total_norm = ||g[0, total)|| * grad_scale;  coef = min(1, max_norm / (total_norm + 1e-6))  (max_norm <= 0: coef = 1)
+ *   g' = g * grad_scale * coef   (stored back, as after clip_grad_norm_);   d = g' + wd_k * w
+ *   TFNAS_OPT_SGD         m' = momentum * m + d;   w' = w - lr_k * m'                 (torch.optim.SGD, dampening 0)
+ *     | TFNAS_OPT_NESTEROV                         w' = w - lr_k * (d + momentum * m')
+ *   TFNAS_OPT_RMSPROP     v' = alpha * v + (1 - alpha) * d^2;   u = d / (sqrt(v') + eps)   (torch.optim.RMSprop, not centered)
+ *                         momentum > 0:  m' = momentum * m + u;  w' = w - lr_k * m'
+ *                         momentum == 0: w' = w - lr_k * u       (m is neither read nor written)
+ *   TFNAS_OPT_RMSPROP_TF  v' = v + (1 - alpha) * (d^2 - v);   m' = momentum * m + lr_k * d / sqrt(v' + eps);   w' = w - m'
+ *                         (TensorFlow's form: eps inside the root, the rate inside the momentum)
+ *   ema != NULL:          ema' = fma(ema_alpha, w' - ema, ema), stored where w' is stored (ema_alpha = 1 - decay, the step weight)
+ *
+ * The square root and the division are the correctly rounded fp32 ones.  The gaps between the slots (zero in every arena) stay
+ * zero under every kind -- which is why eps <= 0 is refused for RMSprop: 0 / (sqrt(0) + 0) would put a NaN there.  Two launches
+ * (the squared-norm pass of tfnas_sgd_clip_step over [0, total), then the update), no atomics, deterministic.  scratch: device
+ * doubles, >= ceil(total / 8192).  norm_out: device float or NULL.
+ * Refused before anything is launched: d, w, g, m, gmap or scratch NULL, v NULL for an RMSprop kind (TFNAS_ENULL); total 0 or
+ * not a multiple of 64; an unknown kind or flag bit (TFNAS_OPT_NESTEROV with a kind other than TFNAS_OPT_SGD included); a
+ * non-finite lr[k] / wd[k] (k < ngroups), momentum, alpha, eps, max_norm or grad_scale; alpha outside [0, 1] or eps <= 0 for an
+ * RMSprop kind; momentum < 0, or <= 0 with Nesterov; with ema: ema_alpha outside [0, 1] or not finite, ema == w, g, m or v
+ * (TFNAS_EINVAL); ngroups outside [1, 8]; scratch_doubles too small (TFNAS_ERANGE). */
+#define TFNAS_OPT_MAX_GROUPS 8
+#define TFNAS_OPT_SGD 0
+#define TFNAS_OPT_RMSPROP 1
+#define TFNAS_OPT_RMSPROP_TF 2
+#define TFNAS_OPT_NESTEROV 1    /* TfnasOptGroups.flags */
+
+typedef struct TfnasOptGroups {
+    int32_t kind;       /* TFNAS_OPT_SGD / _RMSPROP / _RMSPROP_TF */
+    int32_t flags;      /* 0 or TFNAS_OPT_NESTEROV */
+    int32_t ngroups;    /* 1 .. TFNAS_OPT_MAX_GROUPS */
+    float lr[TFNAS_OPT_MAX_GROUPS];
+    float wd[TFNAS_OPT_MAX_GROUPS];
+    float momentum;
+    float alpha;        /* RMSprop: decay of the squared-gradient average (not read by TFNAS_OPT_SGD) */
+    float eps;          /* RMSprop (not read by TFNAS_OPT_SGD) */
+    float max_norm;
+    float grad_scale;
+    float ema_alpha;    /* read only with ema != NULL */
+} TfnasOptGroups;       /* tfnas_sizeof(9) */
+
+int tfnas_opt_groups_step(const TfnasOptGroups *d, float *w, float *g, float *m, float *v, float *ema, const uint8_t *gmap,
+                          uint64_t total, double *scratch, uint64_t scratch_doubles, float *norm_out, void *stream);
 
 /* dst[doff[i] .. +len[i]) = src[off[i] .. +len[i]) for nranges <= 64 ranges (one launch): gathers the sampled candidates'
  * gradient ranges into ONE contiguous buffer = one RCCL all-reduce message (no torch.cat, no copy back: the SGD step reads

@@ -145,6 +145,7 @@ extern "C" uint64_t tfnas_sizeof(int which) {
         case 6: return sizeof(TfnasBnAffine);
         case 7: return TFNAS_PART_ALLOC;      // floats of one `part` scratch region ...
         case 8: return TFNAS_TAIL_SLOTS;      // ... whose last this-many 4-byte words are reserved
+        case 9: return sizeof(TfnasOptGroups);
         default: return 0;
     }
 }
@@ -1089,6 +1090,12 @@ extern "C" int tfnas_ema_lerp(float* ema, const float* src, int nranges, const u
                               float ema_alpha, void* stream) {
     if (!ema || !src || !off || !len) return TFNAS_ENULL;
     return launch_ema_lerp(ema, src, nranges, off, len, ema_alpha, S(stream));
+}
+
+extern "C" int tfnas_opt_groups_step(const TfnasOptGroups* d, float* w, float* g, float* m, float* v, float* ema,
+                                     const uint8_t* gmap, uint64_t total, double* scratch, uint64_t scratch_doubles,
+                                     float* norm_out, void* stream) {
+    return launch_opt_groups_step(d, w, g, m, v, ema, gmap, total, scratch, scratch_doubles, norm_out, S(stream));
 }
 
 extern "C" int tfnas_arch_adam_project(int n, float* const* p, const float* const* g, const int32_t* len, float* m, float* v,

@@ -393,6 +393,8 @@ int launch_sgd_clip_ema_step(float* w, float* g, float* m, int nranges, const ui
                              hipStream_t s);
 int launch_ema_lerp(float* ema, const float* src, int nranges, const uint64_t* off, const uint64_t* len, float ema_alpha,
                     hipStream_t s);
+int launch_opt_groups_step(const TfnasOptGroups* d, float* w, float* g, float* m, float* v, float* ema, const uint8_t* gmap,
+                           uint64_t total, double* scratch, uint64_t scratch_doubles, float* norm_out, hipStream_t s);
 int launch_arch_adam_project(int n, float* const* p, const float* const* g, const int32_t* len, float* m, float* v,
                              float max_norm, float lr, float b1, float b2, float eps, float wd, int step, float grad_scale,
                              float* norm_out, hipStream_t s);

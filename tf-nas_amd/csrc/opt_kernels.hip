@@ -232,6 +232,154 @@ int launch_ema_lerp(float* ema, const float* src, int nranges, const uint64_t* o
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Retrain tail for parameter groups (tfnas_opt_groups_step): the whole arena [0, total) with a per-64-float-block group id
+// (gmap) that selects lr / wd from a table of <= 8 groups; SGD (plain / Nesterov), RMSprop (torch's form, with and without
+// momentum) and RMSprop in TensorFlow's form, each with and without the weight EMA.  Grid, chunking and prologue of k_opt_sgd.
+enum { OG_SGD = 0, OG_NESTEROV = 1, OG_RMS = 2, OG_RMS_NOMOM = 3, OG_RMS_TF = 4 };
+
+struct OptGroupsK {
+    int ngroups, nblocks;
+    float lr[TFNAS_OPT_MAX_GROUPS], wd[TFNAS_OPT_MAX_GROUPS];
+    float momentum, alpha, one_minus_alpha, eps, max_norm, grad_scale, ema_alpha;
+};
+
+// one element of the update; v / m are in-out where the mode keeps them
+template <int MODE>
+__device__ __forceinline__ float og_update(float w, float gc, float& m, float& v, float lr, float wd, const OptGroupsK& A) {
+    const float d = gc + wd * w;
+    if (MODE == OG_SGD || MODE == OG_NESTEROV) {
+        m = A.momentum * m + d;
+        return MODE == OG_SGD ? w - lr * m : w - lr * (d + A.momentum * m);
+    } else if (MODE == OG_RMS || MODE == OG_RMS_NOMOM) {
+        v = A.alpha * v + A.one_minus_alpha * (d * d);
+        const float u = d / (__builtin_sqrtf(v) + A.eps);
+        if (MODE == OG_RMS_NOMOM) return w - lr * u;
+        m = A.momentum * m + u;
+        return w - lr * m;
+    } else {
+        v = v + A.one_minus_alpha * (d * d - v);
+        m = A.momentum * m + (lr * d) / __builtin_sqrtf(v + A.eps);
+        return w - m;
+    }
+}
+
+template <int MODE, bool EMA>
+__global__ __launch_bounds__(256) void k_opt_groups(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, float* __restrict__ ema,
+                                                    const uint8_t* __restrict__ gmap, uint64_t total_floats, OptGroupsK A,
+                                                    const double* __restrict__ partial, float* __restrict__ norm_out) {
+    constexpr bool HAS_M = MODE != OG_RMS_NOMOM, HAS_V = MODE >= OG_RMS;
+    __shared__ double sh[4];
+    __shared__ float s_lr[TFNAS_OPT_MAX_GROUPS], s_wd[TFNAS_OPT_MAX_GROUPS];
+    if (threadIdx.x < TFNAS_OPT_MAX_GROUPS) {             // (visible after the barriers of block_sum_d)
+        s_lr[threadIdx.x] = A.lr[threadIdx.x];
+        s_wd[threadIdx.x] = A.wd[threadIdx.x];
+    }
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < A.nblocks; i += 256) acc += partial[i];
+    acc = block_sum_d(acc, sh);
+    const float total = (float)sqrt(acc) * A.grad_scale;
+    float coef = A.max_norm > 0.f ? A.max_norm / (total + 1e-6f) : 1.f;
+    coef = coef > 1.f ? 1.f : coef;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) *norm_out = total;
+    const float gs = A.grad_scale * coef;
+    const uint64_t beg = (uint64_t)blockIdx.x * OPT_CHUNK;
+    const uint64_t end = beg + OPT_CHUNK < total_floats ? beg + OPT_CHUNK : total_floats;
+    for (uint64_t i = beg + 4 * (uint64_t)threadIdx.x; i < end; i += 1024) {
+        f32x4 gv = ld4(g + i);
+        gv = gv * splat4(gs);
+        st4(g + i, gv);
+        const unsigned id = gmap[i >> 6];                 // the group of this float4's 64-float block: the same for 16 lanes
+        if (id >= (unsigned)A.ngroups) continue;          // not in the table: the block's w / m / v / ema stay as they are
+        const float lr = s_lr[id], wd = s_wd[id];
+        f32x4 wv = ld4(w + i), mv = splat4(0.f), vv = splat4(0.f);
+        if (HAS_M) mv = ld4(m + i);
+        if (HAS_V) vv = ld4(v + i);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float mc = mv[c], vc = vv[c];
+            wv[c] = og_update<MODE>(wv[c], gv[c], mc, vc, lr, wd, A);
+            mv[c] = mc;
+            vv[c] = vc;
+        }
+        if (HAS_V) st4(v + i, vv);
+        if (HAS_M) st4(m + i, mv);
+        st4(w + i, wv);
+        if (EMA) st4(ema + i, ema_lerp4(ld4(ema + i), wv, A.ema_alpha));
+    }
+}
+
+template <int MODE>
+static void og_launch(bool with_ema, int nb, hipStream_t s, float* w, float* g, float* m, float* v, float* ema,
+                      const uint8_t* gmap, uint64_t total, const OptGroupsK& A, const double* partial, float* norm_out) {
+    if (with_ema)
+        hipLaunchKernelGGL((k_opt_groups<MODE, true>), dim3(nb), dim3(256), 0, s, w, g, m, v, ema, gmap, total, A, partial, norm_out);
+    else
+        hipLaunchKernelGGL((k_opt_groups<MODE, false>), dim3(nb), dim3(256), 0, s, w, g, m, v, ema, gmap, total, A, partial, norm_out);
+}
+
+int launch_opt_groups_step(const TfnasOptGroups* d, float* w, float* g, float* m, float* v, float* ema, const uint8_t* gmap,
+                           uint64_t total, double* scratch, uint64_t scratch_doubles, float* norm_out, hipStream_t s) {
+    if (!d || !w || !g || !m || !gmap || !scratch) return TFNAS_ENULL;
+    const bool rms = d->kind == TFNAS_OPT_RMSPROP || d->kind == TFNAS_OPT_RMSPROP_TF;
+    if (d->kind != TFNAS_OPT_SGD && !rms) return TFNAS_EINVAL;
+    if (rms && !v) return TFNAS_ENULL;
+    if (total == 0 || (total & 63)) return TFNAS_EINVAL;
+    if (d->ngroups < 1 || d->ngroups > TFNAS_OPT_MAX_GROUPS) return TFNAS_ERANGE;
+    if (d->flags & ~TFNAS_OPT_NESTEROV) return TFNAS_EINVAL;
+    const bool nesterov = (d->flags & TFNAS_OPT_NESTEROV) != 0;
+    if (nesterov && d->kind != TFNAS_OPT_SGD) return TFNAS_EINVAL;
+    for (int k = 0; k < d->ngroups; ++k)
+        if (!std::isfinite(d->lr[k]) || !std::isfinite(d->wd[k])) return TFNAS_EINVAL;
+    if (!std::isfinite(d->momentum) || !std::isfinite(d->max_norm) || !std::isfinite(d->grad_scale)) return TFNAS_EINVAL;
+    if (!std::isfinite(d->alpha) || !std::isfinite(d->eps)) return TFNAS_EINVAL;
+    if (rms && (!(d->alpha >= 0.f && d->alpha <= 1.f) || !(d->eps > 0.f))) return TFNAS_EINVAL;
+    if (d->momentum < 0.f || (nesterov && !(d->momentum > 0.f))) return TFNAS_EINVAL;
+    if (ema) {
+        if (!ema_alpha_ok(d->ema_alpha)) return TFNAS_EINVAL;
+        if (ema == w || ema == g || ema == m || ema == v) return TFNAS_EINVAL;
+    }
+    const uint64_t nb64 = (total + OPT_CHUNK - 1) / OPT_CHUNK;
+    if (nb64 > scratch_doubles) return TFNAS_ERANGE;
+    if (nb64 > 0x7fffffffull) return TFNAS_ERANGE;
+    const int nb = (int)nb64;
+    OptRanges R;
+    const uint64_t zero = 0;
+    int rc = fill_ranges(R, 1, &zero, nullptr, &total);
+    if (rc) return rc;
+    OptGroupsK A;
+    A.ngroups = d->ngroups;
+    A.nblocks = nb;
+    for (int k = 0; k < TFNAS_OPT_MAX_GROUPS; ++k) {
+        A.lr[k] = k < d->ngroups ? d->lr[k] : 0.f;
+        A.wd[k] = k < d->ngroups ? d->wd[k] : 0.f;
+    }
+    A.momentum = d->momentum;
+    A.alpha = d->alpha;
+    A.one_minus_alpha = (float)(1.0 - (double)d->alpha);
+    A.eps = d->eps;
+    A.max_norm = d->max_norm;
+    A.grad_scale = d->grad_scale;
+    A.ema_alpha = ema ? d->ema_alpha : 0.f;
+    {   // (a scope per kernel: tfnas_prof_collect counts this step's two launches as two)
+        ProfScope _prof(TK_SMALL, s);
+        hipLaunchKernelGGL(k_opt_sqnorm, dim3(nb), dim3(256), 0, s, g, R, scratch);
+    }
+    ProfScope _prof(TK_SMALL, s);
+    const bool e = ema != nullptr;
+    if (d->kind == TFNAS_OPT_SGD) {
+        if (nesterov) og_launch<OG_NESTEROV>(e, nb, s, w, g, m, v, ema, gmap, total, A, scratch, norm_out);
+        else og_launch<OG_SGD>(e, nb, s, w, g, m, v, ema, gmap, total, A, scratch, norm_out);
+    } else if (d->kind == TFNAS_OPT_RMSPROP) {
+        if (d->momentum > 0.f) og_launch<OG_RMS>(e, nb, s, w, g, m, v, ema, gmap, total, A, scratch, norm_out);
+        else og_launch<OG_RMS_NOMOM>(e, nb, s, w, g, m, v, ema, gmap, total, A, scratch, norm_out);
+    } else {
+        og_launch<OG_RMS_TF>(e, nb, s, w, g, m, v, ema, gmap, total, A, scratch, norm_out);
+    }
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Architecture parameters: <= 32 tensors of <= 8 floats.  One workgroup: clip over all of them, Adam, projection.
 struct ArchOpt {
     int n;

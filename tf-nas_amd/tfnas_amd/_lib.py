@@ -230,6 +230,17 @@ class TfnasBnAffine(C.Structure):
                 + [('momentum', C.c_float), ('eval', C.c_int32)])
 
 
+OPT_MAX_GROUPS = 8
+OPT_SGD, OPT_RMSPROP, OPT_RMSPROP_TF = 0, 1, 2      # TfnasOptGroups.kind
+OPT_NESTEROV = 1                                    # TfnasOptGroups.flags
+
+
+class TfnasOptGroups(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ('kind', 'flags', 'ngroups')]
+                + [('lr', C.c_float * OPT_MAX_GROUPS), ('wd', C.c_float * OPT_MAX_GROUPS)]
+                + [(n, C.c_float) for n in ('momentum', 'alpha', 'eps', 'max_norm', 'grad_scale', 'ema_alpha')])
+
+
 _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
 _PROTOS = {
@@ -269,6 +280,7 @@ _PROTOS = {
                                           C.POINTER(C.c_uint64), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                           _P, C.c_float, _P, C.c_uint64, _P, _P]),
     'tfnas_ema_lerp': (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_float, _P]),
+    'tfnas_opt_groups_step': (C.c_int, [C.POINTER(TfnasOptGroups), _P, _P, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
     'tfnas_arch_adam_project': (C.c_int, [C.c_int, _PP, _PP, C.POINTER(C.c_int32), _P, _P, C.c_float, C.c_float, C.c_float,
                                           C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P]),
     'tfnas_arch_fwd': (C.c_int, [C.c_int, C.POINTER(_P), _P, _P, C.c_float, _P, _P, _P]),
@@ -314,6 +326,8 @@ def lib():
         for which, st in enumerate((TfnasGroup, TfnasCellDesc, TfnasCellWs, TfnasStage, TfnasPathDesc, TfnasPathWs, TfnasBnAffine)):
             if l.tfnas_sizeof(which) != C.sizeof(st):
                 raise RuntimeError('tfnas_amd: struct layout mismatch for %s' % st.__name__)
+        if l.tfnas_sizeof(9) != C.sizeof(TfnasOptGroups):
+            raise RuntimeError('tfnas_amd: struct layout mismatch for TfnasOptGroups')
         # the library reads no environment variable (ABI 4): TFNAS_GEMM only seeds its process-wide default here
         g = os.environ.get('TFNAS_GEMM')
         if g is not None:

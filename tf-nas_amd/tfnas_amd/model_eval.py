@@ -329,6 +329,10 @@ class RetrainState:
         self.arena = WeightArena(model)
         self._bound = None
         self._scratch = self._gnorm = None
+        # the 'groups' plan: squared-gradient arena, device group map (+ the membership it was built for), descriptor, step counters
+        self._v = self._gmap = self._gmap_key = self._gdesc = None
+        self._gbound = None
+        self._gsteps = ()
 
     def intact(self):
         return self.arena.intact()
@@ -350,6 +354,129 @@ class RetrainState:
             if not all(p.requires_grad for p in mine) or {id(p) for p in g[0]['params']} != {id(p) for p in mine}:
                 return False
         return True
+
+    @staticmethod
+    def plan(opt, model):
+        """Which fused tail stands in for ``optimizer.step()`` -- pure inspection, nothing is touched.  'sgd': ``fusable`` holds
+        (``tfnas_sgd_clip_step``, as ever).  'groups' (``tfnas_opt_groups_step``): ``torch.optim.SGD`` (dampening 0, not maximize;
+        Nesterov allowed), ``torch.optim.RMSprop`` (not centered / maximize / capturable) or ``optim.RMSpropTF`` with 1..8 param
+        groups that are disjoint and together hold exactly the model's parameters, all trainable; momentum, nesterov, alpha and eps
+        equal across the groups (lr and weight_decay may differ); no step hooks.  None: torch's clip_grad_norm_ +
+        optimizer.step()."""
+        from .optim import RMSpropTF
+        if RetrainState.fusable(opt, model):
+            return 'sgd'
+        g = opt.param_groups
+        if not 1 <= len(g) <= _lib.OPT_MAX_GROUPS:
+            return None
+        if getattr(opt, '_optimizer_step_pre_hooks', None) or getattr(opt, '_optimizer_step_post_hooks', None):
+            return None
+        if any(q.get('maximize') or q.get('differentiable') for q in g):
+            return None
+        if isinstance(opt, torch.optim.SGD):
+            shared = ('momentum', 'nesterov')
+            if any(q.get('dampening') for q in g):
+                return None
+        elif isinstance(opt, (torch.optim.RMSprop, RMSpropTF)):
+            shared = ('momentum', 'alpha', 'eps')
+            if any(q.get('centered') or q.get('capturable') for q in g) or not g[0]['eps'] > 0 or not 0 <= g[0]['alpha'] <= 1:
+                return None
+        else:
+            return None
+        if any(q[k] != g[0][k] for q in g[1:] for k in shared) or not g[0]['momentum'] >= 0:
+            return None
+        ids = [id(p) for q in g for p in q['params']]
+        mine = list(model.parameters())
+        if len(set(ids)) != len(ids) or set(ids) != {id(p) for p in mine} or not all(p.requires_grad for p in mine):
+            return None
+        return 'groups'
+
+    def _bind_groups(self, opt):
+        """The 'groups' plan's share of the state: the optimizer's ``momentum_buffer`` / ``square_avg`` become views into the m / v
+        arenas (existing values are copied in; missing state starts as the optimizer itself would start it), and the device group
+        map is (re)built when the groups' membership is not the one it was built for.  Returns (kind, flags)."""
+        from .optim import RMSpropTF
+        a = self.arena
+        hp = opt.param_groups[0]
+        if isinstance(opt, RMSpropTF):
+            kind, flags, want = _lib.OPT_RMSPROP_TF, 0, ('momentum_buffer', 'square_avg')
+        elif isinstance(opt, torch.optim.RMSprop):
+            kind, flags, want = _lib.OPT_RMSPROP, 0, (('momentum_buffer', 'square_avg') if hp['momentum'] > 0 else ('square_avg',))
+        else:
+            kind, flags = _lib.OPT_SGD, (_lib.OPT_NESTEROV if hp.get('nesterov') else 0)
+            want = ('momentum_buffer',) if hp['momentum'] != 0 else ()
+        if kind != _lib.OPT_SGD and self._v is None:
+            self._v = torch.zeros(a.total, device=a.device, dtype=torch.float32)
+        arenas = {'momentum_buffer': a.m, 'square_avg': self._v}
+
+        def bound(p):
+            st, o = opt.state.get(p, {}), a.slot[id(p)][0]
+            return all(st.get(k) is not None and st[k].data_ptr() == arenas[k].data_ptr() + 4 * o for k in want)
+
+        if not (self._gbound == (id(opt), want) and bound(a.params[0]) and bound(a.params[-1])):
+            with torch.no_grad():
+                if 'momentum_buffer' not in want:
+                    a.m.zero_()                          # (nobody's state: what a later momentum > 0 starts from)
+                steps = []
+                for p in a.params:
+                    o, n = a.slot[id(p)]
+                    st = opt.state[p]
+                    if kind != _lib.OPT_SGD and 'step' not in st:
+                        st['step'] = 0 if kind == _lib.OPT_RMSPROP_TF else torch.zeros(())     # (torch's: a CPU scalar tensor)
+                    for k in want:
+                        view = arenas[k][o:o + n].view(p.shape)
+                        old = st.get(k)
+                        if old is None:
+                            view.fill_(1.0 if (k == 'square_avg' and kind == _lib.OPT_RMSPROP_TF) else 0.0)
+                        elif old.data_ptr() != view.data_ptr():
+                            view.copy_(old)
+                        st[k] = view
+                    if 'step' in st:
+                        steps.append(st)
+                self._gsteps = steps
+            self._gbound = (id(opt), want)
+            self._bound = None                           # (the 'sgd' plan re-binds if it ever gets this arena back)
+        key = tuple(tuple(id(p) for p in q['params']) for q in opt.param_groups)
+        if self._gmap is None or self._gmap_key != key:
+            ids = torch.full((a.total // 64,), 255, dtype=torch.uint8)
+            for k, q in enumerate(opt.param_groups):
+                for p in q['params']:
+                    o, n = a.slot[id(p)]
+                    ids[o // 64:(o + n + 63) // 64] = k
+            self._gmap, self._gmap_key = ids.to(a.device), key
+        return kind, flags
+
+    def _step_groups(self, opt, grad_clip, scale, ema, stream):
+        """clip + the optimizer's update over the whole arena with per-group lr / weight decay: the two launches of
+        ``tfnas_opt_groups_step`` (the EMA of the parameters inside the second one)."""
+        import ctypes as C
+        a = self.arena
+        kind, flags = self._bind_groups(opt)
+        d = self._gdesc
+        if d is None:
+            d = self._gdesc = _lib.TfnasOptGroups()
+        g = opt.param_groups
+        d.kind, d.flags, d.ngroups = kind, flags, len(g)
+        for k, q in enumerate(g):                        # read at every step: schedulers write lr here
+            d.lr[k], d.wd[k] = float(q['lr']), float(q['weight_decay'])
+        d.momentum = float(g[0]['momentum'])
+        d.alpha, d.eps = float(g[0].get('alpha', 0.0)), float(g[0].get('eps', 0.0))
+        d.max_norm, d.grad_scale = float(grad_clip), float(scale)
+        eflat = None
+        if ema is not None:
+            _, bufs = ema._sync(self.model)
+            if ema._arena is not a:
+                raise RuntimeError('RetrainState.step: the EMA could not lay its parameter shadow out on this arena')
+            alpha = ema.alpha()
+            d.ema_alpha, eflat = alpha, ema._pflat
+        _lib.check(_lib.lib().tfnas_opt_groups_step(C.byref(d), _lib.ptr(a.w), _lib.ptr(a.g), _lib.ptr(a.m), _lib.ptr(self._v),
+                                                    _lib.ptr(eflat), _lib.ptr(self._gmap), a.total, _lib.ptr(self._scratch),
+                                                    self._scratch.numel(), _lib.ptr(self._gnorm), stream), 'tfnas_opt_groups_step')
+        if ema is not None:
+            ema._update_buffers(bufs, alpha)
+            ema.updates += 1
+        for st in self._gsteps:                          # what optimizer.step() counts per parameter
+            st['step'] += 1
 
     def _bind_momentum(self, opt):
         a = self.arena
@@ -400,8 +527,10 @@ class RetrainState:
             functions.retrain_join(self.arena.device)
         functions.retrain_context(False, False, owner)
 
-    def step(self, opt, grad_clip, group=None, ema=None):
-        """Join, all-reduce (with a group), then clip + SGD over the whole arena in two launches.  ``ema`` (a WeightEma): the SGD
+    def step(self, opt, grad_clip, group=None, ema=None, plan=None):
+        """Join, all-reduce (with a group), then clip + SGD over the whole arena in two launches.  ``plan`` (what ``plan(opt,
+        model)`` returned, where the caller already asked): 'groups' takes the same two launches through ``tfnas_opt_groups_step``
+        -- parameter groups, Nesterov, RMSprop; 'sgd' makes the calls below.  ``ema`` (a WeightEma): the SGD
         pass keeps the parameters' average as it stores them (``tfnas_sgd_clip_ema_step``, same two launches), ONE further launch
         averages the floating-point buffers, and the EMA's count goes up by one.  The average is taken after the all-reduce, so the
         parameter shadows are identical on all ranks; the buffer shadows are per rank, as the running statistics themselves are
@@ -410,7 +539,11 @@ class RetrainState:
         import torch.distributed as dist
         a = self.arena
         self.end()                                       # the gradients are complete on the current stream from here on
-        self._bind_momentum(opt)
+        if plan is None:
+            plan = self.plan(opt, self.model)
+        groups = plan == 'groups'
+        if not groups:
+            self._bind_momentum(opt)
         hp = opt.param_groups[0]
         scale = 1.0
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
@@ -423,7 +556,9 @@ class RetrainState:
             self._gnorm = torch.zeros(2, device=dev, dtype=torch.float32)
         off, ln = (C.c_uint64 * 1)(0), (C.c_uint64 * 1)(a.total)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if ema is None:
+        if groups:
+            self._step_groups(opt, grad_clip, scale, ema, stream)
+        elif ema is None:
             _lib.check(_lib.lib().tfnas_sgd_clip_step(_lib.ptr(a.w), _lib.ptr(a.g), _lib.ptr(a.m), 1, off, None, ln, float(grad_clip),
                                                       float(hp['lr']), float(hp['momentum']), float(hp['weight_decay']), float(scale),
                                                       _lib.ptr(self._scratch), self._scratch.numel(), _lib.ptr(self._gnorm), stream),
@@ -454,11 +589,12 @@ class WeightEma:
     ``1 - decay``), t = the updates done so far, formed in Python floats and handed to the kernels as the step weight itself.
 
     Parameters: where the model has an intact ``RetrainState`` the shadow is ONE flat tensor with the arena's layout (gaps zero, and
-    they stay zero), and ``RetrainState.step(..., ema=self)`` keeps it inside the SGD pass (``tfnas_sgd_clip_ema_step``: no launch).
+    they stay zero), and ``RetrainState.step(..., ema=self)`` keeps it inside the update pass on both plans (``tfnas_sgd_clip_ema_step``
+    on 'sgd', the ``ema`` argument of ``tfnas_opt_groups_step`` on 'groups': no launch).
     When the arena is rebuilt (``model.to()``, ``p.data = ...``) the shadow re-lays itself by parameter name and keeps its values.
     Float buffers: on a CUDA model they are moved into one flat tensor (path.BufferArena) when the EMA is attached, so that their
-    average is ONE ``tfnas_ema_lerp`` launch per step.  Without an arena (CPU; an optimizer that is not ``RetrainState.fusable``
-    before any fused step) the shadows are per tensor and the update is ``torch._foreach_lerp_``.
+    average is ONE ``tfnas_ema_lerp`` launch per step.  Without an arena (CPU; an optimizer that ``RetrainState.plan`` sends to
+    the torch route, before any fused step) the shadows are per tensor and the update is ``torch._foreach_lerp_``.
 
     Known property of any fp32 EMA (timm's ModelEmaV2 alike): at alpha = 1e-4 an element stops moving once
     |w - ema| < 2^-24 |ema| / alpha, about 6e-4 |ema|."""
@@ -655,7 +791,8 @@ def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None
     model.train()
     tail_plan = _fused_tail_plan(model, criterion) if FUSED_TAIL and x.is_cuda else None
     st = None
-    if fused and x.is_cuda and RetrainState.fusable(optimizer, model):
+    plan = RetrainState.plan(optimizer, model) if fused and x.is_cuda else None
+    if plan is not None:
         st = getattr(model, '_retrain_state', None)
         if st is None or not st.intact():
             st = RetrainState(model)
@@ -680,7 +817,7 @@ def train_step(model, x, target, criterion, optimizer, grad_clip=5.0, group=None
             st.end()
         raise
     if st is not None:
-        st.step(optimizer, grad_clip, group, ema)
+        st.step(optimizer, grad_clip, group, ema, plan)
         return loss.detach(), logits.detach()
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
         grads = [p.grad for p in model.parameters() if p.grad is not None]
@@ -746,7 +883,7 @@ def build_derived_network(num_classes, model_path=None, config_path=None, dropou
 
 def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250, lr=0.2, momentum=0.9, weight_decay=4e-5,
                 label_smooth=0.1, grad_clip=5.0, batch_size=256, snapshot=None, device='cuda', group=None, log=print,
-                ema_decay=None, ema_warmup=True):
+                ema_decay=None, ema_warmup=True, optimizer='sgd', no_decay=(), rmsprop_alpha=0.9, rmsprop_eps=1e-3, lr_at=None):
     """The retrain schedule of train_eval.py:118-226: SGD + cosine learning rate (5 warm-up epochs of linearly increasing rate
     when batch_size > 256), label-smoothed training loss, plain cross-entropy validation every epoch, ``checkpoint.pth.tar`` /
     ``model_best.pth.tar`` with the reference's keys ('epoch', 'state_dict' with DataParallel's ``module.`` prefix,
@@ -756,7 +893,13 @@ def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250
     ema_warmup)`` is updated at every step; each epoch validates the raw weights and the average (history rows gain
     ``val_top1_ema`` / ``val_top5_ema`` / ``val_obj_ema``, the log line shows both); ``best_acc_top1`` / ``top5`` and
     ``model_best.pth.tar`` follow the AVERAGE's top-1; checkpoints gain 'state_dict_ema' (``module.`` prefix, like 'state_dict')
-    and 'ema_updates', which ``snapshot`` restores -- a snapshot without them starts the average from the loaded weights."""
+    and 'ema_updates', which ``snapshot`` restores -- a snapshot without them starts the average from the loaded weights.
+
+    ``optimizer`` ('sgd' | 'sgd-nesterov' | 'rmsprop' | 'rmsprop-tf'; the RMSprop ones with ``rmsprop_alpha`` / ``rmsprop_eps``,
+    'rmsprop-tf' is ``optim.RMSpropTF``) and ``no_decay`` (() | any of 'bn', 'bias': those parameters form a second group without
+    weight decay, ``optim.param_groups``) choose what the published recipes train with; every combination runs on the fused tail
+    (``RetrainState.plan``).  ``lr_at`` (a callable epoch -> learning rate) replaces the cosine rule and its warm-up.  With none
+    of the four passed, optimizer, schedule and checkpoint keys are what they always were."""
     import json
     import math
     import os
@@ -769,7 +912,20 @@ def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250
     with open(os.path.join(save_dir, 'model.config'), 'w') as f:
         json.dump(model.config, f, indent=4)
     crit_smooth = CrossEntropyLabelSmooth(num_classes, label_smooth)
-    opt = torch.optim.SGD(model.parameters(), lr, momentum=momentum, weight_decay=weight_decay)
+    if no_decay:
+        from .optim import param_groups
+        params = param_groups(model, weight_decay, no_decay)
+    else:
+        params = model.parameters()
+    if optimizer in ('sgd', 'sgd-nesterov'):
+        opt = torch.optim.SGD(params, lr, momentum=momentum, weight_decay=weight_decay, nesterov=optimizer == 'sgd-nesterov')
+    elif optimizer == 'rmsprop':
+        opt = torch.optim.RMSprop(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps, weight_decay=weight_decay, momentum=momentum)
+    elif optimizer == 'rmsprop-tf':
+        from .optim import RMSpropTF
+        opt = RMSpropTF(params, lr, alpha=rmsprop_alpha, eps=rmsprop_eps, weight_decay=weight_decay, momentum=momentum)
+    else:
+        raise ValueError("run_retrain: optimizer is 'sgd', 'sgd-nesterov', 'rmsprop' or 'rmsprop-tf', got %r" % (optimizer,))
     best1 = best5 = 0.0
     start = 0
     if snapshot:
@@ -788,6 +944,8 @@ def run_retrain(save_dir, model, make_train_queue, make_val_queue, *, epochs=250
     for epoch in range(start, epochs):
         cur = 0.5 * lr * (1.0 + math.cos(math.pi * epoch / float(epochs)))          # CosineAnnealingLR(T_max=epochs).get_lr()
         warm = epoch < 5 and batch_size > 256
+        if lr_at is not None:
+            cur, warm = float(lr_at(epoch)), False
         for g in opt.param_groups:
             g['lr'] = cur * (epoch + 1) / 5.0 if warm else cur
         meter.reset()
